@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the segmenting watershed transform on MI355X (BASELINE.json metric: Mpixels/s, % of HBM roofline).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config headline|c4|c5]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config headline|c4|c5] [--full] [--dump-outputs DIR]
 
 headline (default)  one 8192x8192 u8 random field per GPU, device-resident: BASELINE's metric.  N GPUs = N independent
                     fields, no collective on the data path ("weak").
@@ -25,8 +25,17 @@ Launch: under torchrun (RANK / WORLD_SIZE in the environment) every process is o
 `python bench.py --gpus N` with N > 1 starts its own N rank processes BEFORE touching a GPU.  When the ranks
 outnumber the visible GPUs (a rehearsal on a one-GPU box) they share devices and the collectives run over gloo.
 
-Rank 0 prints ONE JSON line (contract in the round brief) with `roofline`, `cpu_baseline`, and, for the headline
-configuration on one GPU, `end_to_end` (the host ABI, PCIe included) and `secondary` (a smooth map)."""
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0 (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed step).  Everything else is measured only with
+`--full`: the one-transform-alone leg, `roofline` / `roofline_valu` (a second leg of K steps with HIP events, the box's copy
+bandwidth), the `c3` list figures, `cpu_baseline`, and, for the headline configuration on one GPU, `end_to_end` (the host ABI,
+PCIe included), `call_pair` and `secondary` (smooth maps); `--no-extras` drops the last three groups and `cpu_baseline` again.
+
+`--dump-outputs DIR`: after the timed steps, rank 0 writes what the last timed step computed -- the arrays its caller receives --
+as DIR/<name>.npy in float64 (labels, colours and areas are integers far below 2^53: exact).  An output of more than
+DUMP_SAMPLE entries is written as the entries at DUMP_SAMPLE fixed, seeded positions (ascending flat indices) of it; the lake
+records of c3 (written in no particular order of their runs) are put in (level, colour) order first.  The inputs depend on the
+arguments alone, so two builds can be compared output for output."""
 import argparse
 import json
 import os
@@ -42,6 +51,9 @@ HBM_PEAK_GBS = 8000.0              # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB
 SWEEP_BYTES_PER_PX = 255 * 5 + 4   # per level one u8 + one u32 read, each label written once
 C4_SLICES, C4_SIDE = 64, 4096
 C5_SIDE = 32768
+DUMP_SAMPLE = 1 << 22              # --dump-outputs: entries kept of a larger output (32 MiB as float64)
+DUMP_SAMPLE_RECORDS = 1 << 21      # ... of c3's lake records, three columns each (48 MiB)
+DUMP_MAX_BYTES = 64 << 20
 
 
 def parse_args():
@@ -53,16 +65,22 @@ def parse_args():
     ap.add_argument("--size", type=int, default=0, help="override the field side (headline: 8192, c4 slices: 4096, c5: 32768)")
     ap.add_argument("--slices", type=int, default=C4_SLICES, help="c4: slices in the batch")
     ap.add_argument("--engine", choices=["fused", "sweep"], default="fused")
-    ap.add_argument("--cpu-size", type=int, default=4096, help="side of the CPU-baseline sample field (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="also the legs beside the headline figure: one transform alone, roofline, "
+                                                         "c3 list figures, CPU baseline, end_to_end / call_pair / secondary")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (float64)")
+    ap.add_argument("--cpu-size", type=int, default=4096, help="--full: side of the CPU-baseline sample field (0 = skip)")
     ap.add_argument("--cpu-runs", type=int, default=3)
-    ap.add_argument("--no-cpu-full", action="store_true", help="skip the one CPU run of the bench field itself (~45 s at 8192^2)")
-    ap.add_argument("--no-extras", action="store_true", help="skip end_to_end / secondary / cpu_baseline")
+    ap.add_argument("--no-cpu-full", action="store_true", help="--full: skip the one CPU run of the bench field itself (~45 s at 8192^2)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip end_to_end / call_pair / secondary / host_cube / cpu_baseline")
     ap.add_argument("--local-ranks", type=int, default=1, help="c5 on ONE process: virtual ranks of the local group (1: the field whole)")
     ap.add_argument("--tiles", default="", help="c5: PYxPX -- the field cut in both directions (ws_segment_tiled2d_device) instead of row blocks; PY * PX = the ranks")
     ap.add_argument("--contexts", type=int, default=4, help="headline: engine contexts that take turns, each on its own stream (1: as --no-pipeline)")
     ap.add_argument("--one-stream", action="store_true", help="headline: all contexts on one stream (transforms queue up, never overlap)")
     ap.add_argument("--no-pipeline", action="store_true", help="headline: one context, every transform waited for before the next is queued (the default takes turns on two contexts: ws_segment_device_begin / _end)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ---- self-launch: `python bench.py --gpus N` without torchrun ---------------------------------------------------------
@@ -300,6 +318,47 @@ def secondary_smooth(eng, torch, size, corr=64, runs=3):
             "relax_passes": int(st["relax_passes"]), "coloured_px": int((labels != 0).sum().item())}
 
 
+# ---- --dump-outputs -----------------------------------------------------------------------------------------------------
+
+def _sample(flat, k, seed=0):
+    """`k` entries of the 1-D tensor `flat` at fixed, seeded positions (ascending), or all of it when it has no more."""
+    import numpy as np
+    import torch
+    n = flat.numel()
+    if n <= k:
+        return flat
+    idx = np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+    return flat[torch.from_numpy(idx).to(flat.device)]
+
+
+def lake_records_sample(lakes, offsets):
+    """c3's (colour, area) records as (level, colour, area) rows in (level, colour) order -- the device writes each level's
+    records as runs of increasing colours in no particular order of the runs -- and DUMP_SAMPLE_RECORDS of them."""
+    import numpy as np
+    import torch
+    counts = torch.from_numpy(np.diff(offsets.astype(np.int64))).to(lakes.device)
+    level = torch.repeat_interleave(torch.arange(counts.numel(), dtype=torch.int64, device=lakes.device), counts)
+    order = torch.argsort((level << 32) | lakes[:, 0])
+    pick = _sample(order, DUMP_SAMPLE_RECORDS)
+    return torch.stack([level[pick], lakes[pick, 0], lakes[pick, 1]], dim=1).cpu().numpy()
+
+
+def dump_outputs(path, arrays):
+    """Writes every (name, array) of `arrays` as path/<name>.npy in float64: a device tensor of more than DUMP_SAMPLE entries
+    as a sample of its flat form, a numpy array as it is."""
+    import numpy as np
+    host = {}
+    for name, a in arrays.items():
+        if hasattr(a, "detach"):
+            a = _sample(a.detach().reshape(-1), DUMP_SAMPLE).cpu().numpy() if a.numel() > DUMP_SAMPLE else a.detach().cpu().numpy()
+        host[name] = np.asarray(a).astype(np.float64)
+    total = sum(a.nbytes for a in host.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes"
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(path, f"{name}.npy"), a)
+
+
 # ---- one rank -----------------------------------------------------------------------------------------------------------
 
 def run(args):
@@ -370,16 +429,18 @@ def run(args):
             lakes_buf, offsets, _unc = eng.transform_to_list(img, seeds, merging=True)
             n_records = int(offsets[-1])
             lakes_buf = torch.empty((n_records + 1024, 2), dtype=torch.int64, device=eng.device)
-            seg = eng.segment(img, seeds)
-            a, b = seg[:, :-1], seg[:, 1:]
-            n_edges = int(((a != b) & (a != 0) & (b != 0)).sum().item())
-            a, b = seg[:-1, :], seg[1:, :]
-            n_edges += int(((a != b) & (a != 0) & (b != 0)).sum().item())
-            del seg, a, b
-            c3_info = {"records": n_records, "crossing_edges": n_edges, "levels": 255}
+            if args.full:
+                seg = eng.segment(img, seeds)
+                a, b = seg[:, :-1], seg[:, 1:]
+                n_edges = int(((a != b) & (a != 0) & (b != 0)).sum().item())
+                a, b = seg[:-1, :], seg[1:, :]
+                n_edges += int(((a != b) & (a != 0) & (b != 0)).sum().item())
+                del seg, a, b
+                c3_info = {"records": n_records, "crossing_edges": n_edges, "levels": 255}
+            to_list_last = {}
 
             def step():
-                eng.transform_to_list(img, seeds, merging=True, lakes=lakes_buf)
+                to_list_last["out"] = eng.transform_to_list(img, seeds, merging=True, lakes=lakes_buf)
         elif args.no_pipeline or args.contexts < 2 or args.engine == "sweep":
             def step():
                 (eng.merge if merging else eng.segment)(img, seeds, out=labels)
@@ -516,8 +577,10 @@ def run(args):
             torch.cuda.empty_cache()
             block = wsd.HipBlockEngine(eng, block_img, sl, colours)
 
+            rehearsal_last = {}
+
             def step():
-                _, rounds = wsd.segment_tiled(block, rank, world)
+                rehearsal_last["labels"], rounds = wsd.segment_tiled(block, rank, world)
                 rounds_seen.append(rounds)
             labels = None
             how = f"distributed.py over {backend} (ranks share devices: a protocol rehearsal)"
@@ -542,10 +605,27 @@ def run(args):
         drain()             # the wait for the last two transforms is inside the timed region
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # what the caller of the last timed step receives (c5: this process's ranks' owned rows / tiles of the label plane)
+        if to_list:
+            lakes, offs_, unc_ = to_list_last["out"]
+            outputs = {"lake_offsets": offs_, "lake_uncoloured": unc_, "lake_records": lake_records_sample(lakes, offs_)}
+        elif pipelined:
+            outputs = {"labels": pipe_labels[(args.steps - 1) % args.contexts]}      # the warm-up's drain restarted the turns at 0
+        elif cfg == "c5" and use_c_group:
+            owned = ([lab[rr[0] - rr[2]:rr[1] - rr[2], cc[0] - cc[2]:cc[1] - cc[2]] for rr, cc, lab in spans] if tiles2d else
+                     [lab[r0_ - lo_:r1_ - lo_] for r0_, r1_, lo_, lab in spans])
+            outputs = {"labels": torch.cat([o.reshape(-1) for o in owned])}
+        elif cfg == "c5":
+            outputs = {"labels": rehearsal_last["labels"]}
+        else:
+            outputs = {"labels": labels}
+        dump_outputs(args.dump_outputs, outputs)
+        del outputs
     st_last = eng.stats()
     replayed = bool(st_last.get("graph_launches", 0))      # of the last timed transform
     ms_one_context = None
-    if pipelined:
+    if pipelined and args.full:
         # the same K steps with NOTHING else in flight: every transform is waited for before the next is queued (what a
         # caller of the one-call form gets).  The transforms rotate over the contexts' fields (each context replays its own
         # graph on its own buffers), so that a transform never finds its input in the Infinity Cache from the one before.
@@ -568,7 +648,7 @@ def run(args):
     # the kernels run on) for the roofline object ----
     agg = {"ms_relax": 0.0, "ms_resolve": 0.0, "ms_sweep": 0.0, "ms_other": 0.0, "ms_total": 0.0, "launches_relax": 0,
            "launches_resolve": 0, "launches_sweep": 0, "tiles_run_relax": 0, "relax_tile_iterations": 0}
-    if cfg != "c5":
+    if cfg != "c5" and args.full:
         eng.ctx.set_profiling(True)
         barrier()
         for _ in range(args.steps):
@@ -599,104 +679,105 @@ def run(args):
         b_sweep = npx_rank * SWEEP_BYTES_PER_PX + 16 * n_seeds_rank
         compulsory_GBps = b_min / (ms_step * 1e-3) / 1e9
         sweep_equiv = b_sweep / (ms_step * 1e-3) / 1e9
-        roof = {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s"}
-        if cfg != "c5":
-            if args.engine == "fused":
-                kname, k_ms, k_launches = "k_relax", agg["ms_relax"], agg["launches_relax"]
-                tile_px = 256 * 32
-                # every tile that runs reads its image (1 B) and stamps (4 B) once per pixel -- except in pass 0, which has no
-                # stamps to read: it derives them from the seed bit plane (1/8 B per pixel); every stamp is written once, by
-                # pass 0 (later passes rewrite only what changed).  These are the bytes the kernel ASKS for, re-runs of a
-                # tile included: they are the honest numerator for this kernel's own bandwidth, not a claim that the re-runs
-                # are needed -- `frac_compulsory` below is the figure against the bytes the transform cannot avoid.
-                rows_stack = npx_rank // W
-                tiles_pass0 = args.steps * ((W + 255) // 256) * ((rows_stack + 31) // 32)
-                k_bytes = max(agg["tiles_run_relax"] - tiles_pass0, 0) * tile_px * 5 + tiles_pass0 * tile_px * 1.125 + args.steps * npx_rank * 4
+        roof = roof_valu = None       # --full: the kernel leg's and the copy's figures, against HBM and vector issue
+        if args.full:
+            roof = {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s"}
+            if cfg != "c5":
+                if args.engine == "fused":
+                    kname, k_ms, k_launches = "k_relax", agg["ms_relax"], agg["launches_relax"]
+                    tile_px = 256 * 32
+                    # every tile that runs reads its image (1 B) and stamps (4 B) once per pixel -- except in pass 0, which has no
+                    # stamps to read: it derives them from the seed bit plane (1/8 B per pixel); every stamp is written once, by
+                    # pass 0 (later passes rewrite only what changed).  These are the bytes the kernel ASKS for, re-runs of a
+                    # tile included: they are the honest numerator for this kernel's own bandwidth, not a claim that the re-runs
+                    # are needed -- `frac_compulsory` below is the figure against the bytes the transform cannot avoid.
+                    rows_stack = npx_rank // W
+                    tiles_pass0 = args.steps * ((W + 255) // 256) * ((rows_stack + 31) // 32)
+                    k_bytes = max(agg["tiles_run_relax"] - tiles_pass0, 0) * tile_px * 5 + tiles_pass0 * tile_px * 1.125 + args.steps * npx_rank * 4
+                else:
+                    kname, k_ms, k_launches = "k_flood_step", agg["ms_sweep"], agg["launches_sweep"]
+                    k_bytes = agg["launches_sweep"] * npx_rank * (1 + 4 + 4)
+                k_avg_ms = k_ms / max(k_launches, 1)
+                k_bytes_per_launch = k_bytes / max(k_launches, 1)
+                achieved = k_bytes_per_launch / (k_avg_ms * 1e-3) / 1e9 if k_avg_ms > 0 else 0.0
+                # the same kernel against the bytes its PHASE cannot avoid (every pixel's image byte, seed bit and stamp once):
+                # what is left of `frac` when the re-runs of tiles are not counted as useful bytes
+                k_min_bytes = args.steps * npx_rank * (1 + 0.125 + 4) if args.engine == "fused" else k_bytes
+                k_min_GBps = k_min_bytes / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
+                roof.update({
+                    "kernel": kname, "achieved": round(achieved, 2), "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": None,
+                    "kernel_minimum_bytes_per_step": int(k_min_bytes / args.steps), "frac_kernel_minimum": round(k_min_GBps / HBM_PEAK_GBS, 5),
+                    "avg_launch_ms": round(k_avg_ms, 5), "launches_per_step": round(k_launches / args.steps, 2),
+                    "timing": "HIP events around every launch, in a second leg of the same K steps (events off in the timed leg)",
+                    "tiles_run_per_step": round(agg["tiles_run_relax"] / args.steps, 1),
+                    "tile_sweep_iterations_per_step": round(agg["relax_tile_iterations"] / args.steps, 1),
+                    "algorithmic_bytes_per_launch": int(k_bytes_per_launch),
+                    "note": "achieved/frac: bytes THIS kernel asks for (5 B per pixel of every tile run in passes >= 1 -- 8192-pixel tiles; the 256x8 bands of the seam repair count a quarter -- "
+                            "counted on the device, re-runs included; 1.125 B per pixel in pass 0; 4 B per pixel written once) over "
+                            "its HIP-event time -- DESIGN.md section 5.  The whole-transform figure against unavoidable bytes is "
+                            "frac_compulsory.",
+                    "device_ms_per_step": {k: round(agg[k] / args.steps, 4) for k in ("ms_total", "ms_relax", "ms_resolve", "ms_sweep", "ms_other")},
+                })
+                tpath = os.path.join(ROOT, "profiles", "traffic.json")
+                if cfg == "c3":
+                    roof["note"] += "  (c3: k_relax is the dominant kernel of the merging transform too; the union / relabel part adds ~0.35 ms)"
+                if cfg == "headline" and args.engine == "fused" and H == 8192 and os.path.exists(tpath):
+                    tj = json.load(open(tpath))
+                    roof["traffic"] = int(tj["k_relax"]["bytes_per_launch"])
+                    roof["traffic_source"] = "SINGLE-CONTEXT profile (one transform at a time, not the timed mode with several in flight): " + tj["source"]
+                    if "transform_total_bytes" in tj:
+                        roof["traffic_total"] = int(tj["transform_total_bytes"])       # all kernels of one transform, PMC
+                        roof["traffic_total_over_compulsory"] = round(tj["transform_total_bytes"] / b_min, 3)
+                        roof["frac_traffic_total"] = round(tj["transform_total_bytes"] / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
             else:
-                kname, k_ms, k_launches = "k_flood_step", agg["ms_sweep"], agg["launches_sweep"]
-                k_bytes = agg["launches_sweep"] * npx_rank * (1 + 4 + 4)
-            k_avg_ms = k_ms / max(k_launches, 1)
-            k_bytes_per_launch = k_bytes / max(k_launches, 1)
-            achieved = k_bytes_per_launch / (k_avg_ms * 1e-3) / 1e9 if k_avg_ms > 0 else 0.0
-            # the same kernel against the bytes its PHASE cannot avoid (every pixel's image byte, seed bit and stamp once):
-            # what is left of `frac` when the re-runs of tiles are not counted as useful bytes
-            k_min_bytes = args.steps * npx_rank * (1 + 0.125 + 4) if args.engine == "fused" else k_bytes
-            k_min_GBps = k_min_bytes / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
-            roof.update({
-                "kernel": kname, "achieved": round(achieved, 2), "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": None,
-                "kernel_minimum_bytes_per_step": int(k_min_bytes / args.steps), "frac_kernel_minimum": round(k_min_GBps / HBM_PEAK_GBS, 5),
-                "avg_launch_ms": round(k_avg_ms, 5), "launches_per_step": round(k_launches / args.steps, 2),
-                "timing": "HIP events around every launch, in a second leg of the same K steps (events off in the timed leg)",
-                "tiles_run_per_step": round(agg["tiles_run_relax"] / args.steps, 1),
-                "tile_sweep_iterations_per_step": round(agg["relax_tile_iterations"] / args.steps, 1),
-                "algorithmic_bytes_per_launch": int(k_bytes_per_launch),
-                "note": "achieved/frac: bytes THIS kernel asks for (5 B per pixel of every tile run in passes >= 1 -- 8192-pixel tiles; the 256x8 bands of the seam repair count a quarter -- "
-                        "counted on the device, re-runs included; 1.125 B per pixel in pass 0; 4 B per pixel written once) over "
-                        "its HIP-event time -- DESIGN.md section 5.  The whole-transform figure against unavoidable bytes is "
-                        "frac_compulsory.",
-                "device_ms_per_step": {k: round(agg[k] / args.steps, 4) for k in ("ms_total", "ms_relax", "ms_resolve", "ms_sweep", "ms_other")},
-            })
-            tpath = os.path.join(ROOT, "profiles", "traffic.json")
-            if cfg == "c3":
-                roof["note"] += "  (c3: k_relax is the dominant kernel of the merging transform too; the union / relabel part adds ~0.35 ms)"
-            if cfg == "headline" and args.engine == "fused" and H == 8192 and os.path.exists(tpath):
-                tj = json.load(open(tpath))
-                roof["traffic"] = int(tj["k_relax"]["bytes_per_launch"])
-                roof["traffic_source"] = "SINGLE-CONTEXT profile (one transform at a time, not the timed mode with several in flight): " + tj["source"]
-                if "transform_total_bytes" in tj:
-                    roof["traffic_total"] = int(tj["transform_total_bytes"])       # all kernels of one transform, PMC
-                    roof["traffic_total_over_compulsory"] = round(tj["transform_total_bytes"] / b_min, 3)
-                    roof["frac_traffic_total"] = round(tj["transform_total_bytes"] / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-        else:
-            roof.update({"kernel": "whole tiled transform", "achieved": round(compulsory_GBps, 2),
-                         "frac": round(compulsory_GBps / HBM_PEAK_GBS, 5), "traffic": None,
-                         "note": "compulsory bytes of this rank's row block over the step time (no per-kernel leg in tiled mode)",
-                         "exchange_rounds_per_step": round(sum(rounds_seen) / max(len(rounds_seen), 1), 2)})
-        # the box's own achievable HBM rate (report against both): a 1 GiB device-to-device copy, read + write
-        a = torch.empty(1 << 28, dtype=torch.int32, device=eng.device)
-        b = torch.empty_like(a)
-        b.copy_(a)
-        torch.cuda.synchronize()
-        tc = time.perf_counter()
-        for _ in range(5):
+                roof.update({"kernel": "whole tiled transform", "achieved": round(compulsory_GBps, 2),
+                             "frac": round(compulsory_GBps / HBM_PEAK_GBS, 5), "traffic": None,
+                             "note": "compulsory bytes of this rank's row block over the step time (no per-kernel leg in tiled mode)",
+                             "exchange_rounds_per_step": round(sum(rounds_seen) / max(len(rounds_seen), 1), 2)})
+            # the box's own achievable HBM rate (report against both): a 1 GiB device-to-device copy, read + write
+            a = torch.empty(1 << 28, dtype=torch.int32, device=eng.device)
+            b = torch.empty_like(a)
             b.copy_(a)
-        torch.cuda.synchronize()
-        copy_GBps = 5 * 2 * a.numel() * 4 / (time.perf_counter() - tc) / 1e9
-        del a, b
-        roof["copy_GBps_measured"] = round(copy_GBps, 1)
-        roof["frac_compulsory_of_copy"] = round(compulsory_GBps / copy_GBps, 5)
-        # whole transform against the bytes it cannot avoid -- the honest roofline fraction
-        roof["compulsory_bytes_per_step"] = int(b_min)
-        roof["compulsory_GBps"] = round(compulsory_GBps, 1)
-        roof["frac_compulsory"] = round(compulsory_GBps / HBM_PEAK_GBS, 5)
-        # speed-equivalent only (NOT a roofline fraction): how fast a literal 255-sweep engine would have to move its
-        # bytes to finish in the same time; the figure BASELINE.md's ">= 30 %" target is phrased in
-        roof["sweep_model_speed_equivalent"] = {"bytes_per_step": int(b_sweep), "equivalent_GBps": round(sweep_equiv, 1),
-                                                 "times_hbm_peak": round(sweep_equiv / HBM_PEAK_GBS, 3),
-                                                 "note": "speed-equivalent of a sweep-per-level engine, not bandwidth"}
-        # The other ceiling: vector issue.  The transform's kernels execute `lane_instr_per_px` vector instructions
-        # per pixel (SQ_INSTS_VALU, profiles/valu.json: a single-context profile of this build's kernels) and a SIMD spends
-        # `cycles_per_wave_instr` cycles on each (SQ_ACTIVE_INST_VALU; the microbenchmark has the same figure for the relaxation's
-        # mix: v_min3 / v_med3 / v_min issue at half rate on gfx950).  peak = 1024 SIMDs x 64 lanes x 2.4 GHz / that.
-        roof_valu = None
-        vpath = os.path.join(ROOT, "profiles", "valu.json")
-        if cfg == "headline" and args.engine == "fused" and H == 8192 and os.path.exists(vpath):
-            vj = json.load(open(vpath))
-            cpi = float(vj["cycles_per_wave_instr_measured"])
-            peak_mix = 1024 * 64 * 2.4e9 / cpi
-            lane_ops = float(vj["lane_instr_per_px"]) * npx_rank
-            roof_valu = {"peak_lane_ops_per_s": round(peak_mix, 0), "peak_note": f"1024 SIMDs x 64 lanes x 2.4 GHz / {cpi:.2f} cycles per wave-instruction of THIS instruction mix "
-                                                                              "(full-rate instructions alone: 3.2 cycles measured, 2 by the data sheet)",
-                         "lane_ops_per_px": round(float(vj["lane_instr_per_px"]), 1), "lane_ops_per_step": int(lane_ops),
-                         "achieved_lane_ops_per_s": round(lane_ops / (ms_step * 1e-3), 0), "frac": round(lane_ops / (ms_step * 1e-3) / peak_mix, 4),
-                         "frac_of_datasheet_peak": round(lane_ops / (ms_step * 1e-3) / (1024 * 64 * 2.4e9 / 2.0), 4),
-                         "floor_ms_per_step": round(lane_ops / peak_mix * 1e3, 4), "source": vj["source"], "microbenchmark": vj["microbenchmark"]}
-            if ms_one_context is not None:
-                roof_valu["frac_one_transform_alone"] = round(lane_ops / (ms_one_context * 1e-3) / peak_mix, 4)
-            roof["tighter_bound"] = "valu" if roof_valu["frac"] > roof.get("frac_compulsory", 0.0) else "hbm"
-            roof["tighter_bound_note"] = ("pass 0 of the relaxation and k_resolve_local keep a vector instruction active on every SIMD 88 % / 83 % of their cycles "
-                                          "(profiles/r3_v0_issue_counters.json): the transform is bound by vector issue, not by HBM; `bound` stays \"hbm\" because "
-                                          "BASELINE's metric is phrased against the HBM roofline")
+            torch.cuda.synchronize()
+            tc = time.perf_counter()
+            for _ in range(5):
+                b.copy_(a)
+            torch.cuda.synchronize()
+            copy_GBps = 5 * 2 * a.numel() * 4 / (time.perf_counter() - tc) / 1e9
+            del a, b
+            roof["copy_GBps_measured"] = round(copy_GBps, 1)
+            roof["frac_compulsory_of_copy"] = round(compulsory_GBps / copy_GBps, 5)
+            # whole transform against the bytes it cannot avoid -- the honest roofline fraction
+            roof["compulsory_bytes_per_step"] = int(b_min)
+            roof["compulsory_GBps"] = round(compulsory_GBps, 1)
+            roof["frac_compulsory"] = round(compulsory_GBps / HBM_PEAK_GBS, 5)
+            # speed-equivalent only (NOT a roofline fraction): how fast a literal 255-sweep engine would have to move its
+            # bytes to finish in the same time; the figure BASELINE.md's ">= 30 %" target is phrased in
+            roof["sweep_model_speed_equivalent"] = {"bytes_per_step": int(b_sweep), "equivalent_GBps": round(sweep_equiv, 1),
+                                                     "times_hbm_peak": round(sweep_equiv / HBM_PEAK_GBS, 3),
+                                                     "note": "speed-equivalent of a sweep-per-level engine, not bandwidth"}
+            # The other ceiling: vector issue.  The transform's kernels execute `lane_instr_per_px` vector instructions
+            # per pixel (SQ_INSTS_VALU, profiles/valu.json: a single-context profile of this build's kernels) and a SIMD spends
+            # `cycles_per_wave_instr` cycles on each (SQ_ACTIVE_INST_VALU; the microbenchmark has the same figure for the relaxation's
+            # mix: v_min3 / v_med3 / v_min issue at half rate on gfx950).  peak = 1024 SIMDs x 64 lanes x 2.4 GHz / that.
+            vpath = os.path.join(ROOT, "profiles", "valu.json")
+            if cfg == "headline" and args.engine == "fused" and H == 8192 and os.path.exists(vpath):
+                vj = json.load(open(vpath))
+                cpi = float(vj["cycles_per_wave_instr_measured"])
+                peak_mix = 1024 * 64 * 2.4e9 / cpi
+                lane_ops = float(vj["lane_instr_per_px"]) * npx_rank
+                roof_valu = {"peak_lane_ops_per_s": round(peak_mix, 0), "peak_note": f"1024 SIMDs x 64 lanes x 2.4 GHz / {cpi:.2f} cycles per wave-instruction of THIS instruction mix "
+                                                                                  "(full-rate instructions alone: 3.2 cycles measured, 2 by the data sheet)",
+                             "lane_ops_per_px": round(float(vj["lane_instr_per_px"]), 1), "lane_ops_per_step": int(lane_ops),
+                             "achieved_lane_ops_per_s": round(lane_ops / (ms_step * 1e-3), 0), "frac": round(lane_ops / (ms_step * 1e-3) / peak_mix, 4),
+                             "frac_of_datasheet_peak": round(lane_ops / (ms_step * 1e-3) / (1024 * 64 * 2.4e9 / 2.0), 4),
+                             "floor_ms_per_step": round(lane_ops / peak_mix * 1e3, 4), "source": vj["source"], "microbenchmark": vj["microbenchmark"]}
+                if ms_one_context is not None:
+                    roof_valu["frac_one_transform_alone"] = round(lane_ops / (ms_one_context * 1e-3) / peak_mix, 4)
+                roof["tighter_bound"] = "valu" if roof_valu["frac"] > roof.get("frac_compulsory", 0.0) else "hbm"
+                roof["tighter_bound_note"] = ("pass 0 of the relaxation and k_resolve_local keep a vector instruction active on every SIMD 88 % / 83 % of their cycles "
+                                              "(profiles/r3_v0_issue_counters.json): the transform is bound by vector issue, not by HBM; `bound` stays \"hbm\" because "
+                                              "BASELINE's metric is phrased against the HBM roofline")
         out = {
             "metric": ("Mpixels/s segmenting watershed, 8192x8192 u8, device-resident"
                        + (f" (throughput, {args.contexts} transforms of distinct fields in flight; one transform alone: value_one_transform_alone)" if pipelined else "")) if cfg == "headline"
@@ -716,7 +797,8 @@ def run(args):
                                           if args.one_stream else
                                           "each on its own stream: a transform is queued before the one before it has been waited for, and "
                                           "transforms of different contexts overlap on the GPU (throughput, not the latency of one transform)")
-                                       + f" -- one context, every transform waited for before the next is queued: {ms_one_context:.4f} ms per step"
+                                       if pipelined else "") +
+                                      (f" -- one context, every transform waited for before the next is queued: {ms_one_context:.4f} ms per step"
                                        if ms_one_context is not None else "")},
                            **units),
             "roofline": roof,
@@ -740,9 +822,9 @@ def run(args):
             out["ms_one_transform_alone"] = round(ms_one_context, 4)
             out["value_one_transform_alone"] = round(npx_rank * world / (ms_one_context * 1e-3) / 1e6, 2)
             roof["frac_compulsory_one_transform_alone"] = round(b_min / (ms_one_context * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
-        if labels is not None:
+        if labels is not None and args.full:
             out["config"]["coloured_px"] = int((labels != 0).sum().item())
-        extras = cfg == "headline" and world == 1 and not args.no_extras
+        extras = args.full and cfg == "headline" and world == 1 and not args.no_extras
         if extras and args.engine == "fused":
             del labels
             out["secondary"] = secondary_smooth(eng, torch, H)
@@ -753,9 +835,9 @@ def run(args):
             out["call_pair"] = call_pair_device(eng, torch, H, W)
             torch.cuda.empty_cache()
             out["end_to_end"] = end_to_end(pkg, eng, H, W)
-        if cfg == "c4" and world == 1 and not args.no_extras:
+        if args.full and cfg == "c4" and world == 1 and not args.no_extras:
             out["host_cube"] = host_cube(pkg, cube[:min(len(mine), 16)].cpu().numpy(), H, W)
-        out["cpu_baseline"] = cpu_baseline(args.cpu_size, 1, args.cpu_runs, 0 if args.no_cpu_full or cfg != "headline" else H) if (world == 1 and args.cpu_size > 0 and not args.no_extras) else None
+        out["cpu_baseline"] = cpu_baseline(args.cpu_size, 1, args.cpu_runs, 0 if args.no_cpu_full or cfg != "headline" else H) if (args.full and world == 1 and args.cpu_size > 0 and not args.no_extras) else None
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

@@ -190,3 +190,47 @@ def test_bench_and_entry_point_compile_and_parse_their_arguments():
     finally:
         sys.argv = argv
     assert d.gpus == 1 and d.config == "headline" and d.steps >= 1 and d.warmup >= 0
+
+
+def test_bench_full_and_dump_outputs(tmp_path):
+    # a plain bench run measures the headline figure alone; --full adds the other legs; --dump-outputs DIR writes what the
+    # last timed step computed as float64 .npy files, a larger output as a fixed, seeded sample of it
+    import importlib.util
+    import torch
+    spec = importlib.util.spec_from_file_location("ws_bench_module", os.path.join(ROOT, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--steps", "5", "--warmup", "2"]
+        a = mod.parse_args()
+        sys.argv = ["bench.py", "--full", "--dump-outputs", str(tmp_path / "d")]
+        b = mod.parse_args()
+        sys.argv = ["bench.py", "--steps", "0"]
+        with pytest.raises(SystemExit):
+            mod.parse_args()
+    finally:
+        sys.argv = argv
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 5, 2)
+    assert b.full and b.dump_outputs == str(tmp_path / "d")
+
+    mod.DUMP_SAMPLE = 1000
+    labels = torch.arange(64 * 80, dtype=torch.int32).reshape(64, 80)
+    small = torch.arange(7, dtype=torch.int32)
+    for d in ("d1", "d2"):
+        mod.dump_outputs(str(tmp_path / d), {"labels": labels, "small": small, "offsets": np.arange(4, dtype=np.uint64)})
+    got = {n: np.load(tmp_path / "d1" / f"{n}.npy") for n in ("labels", "small", "offsets")}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert got["labels"].shape == (1000,) and len(set(got["labels"].tolist())) == 1000
+    assert (np.diff(got["labels"]) > 0).all() and got["labels"].max() < 64 * 80      # ascending positions of the flat plane
+    assert (got["labels"] == np.load(tmp_path / "d2" / "labels.npy")).all()       # the same positions every run
+    assert (got["small"] == np.arange(7)).all() and (got["offsets"] == np.arange(4)).all()
+
+    # c3's lake records: each level's runs of increasing colours come in no particular order; the dump puts them in
+    # (level, colour) order, whatever order the runs had
+    offsets = np.array([0, 3, 5], dtype=np.uint64)
+    one = torch.tensor([[4, 10], [7, 11], [2, 12], [9, 20], [3, 21]], dtype=torch.int64)
+    two = torch.tensor([[2, 12], [4, 10], [7, 11], [3, 21], [9, 20]], dtype=torch.int64)
+    want = np.array([[0, 2, 12], [0, 4, 10], [0, 7, 11], [1, 3, 21], [1, 9, 20]])
+    assert (mod.lake_records_sample(one, offsets) == want).all()
+    assert (mod.lake_records_sample(two, offsets) == want).all()

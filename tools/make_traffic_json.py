@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""profiles/traffic.json (what bench.py quotes as `roofline.traffic*`) from a pmc_hbm_bytes.json of tools/profile_round.sh.
+"""profiles/traffic.json (what bench.py --full quotes as `roofline.traffic*`) from a pmc_hbm_bytes.json of tools/profile_round.sh.
 usage: make_traffic_json.py <pmc_hbm_bytes.json> <build tag> [transforms in the probe = 4] > profiles/traffic.json"""
 import json, sys
 src, tag = sys.argv[1], sys.argv[2]

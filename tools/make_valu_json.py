@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""profiles/valu.json (what bench.py quotes as `roofline_valu`) from an issue-counter summary of tools/profile_issue_counters.sh.
+"""profiles/valu.json (what bench.py --full quotes as `roofline_valu`) from an issue-counter summary of tools/profile_issue_counters.sh.
 usage: make_valu_json.py <issue_counters.json> <build tag> [transforms in the probe = 4] > profiles/valu.json
 Vector instructions per pixel of one 8192^2 transform, by kernel, and the cycles a SIMD spends on one of them (the SQ's own
 count: SQ_ACTIVE_INST_VALU over SQ_INSTS_VALU, quad-cycles x 4)."""
