@@ -273,6 +273,15 @@ int ws_segment_batch(ws_ctx *ctx, const uint8_t *cube, size_t n_slices, size_t h
                      size_t slice_stride, const uint64_t *seeds_rc, const size_t *seed_offsets, const ws_options *opt,
                      uint64_t *out_labels, size_t *n_seeds, size_t *failed_slice);
 
+/* ws_transform_to_list_batch_device from HOST memory: the cube and the (row, col) seed pairs as ws_segment_batch takes them
+ * (seeds_rc == NULL: every slice's own find_local_minima, n_seeds[k], nullable, receives how many), the records into the host's
+ * `lakes` (cap of them; the same transfer as ws_transform_to_list).  Offsets, uncoloured, WS_ERR_CAPACITY and *failed_slice as the
+ * device form.  Context workspace: the cube, the seeds and cap records on the device besides the device form's. */
+int ws_transform_to_list_batch(ws_ctx *ctx, int merging, const uint8_t *cube, size_t n_slices, size_t h, size_t w, size_t row_stride,
+                               size_t slice_stride, const uint64_t *seeds_rc, const size_t *seed_offsets, const ws_options *opt,
+                               ws_lake *lakes, size_t cap, size_t *n_lakes, uint64_t *offsets, uint64_t *uncoloured, size_t *n_seeds,
+                               size_t *failed_slice);
+
 /* ---- device-resident entry points (inputs and outputs stay in HBM) ------------------- */
 
 /* d_img: device u8 plane; d_seeds_rc: device (row, col) pairs as uint32_t[2];
@@ -336,6 +345,30 @@ int ws_transform_to_list_device(ws_ctx *ctx, int merging, const uint8_t *d_img, 
 int ws_lists_from_arrival_device(ws_ctx *ctx, int merging, const uint32_t *d_keys, const uint32_t *d_seg_labels, size_t h, size_t w,
                                  size_t n_seeds, const ws_options *opt, ws_lake *d_lakes, size_t cap, size_t *n_lakes,
                                  uint64_t *offsets, uint64_t *uncoloured);
+/* transform_to_list of every slice of a cube (tests/integration.rs:122-601: find_local_minima and transform_to_list on one
+ * slice after the other), merging (merging != 0) or segmenting, everything in HBM.  Slices, seeds, seed_offsets (n_slices + 1
+ * entries, on the HOST) and *failed_slice as ws_segment_batch_device; L = opt->max_water_level.
+ * Layout, slice-major then level: the records of slice k at level l are d_lakes[offsets[k * (L + 1) + l] .. offsets[k * (L + 1) + l + 1])
+ * (offsets: n_slices * (L + 1) + 1 entries on the host), in the slice's own colours 1 .. n_k; uncoloured[k * (L + 1) + l] (n_slices *
+ * (L + 1) entries on the host) is index 0 of the reference's vector for that slice and level.  Every (slice, level) holds the same
+ * records as ws_transform_to_list_device on that slice, in no particular order.  *n_lakes receives the total; WS_ERR_CAPACITY when
+ * cap is too small (then only *n_lakes is meaningful: call again with that many).
+ * When the slices stack (the conditions of ws_segment_batch_device, and a seed in every group of slices) the whole cube runs as one
+ * flood and ONE set of per-level launches over the stack, whose records are then split into the layout above; anything else runs
+ * as a loop of ws_transform_to_list_device.  Scratch of the stacked form, kept by the context: 4 B per pixel of the stack (its
+ * labels), 16 B per record of cap (the stack's records before the split), and 8 B per (slice, level) bin.  Statistics are summed
+ * over the call's transforms; afterwards ws_last_arrival_device reports "unsupported". */
+int ws_transform_to_list_batch_device(ws_ctx *ctx, int merging, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w,
+                                      size_t row_stride, size_t slice_stride, const uint32_t *d_seeds_rc, const size_t *seed_offsets,
+                                      const ws_options *opt, ws_lake *d_lakes, size_t cap, size_t *n_lakes, uint64_t *offsets,
+                                      uint64_t *uncoloured, size_t *failed_slice);
+/* The merging transform's final canonical labels of every slice of a cube: arguments as ws_segment_batch_device, labels as
+ * ws_merge_device on each slice, bit for bit (the smallest seed colour of the lake, in the slice's own colours).  Slices that stack
+ * run as one flood and one union pass over the stack; the rest as a loop of ws_merge_device.  Scratch: the union-find of all the
+ * stack's colours (16 B a colour). */
+int ws_merge_batch_device(ws_ctx *ctx, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w, size_t row_stride,
+                          size_t slice_stride, const uint32_t *d_seeds_rc, const size_t *seed_offsets, const ws_options *opt,
+                          uint32_t *d_labels, size_t *failed_slice);
 /* Arrival stamps of the last ws_segment_device / ws_merge_device call on this context:
  * (level << 24 | ring), 0 for seeds, 0xFF000000 for never coloured.  Device pointer owned
  * by the context, valid until the next call; shape as the label plane. */

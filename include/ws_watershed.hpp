@@ -206,6 +206,40 @@ class Watershed : public WatershedUtils {  // lib.rs:1206-1238
     return out;
   }
 
+  // not in the reference: transform_to_list(cube[k], find_local_minima(cube[k])) of every slice of a contiguous u8 cube
+  // (n_slices x rows x cols) as one call (ws_transform_to_list_batch), sparse: per slice, per level the uncoloured count and the
+  // (colour, area) of every lake with pixels, in no particular order.  n_seeds (nullable) receives the slices' minima counts.
+  struct SparseLevel {
+    std::uint8_t level;
+    usize uncoloured;
+    std::vector<ws_lake> lakes;
+  };
+  std::vector<std::vector<SparseLevel>> transform_to_list_cube(const std::uint8_t *cube, std::size_t n_slices, std::size_t rows,
+                                                               std::size_t cols, std::vector<std::size_t> *n_seeds = nullptr) const {
+    const std::size_t levels = std::size_t(opt_.max_water_level) + 1;
+    std::vector<std::uint64_t> offsets(n_slices * levels + 1), unc(n_slices * levels);
+    std::vector<std::size_t> counts(n_slices);
+    // one record per pixel of the cube; a too small guess costs a second transform, not a wrong answer
+    std::size_t cap = std::min<std::size_t>(n_slices * rows * cols + 1024, std::size_t(1) << 28), n = 0, failed = 0;
+    std::vector<ws_lake> lakes;
+    for (;;) {
+      lakes.resize(cap);
+      int rc = ws_transform_to_list_batch(ctx_->get(), merging_, cube, n_slices, rows, cols, cols, rows * cols, nullptr, nullptr, &opt_,
+                                          lakes.data(), cap, &n, offsets.data(), unc.data(), counts.data(), &failed);
+      if (rc == WS_ERR_CAPACITY && n > cap) { cap = n; continue; }
+      ctx_->check(rc);
+      break;
+    }
+    std::vector<std::vector<SparseLevel>> out(n_slices);
+    for (std::size_t k = 0; k < n_slices; ++k)
+      for (std::size_t l = 0; l < levels; ++l) {
+        const std::size_t b = k * levels + l;
+        out[k].push_back({std::uint8_t(l), (usize)unc[b], std::vector<ws_lake>(lakes.begin() + offsets[b], lakes.begin() + offsets[b + 1])});
+      }
+    if (n_seeds) *n_seeds = counts;
+    return out;
+  }
+
  protected:
   Watershed(ws_options o, Hook h, std::shared_ptr<Context> c, int merging)
       : WatershedUtils(std::move(c)), opt_(o), hook_(std::move(h)), merging_(merging) {}

@@ -171,6 +171,17 @@ extern "C" {
         cap: usize, n_lakes: *mut usize, offsets: *mut u64, uncoloured: *mut u64) -> c_int;
     pub fn ws_lists_from_arrival_device(ctx: *mut ws_ctx, merging: c_int, d_keys: *const u32, d_seg_labels: *const u32, h: usize, w: usize, n_seeds: usize,
                                         opt: *const ws_options, d_lakes: *mut ws_lake, cap: usize, n_lakes: *mut usize, offsets: *mut u64, uncoloured: *mut u64) -> c_int;
+    pub fn ws_transform_to_list_batch(ctx: *mut ws_ctx, merging: c_int, cube: *const u8, n_slices: usize, h: usize, w: usize, row_stride: usize,
+                                      slice_stride: usize, seeds_rc: *const u64, seed_offsets: *const usize, opt: *const ws_options,
+                                      lakes: *mut ws_lake, cap: usize, n_lakes: *mut usize, offsets: *mut u64, uncoloured: *mut u64,
+                                      n_seeds: *mut usize, failed_slice: *mut usize) -> c_int;
+    pub fn ws_transform_to_list_batch_device(ctx: *mut ws_ctx, merging: c_int, d_cube: *const u8, n_slices: usize, h: usize, w: usize,
+                                             row_stride: usize, slice_stride: usize, d_seeds_rc: *const u32, seed_offsets: *const usize,
+                                             opt: *const ws_options, d_lakes: *mut ws_lake, cap: usize, n_lakes: *mut usize, offsets: *mut u64,
+                                             uncoloured: *mut u64, failed_slice: *mut usize) -> c_int;
+    pub fn ws_merge_batch_device(ctx: *mut ws_ctx, d_cube: *const u8, n_slices: usize, h: usize, w: usize, row_stride: usize,
+                                 slice_stride: usize, d_seeds_rc: *const u32, seed_offsets: *const usize, opt: *const ws_options,
+                                 d_labels: *mut u32, failed_slice: *mut usize) -> c_int;
     pub fn ws_merge_transform_stub(h: usize, w: usize, out_labels: *mut u64) -> c_int;
     pub fn ws_segment_batch(ctx: *mut ws_ctx, cube: *const u8, n_slices: usize, h: usize, w: usize, row_stride: usize, slice_stride: usize,
                             seeds_rc: *const u64, seed_offsets: *const usize, opt: *const ws_options, out_labels: *mut u64,

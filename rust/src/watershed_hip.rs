@@ -338,6 +338,56 @@ fn run_to_list(merging: bool, opt: &Options, input: nd::ArrayView2<u8>, seeds: &
         .collect()
 }
 
+/// One slice's lists in sparse form: (level, uncoloured pixels, [(colour, area)]) per level.
+pub type SparseLists = Vec<(u8, usize, Vec<(usize, usize)>)>;
+
+/// transform_to_list of every slice of a cube, with each slice's own local minima as its seeds: one call of
+/// `ws_transform_to_list_batch`.  Returns the slices' lists and their seed counts.
+fn run_to_list_cube(merging: bool, opt: &Options, cube: nd::ArrayView3<u8>) -> (Vec<SparseLists>, Vec<usize>) {
+    let (n, h, w) = cube.dim();
+    let std_cube = cube.as_standard_layout();      // contiguous (slice, row, column); a copy only if the view is strided
+    let o = opt.ffi();
+    let levels = opt.max_water_level as usize + 1;
+    let mut offsets = vec![0u64; n * levels + 1];
+    let mut uncoloured = vec![0u64; n * levels];
+    let mut n_seeds = vec![0usize; n];
+    // one record per pixel of the cube (a random field needs ~10, a smooth map far fewer); a guess that is too small costs a
+    // second transform (WS_ERR_CAPACITY reports the exact count), never a wrong answer
+    let mut cap = (n * h * w + 1024).min(1 << 28);
+    let mut lakes: Vec<hip_ffi::ws_lake>;
+    let mut total = 0usize;
+    let mut failed = 0usize;
+    loop {
+        lakes = vec![hip_ffi::ws_lake::default(); cap];
+        let rc = shim::with_ctx(|ctx| unsafe {
+            let rc = hip_ffi::ws_transform_to_list_batch(ctx, merging as c_int, std_cube.as_ptr(), n, h, w, w, h * w, std::ptr::null(),
+                                                         std::ptr::null(), &o, lakes.as_mut_ptr(), cap, &mut total, offsets.as_mut_ptr(),
+                                                         uncoloured.as_mut_ptr(), n_seeds.as_mut_ptr(), &mut failed);
+            if rc != hip_ffi::WS_ERR_CAPACITY {
+                shim::check(ctx, rc, "ws_transform_to_list_batch");
+            }
+            rc
+        });
+        if rc == hip_ffi::WS_ERR_CAPACITY && total > cap {
+            cap = total;
+            continue;
+        }
+        break;
+    }
+    let lists = (0..n)
+        .map(|k| {
+            (0..levels)
+                .map(|l| {
+                    let b = k * levels + l;
+                    let recs = lakes[offsets[b] as usize..offsets[b + 1] as usize].iter().map(|r| (r.colour as usize, r.area as usize)).collect();
+                    (l as u8, uncoloured[b] as usize, recs)
+                })
+                .collect()
+        })
+        .collect();
+    (lists, n_seeds)
+}
+
 fn history_hook(ctx: HookCtx) -> (u8, nd::Array2<usize>) {
     (ctx.water_level, ctx.colours.to_owned()) // lib.rs:1545, 1831
 }
@@ -411,6 +461,13 @@ impl<T> SegmentingWatershed<T> {
         });
         out
     }
+
+    /// Not in the reference: `transform_to_list(cube[k], &find_local_minima(cube[k]))` for every slice of a cube, as one call
+    /// (`ws_transform_to_list_batch`), in sparse form -- per slice and level the uncoloured count and the (colour, area) of every
+    /// lake with pixels, in no particular order -- and the number of minima of every slice.
+    pub fn transform_to_list_cube(&self, cube: nd::ArrayView3<u8>) -> (Vec<SparseLists>, Vec<usize>) {
+        run_to_list_cube(false, &self.opt, cube)
+    }
 }
 
 impl<T> Watershed<T> for MergingWatershed<T> {
@@ -437,6 +494,11 @@ impl<T> Watershed<T> for MergingWatershed<T> {
 }
 
 impl<T> MergingWatershed<T> {
+    /// Not in the reference: the merging `transform_to_list(cube[k], &find_local_minima(cube[k]))` of every slice of a cube as one
+    /// call; as `SegmentingWatershed::transform_to_list_cube`.
+    pub fn transform_to_list_cube(&self, cube: nd::ArrayView3<u8>) -> (Vec<SparseLists>, Vec<usize>) {
+        run_to_list_cube(true, &self.opt, cube)
+    }
     /// Not in the reference: the merged label plane after the last level (canonical ids: the smallest seed colour of
     /// every lake).  The reference's own `transform` is the stub above.
     pub fn transform_final(&self, input: nd::ArrayView2<u8>, seeds: &[(usize, usize)]) -> nd::Array2<usize> {

@@ -116,6 +116,11 @@ SIGNATURES = {
     "ws_transform_to_list_device": (ctypes.c_int, [vp, ctypes.c_int, vp, sz, sz, sz, vp, sz, ctypes.POINTER(Options), vp, sz,
                                                    szp, vp, vp]),
     "ws_lists_from_arrival_device": (ctypes.c_int, [vp, ctypes.c_int, vp, vp, sz, sz, sz, ctypes.POINTER(Options), vp, sz, szp, vp, vp]),
+    "ws_transform_to_list_batch_device": (ctypes.c_int, [vp, ctypes.c_int, vp, sz, sz, sz, sz, sz, vp, szp, ctypes.POINTER(Options),
+                                                         vp, sz, szp, vp, vp, szp]),
+    "ws_transform_to_list_batch": (ctypes.c_int, [vp, ctypes.c_int, vp, sz, sz, sz, sz, sz, vp, szp, ctypes.POINTER(Options),
+                                                  vp, sz, szp, vp, vp, szp, szp]),
+    "ws_merge_batch_device": (ctypes.c_int, [vp, vp, sz, sz, sz, sz, sz, vp, szp, ctypes.POINTER(Options), vp, szp]),
     "ws_merge_transform_stub": (ctypes.c_int, [sz, sz, vp]),
     "ws_segment_batch": (ctypes.c_int, [vp, vp, sz, sz, sz, sz, sz, vp, szp, ctypes.POINTER(Options), vp, szp, szp]),
     "ws_segment_batch_host": (ctypes.c_int, [vp, vp, sz, sz, sz, sz, sz, vp, szp, ctypes.POINTER(Options), vp, szp, szp]),

@@ -365,6 +365,59 @@ class _Transform(WatershedUtils):
         return [(lvl, int(unc[lvl]), lakes[off[lvl]:off[lvl + 1], 0], lakes[off[lvl]:off[lvl + 1], 1]) for lvl in range(levels)]
 
 
+    def transform_to_list_cube(self, cube, seeds=None):
+        """transform_to_list_sparse of every slice cube[k] of a 3-D u8 array with seeds[k] -- or, with seeds None, the slice's own
+        find_local_minima -- in ONE call of the library (ws_transform_to_list_batch: slices that stack run one set of per-level
+        launches for the whole cube).  Returns, per slice, [(level, uncoloured, colours[], areas[])] in the slice's own colours
+        (and, with seeds None, the number of minima of every slice).  Not a method of the reference."""
+        c = np.asarray(cube)
+        if c.ndim != 3:
+            raise ValueError("cube must be 3-D: (slices, rows, columns)")
+        c = np.ascontiguousarray(c, dtype=np.uint8)
+        n, h, w = c.shape
+        if seeds is None:
+            flat, offs = None, None
+        else:
+            if len(seeds) != n:
+                raise ValueError("one seed list per slice")
+            lists = [np.asarray(s, dtype=np.uint64).reshape(-1, 2) for s in seeds]
+            offs = np.zeros(n + 1, dtype=np.uintp)
+            offs[1:] = np.cumsum([len(l) for l in lists])
+            flat = np.ascontiguousarray(np.concatenate(lists, axis=0) if lists else np.zeros((0, 2), dtype=np.uint64))
+            if flat.shape[0] == 0:
+                flat = np.zeros((1, 2), dtype=np.uint64)
+        ctx = self._ctx()
+        levels = self.max_water_level + 1
+        offsets = np.zeros(n * levels + 1, dtype=np.uint64)
+        unc = np.zeros(max(n * levels, 1), dtype=np.uint64)
+        counts = np.zeros(max(n, 1), dtype=np.uintp)
+        total = ctypes.c_size_t(0)
+        failed = ctypes.c_size_t(0)
+        # one record per pixel of the cube (a random field needs ~10, a smooth map far fewer); a too small guess costs a second
+        # transform, not a wrong answer
+        cap = min(n * h * w + 1024, 1 << 28)
+        while True:
+            lakes = np.empty((cap, 2), dtype=np.uint64)
+            rc = _ffi.lib().ws_transform_to_list_batch(ctx.handle, int(self._merging), c.ctypes.data, n, h, w, w, h * w,
+                                                       flat.ctypes.data if flat is not None else None,
+                                                       offs.ctypes.data_as(_ffi.szp) if offs is not None else None,
+                                                       ctypes.byref(self._opt), lakes.ctypes.data, cap, ctypes.byref(total),
+                                                       offsets.ctypes.data, unc.ctypes.data, counts.ctypes.data_as(_ffi.szp),
+                                                       ctypes.byref(failed))
+            if rc == _ffi.WS_ERR_CAPACITY and total.value > cap:
+                cap = total.value
+                continue
+            ctx.check(rc)
+            break
+        off = offsets.astype(np.int64)
+        out = []
+        for k in range(n):      # views into one record array
+            b = k * levels
+            out.append([(lvl, int(unc[b + lvl]), lakes[off[b + lvl]:off[b + lvl + 1], 0], lakes[off[b + lvl]:off[b + lvl + 1], 1])
+                        for lvl in range(levels)])
+        return out if seeds is not None else (out, counts[:n].astype(np.int64))
+
+
 class SegmentingWatershed(_Transform):
     """lib.rs:1609-1849"""
     _merging = False

@@ -48,6 +48,9 @@ struct ws_ctx {
 
   wsapi::DevBuf img, keys, labels, labels2, stamps, flags, seeds, seeds64, out64, counts, aux, seed_stack, min_counts, min_nibbles;
   wsapi::DevBuf uf_parent, uf_size, uf_hooked, uf_death, uf_sd, alive, px_items, edge_items, mflags, lakes, refs, seed_tab, tile_list;
+  // ws_transform_to_list_batch(_device) / ws_merge_batch_device: the stack's labels, its lake records before the split into
+  // slices (16 B a record), the split's bins, the host form's cube and seeds
+  wsapi::DevBuf stack_labels, stack_records, stack_bins, batch_cube, batch_seeds;
   uint32_t *pinned = nullptr;      // FLAG_WORDS words of pinned host memory: the host's mirror of the flag block
   uint32_t *pinned_dev = nullptr;  // the same words as the device sees them (nullptr: not mapped, copies only)
   hipEvent_t ring_ev[wsk::COUNTER_RING]{};   // flag slot copied to the host
@@ -109,9 +112,10 @@ struct ws_ctx {
     size_t n_colours = 0, n = 0, cap = 0;
     const void *records = nullptr;      // the buffer the lake records go to (the context's, or a caller's device buffer)
     const void *keys = nullptr, *seg = nullptr;      // the planes the buckets are built from (the context's, or a caller's: the arrival form)
+    size_t slice_h = 0;                              // a stack of slices (ws_transform_to_list_batch_device): rows of one slice
     uint64_t generation = 0;
     bool operator==(const ListKey &o) const {
-      return generation == o.generation && generation != 0 && merging == o.merging && want_list == o.want_list && levels == o.levels &&
+      return generation == o.generation && generation != 0 && merging == o.merging && want_list == o.want_list && levels == o.levels && slice_h == o.slice_h &&
              n_colours == o.n_colours && n == o.n && cap == o.cap && records == o.records && keys == o.keys && seg == o.seg;
     }
   };
@@ -277,6 +281,10 @@ int run_fused_form(ws_ctx *c, const uint8_t *d_img, size_t stride, int ph, int p
                    int slice_h = 0, const uint32_t *slice_first = nullptr, bool padded = false, MinimaSeeds *minima = nullptr);
 int run_fused(ws_ctx *c, const uint8_t *d_img, size_t stride, int ph, int pw, uint32_t max_level,
               const uint32_t *d_seeds, size_t n_seeds, uint32_t *d_labels, bool padded = false);
+int flood_stack(ws_ctx *c, const uint8_t *d_src, size_t stride, size_t g, size_t ph, size_t pw, const uint32_t *d_seeds_rc,
+                const uint32_t *first, const ws_options *opt, uint32_t *d_labels, bool *mispredicted);
+// the slices' colour bases that flood_stack left on the device behind the stacked seeds
+inline const uint32_t *stacked_first(const ws_ctx *c, size_t n_seeds) { return (const uint32_t *)c->seed_stack.p + 2 * n_seeds; }
 
 inline int pick_engine(const ws_options *opt) {
   return opt->engine == WS_ENGINE_SWEEP ? WS_ENGINE_SWEEP : WS_ENGINE_FUSED;

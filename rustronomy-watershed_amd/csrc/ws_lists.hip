@@ -24,13 +24,14 @@ constexpr uint32_t LIST_GROUP = 16;                       // levels per host cop
 // down -- per pixel; a random field is close to that).  A context whose buffers already hold the worst case reads
 // nothing back; otherwise the two totals (16 bytes) are read once and the buffers sized by them, so that a sparse or
 // partly flooded plane near the 2^32-pixel limit does not ask for 80 GB it will not use.
-int build_buckets(ws_ctx *c, const uint32_t *keys, const uint32_t *seg_labels, int ph, int pw) {
+// slice_base (nullable): the plane is a stack of slices of slice_h rows (level_hist)
+int build_buckets(ws_ctx *c, const uint32_t *keys, const uint32_t *seg_labels, int ph, int pw, int slice_h = 0, const uint32_t *slice_base = nullptr) {
   int rc;
   const size_t n = (size_t)ph * pw;
   if ((rc = ensure(c, c->mflags, MF_WORDS * sizeof(uint64_t)))) return rc;
   u64c *mf = (u64c *)c->mflags.p;
   HIP_TRY(c, hipMemsetAsync(mf, 0, MF_WORDS * sizeof(uint64_t), c->stream));
-  HIP_TRY(c, level_hist(c->stream, keys, seg_labels, ph, pw, mf + MF_HIST_PX, mf + MF_HIST_ED));
+  HIP_TRY(c, level_hist(c->stream, keys, seg_labels, ph, pw, mf + MF_HIST_PX, mf + MF_HIST_ED, slice_h, slice_base));
   HIP_TRY(c, level_offsets(c->stream, mf + MF_HIST_PX, mf + MF_HIST_ED, mf + MF_OFF_PX, mf + MF_OFF_ED, mf + MF_CUR_PX, mf + MF_CUR_ED));
   size_t need_px = (n ? n : 1) * sizeof(uint32_t), need_ed = (n ? 2 * n : 1) * sizeof(uint2);
   if (c->px_items.cap < need_px || c->edge_items.cap < need_ed) {
@@ -44,7 +45,7 @@ int build_buckets(ws_ctx *c, const uint32_t *keys, const uint32_t *seg_labels, i
   if ((rc = ensure(c, c->px_items, need_px))) return rc;
   if ((rc = ensure(c, c->edge_items, need_ed))) return rc;
   HIP_TRY(c, level_scatter(c->stream, keys, seg_labels, ph, pw, mf + MF_CUR_PX, mf + MF_CUR_ED,
-                           (uint32_t *)c->px_items.p, (uint2 *)c->edge_items.p));
+                           (uint32_t *)c->px_items.p, (uint2 *)c->edge_items.p, slice_h, slice_base));
   return WS_OK;
 }
 
@@ -121,7 +122,32 @@ struct DeviceLists {
   // the arrival form (ws_lists_from_arrival_device): the segmenting transform has been run elsewhere -- its stamps and labels
   // are all the per-level paths read; no image, no seed list, h x w is the plane as it stands
   const uint32_t *d_keys = nullptr, *d_seg = nullptr;
+  // ... of a stack of slices of slice_h rows whose labels restart at 1 in every slice: colour c of slice k is c + d_slice_base[k]
+  // (ws_transform_to_list_batch_device)
+  int slice_h = 0;
+  const uint32_t *d_slice_base = nullptr;
 };
+
+// Records [from, end) of the device array d_rec into the host's `lakes`, on stream `on` (returns with the copy complete when the
+// chunked road is taken; otherwise queued).  A piece of two million records and more (2048^2 planes on) crosses the bus as u32 --
+// a colour and an area of a plane below 2^31 pixels fit -- and is widened into the caller's records by the host's threads
+// (ws_hostcopy.hip; pieces of at most n records: the narrowed words borrow the u64 label buffer, n x 8 bytes).
+// A piece that is too short for the chunked road must NOT go down it: labels_to_host_u64's other path widens into the very
+// buffer the narrowed words sit in (and may reallocate it).  Such pieces are copied as they are.
+int records_to_host(ws_ctx *c, const ws_lake *d_rec, ws_lake *lakes, size_t from, size_t end, size_t n, hipStream_t on) {
+  const bool may_narrow = n < 0x80000000ull && c->out64.p && c->out64.cap >= n * sizeof(uint64_t);
+  while (from < end) {
+    const size_t piece = std::min<size_t>(end - from, n);
+    if (may_narrow && 2 * piece >= ((size_t)1 << 22) && host_copy_in_chunks(c, 2 * piece)) {      // (from 2 M records a piece: below, starting the threads costs what they save -- 1024^2: 4.5 against 4.1 ms)
+      HIP_TRY(c, narrow_words(on, (const uint64_t *)(d_rec + from), (uint32_t *)c->out64.p, 2 * piece));
+      if (int rc = labels_to_host_u64(c, (const uint32_t *)c->out64.p, (uint64_t *)(lakes + from), 2 * piece, on)) return rc;
+    } else {
+      HIP_TRY(c, hipMemcpyAsync(lakes + from, d_rec + from, piece * sizeof(ws_lake), hipMemcpyDeviceToHost, on));
+    }
+    from += piece;
+  }
+  return WS_OK;
+}
 int merge_host(ws_ctx *c, bool merging, const uint8_t *img, size_t h, size_t w, size_t stride, const uint64_t *seeds_rc,
                size_t n_seeds, const ws_options *opt, ws_level_cb cb, void *user, uint64_t *out_labels,
                ws_lake *lakes, size_t cap, size_t *n_lakes, uint64_t *offsets, uint64_t *uncoloured, const DeviceLists *dev = nullptr) {
@@ -168,7 +194,7 @@ int merge_host(ws_ctx *c, bool merging, const uint8_t *img, size_t h, size_t w, 
   }
   if (want_list && !dev && (rc = ensure(c, c->lakes, (cap ? cap : 1) * 2 * sizeof(uint64_t)))) return rc;
   uint64_t *d_records = dev ? (uint64_t *)dev->d_lakes : (uint64_t *)c->lakes.p;      // (colour, area) pairs
-  if ((rc = build_buckets(c, keys, seg, (int)ph, (int)pw))) return rc;
+  if ((rc = build_buckets(c, keys, seg, (int)ph, (int)pw, dev ? dev->slice_h : 0, dev ? dev->d_slice_base : nullptr))) return rc;
   uint32_t *parent = (uint32_t *)c->uf_parent.p;
   u64c *mf = (u64c *)c->mflags.p;
   HIP_TRY(c, uf_init(c->stream, parent, (uint32_t *)c->uf_size.p, n_seeds + 1));
@@ -215,6 +241,7 @@ int merge_host(ws_ctx *c, bool merging, const uint8_t *img, size_t h, size_t w, 
   key.merging = merging; key.want_list = want_list; key.levels = levels; key.n_colours = n_seeds + 1; key.n = n; key.cap = cap;
   key.records = d_records;
   key.keys = keys; key.seg = seg;
+  key.slice_h = dev && dev->d_slice_base ? (size_t)dev->slice_h : 0;
   key.generation = c->buffer_generation;
   const bool graph_able = !cb && c->stream != nullptr && !c->graph_unusable && !c->profiling && n != 0;
   bool use_graphs = graph_able && key == c->list_seen_key;
@@ -281,23 +308,9 @@ int merge_host(ws_ctx *c, bool merging, const uint8_t *img, size_t h, size_t w, 
       HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
       for (uint32_t l = g0; l < g1; ++l) offsets[l + 1] += offsets[l];      // counts -> offsets
       const size_t end = std::min<size_t>(offsets[g1], cap);
-      if (!dev && end > copied) {
-        // A group of two million records and more (2048^2 planes on) crosses the bus as u32 -- a colour and an area of a plane below
-        // 2^31 pixels fit -- and is widened into the caller's records by the host's threads while later levels are computed
-        // (ws_hostcopy.hip; pieces of at most n records: the narrowed words borrow the u64 label buffer, n x 8 bytes).
-        // A piece that is too short for the chunked road must NOT go down it: labels_to_host_u64's other path widens into the very
-        // buffer the narrowed words sit in (and may reallocate it).  Such pieces are copied as they are.
-        const bool may_narrow = n < 0x80000000ull && c->out64.p && c->out64.cap >= n * sizeof(uint64_t);
-        while (copied < end) {
-          const size_t piece = std::min<size_t>(end - copied, n);
-          if (may_narrow && 2 * piece >= ((size_t)1 << 22) && host_copy_in_chunks(c, 2 * piece)) {      // (from 2 M records a piece: below, starting the threads costs what they save -- 1024^2: 4.5 against 4.1 ms)
-            HIP_TRY(c, narrow_words(c->copy_stream, (const uint64_t *)((const ws_lake *)c->lakes.p + copied), (uint32_t *)c->out64.p, 2 * piece));
-            if ((rc = labels_to_host_u64(c, (const uint32_t *)c->out64.p, (uint64_t *)(lakes + copied), 2 * piece, c->copy_stream))) return rc;
-          } else {
-            HIP_TRY(c, hipMemcpyAsync(lakes + copied, (const ws_lake *)c->lakes.p + copied, piece * sizeof(ws_lake), hipMemcpyDeviceToHost, c->copy_stream));
-          }
-          copied += piece;
-        }
+      if (!dev && end > copied) {      // (the records of this group travel while later levels are computed)
+        if ((rc = records_to_host(c, (const ws_lake *)c->lakes.p, lakes, copied, end, n, c->copy_stream))) return rc;
+        copied = end;
       }
     }
     HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
@@ -322,6 +335,187 @@ int merge_host(ws_ctx *c, bool merging, const uint8_t *img, size_t h, size_t w, 
   if (merging)
     for (uint32_t l = 0; l < levels; ++l) c->stats.merge_levels += bounds[NLEVELS + 1 + l + 1] > bounds[NLEVELS + 1 + l] ? 1u : 0u;
   if (want_list && *n_lakes > cap) return fail(c, WS_ERR_CAPACITY, "lake buffer too small");
+  return WS_OK;
+}
+
+void stats_add(ws_stats &a, const ws_stats &b) {
+  a.relax_passes += b.relax_passes; a.resolve_passes += b.resolve_passes; a.sweep_steps += b.sweep_steps;
+  a.merge_levels = std::max(a.merge_levels, b.merge_levels);
+  a.tiles_run_relax += b.tiles_run_relax; a.tiles_run_resolve += b.tiles_run_resolve;
+  a.ms_relax += b.ms_relax; a.ms_resolve += b.ms_resolve; a.ms_sweep += b.ms_sweep; a.ms_other += b.ms_other; a.ms_total += b.ms_total;
+  a.launches_relax += b.launches_relax; a.launches_resolve += b.launches_resolve; a.launches_sweep += b.launches_sweep;
+  a.relax_tile_iterations += b.relax_tile_iterations; a.graph_launches += b.graph_launches;
+}
+
+// The stack of ws_segment_batch_device (same conditions: see the header) for a batch whose every group of slices has a seed;
+// groups of batch_max_px / plane slices.  false: the slice-by-slice loop takes the batch.
+bool stackable(ws_ctx *c, size_t n_slices, size_t h, size_t w, size_t stride, size_t ph, size_t pw, const size_t *seed_offsets,
+               const ws_options *opt, size_t *per_group) {
+  static const bool off = tuning_env("WS_NO_BATCH_STACK") != nullptr || tuning_env("WS_NO_SEED_TABLES") != nullptr;      // A/B knobs for tools/
+  const size_t plane = ph * pw;
+  if (off || n_slices < 2 || pick_engine(opt) != WS_ENGINE_FUSED || !c->expect_sorted || (pw & 3) != 0 || plane == 0 ||
+      plane % 128 != 0 || plane >= 0x40000000ull || stride != w || h * w == 0)
+    return false;
+  if (seed_offsets[n_slices] - seed_offsets[0] >= 0xFFFFFFFFull) return false;
+  *per_group = std::max<size_t>(1, c->batch_max_px / plane);
+  for (size_t k0 = 0; k0 < n_slices; k0 += *per_group)      // (a flood needs a seed)
+    if (seed_offsets[std::min(k0 + *per_group, n_slices)] == seed_offsets[k0]) return false;
+  return true;
+}
+
+// ws_transform_to_list_batch_device on a stack: per group of slices, the flood of the stack (flood_stack), the per-level driver
+// over the stack's numbering of colours (merge_host, arrival form: the bucketing adds the slice's base to every colour and pairs
+// no pixels across a slice border), then the split of the group's records (level-major, stack colours) into the caller's
+// slice-major layout in the slices' own colours.  *done = false: nothing was decided, the loop takes the batch.
+int lists_batch_stacked(ws_ctx *c, bool merging, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w, size_t stride,
+                        const uint32_t *d_seeds_rc, const size_t *seed_offsets, const ws_options *opt, ws_lake *d_lakes, size_t cap,
+                        size_t *n_lakes, uint64_t *offsets, uint64_t *uncoloured, bool *done) {
+  *done = false;
+  size_t ph, pw, per_group = 0;
+  int rc = check_plane(c, h, w, stride, opt, &ph, &pw);
+  if (rc) return rc;
+  if (!stackable(c, n_slices, h, w, stride, ph, pw, seed_offsets, opt, &per_group)) return WS_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t plane = ph * pw;
+  const uint32_t levels = (uint32_t)opt->max_water_level + 1;
+  ws_stats acc{};
+  size_t need = 0;      // records of the groups so far; while need <= cap they are in d_lakes[0 .. need)
+  std::vector<uint32_t> first;
+  std::vector<uint64_t> goff(levels + 1), gunc(levels);
+  std::vector<u64c> bins;
+  for (size_t k0 = 0; k0 < n_slices; k0 += per_group) {
+    const size_t g = std::min(per_group, n_slices - k0);
+    const size_t s0 = seed_offsets[k0], ns = seed_offsets[k0 + g] - s0;
+    const size_t gcap = need <= cap ? cap - need : 0, n_bins = g * levels;
+    if ((rc = ensure(c, c->stack_labels, g * plane * sizeof(uint32_t)))) return rc;
+    if ((rc = ensure(c, c->stack_records, std::max<size_t>(gcap, 1) * sizeof(ws_lake)))) return rc;
+    if ((rc = ensure(c, c->stack_bins, (levels + 1 + n_bins + g * NLEVELS) * sizeof(u64c)))) return rc;
+    first.resize(g + 1);
+    for (size_t k = 0; k <= g; ++k) first[k] = (uint32_t)(seed_offsets[k0 + k] - s0);
+    stats_begin(c);
+    bool mispredicted = false;
+    uint32_t *labels = (uint32_t *)c->stack_labels.p;
+    rc = flood_stack(c, d_cube + k0 * h * stride, stride, g, ph, pw, d_seeds_rc + 2 * s0, first.data(), opt, labels, &mispredicted);
+    c->have_keys = false;      // the stamps are those of a stack, not of an image
+    if (rc != WS_OK || mispredicted) {      // the loop repeats the work and names the slice
+      (void)stats_end(c);
+      c->err.clear();
+      return WS_OK;
+    }
+    if ((rc = stats_end(c))) return rc;
+    stats_add(acc, c->stats);
+    const uint32_t *d_base = stacked_first(c, ns);
+    u64c *d_off = (u64c *)c->stack_bins.p, *d_bins = d_off + levels + 1, *d_hist = d_bins + n_bins;
+    HIP_TRY(c, hipMemsetAsync(d_bins, 0, (n_bins + g * NLEVELS) * sizeof(u64c), c->stream));
+    HIP_TRY(c, slice_arrivals(c->stream, (const uint32_t *)c->keys.p, plane, g, d_hist));
+    DeviceLists dev{nullptr, nullptr, (ws_lake *)c->stack_records.p};
+    dev.d_keys = (const uint32_t *)c->keys.p;
+    dev.d_seg = labels;
+    dev.slice_h = (int)ph;
+    dev.d_slice_base = d_base;
+    size_t got = 0;
+    rc = merge_host(c, merging, nullptr, g * ph, pw, pw, nullptr, ns, opt, nullptr, nullptr, nullptr, nullptr, gcap, &got, goff.data(),
+                    gunc.data(), &dev);
+    if (rc != WS_OK && rc != WS_ERR_CAPACITY) return rc;
+    stats_add(acc, c->stats);
+    need += got;
+    if (rc == WS_ERR_CAPACITY || need > cap) {      // counted, not written: the caller learns how many records to make room for
+      c->err.clear();
+      continue;
+    }
+    // counts per (slice, level) -> the bins' first records in the caller's layout, which the scatter takes as its cursors.
+    // A bin holds at most one record per colour of its slice; segmenting lists that have ALL of them (every seed owns its pixel
+    // from level 0 on: the usual case) are known without a pass over the records.
+    HIP_TRY(c, hipMemcpyAsync(d_off, goff.data(), (levels + 1) * sizeof(u64c), hipMemcpyHostToDevice, c->stream));
+    const bool full = !merging && got == (size_t)levels * ns;
+    if (!full)
+      HIP_TRY(c, split_records(c->stream, false, (const uint64_t *)c->stack_records.p, got, d_off, levels, d_base, (uint32_t)g, d_bins, nullptr));
+    bins.resize(n_bins + g * NLEVELS);
+    HIP_TRY(c, hipMemcpyAsync(bins.data(), d_bins, bins.size() * sizeof(u64c), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (full)
+      for (size_t k = 0; k < g; ++k)
+        for (uint32_t l = 0; l < levels; ++l) bins[k * levels + l] = first[k + 1] - first[k];
+    u64c at = need - got;
+    for (size_t b = 0; b < n_bins; ++b) {
+      const u64c count = bins[b];
+      offsets[k0 * levels + b] = at;
+      bins[b] = at;
+      at += count;
+    }
+    if (at != need) return fail(c, WS_ERR_HIP, "internal: the split of the stack's records lost some");
+    for (size_t k = 0; k < g; ++k) {      // index 0 of lib.rs:630's vector: the slice's pixels not yet coloured
+      u64c arrived = 0;
+      for (uint32_t l = 0; l < levels; ++l) {
+        arrived += bins[n_bins + k * NLEVELS + l];
+        uncoloured[(k0 + k) * levels + l] = plane - arrived;
+      }
+    }
+    HIP_TRY(c, hipMemcpyAsync(d_bins, bins.data(), n_bins * sizeof(u64c), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, split_records(c->stream, true, (const uint64_t *)c->stack_records.p, got, d_off, levels, d_base, (uint32_t)g, d_bins,
+                             (uint64_t *)d_lakes));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));      // `bins` and `goff` are the next group's
+  }
+  offsets[n_slices * levels] = need;
+  *n_lakes = need;
+  c->stats = acc;
+  *done = true;
+  if (need > cap) return fail(c, WS_ERR_CAPACITY, "lake buffer too small");
+  return WS_OK;
+}
+
+// ws_merge_batch_device on a stack: the flood of each group of slices into the caller's labels, then the unions of the final
+// level over the stack's numbering of colours and a relabel back to every slice's own (merge_stack).
+int merge_batch_stacked(ws_ctx *c, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w, size_t stride, const uint32_t *d_seeds_rc,
+                        const size_t *seed_offsets, const ws_options *opt, uint32_t *d_labels, bool *done) {
+  *done = false;
+  size_t ph, pw, per_group = 0;
+  int rc = check_plane(c, h, w, stride, opt, &ph, &pw);
+  if (rc) return rc;
+  if (!stackable(c, n_slices, h, w, stride, ph, pw, seed_offsets, opt, &per_group)) return WS_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t plane = ph * pw;
+  ws_stats acc{};
+  std::vector<uint32_t> first;
+  for (size_t k0 = 0; k0 < n_slices; k0 += per_group) {
+    const size_t g = std::min(per_group, n_slices - k0);
+    const size_t s0 = seed_offsets[k0], ns = seed_offsets[k0 + g] - s0;
+    if ((rc = ensure_uf(c, ns + 1))) return rc;
+    first.resize(g + 1);
+    for (size_t k = 0; k <= g; ++k) first[k] = (uint32_t)(seed_offsets[k0 + k] - s0);
+    stats_begin(c);
+    bool mispredicted = false;
+    uint32_t *labels = d_labels + k0 * plane;
+    rc = flood_stack(c, d_cube + k0 * h * stride, stride, g, ph, pw, d_seeds_rc + 2 * s0, first.data(), opt, labels, &mispredicted);
+    c->have_keys = false;
+    if (rc != WS_OK || mispredicted) {
+      (void)stats_end(c);
+      c->err.clear();
+      return WS_OK;
+    }
+    HIP_TRY(c, uf_init(c->stream, (uint32_t *)c->uf_parent.p, (uint32_t *)c->uf_size.p, ns + 1));
+    {
+      Span sp(c, KC_OTHER);
+      HIP_TRY(c, merge_stack(c->stream, labels, (int)ph, (int)pw, g, stacked_first(c, ns), (uint32_t *)c->uf_parent.p, ns + 1));
+    }
+    if ((rc = stats_end(c))) return rc;
+    stats_add(acc, c->stats);
+  }
+  c->stats = acc;
+  c->stats.merge_levels = 1;
+  *done = true;
+  return WS_OK;
+}
+
+// the checks the batch entry points share (as ws_segment_batch_device's)
+int check_batch(ws_ctx *c, size_t n_slices, size_t h, size_t row_stride, size_t slice_stride, const size_t *seed_offsets,
+                const ws_options *opt) {
+  if (n_slices && !seed_offsets) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  if (!opt) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  if (int v = ws_options_validate(opt)) return fail(c, v, ws_strerror(v));
+  if (n_slices > 1 && slice_stride < h * row_stride) return fail(c, WS_ERR_BAD_ARG, "slice_stride < h * row_stride");
+  for (size_t k = 0; k < n_slices; ++k)
+    if (seed_offsets[k + 1] < seed_offsets[k]) return fail(c, WS_ERR_BAD_ARG, "seed_offsets must not decrease");
   return WS_OK;
 }
 
@@ -466,6 +660,129 @@ int ws_transform_to_list(ws_ctx *c, int merging, const uint8_t *img, size_t h, s
   if (!n_lakes || !offsets || !uncoloured || (!lakes && cap)) return fail(c, WS_ERR_BAD_ARG, "null output pointer");
   return merge_host(c, merging != 0, img, h, w, stride, seeds_rc, n_seeds, opt, nullptr, nullptr, nullptr, lakes, cap, n_lakes,
                     offsets, uncoloured);
+}
+
+int ws_transform_to_list_batch_device(ws_ctx *c, int merging, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w,
+                                      size_t row_stride, size_t slice_stride, const uint32_t *d_seeds_rc, const size_t *seed_offsets,
+                                      const ws_options *opt, ws_lake *d_lakes, size_t cap, size_t *n_lakes, uint64_t *offsets,
+                                      uint64_t *uncoloured, size_t *failed_slice) {
+  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
+  if (!c) return WS_ERR_BAD_ARG;
+  if (failed_slice) *failed_slice = 0;
+  if (!n_lakes || !offsets || !uncoloured || (!d_lakes && cap)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  if (int rc = check_batch(c, n_slices, h, row_stride, slice_stride, seed_offsets, opt)) return rc;
+  if (n_slices && ((!d_cube && h * w) || (!d_seeds_rc && seed_offsets[n_slices] > seed_offsets[0]))) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  const size_t levels = (size_t)opt->max_water_level + 1;
+  if (n_slices > 1 && slice_stride == h * row_stride && d_cube && d_seeds_rc) {
+    bool done = false;
+    const int rc = lists_batch_stacked(c, merging != 0, d_cube, n_slices, h, w, row_stride, d_seeds_rc, seed_offsets, opt, d_lakes, cap,
+                                       n_lakes, offsets, uncoloured, &done);
+    if (done || (rc != WS_OK && rc != WS_ERR_CAPACITY)) return rc;
+  }
+  // the loop: one ws_transform_to_list_device per slice, its records behind the previous slices'
+  std::vector<uint64_t> off(levels + 1);
+  ws_stats acc{};
+  size_t need = 0;
+  for (size_t k = 0; k < n_slices; ++k) {
+    const size_t ns = seed_offsets[k + 1] - seed_offsets[k];
+    const bool room = need <= cap;
+    size_t got = 0;
+    const int rc = ws_transform_to_list_device(c, merging, d_cube + k * slice_stride, h, w, row_stride, ns ? d_seeds_rc + 2 * seed_offsets[k] : nullptr,
+                                               ns, opt, room ? d_lakes + need : nullptr, room ? cap - need : 0, &got, off.data(),
+                                               uncoloured + k * levels);
+    if (rc != WS_OK && rc != WS_ERR_CAPACITY) { if (failed_slice) *failed_slice = k; return rc; }
+    stats_add(acc, c->stats);
+    for (size_t l = 0; l < levels; ++l) offsets[k * levels + l] = need + off[l];
+    need += got;
+  }
+  offsets[n_slices * levels] = need;
+  *n_lakes = need;
+  c->stats = acc;
+  c->have_keys = false;      // as after a stacked batch: the stamps are no single slice's business
+  if (need > cap) return fail(c, WS_ERR_CAPACITY, "lake buffer too small");
+  c->err.clear();
+  return WS_OK;
+}
+
+int ws_transform_to_list_batch(ws_ctx *c, int merging, const uint8_t *cube, size_t n_slices, size_t h, size_t w, size_t row_stride,
+                               size_t slice_stride, const uint64_t *seeds_rc, const size_t *seed_offsets, const ws_options *opt,
+                               ws_lake *lakes, size_t cap, size_t *n_lakes, uint64_t *offsets, uint64_t *uncoloured, size_t *n_seeds,
+                               size_t *failed_slice) {
+  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
+  if (!c) return WS_ERR_BAD_ARG;
+  if (failed_slice) *failed_slice = 0;
+  if (!n_lakes || !offsets || !uncoloured || (!lakes && cap) || (!cube && h * w && n_slices)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  if (int rc = check_batch(c, seeds_rc ? n_slices : 0, h, row_stride, slice_stride, seed_offsets, opt)) return rc;
+  size_t ph, pw;
+  int rc = check_plane(c, h, w, row_stride, opt, &ph, &pw);
+  if (rc) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t hw = h * w, plane = ph * pw;
+  // the cube as contiguous slices, the seeds as u32 pairs (the device form's inputs), then the records back as ws_transform_to_list's are
+  if ((rc = ensure(c, c->batch_cube, std::max<size_t>(n_slices * hw, 1)))) return rc;
+  uint8_t *d_cube = (uint8_t *)c->batch_cube.p;
+  if (hw)
+    for (size_t k = 0; k < n_slices; ++k)
+      HIP_TRY(c, hipMemcpy2DAsync(d_cube + k * hw, w, cube + k * slice_stride, row_stride, w, h, hipMemcpyHostToDevice, c->stream));
+  std::vector<size_t> offs(n_slices + 1, 0);
+  if (seeds_rc) {
+    const size_t s0 = seed_offsets[0], total = seed_offsets[n_slices] - s0;
+    std::vector<uint32_t> s32(2 * total);
+    for (size_t i = 0; i < 2 * total; ++i)      // (a coordinate past u32 is out of bounds either way: it stays so)
+      s32[i] = (uint32_t)std::min<uint64_t>(seeds_rc[2 * s0 + i], 0xFFFFFFFFull);
+    if ((rc = ensure(c, c->batch_seeds, std::max<size_t>(total, 1) * 2 * sizeof(uint32_t)))) return rc;
+    if (total) HIP_TRY(c, hipMemcpyAsync(c->batch_seeds.p, s32.data(), 2 * total * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (size_t k = 0; k <= n_slices; ++k) offs[k] = seed_offsets[k] - s0;
+  } else {      // every slice's own find_local_minima (lib.rs:1178-1197), its seeds behind the previous slices'
+    const size_t bound = h >= 3 && w >= 3 ? ((h - 1) / 2 + 1) * ((w - 1) / 2 + 1) : 0;
+    if ((rc = ensure(c, c->batch_seeds, std::max<size_t>(n_slices * bound, 1) * 2 * sizeof(uint32_t)))) return rc;
+    for (size_t k = 0; k < n_slices; ++k) {
+      size_t found = 0;
+      if (bound && (rc = ws_find_local_minima_device(c, d_cube + k * hw, h, w, w, (uint32_t *)c->batch_seeds.p + 2 * offs[k], bound, &found))) {
+        if (failed_slice) *failed_slice = k;
+        return rc;
+      }
+      offs[k + 1] = offs[k] + found;
+    }
+  }
+  if (n_seeds)
+    for (size_t k = 0; k < n_slices; ++k) n_seeds[k] = offs[k + 1] - offs[k];
+  if ((rc = ensure(c, c->lakes, std::max<size_t>(cap, 1) * sizeof(ws_lake)))) return rc;
+  if ((rc = ensure(c, c->out64, std::max<size_t>(plane, 1) * sizeof(uint64_t)))) return rc;      // (the narrowed records' staging)
+  rc = ws_transform_to_list_batch_device(c, merging, d_cube, n_slices, h, w, w, hw, (const uint32_t *)c->batch_seeds.p, offs.data(), opt,
+                                         (ws_lake *)c->lakes.p, cap, n_lakes, offsets, uncoloured, failed_slice);
+  if (rc) return rc;
+  if ((rc = records_to_host(c, (const ws_lake *)c->lakes.p, lakes, 0, *n_lakes, std::max<size_t>(plane, 1), c->stream))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return WS_OK;
+}
+
+int ws_merge_batch_device(ws_ctx *c, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w, size_t row_stride, size_t slice_stride,
+                          const uint32_t *d_seeds_rc, const size_t *seed_offsets, const ws_options *opt, uint32_t *d_labels,
+                          size_t *failed_slice) {
+  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
+  if (!c) return WS_ERR_BAD_ARG;
+  if (failed_slice) *failed_slice = 0;
+  if (int rc = check_batch(c, n_slices, h, row_stride, slice_stride, seed_offsets, opt)) return rc;
+  const size_t e = opt->edge_correction ? 2 : 0, plane = (h + e) * (w + e);
+  if (n_slices > 1 && slice_stride == h * row_stride && d_cube && d_seeds_rc && d_labels) {
+    bool done = false;
+    const int rc = merge_batch_stacked(c, d_cube, n_slices, h, w, row_stride, d_seeds_rc, seed_offsets, opt, d_labels, &done);
+    if (rc != WS_OK) return rc;
+    if (done) return WS_OK;
+  }
+  ws_stats acc{};
+  for (size_t k = 0; k < n_slices; ++k) {
+    const size_t ns = seed_offsets[k + 1] - seed_offsets[k];
+    const int rc = ws_merge_device(c, d_cube + k * slice_stride, h, w, row_stride, ns ? d_seeds_rc + 2 * seed_offsets[k] : nullptr, ns, opt,
+                                   d_labels + k * plane);
+    if (rc != WS_OK) { if (failed_slice) *failed_slice = k; return rc; }
+    stats_add(acc, c->stats);
+  }
+  c->stats = acc;
+  c->have_keys = false;
+  return WS_OK;
 }
 
 }  // extern "C"

@@ -87,10 +87,16 @@ __device__ __forceinline__ bool interior(int y, int x, int H, int W) {
 // four pixels and the four below them are 16-byte loads.
 typedef uint32_t u32x4_m __attribute__((ext_vector_type(4)));
 
+// STACK: H rows of slices of slice_h rows each (ws_transform_to_list_batch_device): "interior" and the pixel below are taken
+// within the row's slice -- no pair crosses a slice border -- and colours become colour + base[slice], one numbering for the stack
+template <bool STACK = false>
 __device__ __forceinline__ void gather_items(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ labels,
-                                             int H, int W, int y, int x0, PixelItems &it) {
+                                             int H, int W, int y, int x0, PixelItems &it, int slice_h = 0,
+                                             const uint32_t *__restrict__ base = nullptr) {
   uint32_t kp[5], lp[5], kd[4], ld[4];      // the row's pixels x0 .. x0 + 4 and the pixels below x0 .. x0 + 3
   const int yd = min(y + 1, H - 1);
+  const int ys = STACK ? y % slice_h : y, hs = STACK ? slice_h : H;      // row and height within the slice
+  const uint32_t add = STACK ? base[y / slice_h] : 0u;
   if ((W & 3) == 0 && x0 + 3 < W) {
     const size_t p = (size_t)y * W + x0, q = (size_t)yd * W + x0;
     const u32x4_m a = *reinterpret_cast<const u32x4_m *>(keys + p), b = *reinterpret_cast<const u32x4_m *>(labels + p);
@@ -119,16 +125,16 @@ __device__ __forceinline__ void gather_items(const uint32_t *__restrict__ keys, 
     const int x = x0 + k;
     const bool here = x < W && kp[k] != KEY_INF;            // uncoloured pixels carry no lake
     const uint32_t vp = kp[k] >> 24;
-    if (here) { it.px_lvl[k] = vp; it.px_col[k] = lp[k]; }
-    const bool ip = interior(y, x, H, W);
+    if (here) { it.px_lvl[k] = vp; it.px_col[k] = lp[k] + add; }
+    const bool ip = interior(ys, x, hs, W);
     // find_merge only sees pairs around a 3x3 window centre (lib.rs:411-434)
-    if (here && x + 1 < W && kp[k + 1] != KEY_INF && lp[k + 1] != lp[k] && (ip || interior(y, x + 1, H, W))) {
+    if (here && x + 1 < W && kp[k + 1] != KEY_INF && lp[k + 1] != lp[k] && (ip || interior(ys, x + 1, hs, W))) {
       it.er_lvl[k] = max(vp, kp[k + 1] >> 24);
-      it.er[k] = make_uint2(lp[k], lp[k + 1]);
+      it.er[k] = make_uint2(lp[k] + add, lp[k + 1] + add);
     }
-    if (here && y + 1 < H && kd[k] != KEY_INF && ld[k] != lp[k] && (ip || interior(y + 1, x, H, W))) {
+    if (here && ys + 1 < hs && kd[k] != KEY_INF && ld[k] != lp[k] && (ip || interior(ys + 1, x, hs, W))) {
       it.ed_lvl[k] = max(vp, kd[k] >> 24);
-      it.ed[k] = make_uint2(lp[k], ld[k]);
+      it.ed[k] = make_uint2(lp[k] + add, ld[k] + add);
     }
   }
 }
@@ -139,8 +145,10 @@ __device__ __forceinline__ void gather_items(const uint32_t *__restrict__ keys, 
 constexpr int SEG_RUN_MAX = 16;
 static int seg_run_for(size_t total) { return (int)std::min<size_t>(std::max<size_t>(total / 4096, 1), SEG_RUN_MAX); }      // small planes keep a workgroup per segment
 
+template <bool STACK>
 __global__ __launch_bounds__(256) void k_level_hist(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ labels,
-                                                    int H, int W, int segs, int SEG_RUN, u64c *hist_px, u64c *hist_edge) {
+                                                    int H, int W, int segs, int SEG_RUN, u64c *hist_px, u64c *hist_edge,
+                                                    int slice_h, const uint32_t *__restrict__ base) {
   __shared__ uint32_t s_px[NLEVELS], s_ed[NLEVELS];
   s_px[threadIdx.x] = 0;
   s_ed[threadIdx.x] = 0;
@@ -151,7 +159,7 @@ __global__ __launch_bounds__(256) void k_level_hist(const uint32_t *__restrict__
     if (sg >= total) break;
     const int y = (int)(sg / segs), seg = (int)(sg % segs);
     PixelItems it;
-    gather_items(keys, labels, H, W, y, seg * MSEG + threadIdx.x * 4, it);
+    gather_items<STACK>(keys, labels, H, W, y, seg * MSEG + threadIdx.x * 4, it, slice_h, base);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       if (it.px_lvl[k] != 0xFFFFFFFFu) atomicAdd(&s_px[it.px_lvl[k]], 1u);
@@ -165,12 +173,14 @@ __global__ __launch_bounds__(256) void k_level_hist(const uint32_t *__restrict__
 }
 
 hipError_t level_hist(hipStream_t s, const uint32_t *keys, const uint32_t *labels, int h, int w,
-                      u64c *hist_px, u64c *hist_edge) {
+                      u64c *hist_px, u64c *hist_edge, int slice_h, const uint32_t *slice_base) {
   if (h == 0 || w == 0) return hipSuccess;
   const int segs = (w + MSEG - 1) / MSEG;
   const size_t total = (size_t)h * segs;
   const int run = seg_run_for(total);
-  k_level_hist<<<(unsigned)((total + run - 1) / run), 256, 0, s>>>(keys, labels, h, w, segs, run, hist_px, hist_edge);
+  const unsigned blocks = (unsigned)((total + run - 1) / run);
+  if (slice_base) k_level_hist<true><<<blocks, 256, 0, s>>>(keys, labels, h, w, segs, run, hist_px, hist_edge, slice_h, slice_base);
+  else k_level_hist<false><<<blocks, 256, 0, s>>>(keys, labels, h, w, segs, run, hist_px, hist_edge, 0, nullptr);
   return hipGetLastError();
 }
 
@@ -203,9 +213,10 @@ hipError_t level_offsets(hipStream_t s, const u64c *hist_px, const u64c *hist_ed
 
 // Two walks over the workgroup's SEG_RUN segments: the first counts its items per level in LDS, then ONE reservation per
 // (workgroup, level), then the second walk gathers the items again (L2 still holds them) and writes them behind LDS cursors.
+template <bool STACK>
 __global__ __launch_bounds__(256) void k_level_scatter(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ labels,
                                                        int H, int W, int segs, int SEG_RUN, u64c *cursor_px, u64c *cursor_edge,
-                                                       uint32_t *px_items, uint2 *edge_items) {
+                                                       uint32_t *px_items, uint2 *edge_items, int slice_h, const uint32_t *__restrict__ base) {
   __shared__ uint32_t s_px[NLEVELS], s_ed[NLEVELS];
   __shared__ u64c s_bpx[NLEVELS], s_bed[NLEVELS];
   s_px[threadIdx.x] = 0;
@@ -216,7 +227,7 @@ __global__ __launch_bounds__(256) void k_level_scatter(const uint32_t *__restric
     const size_t sg = (size_t)blockIdx.x * SEG_RUN + j;
     if (sg >= total) break;
     PixelItems it;
-    gather_items(keys, labels, H, W, (int)(sg / segs), (int)(sg % segs) * MSEG + threadIdx.x * 4, it);
+    gather_items<STACK>(keys, labels, H, W, (int)(sg / segs), (int)(sg % segs) * MSEG + threadIdx.x * 4, it, slice_h, base);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       if (it.px_lvl[k] != 0xFFFFFFFFu) atomicAdd(&s_px[it.px_lvl[k]], 1u);
@@ -239,7 +250,7 @@ __global__ __launch_bounds__(256) void k_level_scatter(const uint32_t *__restric
     const size_t sg = (size_t)blockIdx.x * SEG_RUN + j;
     if (sg >= total) break;
     PixelItems it;
-    gather_items(keys, labels, H, W, (int)(sg / segs), (int)(sg % segs) * MSEG + threadIdx.x * 4, it);
+    gather_items<STACK>(keys, labels, H, W, (int)(sg / segs), (int)(sg % segs) * MSEG + threadIdx.x * 4, it, slice_h, base);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       if (it.px_lvl[k] != 0xFFFFFFFFu) {
@@ -259,12 +270,16 @@ __global__ __launch_bounds__(256) void k_level_scatter(const uint32_t *__restric
 }
 
 hipError_t level_scatter(hipStream_t s, const uint32_t *keys, const uint32_t *labels, int h, int w,
-                         u64c *cursor_px, u64c *cursor_edge, uint32_t *px_items, uint2 *edge_items) {
+                         u64c *cursor_px, u64c *cursor_edge, uint32_t *px_items, uint2 *edge_items, int slice_h, const uint32_t *slice_base) {
   if (h == 0 || w == 0) return hipSuccess;
   const int segs = (w + MSEG - 1) / MSEG;
   const size_t total = (size_t)h * segs;
   const int run = seg_run_for(total);
-  k_level_scatter<<<(unsigned)((total + run - 1) / run), 256, 0, s>>>(keys, labels, h, w, segs, run, cursor_px, cursor_edge, px_items, edge_items);
+  const unsigned blocks = (unsigned)((total + run - 1) / run);
+  if (slice_base)
+    k_level_scatter<true><<<blocks, 256, 0, s>>>(keys, labels, h, w, segs, run, cursor_px, cursor_edge, px_items, edge_items, slice_h, slice_base);
+  else
+    k_level_scatter<false><<<blocks, 256, 0, s>>>(keys, labels, h, w, segs, run, cursor_px, cursor_edge, px_items, edge_items, 0, nullptr);
   return hipGetLastError();
 }
 
@@ -1217,6 +1232,193 @@ hipError_t relabel_u64(hipStream_t s, const uint32_t *keys, const uint32_t *labe
   if (n == 0) return hipSuccess;
   const int blocks = (int)((n + 1023) / 1024 < 8192 ? (n + 1023) / 1024 : 8192);
   k_relabel<uint64_t><<<blocks, 256, 0, s>>>(keys, labels, parent, out, n, level);
+  return hipGetLastError();
+}
+
+// ---- a stack of slices (ws_transform_to_list_batch_device, ws_merge_batch_device) --------------------------------------------
+//
+// The slices of a cube flooded as ONE plane of g x slice_h rows (ws_segment.hip, segment_batch_stacked): labels restart at 1 in
+// every slice, colour c of slice k is c + base[k] in the stack's numbering (base: g + 1 words, base[g] = the stack's colours).
+
+// slice of a stack colour (1 .. base[g]): the k with base[k] < c <= base[k + 1] (a seedless slice has base[k] == base[k + 1])
+__device__ __forceinline__ uint32_t slice_of_colour(const uint32_t *base, uint32_t g, uint32_t c) {
+  uint32_t lo = 0, hi = g - 1;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi + 1) >> 1;
+    if (base[mid] < c) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// level of record i: the l in [lo, hi] with off[l] <= i < off[l + 1] (off: prefix sums of the levels' record counts)
+__device__ __forceinline__ uint32_t level_of_record(const u64c *__restrict__ off, uint32_t lo, uint32_t hi, u64c i) {
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi + 1) >> 1;
+    if (off[mid] <= i) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// Per (slice, level): pixels that arrive (their stamp's level), hist[k * NLEVELS + level].  Workgroup (x, k) walks a part of
+// slice k, counts in LDS and adds once per level it saw.
+__global__ __launch_bounds__(256) void k_slice_arrivals(const uint32_t *__restrict__ keys, size_t plane, u64c *hist) {
+  __shared__ uint32_t s_h[NLEVELS];
+  s_h[threadIdx.x] = 0;
+  __syncthreads();
+  const size_t k = blockIdx.y, nv = plane / 4;      // plane % 4 == 0 (stacks have plane % 128 == 0)
+  const u32x4_m *kv = reinterpret_cast<const u32x4_m *>(keys + k * plane);
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (size_t)gridDim.x * blockDim.x) {
+    const u32x4_m v = kv[i];
+    if (v.x != KEY_INF) atomicAdd(&s_h[v.x >> 24], 1u);
+    if (v.y != KEY_INF) atomicAdd(&s_h[v.y >> 24], 1u);
+    if (v.z != KEY_INF) atomicAdd(&s_h[v.z >> 24], 1u);
+    if (v.w != KEY_INF) atomicAdd(&s_h[v.w >> 24], 1u);
+  }
+  __syncthreads();
+  if (s_h[threadIdx.x]) atomicAdd(&hist[k * NLEVELS + threadIdx.x], (u64c)s_h[threadIdx.x]);
+}
+
+hipError_t slice_arrivals(hipStream_t s, const uint32_t *keys, size_t plane, size_t n_slices, u64c *hist) {
+  if (plane == 0 || n_slices == 0) return hipSuccess;
+  const unsigned bx = (unsigned)std::min<size_t>(std::max<size_t>(plane / (4 * 256 * 16), 1), 256);      // ~16 words a thread
+  k_slice_arrivals<<<dim3(bx, (unsigned)n_slices), 256, 0, s>>>(keys, plane, hist);
+  return hipGetLastError();
+}
+
+// The stack's records (level-major, stack colours) into the caller's slice-major layout.  A workgroup takes SPLIT_CHUNK
+// consecutive records; they span the levels l_lo .. l_hi (one, mostly), so its bins are (l - l_lo, slice) -- counted in LDS and
+// sent on with ONE atomic per (workgroup, bin).  A chunk with more bins than LDS holds (many tiny slices) adds record by record.
+// The slices' colour bases sit in LDS for the binary search of a record's slice (up to SPLIT_LDS_BASE of them).
+//   SCATTER false: bins[k * levels + l] += count.   true: bins are cursors (the caller's offsets of the bins); every record is
+//   written behind its bin's cursor as (colour - base[k], area).
+constexpr int SPLIT_PER_THREAD = 16;
+constexpr int SPLIT_CHUNK = 256 * SPLIT_PER_THREAD;
+constexpr uint32_t SPLIT_LDS_BINS = 2048, SPLIT_LDS_BASE = 2048;
+typedef unsigned long long u64x2_m __attribute__((ext_vector_type(2)));
+template <bool SCATTER>
+__global__ __launch_bounds__(256) void k_split_records(const uint64_t *__restrict__ rec, size_t n_rec, const u64c *__restrict__ off,
+                                                       uint32_t levels, const uint32_t *__restrict__ base, uint32_t g, u64c *bins,
+                                                       uint64_t *out) {
+  __shared__ uint32_t s_cnt[SPLIT_LDS_BINS];
+  __shared__ uint32_t s_base[SPLIT_LDS_BASE];
+  __shared__ u64c s_pos[SCATTER ? SPLIT_LDS_BINS : 1];
+  const bool lds_base = g <= SPLIT_LDS_BASE;
+  if (lds_base)
+    for (uint32_t k = threadIdx.x; k < g; k += 256) s_base[k] = base[k];
+  const uint32_t *bs = lds_base ? s_base : base;
+  const size_t r0 = (size_t)blockIdx.x * SPLIT_CHUNK;
+  const size_t r1 = min(r0 + (size_t)SPLIT_CHUNK, n_rec);
+  const uint32_t l_lo = level_of_record(off, 0, levels - 1, r0), l_hi = level_of_record(off, l_lo, levels - 1, r1 - 1);
+  const uint32_t nb = (l_hi - l_lo + 1) * g;
+  const bool lds = nb <= SPLIT_LDS_BINS;      // workgroup uniform
+  __syncthreads();
+  const u64x2_m *rv = reinterpret_cast<const u64x2_m *>(rec);
+  uint32_t bin[SPLIT_PER_THREAD];
+  u64x2_m r[SPLIT_PER_THREAD];
+#pragma unroll
+  for (int j = 0; j < SPLIT_PER_THREAD; ++j) {
+    const size_t i = r0 + (size_t)j * 256 + threadIdx.x;
+    bin[j] = 0xFFFFFFFFu;
+    if (i < r1) {
+      r[j] = rv[i];
+      const uint32_t c = (uint32_t)r[j].x;
+      const uint32_t k = slice_of_colour(bs, g, c), l = level_of_record(off, l_lo, l_hi, i);
+      r[j].x = c - bs[k];
+      bin[j] = lds ? (l - l_lo) * g + k : k * levels + l;
+    }
+  }
+  if (!lds) {
+#pragma unroll
+    for (int j = 0; j < SPLIT_PER_THREAD; ++j) {
+      if (bin[j] == 0xFFFFFFFFu) continue;
+      const u64c p = atomicAdd(&bins[bin[j]], 1ull);
+      if (SCATTER) { out[2 * p] = r[j].x; out[2 * p + 1] = r[j].y; }      // (the caller's records need only be 8-byte aligned)
+    }
+    return;
+  }
+  for (uint32_t b = threadIdx.x; b < nb; b += 256) s_cnt[b] = 0;
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < SPLIT_PER_THREAD; ++j)
+    if (bin[j] != 0xFFFFFFFFu) atomicAdd(&s_cnt[bin[j]], 1u);
+  __syncthreads();
+  for (uint32_t b = threadIdx.x; b < nb; b += 256) {
+    const uint32_t n = s_cnt[b];
+    const uint32_t k = b % g, l = l_lo + b / g;
+    if (!SCATTER) {
+      if (n) atomicAdd(&bins[(size_t)k * levels + l], (u64c)n);
+    } else {
+      s_pos[b] = n ? atomicAdd(&bins[(size_t)k * levels + l], (u64c)n) : 0ull;
+      s_cnt[b] = 0;
+    }
+  }
+  if (!SCATTER) return;
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < SPLIT_PER_THREAD; ++j) {
+    if (bin[j] == 0xFFFFFFFFu) continue;
+    const u64c p = s_pos[bin[j]] + atomicAdd(&s_cnt[bin[j]], 1u);
+    out[2 * p] = r[j].x;
+    out[2 * p + 1] = r[j].y;
+  }
+}
+
+hipError_t split_records(hipStream_t s, bool scatter, const uint64_t *rec, size_t n_rec, const u64c *off, uint32_t levels,
+                         const uint32_t *base, uint32_t g, u64c *bins, uint64_t *out) {
+  if (n_rec == 0) return hipSuccess;
+  const unsigned blocks = (unsigned)((n_rec + SPLIT_CHUNK - 1) / SPLIT_CHUNK);
+  if (scatter) k_split_records<true><<<blocks, 256, 0, s>>>(rec, n_rec, off, levels, base, g, bins, out);
+  else k_split_records<false><<<blocks, 256, 0, s>>>(rec, n_rec, off, levels, base, g, bins, nullptr);
+  return hipGetLastError();
+}
+
+// Final level of the merging transform over a stack: every pair of touching pixels with different labels, at least one of
+// them interior to its slice, joins the two stack colours (as union_image on one plane; a pixel is coloured exactly when its
+// label is non-zero).  No pair crosses a slice border.
+__global__ __launch_bounds__(256) void k_union_stack(const uint32_t *__restrict__ labels, int slice_h, int W, size_t n,
+                                                     const uint32_t *__restrict__ base, uint32_t *parent) {
+  for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (size_t)gridDim.x * blockDim.x) {
+    const uint32_t a = labels[p];
+    if (!a) continue;
+    const int x = (int)(p % W);
+    const size_t row = p / W;
+    const int ys = (int)(row % slice_h);
+    const uint32_t add = base[row / slice_h];
+    const bool ip = interior(ys, x, slice_h, W);
+    if (x + 1 < W) {
+      const uint32_t b = labels[p + 1];
+      if (b && b != a && (ip || interior(ys, x + 1, slice_h, W))) uf_union(parent, a + add, b + add);
+    }
+    if (ys + 1 < slice_h) {
+      const uint32_t b = labels[p + W];
+      if (b && b != a && (ip || interior(ys + 1, x, slice_h, W))) uf_union(parent, a + add, b + add);
+    }
+  }
+}
+
+// labels[p] = root(labels[p] + base[slice]) - base[slice] in place: the smallest seed colour of the lake, in the slice's numbering
+__global__ __launch_bounds__(256) void k_relabel_stack(uint32_t *labels, size_t plane, size_t n, const uint32_t *__restrict__ base,
+                                                       const uint32_t *__restrict__ parent) {
+  for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (size_t)gridDim.x * blockDim.x) {
+    const uint32_t a = labels[p];
+    if (!a) continue;
+    const uint32_t add = base[p / plane];
+    labels[p] = parent[a + add] - add;
+  }
+}
+
+hipError_t merge_stack(hipStream_t s, uint32_t *labels, int slice_h, int w, size_t n_slices, const uint32_t *base, uint32_t *parent,
+                       size_t n_colours) {
+  const size_t n = (size_t)slice_h * w * n_slices;
+  if (n == 0) return hipSuccess;
+  const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 16384);
+  k_union_stack<<<blocks, 256, 0, s>>>(labels, slice_h, w, n, base, parent);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const int fb = (int)std::min<size_t>((n_colours + 255) / 256, 8192);
+  k_uf_flatten<<<fb > 0 ? fb : 1, 256, 0, s>>>(parent, n_colours);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  k_relabel_stack<<<blocks, 256, 0, s>>>(labels, (size_t)slice_h * w, n, base, parent);
   return hipGetLastError();
 }
 

@@ -25,11 +25,14 @@ typedef unsigned long long u64c;
 hipError_t uf_init(hipStream_t s, uint32_t *parent, uint32_t *size, size_t n);
 
 // per-level histograms of arriving pixels and of label-crossing edges (256 bins each)
+// slice_base (nullable): the plane is a stack of slices of slice_h rows whose labels restart at 1 in every slice; colour c of
+// slice k is c + slice_base[k] (one numbering for the stack) and no pair crosses a slice border
 hipError_t level_hist(hipStream_t s, const uint32_t *keys, const uint32_t *labels, int h, int w,
-                      u64c *hist_px, u64c *hist_edge);
+                      u64c *hist_px, u64c *hist_edge, int slice_h = 0, const uint32_t *slice_base = nullptr);
 // bucketed scatter: px_items[cursor_px[lvl]++] = colour, edge_items[cursor_edge[lvl]++] = (a,b)
 hipError_t level_scatter(hipStream_t s, const uint32_t *keys, const uint32_t *labels, int h, int w,
-                         u64c *cursor_px, u64c *cursor_edge, uint32_t *px_items, uint2 *edge_items);
+                         u64c *cursor_px, u64c *cursor_edge, uint32_t *px_items, uint2 *edge_items,
+                         int slice_h = 0, const uint32_t *slice_base = nullptr);
 
 // exclusive prefix sums of the histograms (NLEVELS + 1 entries each) and the scatter cursors, all on the device
 hipError_t level_offsets(hipStream_t s, const u64c *hist_px, const u64c *hist_ed, u64c *off_px, u64c *off_ed, u64c *cur_px, u64c *cur_ed);
@@ -92,5 +95,17 @@ hipError_t relabel_u32(hipStream_t s, const uint32_t *keys, const uint32_t *labe
                        uint32_t *out, size_t n, uint32_t level);
 hipError_t relabel_u64(hipStream_t s, const uint32_t *keys, const uint32_t *labels, uint32_t *parent,
                        uint64_t *out, size_t n, uint32_t level);
+
+// A stack of n_slices slices of slice_h x w pixels flooded as one plane (labels restart at 1 in every slice; base: n_slices + 1
+// words, colour c of slice k is c + base[k] in the stack's numbering).
+// hist[k * NLEVELS + l] += pixels of slice k that arrive at level l (n_slices * NLEVELS words, zeroed by the caller)
+hipError_t slice_arrivals(hipStream_t s, const uint32_t *keys, size_t plane, size_t n_slices, u64c *hist);
+// the stack's lake records (level-major, off: levels + 1 prefix sums, stack colours) into slice-major bins k * levels + l:
+// scatter false adds the bins' counts into `bins`; true writes every record, as (colour - base[k], area), at out[bins[bin]++]
+hipError_t split_records(hipStream_t s, bool scatter, const uint64_t *rec, size_t n_rec, const u64c *off, uint32_t levels,
+                         const uint32_t *base, uint32_t g, u64c *bins, uint64_t *out);
+// merging transform, final canonical labels of every slice, in place (parent: n_colours = base[n_slices] + 1 words, uf_init'ed)
+hipError_t merge_stack(hipStream_t s, uint32_t *labels, int slice_h, int w, size_t n_slices, const uint32_t *base, uint32_t *parent,
+                       size_t n_colours);
 
 }  // namespace wsk

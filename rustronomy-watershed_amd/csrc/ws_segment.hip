@@ -268,6 +268,25 @@ int run_fused(ws_ctx *c, const uint8_t *d_img, size_t stride, int ph, int pw, ui
   return rc;
 }
 
+// One stack of g slices as one transform: first (host, g + 1 words) = the slices' first seeds in the group's list (first[g] =
+// its length); the group's seeds move to stacked coordinates in c->seed_stack, followed by `first` (the slices' colour bases:
+// stacked_first()).  The stamps of the stack stay in c->keys.  Returns with the stream drained.
+int flood_stack(ws_ctx *c, const uint8_t *d_src, size_t stride, size_t g, size_t ph, size_t pw, const uint32_t *d_seeds_rc,
+                const uint32_t *first, const ws_options *opt, uint32_t *d_labels, bool *mispredicted) {
+  int rc;
+  const size_t ns = first[g];
+  if ((rc = ensure(c, c->seed_stack, (ns * 2 + g + 1) * sizeof(uint32_t)))) return rc;
+  uint32_t *stacked = (uint32_t *)c->seed_stack.p, *d_first = stacked + ns * 2;
+  HIP_TRY(c, hipMemcpyAsync(d_first, first, (g + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, stack_seeds(c->stream, d_seeds_rc, ns, d_first, g, (int)ph, (int)pw, stacked, seed_shift_of(opt)));
+  *mispredicted = false;
+  // (edge correction: the slices' rings of zeros are virtual)
+  rc = run_fused_form(c, d_src, stride, (int)(g * ph), (int)pw, opt->max_water_level, stacked, ns, d_labels, true,
+                      mispredicted, (int)ph, d_first, opt->edge_correction != 0);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));      // `first` is the caller's, and reused by its next group
+  return rc;
+}
+
 }  // namespace wsapi
 
 using namespace wsapi;
@@ -616,18 +635,11 @@ static int segment_batch_stacked(ws_ctx *c, const uint8_t *d_cube, size_t n_slic
     const size_t s0 = seed_offsets[k0], ns = seed_offsets[k0 + g] - s0;
     if (ns == 0) return WS_OK;
     stats_begin(c);
-    const uint8_t *src = d_cube + k0 * h * stride;      // edge correction: the slices' rings of zeros are virtual
-    const size_t src_stride = stride;
     first.resize(g + 1);
     for (size_t k = 0; k <= g; ++k) first[k] = (uint32_t)(seed_offsets[k0 + k] - s0);
-    if ((rc = ensure(c, c->seed_stack, (ns * 2 + g + 1) * sizeof(uint32_t)))) return rc;
-    uint32_t *stacked = (uint32_t *)c->seed_stack.p, *d_first = stacked + ns * 2;
-    HIP_TRY(c, hipMemcpyAsync(d_first, first.data(), (g + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, stack_seeds(c->stream, d_seeds_rc + 2 * s0, ns, d_first, g, (int)ph, (int)pw, stacked, seed_shift_of(opt)));
     bool mispredicted = false;
-    rc = run_fused_form(c, src, src_stride, (int)(g * ph), (int)pw, opt->max_water_level, stacked, ns, d_labels + k0 * plane, true,
-                        &mispredicted, (int)ph, d_first, opt->edge_correction != 0);
-    HIP_TRY(c, hipStreamSynchronize(c->stream));      // `first` is reused by the next group
+    rc = flood_stack(c, d_cube + k0 * h * stride, stride, g, ph, pw, d_seeds_rc + 2 * s0, first.data(), opt, d_labels + k0 * plane,
+                     &mispredicted);
     if (rc != WS_OK || mispredicted) {      // the loop repeats the work and names the slice
       (void)stats_end(c);                   // closes the span opened above; the loop's transforms keep their own statistics
       c->err.clear();

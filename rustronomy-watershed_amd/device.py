@@ -183,6 +183,62 @@ class DeviceEngine:
             break
         return lakes[: n.value], offsets, unc
 
+    @staticmethod
+    def _batch_args(cube, seeds, seed_offsets):
+        if cube.dim() != 3:
+            raise ValueError("cube must be 3-D: (slices, rows, columns)")
+        if len(seed_offsets) != cube.shape[0] + 1:
+            raise ValueError("seed_offsets needs one entry per slice and one more")
+        assert cube.dtype == torch.uint8 and cube.is_contiguous() and cube.is_cuda
+        assert seeds.dtype == torch.int32 and seeds.is_cuda and (seeds.numel() == 0 or seeds.is_contiguous())
+        s = cube.shape[0]
+        return (ctypes.c_size_t * (s + 1))(*[int(x) for x in seed_offsets])
+
+    def transform_to_list_batch(self, cube, seeds, seed_offsets, merging=True, max_level=254, edge=False, lakes=None):
+        """transform_to_list of every slice of a cube (ws_transform_to_list_batch_device), records left in HBM.  cube: (S, H, W)
+        uint8; seeds: all slices' (row, col) pairs concatenated, int32 (n, 2); seed_offsets: S + 1 host integers.  Returns (lakes
+        (n, 2) int64 device tensor of (colour, area), offsets numpy (S * levels + 1), uncoloured numpy (S * levels)): slice k's
+        records at level l are lakes[offsets[k * levels + l] : offsets[k * levels + l + 1]], in the slice's own colours."""
+        import numpy as np
+        offs = self._batch_args(cube, seeds, seed_offsets)
+        s, h, w = cube.shape
+        levels = max_level + 1
+        opt = self.options(max_level, edge)
+        offsets = np.zeros(s * levels + 1, dtype=np.uint64)
+        unc = np.zeros(max(s * levels, 1), dtype=np.uint64)
+        n = ctypes.c_size_t(0)
+        failed = ctypes.c_size_t(0)
+        ns = int(seed_offsets[-1]) - int(seed_offsets[0])
+        cap = int(lakes.shape[0]) if lakes is not None else max(ns, 1) * levels // 2 + 1024
+        while True:
+            if lakes is None or lakes.shape[0] < cap:
+                lakes = torch.empty((cap, 2), dtype=torch.int64, device=self.device)
+            rc = _ffi.lib().ws_transform_to_list_batch_device(self.ctx.handle, int(merging), cube.data_ptr(), s, h, w, w, h * w,
+                                                              seeds.data_ptr() if seeds.numel() else None, offs, ctypes.byref(opt),
+                                                              lakes.data_ptr(), cap, ctypes.byref(n), offsets.ctypes.data,
+                                                              unc.ctypes.data, ctypes.byref(failed))
+            if rc == _ffi.WS_ERR_CAPACITY and n.value > cap:
+                cap = n.value
+                continue
+            self.ctx.check(rc)
+            break
+        return lakes[: n.value], offsets, unc[: s * levels]
+
+    def merge_batch(self, cube, seeds, seed_offsets, max_level=254, edge=False, out=None, seed_shift=False):
+        """The merging transform's final labels of every slice of a cube (ws_merge_batch_device); arguments as segment_batch.
+        Returns (S, H', W') int32 labels, slice k as merge(cube[k], its seeds)."""
+        offs = self._batch_args(cube, seeds, seed_offsets)
+        s, h, w = cube.shape
+        e = 2 if edge else 0
+        if out is None:
+            out = torch.empty((s, h + e, w + e), dtype=torch.int32, device=self.device)
+        opt = self.options(max_level, edge, None, seed_shift)
+        failed = ctypes.c_size_t(0)
+        self.ctx.check(_ffi.lib().ws_merge_batch_device(self.ctx.handle, cube.data_ptr(), s, h, w, w, h * w,
+                                                        seeds.data_ptr() if seeds.numel() else None, offs,
+                                                        ctypes.byref(opt), out.data_ptr(), ctypes.byref(failed)))
+        return out
+
     def level_snapshot(self, labels, water_level, out=None):
         """The segmenting label plane after `water_level` (transform_history's entry for that level), on the device."""
         if out is None:
