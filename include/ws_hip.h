@@ -380,6 +380,27 @@ int ws_copy_last_arrival_device(ws_ctx *ctx, uint32_t *d_dst, size_t n_elems);
  * once its arrival level is <= water_level, 0 before -- from d_labels (what the last ws_segment_device on this context
  * wrote) and the context's arrival stamps; d_out is a plane of the same shape (may equal d_labels).  Stream ordered. */
 int ws_level_snapshot_device(ws_ctx *ctx, const uint32_t *d_labels, uint8_t water_level, uint32_t *d_out);
+/* transform_history (lib.rs:1233-1237; merging 1538-1549, segmenting 1824-1835) for a caller-chosen list of water levels, in
+ * one transform and with the planes left in HBM: plane k -- the label plane the reference's hook sees after water level
+ * levels[k] -- goes to d_out + k * plane_stride (u32 words, plane_stride >= the padded h * w; the fast path, 16-byte stores,
+ * needs plane_stride % 4 == 0 and d_out 16-byte aligned -- otherwise every pixel is stored on its own).  levels: n_levels host bytes,
+ * each <= opt->max_water_level, in any order, repeats allowed; 1 <= n_levels <= 256, or 0: nothing runs, nothing is written.
+ * merging != 0: the merging transform, whose planes carry canonical ids (the smallest seed colour of the lake, as
+ * ws_merge_with_hook delivers them); 0: the segmenting one (ws_level_snapshot_device's planes).  Image, seeds, edge correction
+ * and duplicate seeds as ws_segment_device / ws_merge_device; the flood is the fused one whatever opt->engine says.  A level
+ * above max_water_level or a short plane_stride (also with n_levels == 0) is WS_ERR_BAD_ARG before anything runs.  Afterwards ws_last_arrival_device
+ * reports this transform's stamps.  The merging transform keeps a level-stamped merge forest while its per-level unions run
+ * (8 B per colour of context workspace), then ONE pass over the plane writes every requested level. */
+int ws_transform_history_device(ws_ctx *ctx, int merging, const uint8_t *d_img, size_t h, size_t w, size_t row_stride,
+                                const uint32_t *d_seeds_rc, size_t n_seeds, const ws_options *opt,
+                                const uint8_t *levels, size_t n_levels, uint32_t *d_out, size_t plane_stride);
+/* The same from and into HOST memory: u64 planes (usize, as the reference's), n_levels * padded h * w words, contiguous, plane
+ * k for levels[k].  Scratch, kept by the context: the planes are rendered in chunks of at most 256 MiB of u32 words on the
+ * device (at least one plane); a chunk of 2^21 words and more crosses the bus as u32, widened by the host threads
+ * (ws_ctx_set_host_threads), smaller ones plane by plane. */
+int ws_transform_history(ws_ctx *ctx, int merging, const uint8_t *img, size_t h, size_t w, size_t row_stride,
+                         const uint64_t *seeds_rc, size_t n_seeds, const ws_options *opt,
+                         const uint8_t *levels, size_t n_levels, uint64_t *out);
 
 /* ---- input preparation (first "next" row) ---------------------------------------
  *

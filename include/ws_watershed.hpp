@@ -177,6 +177,24 @@ class Watershed : public WatershedUtils {  // lib.rs:1206-1238
     };
     return run<R>(input, seeds, &h, nullptr);
   }
+  // not in the reference: transform_history for the water levels in `levels` only (any order, repeats allowed, at most 256) as
+  // one call of the library (ws_transform_history: no per-level hook); entry k is levels[k]'s.  With every level 0..=max in
+  // order it equals transform_history.
+  std::vector<std::pair<std::uint8_t, Array2<usize>>> transform_history_levels(ArrayView2<std::uint8_t> input, const std::vector<Seed> &seeds,
+                                                                               const std::vector<std::uint8_t> &levels) const {
+    const std::size_t e = opt_.edge_correction ? 2 : 0, rows = input.rows + e, cols = input.cols + e, npx = rows * cols;
+    auto packed = detail::pack(seeds);
+    std::vector<usize> flat(levels.size() * npx);
+    ctx_->check(ws_transform_history(ctx_->get(), merging_, input.ptr, input.rows, input.cols, input.row_stride, packed.data(), seeds.size(),
+                                     &opt_, levels.data(), levels.size(), flat.data()));
+    std::vector<std::pair<std::uint8_t, Array2<usize>>> out;
+    for (std::size_t k = 0; k < levels.size(); ++k) {
+      Array2<usize> a(rows, cols);
+      std::copy(flat.begin() + k * npx, flat.begin() + (k + 1) * npx, a.data.begin());
+      out.emplace_back(levels[k], std::move(a));
+    }
+    return out;
+  }
   // lib.rs:1220-1224: Vec<(u8, Vec<usize>)>, each inner Vec of length pixels+1 (lib.rs:630)
   std::vector<std::pair<std::uint8_t, std::vector<usize>>> transform_to_list(ArrayView2<std::uint8_t> input,
                                                                               const std::vector<Seed> &seeds) const {

@@ -136,6 +136,8 @@ SIGNATURES = {
     "ws_last_arrival_device": (ctypes.c_int, [vp, ctypes.POINTER(vp), szp, szp]),
     "ws_copy_last_arrival_device": (ctypes.c_int, [vp, vp, sz]),
     "ws_level_snapshot_device": (ctypes.c_int, [vp, vp, ctypes.c_uint8, vp]),
+    "ws_transform_history_device": (ctypes.c_int, [vp, ctypes.c_int, vp, sz, sz, sz, vp, sz, ctypes.POINTER(Options), vp, sz, vp, sz]),
+    "ws_transform_history": (ctypes.c_int, [vp, ctypes.c_int, vp, sz, sz, sz, vp, sz, ctypes.POINTER(Options), vp, sz, vp]),
     "ws_pre_processor": (ctypes.c_int, [vp, vp, ctypes.c_int, sz, ctypes.c_uint8, vp]),
     "ws_pre_processor_device": (ctypes.c_int, [vp, vp, ctypes.c_int, sz, ctypes.c_uint8, vp]),
     "ws_block_init": (ctypes.c_int, [vp, sz, sz, vp, vp, sz, vp, vp]),

@@ -147,6 +147,23 @@ def _as_seeds(seeds):
     return s, int(s.shape[0])
 
 
+def _history_levels(levels, max_level):
+    """The level list of a transform_history for chosen levels (ws_transform_history(_device)) as u8, checked before any device
+    work: None = every level 0..=max_level; otherwise at most 256 integers in 0..=max_level, any order, repeats allowed."""
+    if levels is None:
+        return np.arange(int(max_level) + 1, dtype=np.uint8)
+    lv = np.asarray(levels).reshape(-1)
+    if lv.size == 0:
+        return np.zeros(0, dtype=np.uint8)
+    if not np.issubdtype(lv.dtype, np.integer):
+        raise ValueError("water levels must be integers")
+    if lv.size > 256:
+        raise ValueError(f"at most 256 water levels per call, not {lv.size}")
+    if int(lv.min()) < 0 or int(lv.max()) > int(max_level):
+        raise ValueError(f"water levels must lie in 0..={int(max_level)} (max_water_level)")
+    return np.ascontiguousarray(lv, dtype=np.uint8)
+
+
 class TransformBuilder:
     """lib.rs:908-1047.  `TransformBuilder()` is both `new()` and `default()`."""
 
@@ -302,6 +319,28 @@ class _Transform(WatershedUtils):
 
     def transform_history(self, input, seeds):            # lib.rs:1233-1237, 1538-1549, 1824-1835
         return self._run_with_hook(input, seeds, lambda ctx: (ctx.water_level, ctx.colours.copy()), False)[0]
+
+    def transform_history_levels(self, input, seeds, levels=None, out=None):
+        """transform_history for the water levels in `levels` only -- any order, repeats allowed, at most 256; None: every level
+        -- as ONE call of the library (ws_transform_history: no per-level hook, the planes rendered on the device in one pass).
+        Returns [(level, u64 plane)] in the order of `levels`; with levels=None exactly what transform_history returns.  Not a
+        method of the reference.  `out`: a reusable C-contiguous (K, H', W') uint64 array the planes are written into (the
+        planes returned are views of it)."""
+        lv = _history_levels(levels, self.max_water_level)
+        a, stride = _as_image(input)
+        s, ns = _as_seeds(seeds)
+        h, w = a.shape
+        ph, pw = self._shape(a)
+        if out is None:
+            out = np.empty((lv.size, ph, pw), dtype=np.uint64)
+        elif out.dtype != np.uint64 or not out.flags.c_contiguous or out.shape != (lv.size, ph, pw):
+            raise ValueError(f"out must be a C-contiguous uint64 array of shape {(lv.size, ph, pw)}")
+        if lv.size:
+            ctx = self._ctx()
+            rc = _ffi.lib().ws_transform_history(ctx.handle, int(self._merging), a.ctypes.data, h, w, stride, s.ctypes.data, ns,
+                                                 ctypes.byref(self._opt), lv.ctypes.data, lv.size, out.ctypes.data)
+            ctx.check(rc)
+        return [(int(lvl), out[k]) for k, lvl in enumerate(lv)]
 
     def transform_to_list(self, input, seeds):            # lib.rs:1220-1224, 1551-1561, 1837-1847
         """[(level, lake_sizes)] with lake_sizes a uint64 vector of length pixels+1 (lib.rs:630)."""

@@ -51,6 +51,9 @@ struct ws_ctx {
   // ws_transform_to_list_batch(_device) / ws_merge_batch_device: the stack's labels, its lake records before the split into
   // slices (16 B a record), the split's bins, the host form's cube and seeds
   wsapi::DevBuf stack_labels, stack_records, stack_bins, batch_cube, batch_seeds;
+  // ws_transform_history(_device): the hook parent of every colour of the stamped merge forest (its death levels: uf_death), and
+  // the host form's u32 planes before they cross the bus
+  wsapi::DevBuf uf_hook, history_planes;
   uint32_t *pinned = nullptr;      // FLAG_WORDS words of pinned host memory: the host's mirror of the flag block
   uint32_t *pinned_dev = nullptr;  // the same words as the device sees them (nullptr: not mapped, copies only)
   hipEvent_t ring_ev[wsk::COUNTER_RING]{};   // flag slot copied to the host
@@ -113,9 +116,10 @@ struct ws_ctx {
     const void *records = nullptr;      // the buffer the lake records go to (the context's, or a caller's device buffer)
     const void *keys = nullptr, *seg = nullptr;      // the planes the buckets are built from (the context's, or a caller's: the arrival form)
     size_t slice_h = 0;                              // a stack of slices (ws_transform_to_list_batch_device): rows of one slice
+    bool history = false;                            // ws_transform_history(_device): the unions stamp the merge forest
     uint64_t generation = 0;
     bool operator==(const ListKey &o) const {
-      return generation == o.generation && generation != 0 && merging == o.merging && want_list == o.want_list && levels == o.levels && slice_h == o.slice_h &&
+      return generation == o.generation && generation != 0 && merging == o.merging && want_list == o.want_list && history == o.history && levels == o.levels && slice_h == o.slice_h &&
              n_colours == o.n_colours && n == o.n && cap == o.cap && records == o.records && keys == o.keys && seg == o.seg;
     }
   };

@@ -75,14 +75,22 @@ struct FusedEmit {
   bool live = false;           // many colours: records from the list of LIVE lakes (ws_merge.hip) instead of a look at every colour per level
   unsigned emit_grid = 0;      // workgroups of the live-list walk
 };
+//   history_hook (transform_history): the unions also stamp the merge forest (hook parents here, death levels in uf_death); nothing else
 template <class F>
-int level_range(ws_ctx *c, uint32_t l0, uint32_t l1, bool merging, bool want_sizes, unsigned grid, F per_level, const FusedEmit &fe = FusedEmit()) {
+int level_range(ws_ctx *c, uint32_t l0, uint32_t l1, bool merging, bool want_sizes, unsigned grid, F per_level, const FusedEmit &fe = FusedEmit(),
+                uint32_t *history_hook = nullptr) {
   uint32_t *parent = (uint32_t *)c->uf_parent.p, *size = (uint32_t *)c->uf_size.p, *hooked = (uint32_t *)c->uf_hooked.p;
   u64c *mf = (u64c *)c->mflags.p;
   uint32_t *hooked_count = (uint32_t *)(mf + MF_HOOKED);
   const uint32_t *px_items = (const uint32_t *)c->px_items.p;
   const uint2 *edge_items = (const uint2 *)c->edge_items.p;
   for (uint32_t l = l0; l < l1; ++l) {
+    if (history_hook) {
+      HIP_TRY(c, union_stamped_ranged(c->stream, edge_items, mf + MF_OFF_ED + l, grid, parent, (uint32_t *)c->uf_death.p, history_hook, l));
+      int rc = per_level(l);
+      if (rc) return rc;
+      continue;
+    }
     if (fe.on && !fe.live) {
       HIP_TRY(c, union_emit(c->stream, edge_items, mf + MF_OFF_ED + l, grid, parent, hooked, hooked_count + l, (uint32_t *)c->uf_death.p, l,
                             size, fe.n_colours, fe.lakes, fe.cap, mf + MF_LAKE_COUNT));
@@ -150,7 +158,8 @@ int records_to_host(ws_ctx *c, const ws_lake *d_rec, ws_lake *lakes, size_t from
 }
 int merge_host(ws_ctx *c, bool merging, const uint8_t *img, size_t h, size_t w, size_t stride, const uint64_t *seeds_rc,
                size_t n_seeds, const ws_options *opt, ws_level_cb cb, void *user, uint64_t *out_labels,
-               ws_lake *lakes, size_t cap, size_t *n_lakes, uint64_t *offsets, uint64_t *uncoloured, const DeviceLists *dev = nullptr) {
+               ws_lake *lakes, size_t cap, size_t *n_lakes, uint64_t *offsets, uint64_t *uncoloured, const DeviceLists *dev = nullptr,
+               bool history = false) {      // history: no lists, no hook; merging: unions that stamp the merge forest (the planes are rendered afterwards)
   if (!c) return WS_ERR_BAD_ARG;
   size_t ph, pw;
   const bool from_arrival = dev && dev->d_keys;
@@ -181,8 +190,10 @@ int merge_host(ws_ctx *c, bool merging, const uint8_t *img, size_t h, size_t w, 
   // the flood itself is the segmenting one (same coloured set, same arrival stamps: lib.rs:1394-1438 == 1704-1748)
   if (!from_arrival && (rc = run_fused(c, d_img, d_stride, (int)ph, (int)pw, opt->max_water_level, d_seeds, n_seeds, (uint32_t *)c->labels.p, opt->edge_correction != 0))) return rc;
   const uint32_t *keys = from_arrival ? dev->d_keys : (const uint32_t *)c->keys.p;
+  if (history && !merging) return stats_end(c);      // the segmenting history is the flood's stamps and labels: nothing per level
   // every buffer first, so that nothing moves once launches (or captured graphs) hold its address
   if ((rc = ensure_uf(c, n_seeds + 1))) return rc;
+  if (history && (rc = ensure(c, c->uf_hook, (n_seeds + 1) * sizeof(uint32_t)))) return rc;
   // Planes with a million colours and more (4096^2 random fields on) write their lake records from the list of the lakes
   // still alive, not from a look at every colour at every level (8192^2: 66.8 -> 20.5 ms); below that the per-level
   // launches are latency-bound either way and the older, shorter kernels win (1024^2, the core_bench shape: 3.8 against 5.0 ms).
@@ -211,9 +222,10 @@ int merge_host(ws_ctx *c, bool merging, const uint8_t *img, size_t h, size_t w, 
   if (fe.on && fe.live) {
     fe.emit_grid = (unsigned)std::min<size_t>(std::max<size_t>((n_seeds + 4095) / 4096, 1), 1024);
     HIP_TRY(c, sd_init(c->stream, (uint2 *)c->uf_sd.p, n_seeds + 1));      // no pixels yet, every colour a root
-  } else if (fe.on) {
+  } else if (fe.on || history) {
     HIP_TRY(c, hipMemsetAsync(c->uf_death.p, 0xFF, (n_seeds + 1) * sizeof(uint32_t), c->stream));      // every colour a root
   }
+  uint32_t *history_hook = history ? (uint32_t *)c->uf_hook.p : nullptr;
   auto per_level = [&](uint32_t l) -> int {
     if (want_list && !fe.on)      // the kernel leaves this level's record count in its counter; offsets are prefix sums, taken on the host
       HIP_TRY(c, emit_lakes(c->stream, parent, (const uint32_t *)c->uf_size.p, n_seeds + 1, d_records, cap, mf + MF_LAKE_COUNT, l));
@@ -242,6 +254,7 @@ int merge_host(ws_ctx *c, bool merging, const uint8_t *img, size_t h, size_t w, 
   key.records = d_records;
   key.keys = keys; key.seg = seg;
   key.slice_h = dev && dev->d_slice_base ? (size_t)dev->slice_h : 0;
+  key.history = history;      // (its unions are other kernels: never replay a history graph for lists or final labels, nor the reverse)
   key.generation = c->buffer_generation;
   const bool graph_able = !cb && c->stream != nullptr && !c->graph_unusable && !c->profiling && n != 0;
   bool use_graphs = graph_able && key == c->list_seen_key;
@@ -260,7 +273,7 @@ int merge_host(ws_ctx *c, bool merging, const uint8_t *img, size_t h, size_t w, 
       if (!c->list_graphs[gi]) {
         hipGraph_t graph = nullptr;
         if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-          const int lrc = level_range(c, g0, g1, merging, want_list, grid, per_level, fe);
+          const int lrc = level_range(c, g0, g1, merging, want_list, grid, per_level, fe, history_hook);
           const hipError_t e2 = hipStreamEndCapture(c->stream, &graph);
           if (lrc == WS_OK && e2 == hipSuccess && hipGraphInstantiate(&c->list_graphs[gi], graph, nullptr, nullptr, 0) != hipSuccess) c->list_graphs[gi] = nullptr;
           if (graph) (void)hipGraphDestroy(graph);
@@ -277,7 +290,7 @@ int merge_host(ws_ctx *c, bool merging, const uint8_t *img, size_t h, size_t w, 
         done = true;
       }
     }
-    if (!done && (rc = level_range(c, g0, g1, merging, want_list, grid, per_level, fe))) return rc;
+    if (!done && (rc = level_range(c, g0, g1, merging, want_list, grid, per_level, fe, history_hook))) return rc;
     // a marker per group, so that the records of finished levels can travel to the host while later levels are computed
     if (want_list) HIP_TRY(c, hipEventRecord(c->kern_ev[gi], c->stream));
   }
@@ -519,9 +532,92 @@ int check_batch(ws_ctx *c, size_t n_slices, size_t h, size_t row_stride, size_t 
   return WS_OK;
 }
 
+// ---- transform_history (lib.rs:1233-1237, 1538-1549, 1824-1835) for a list of levels ------------------------------------------------
+
+constexpr size_t HISTORY_SCRATCH_BYTES = (size_t)256 << 20;      // the host form's u32 planes on the device, at most, per chunk of levels
+
+// what both forms check before anything runs; *n_px: pixels of the (padded) plane
+int check_history(ws_ctx *c, size_t h, size_t w, size_t stride, const ws_options *opt, const uint8_t *levels, size_t n_levels, size_t *n_px) {
+  size_t ph, pw;
+  if (int rc = check_plane(c, h, w, stride, opt, &ph, &pw)) return rc;
+  if (n_levels > (size_t)HISTORY_MAX_LEVELS) return fail(c, WS_ERR_BAD_ARG, "more than 256 levels");
+  if (n_levels && !levels) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  for (size_t k = 0; k < n_levels; ++k)
+    if (levels[k] > opt->max_water_level) return fail(c, WS_ERR_BAD_ARG, "a level above max_water_level");
+  *n_px = ph * pw;
+  return WS_OK;
+}
+
+// levels[k0 .. k1) in ascending order (stable: repeats keep their order), each with its plane k - k0
+HistoryTable history_table(const uint8_t *levels, size_t k0, size_t k1) {
+  HistoryTable t{};
+  t.n = (uint32_t)(k1 - k0);
+  for (size_t k = k0; k < k1; ++k) t.e[k - k0] = (uint32_t)levels[k] | (uint32_t)(k - k0) << 8;
+  std::stable_sort(t.e, t.e + t.n, [](uint32_t a, uint32_t b) { return (a & 0xFFu) < (b & 0xFFu); });
+  return t;
+}
+
+// the planes of tab's levels from the transform merge_host(history) has just run on this context
+int render_levels(ws_ctx *c, bool merging, const HistoryTable &tab, uint32_t *d_out, size_t plane_stride, size_t n) {
+  HIP_TRY(c, render_history(c->stream, merging, (const uint32_t *)c->keys.p, (const uint32_t *)c->labels.p, (const uint32_t *)c->uf_death.p,
+                            (const uint32_t *)c->uf_hook.p, tab, d_out, plane_stride, n));
+  return WS_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int ws_transform_history_device(ws_ctx *c, int merging, const uint8_t *d_img, size_t h, size_t w, size_t stride, const uint32_t *d_seeds_rc,
+                                size_t n_seeds, const ws_options *opt, const uint8_t *levels, size_t n_levels, uint32_t *d_out,
+                                size_t plane_stride) {
+  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
+  if (!c) return WS_ERR_BAD_ARG;
+  if ((!d_img && h * w) || (!d_seeds_rc && n_seeds)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  size_t n = 0;
+  if (int rc = check_history(c, h, w, stride, opt, levels, n_levels, &n)) return rc;
+  if (plane_stride < n) return fail(c, WS_ERR_BAD_ARG, "plane_stride is shorter than the plane");
+  if (n_levels == 0) return WS_OK;
+  if (!d_out && n) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  const DeviceLists dev{d_img, d_seeds_rc, nullptr};
+  if (int rc = merge_host(c, merging != 0, nullptr, h, w, stride, nullptr, n_seeds, opt, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
+                          nullptr, &dev, true))
+    return rc;
+  return render_levels(c, merging != 0, history_table(levels, 0, n_levels), d_out, plane_stride, n);
+}
+
+int ws_transform_history(ws_ctx *c, int merging, const uint8_t *img, size_t h, size_t w, size_t stride, const uint64_t *seeds_rc,
+                         size_t n_seeds, const ws_options *opt, const uint8_t *levels, size_t n_levels, uint64_t *out) {
+  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
+  if (!c) return WS_ERR_BAD_ARG;
+  if ((!img && h * w) || (!seeds_rc && n_seeds)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  size_t n = 0;
+  if (int rc = check_history(c, h, w, stride, opt, levels, n_levels, &n)) return rc;
+  if (n_levels == 0) return WS_OK;
+  if (!out && n) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  if (int rc = merge_host(c, merging != 0, img, h, w, stride, seeds_rc, n_seeds, opt, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
+                          nullptr, nullptr, true))
+    return rc;
+  if (n == 0) return WS_OK;
+  // chunks of levels rendered into bounded scratch; a chunk's planes are contiguous there and in `out`, so a chunk of 2^21 words
+  // and more crosses the bus in ONE labels_to_host_u64 as u32, widened by the host threads while its next pieces are in flight.
+  // Smaller chunks, or no host threads (ws_ctx_set_host_threads(0)): plane by plane, widened on the device in the u64 buffer
+  // the context already holds for one plane
+  const size_t per = std::max<size_t>(1, std::min<size_t>(n_levels, HISTORY_SCRATCH_BYTES / (n * sizeof(uint32_t))));
+  if (int rc = ensure(c, c->history_planes, per * n * sizeof(uint32_t))) return rc;
+  uint32_t *planes = (uint32_t *)c->history_planes.p;
+  for (size_t k0 = 0; k0 < n_levels; k0 += per) {
+    const size_t k1 = std::min(k0 + per, n_levels);
+    if (int rc = render_levels(c, merging != 0, history_table(levels, k0, k1), planes, n, n)) return rc;
+    if (host_copy_in_chunks(c, (k1 - k0) * n)) {
+      if (int rc = labels_to_host_u64(c, planes, out + k0 * n, (k1 - k0) * n)) return rc;
+    } else {
+      for (size_t k = k0; k < k1; ++k)
+        if (int rc = labels_to_host_u64(c, planes + (k - k0) * n, out + k * n, n)) return rc;
+    }
+  }
+  return WS_OK;
+}
 
 // half: 0 the whole call; 1 ws_merge_device_begin (returns WS_INTERNAL_PENDING when the graph and the speculative unions
 // have been queued and the host half is still to come); 2 ws_merge_device_end (that host half)

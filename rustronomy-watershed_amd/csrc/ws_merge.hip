@@ -1235,6 +1235,103 @@ hipError_t relabel_u64(hipStream_t s, const uint32_t *keys, const uint32_t *labe
   return hipGetLastError();
 }
 
+// ---- transform_history on the device (ws_transform_history_device) --------------------------------------------------------------
+//
+// The per-level unions leave a level-stamped merge forest beside the union-find: when a CAS hooks root b under a, hook[b] = a
+// and death[b] = the level.  parent[] cannot serve: path halving rewrites it in later levels.  The lake of colour c at level L
+// is then found by walking hook[] from c while death[x] <= L (DESIGN.md section 4.1 has the argument that the walk ends at the
+// lake's smallest colour, the canonical id, whatever order the racing CASes took).
+
+// uf_union that also names the root the loser was hooked under
+__device__ __forceinline__ uint32_t uf_union_to(uint32_t *parent, uint32_t a, uint32_t b, uint32_t *winner) {
+  for (;;) {
+    a = uf_find(parent, a);
+    b = uf_find(parent, b);
+    if (a == b) return 0xFFFFFFFFu;
+    if (a > b) { const uint32_t t = a; a = b; b = t; }
+    const uint32_t old = atomicCAS(parent + b, b, a);
+    if (old == b) { *winner = a; return b; }
+    b = old;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_union_stamped(const uint2 *__restrict__ edge_items, const u64c *__restrict__ range, uint32_t *parent,
+                                                       uint32_t *death, uint32_t *hook, uint32_t level) {
+  edge_items += range[0];
+  const size_t n = (size_t)(range[1] - range[0]);
+  const size_t step = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
+    const uint2 e = edge_items[i];
+    uint32_t a = 0;
+    const uint32_t lost = uf_union_to(parent, e.x, e.y, &a);
+    if (lost != 0xFFFFFFFFu) {      // once per colour: only the CAS that ends its time as a root gets here
+      hook[lost] = a;
+      death[lost] = level;
+    }
+  }
+}
+
+hipError_t union_stamped_ranged(hipStream_t s, const uint2 *edge_items, const u64c *range, unsigned grid, uint32_t *parent, uint32_t *death,
+                                uint32_t *hook, uint32_t level) {
+  k_union_stamped<<<grid, 256, 0, s>>>(edge_items, range, parent, death, hook, level);
+  return hipGetLastError();
+}
+
+// One pass for every requested level: a pixel's stamp and colour are read once, then the levels are walked in ascending order
+// and every plane gets its four pixels as one 16-byte store.  The merging colour follows the stamped forest up as L grows:
+// the walk only ever moves on, and death[] of the colour it stands on is kept in a register, so a level at which the lake did
+// not merge costs no load.
+template <bool MERGING>
+__global__ __launch_bounds__(256) void k_render_history(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ labels,
+                                                        const uint32_t *__restrict__ death, const uint32_t *__restrict__ hook,
+                                                        HistoryTable tab, uint32_t *out, size_t plane_stride, size_t n) {
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, step = (size_t)gridDim.x * blockDim.x;
+  const bool vec = ((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(labels) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0 &&
+                   (plane_stride & 3u) == 0;
+  const size_t nq = vec ? n / 4 : 0;
+  for (size_t q = tid; q < nq; q += step) {
+    const u32x4_m k = reinterpret_cast<const u32x4_m *>(keys)[q], l = reinterpret_cast<const u32x4_m *>(labels)[q];
+    uint32_t arr[4] = {k.x >> 24, k.y >> 24, k.z >> 24, k.w >> 24};      // arrival level; KEY_INF: 255, above every level
+    uint32_t col[4] = {l.x, l.y, l.z, l.w}, d[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      if (col[p] == 0u) arr[p] = 0xFFu;
+      d[p] = MERGING && arr[p] != 0xFFu ? death[col[p]] : 0xFFFFFFFFu;
+    }
+    for (uint32_t j = 0; j < tab.n; ++j) {
+      const uint32_t e = tab.e[j], L = e & 0xFFu;
+      uint32_t v[4];
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        if (MERGING && arr[p] <= L)
+          while (d[p] <= L) { col[p] = hook[col[p]]; d[p] = death[col[p]]; }
+        v[p] = arr[p] <= L ? col[p] : 0u;
+      }
+      reinterpret_cast<u32x4_m *>(out + (size_t)(e >> 8) * plane_stride)[q] = u32x4_m{v[0], v[1], v[2], v[3]};
+    }
+  }
+  for (size_t i = nq * 4 + tid; i < n; i += step) {      // the tail (all of the plane when a pointer or the stride is not 16-byte aligned)
+    uint32_t a = keys[i] >> 24, c = labels[i];
+    if (c == 0u) a = 0xFFu;
+    uint32_t dc = MERGING && a != 0xFFu ? death[c] : 0xFFFFFFFFu;
+    for (uint32_t j = 0; j < tab.n; ++j) {
+      const uint32_t e = tab.e[j], L = e & 0xFFu;
+      if (MERGING && a <= L)
+        while (dc <= L) { c = hook[c]; dc = death[c]; }
+      out[(size_t)(e >> 8) * plane_stride + i] = a <= L ? c : 0u;
+    }
+  }
+}
+
+hipError_t render_history(hipStream_t s, bool merging, const uint32_t *keys, const uint32_t *labels, const uint32_t *death, const uint32_t *hook,
+                          const HistoryTable &tab, uint32_t *out, size_t plane_stride, size_t n) {
+  if (n == 0 || tab.n == 0) return hipSuccess;
+  const unsigned blocks = (unsigned)std::min<size_t>((n / 4 + 255) / 256 + 1, 16384);
+  if (merging) k_render_history<true><<<blocks, 256, 0, s>>>(keys, labels, death, hook, tab, out, plane_stride, n);
+  else k_render_history<false><<<blocks, 256, 0, s>>>(keys, labels, nullptr, nullptr, tab, out, plane_stride, n);
+  return hipGetLastError();
+}
+
 // ---- a stack of slices (ws_transform_to_list_batch_device, ws_merge_batch_device) --------------------------------------------
 //
 // The slices of a cube flooded as ONE plane of g x slice_h rows (ws_segment.hip, segment_batch_stacked): labels restart at 1 in

@@ -96,6 +96,21 @@ hipError_t relabel_u32(hipStream_t s, const uint32_t *keys, const uint32_t *labe
 hipError_t relabel_u64(hipStream_t s, const uint32_t *keys, const uint32_t *labels, uint32_t *parent,
                        uint64_t *out, size_t n, uint32_t level);
 
+// transform_history (ws_transform_history_device): the unions of `level` that also stamp the merge forest -- hook[b] = the root b
+// was hooked under, death[b] = level (death: 0xFFFFFFFF at the start; hook is read only where death is set)
+hipError_t union_stamped_ranged(hipStream_t s, const uint2 *edge_items, const u64c *range, unsigned grid, uint32_t *parent, uint32_t *death,
+                                uint32_t *hook, uint32_t level);
+// the requested levels in ascending order: e[j] = level | slot << 8 (slot: the output plane, at out + slot * plane_stride)
+constexpr int HISTORY_MAX_LEVELS = 256;
+struct HistoryTable {
+  uint32_t n;
+  uint32_t e[HISTORY_MAX_LEVELS];
+};
+// one pass over the plane's stamps and segmenting colours for all of tab's levels: out = coloured by L ? colour : 0, the colour
+// being the segmenting one or (merging) the lake's canonical id at L found up the stamped forest
+hipError_t render_history(hipStream_t s, bool merging, const uint32_t *keys, const uint32_t *labels, const uint32_t *death, const uint32_t *hook,
+                          const HistoryTable &tab, uint32_t *out, size_t plane_stride, size_t n);
+
 // A stack of n_slices slices of slice_h x w pixels flooded as one plane (labels restart at 1 in every slice; base: n_slices + 1
 // words, colour c of slice k is c + base[k] in the stack's numbering).
 // hist[k * NLEVELS + l] += pixels of slice k that arrive at level l (n_slices * NLEVELS words, zeroed by the caller)

@@ -246,5 +246,28 @@ class DeviceEngine:
         self.ctx.check(_ffi.lib().ws_level_snapshot_device(self.ctx.handle, labels.data_ptr(), int(water_level), out.data_ptr()))
         return out
 
+    def transform_history(self, img, seeds, levels=None, merging=False, max_level=254, edge=False, out=None):
+        """transform_history for the water levels in `levels` (any order, repeats allowed, at most 256; None: 0..=max_level) with
+        everything in HBM (ws_transform_history_device): a (K, H', W') int32 tensor whose plane k is the label plane the reference's
+        hook sees after levels[k] -- merging: canonical lake ids.  `out`: a reusable (K, H', W') int32 device tensor."""
+        from .api import _history_levels
+        lv = _history_levels(levels, max_level)
+        assert img.dtype == torch.uint8 and img.dim() == 2 and img.is_contiguous() and img.is_cuda
+        assert seeds.dtype == torch.int32 and seeds.is_cuda and (seeds.numel() == 0 or seeds.is_contiguous())
+        h, w = img.shape
+        ph, pw = self._plane(img, edge)
+        if out is None:
+            out = torch.empty((lv.size, ph, pw), dtype=torch.int32, device=self.device)
+        elif out.dtype != torch.int32 or not out.is_contiguous() or tuple(out.shape) != (lv.size, ph, pw):
+            raise ValueError(f"out must be a contiguous int32 tensor of shape {(lv.size, ph, pw)}")
+        if lv.size == 0:
+            return out
+        opt = self.options(max_level, edge)
+        ns = seeds.shape[0] if seeds.dim() == 2 else 0
+        self.ctx.check(_ffi.lib().ws_transform_history_device(self.ctx.handle, int(merging), img.data_ptr(), h, w, w,
+                                                              seeds.data_ptr() if ns else None, ns, ctypes.byref(opt),
+                                                              lv.ctypes.data, lv.size, out.data_ptr(), ph * pw))
+        return out
+
     def stats(self):
         return self.ctx.stats()
