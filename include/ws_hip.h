@@ -401,6 +401,30 @@ int ws_transform_history_device(ws_ctx *ctx, int merging, const uint8_t *d_img, 
 int ws_transform_history(ws_ctx *ctx, int merging, const uint8_t *img, size_t h, size_t w, size_t row_stride,
                          const uint64_t *seeds_rc, size_t n_seeds, const ws_options *opt,
                          const uint8_t *levels, size_t n_levels, uint64_t *out);
+/* transform_history of every slice of a cube for a list of water levels (tests/integration.rs:267,356 take a cube apart slice by
+ * slice), everything in HBM.  Slices, seeds, seed_offsets (n_slices + 1 entries, on the HOST), edge correction, duplicate seeds
+ * and *failed_slice as ws_transform_to_list_batch_device; levels, n_levels (0: nothing runs, nothing is written), merging and the
+ * planes as ws_transform_history_device.  Layout, slice-major then list order: plane (k, j) -- slice k's label plane after water
+ * level levels[j], in the slice's own colours, bit-identical to what ws_transform_history_device writes for that slice alone --
+ * is at d_out + (k * n_levels + j) * plane_stride.  A bad level or a short plane_stride is WS_ERR_BAD_ARG before anything runs.
+ * When the slices stack (as ws_transform_to_list_batch_device) every group of slices runs as one flood, and merging as ONE run
+ * of the stamping per-level unions over the stack's colours, then one render pass writes all of the group's planes; anything
+ * else runs as a loop of ws_transform_history_device.  Scratch of the stacked form, kept by the context: 4 B per pixel of the
+ * stack (its labels) and, merging, the merge forest of all its colours (8 B a colour).  Statistics are summed over the call's
+ * transforms; afterwards ws_last_arrival_device reports "unsupported". */
+int ws_transform_history_batch_device(ws_ctx *ctx, int merging, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w,
+                                      size_t row_stride, size_t slice_stride, const uint32_t *d_seeds_rc, const size_t *seed_offsets,
+                                      const ws_options *opt, const uint8_t *levels, size_t n_levels,
+                                      uint32_t *d_out, size_t plane_stride, size_t *failed_slice);
+/* The same from and into HOST memory: the cube and the (row, col) seed pairs as ws_transform_to_list_batch takes them (seeds_rc ==
+ * NULL: every slice's own find_local_minima, n_seeds[k], nullable, receives how many); u64 planes, contiguous, plane (k, j) at
+ * out + (k * n_levels + j) * padded h * w.  Scratch, kept by the context: the cube and the seeds on the device, and the planes
+ * rendered in chunks of at most 256 MiB of u32 words -- a run of whole slices where a slice's planes fit (it crosses the bus as
+ * ONE copy of u32 words widened by the host threads), a run of one slice's levels where they do not. */
+int ws_transform_history_batch(ws_ctx *ctx, int merging, const uint8_t *cube, size_t n_slices, size_t h, size_t w,
+                               size_t row_stride, size_t slice_stride, const uint64_t *seeds_rc, const size_t *seed_offsets,
+                               const ws_options *opt, const uint8_t *levels, size_t n_levels,
+                               uint64_t *out, size_t *n_seeds, size_t *failed_slice);
 
 /* ---- input preparation (first "next" row) ---------------------------------------
  *

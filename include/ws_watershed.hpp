@@ -257,6 +257,30 @@ class Watershed : public WatershedUtils {  // lib.rs:1206-1238
     if (n_seeds) *n_seeds = counts;
     return out;
   }
+  // not in the reference: transform_history_levels(cube[k], find_local_minima(cube[k]), levels) of every slice of a contiguous u8
+  // cube (n_slices x rows x cols) as one call (ws_transform_history_batch); entry [k][j] is slice k's plane for levels[j], in the
+  // slice's own colours.  n_seeds (nullable) receives the slices' minima counts.
+  std::vector<std::vector<std::pair<std::uint8_t, Array2<usize>>>> transform_history_cube(const std::uint8_t *cube, std::size_t n_slices,
+                                                                                          std::size_t rows, std::size_t cols,
+                                                                                          const std::vector<std::uint8_t> &levels,
+                                                                                          std::vector<std::size_t> *n_seeds = nullptr) const {
+    const std::size_t e = opt_.edge_correction ? 2 : 0, prow = rows + e, pcol = cols + e, npx = prow * pcol, nl = levels.size();
+    std::vector<usize> flat(n_slices * nl * npx);
+    std::vector<std::size_t> counts(n_slices);
+    std::size_t failed = 0;
+    ctx_->check(ws_transform_history_batch(ctx_->get(), merging_, cube, n_slices, rows, cols, cols, rows * cols, nullptr, nullptr, &opt_,
+                                           levels.data(), nl, flat.data(), counts.data(), &failed));
+    std::vector<std::vector<std::pair<std::uint8_t, Array2<usize>>>> out(n_slices);
+    for (std::size_t k = 0; k < n_slices; ++k)
+      for (std::size_t j = 0; j < nl; ++j) {
+        Array2<usize> a(prow, pcol);
+        const auto from = flat.begin() + (k * nl + j) * npx;
+        std::copy(from, from + npx, a.data.begin());
+        out[k].emplace_back(levels[j], std::move(a));
+      }
+    if (n_seeds) *n_seeds = counts;
+    return out;
+  }
 
  protected:
   Watershed(ws_options o, Hook h, std::shared_ptr<Context> c, int merging)

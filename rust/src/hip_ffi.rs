@@ -179,6 +179,13 @@ extern "C" {
                                              row_stride: usize, slice_stride: usize, d_seeds_rc: *const u32, seed_offsets: *const usize,
                                              opt: *const ws_options, d_lakes: *mut ws_lake, cap: usize, n_lakes: *mut usize, offsets: *mut u64,
                                              uncoloured: *mut u64, failed_slice: *mut usize) -> c_int;
+    pub fn ws_transform_history_batch(ctx: *mut ws_ctx, merging: c_int, cube: *const u8, n_slices: usize, h: usize, w: usize, row_stride: usize,
+                                      slice_stride: usize, seeds_rc: *const u64, seed_offsets: *const usize, opt: *const ws_options,
+                                      levels: *const u8, n_levels: usize, out: *mut u64, n_seeds: *mut usize, failed_slice: *mut usize) -> c_int;
+    pub fn ws_transform_history_batch_device(ctx: *mut ws_ctx, merging: c_int, d_cube: *const u8, n_slices: usize, h: usize, w: usize,
+                                             row_stride: usize, slice_stride: usize, d_seeds_rc: *const u32, seed_offsets: *const usize,
+                                             opt: *const ws_options, levels: *const u8, n_levels: usize, d_out: *mut u32, plane_stride: usize,
+                                             failed_slice: *mut usize) -> c_int;
     pub fn ws_merge_batch_device(ctx: *mut ws_ctx, d_cube: *const u8, n_slices: usize, h: usize, w: usize, row_stride: usize,
                                  slice_stride: usize, d_seeds_rc: *const u32, seed_offsets: *const usize, opt: *const ws_options,
                                  d_labels: *mut u32, failed_slice: *mut usize) -> c_int;

@@ -388,6 +388,33 @@ fn run_to_list_cube(merging: bool, opt: &Options, cube: nd::ArrayView3<u8>) -> (
     (lists, n_seeds)
 }
 
+/// One slice's planes of transform_history for chosen water levels: (level, label plane) in the order of the levels.
+pub type HistoryPlanes = Vec<(u8, nd::Array2<usize>)>;
+
+/// transform_history of every slice of a cube for the water levels in `levels` (any order, repeats allowed, at most 256), with
+/// each slice's own local minima as its seeds: one call of `ws_transform_history_batch`.  Returns the slices' planes and their
+/// seed counts.
+fn run_history_cube(merging: bool, opt: &Options, cube: nd::ArrayView3<u8>, levels: &[u8]) -> (Vec<HistoryPlanes>, Vec<usize>) {
+    let (n, h, w) = cube.dim();
+    let std_cube = cube.as_standard_layout();
+    let o = opt.ffi();
+    let (ph, pw) = opt.plane(h, w);
+    let nl = levels.len();
+    let mut planes = nd::Array4::<usize>::zeros((n, nl, ph, pw));
+    let mut n_seeds = vec![0usize; n];
+    let mut failed = 0usize;
+    shim::with_ctx(|ctx| unsafe {
+        let rc = hip_ffi::ws_transform_history_batch(ctx, merging as c_int, std_cube.as_ptr(), n, h, w, w, h * w, std::ptr::null(),
+                                                     std::ptr::null(), &o, levels.as_ptr(), nl, planes.as_mut_ptr() as *mut u64,
+                                                     n_seeds.as_mut_ptr(), &mut failed);
+        shim::check(ctx, rc, "ws_transform_history_batch");
+    });
+    let out = (0..n)
+        .map(|k| (0..nl).map(|j| (levels[j], planes.slice(nd::s![k, j, .., ..]).to_owned())).collect())
+        .collect();
+    (out, n_seeds)
+}
+
 fn history_hook(ctx: HookCtx) -> (u8, nd::Array2<usize>) {
     (ctx.water_level, ctx.colours.to_owned()) // lib.rs:1545, 1831
 }
@@ -468,6 +495,13 @@ impl<T> SegmentingWatershed<T> {
     pub fn transform_to_list_cube(&self, cube: nd::ArrayView3<u8>) -> (Vec<SparseLists>, Vec<usize>) {
         run_to_list_cube(false, &self.opt, cube)
     }
+
+    /// Not in the reference: `transform_history` of every slice of a cube (seeds: each slice's `find_local_minima`) for the water
+    /// levels in `levels` only, as one call (`ws_transform_history_batch`): per slice, (level, label plane) in the order of
+    /// `levels` -- and the number of minima of every slice.
+    pub fn transform_history_cube(&self, cube: nd::ArrayView3<u8>, levels: &[u8]) -> (Vec<HistoryPlanes>, Vec<usize>) {
+        run_history_cube(false, &self.opt, cube, levels)
+    }
 }
 
 impl<T> Watershed<T> for MergingWatershed<T> {
@@ -498,6 +532,11 @@ impl<T> MergingWatershed<T> {
     /// call; as `SegmentingWatershed::transform_to_list_cube`.
     pub fn transform_to_list_cube(&self, cube: nd::ArrayView3<u8>) -> (Vec<SparseLists>, Vec<usize>) {
         run_to_list_cube(true, &self.opt, cube)
+    }
+    /// Not in the reference: the merging `transform_history` of every slice of a cube for chosen water levels as one call (planes
+    /// of canonical ids); as `SegmentingWatershed::transform_history_cube`.
+    pub fn transform_history_cube(&self, cube: nd::ArrayView3<u8>, levels: &[u8]) -> (Vec<HistoryPlanes>, Vec<usize>) {
+        run_history_cube(true, &self.opt, cube, levels)
     }
     /// Not in the reference: the merged label plane after the last level (canonical ids: the smallest seed colour of
     /// every lake).  The reference's own `transform` is the stub above.

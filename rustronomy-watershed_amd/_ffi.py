@@ -138,6 +138,10 @@ SIGNATURES = {
     "ws_level_snapshot_device": (ctypes.c_int, [vp, vp, ctypes.c_uint8, vp]),
     "ws_transform_history_device": (ctypes.c_int, [vp, ctypes.c_int, vp, sz, sz, sz, vp, sz, ctypes.POINTER(Options), vp, sz, vp, sz]),
     "ws_transform_history": (ctypes.c_int, [vp, ctypes.c_int, vp, sz, sz, sz, vp, sz, ctypes.POINTER(Options), vp, sz, vp]),
+    "ws_transform_history_batch_device": (ctypes.c_int, [vp, ctypes.c_int, vp, sz, sz, sz, sz, sz, vp, szp, ctypes.POINTER(Options),
+                                                         vp, sz, vp, sz, szp]),
+    "ws_transform_history_batch": (ctypes.c_int, [vp, ctypes.c_int, vp, sz, sz, sz, sz, sz, vp, szp, ctypes.POINTER(Options),
+                                                  vp, sz, vp, szp, szp]),
     "ws_pre_processor": (ctypes.c_int, [vp, vp, ctypes.c_int, sz, ctypes.c_uint8, vp]),
     "ws_pre_processor_device": (ctypes.c_int, [vp, vp, ctypes.c_int, sz, ctypes.c_uint8, vp]),
     "ws_block_init": (ctypes.c_int, [vp, sz, sz, vp, vp, sz, vp, vp]),

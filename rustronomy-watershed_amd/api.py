@@ -456,6 +456,51 @@ class _Transform(WatershedUtils):
                         for lvl in range(levels)])
         return out if seeds is not None else (out, counts[:n].astype(np.int64))
 
+    def transform_history_cube(self, cube, seeds=None, levels=None, out=None):
+        """transform_history_levels of every slice cube[k] of a 3-D u8 array with seeds[k] -- or, with seeds None, the slice's own
+        find_local_minima -- for the water levels in `levels` (any order, repeats allowed, at most 256; None: every level), in ONE
+        call of the library (ws_transform_history_batch: slices that stack run one flood and one set of per-level launches for
+        the whole cube).  Returns, per slice, [(level, u64 plane)] in the order of `levels`, the planes views of one (S, K, H', W')
+        array in the slice's own colours (and, with seeds None, the number of minima of every slice).  `out`: a reusable
+        C-contiguous (S, K, H', W') uint64 array.  Not a method of the reference."""
+        c = np.asarray(cube)
+        if c.ndim != 3:
+            raise ValueError("cube must be 3-D: (slices, rows, columns)")
+        n = c.shape[0]
+        if seeds is not None and len(seeds) != n:
+            raise ValueError("one seed list per slice")
+        lv = _history_levels(levels, self.max_water_level)
+        c = np.ascontiguousarray(c, dtype=np.uint8)
+        _, h, w = c.shape
+        e = 2 if self.edge_correction else 0
+        ph, pw = h + e, w + e
+        shape = (n, lv.size, ph, pw)
+        if out is None:
+            out = np.empty(shape, dtype=np.uint64)
+        elif out.dtype != np.uint64 or not out.flags.c_contiguous or out.shape != shape:
+            raise ValueError(f"out must be a C-contiguous uint64 array of shape {shape}")
+        if seeds is None:
+            flat, offs = None, None
+        else:
+            lists = [np.asarray(s, dtype=np.uint64).reshape(-1, 2) for s in seeds]
+            offs = np.zeros(n + 1, dtype=np.uintp)
+            offs[1:] = np.cumsum([len(l) for l in lists])
+            flat = np.ascontiguousarray(np.concatenate(lists, axis=0) if lists else np.zeros((0, 2), dtype=np.uint64))
+            if flat.shape[0] == 0:
+                flat = np.zeros((1, 2), dtype=np.uint64)
+        counts = np.zeros(max(n, 1), dtype=np.uintp)
+        if lv.size and n:
+            ctx = self._ctx()
+            failed = ctypes.c_size_t(0)
+            rc = _ffi.lib().ws_transform_history_batch(ctx.handle, int(self._merging), c.ctypes.data, n, h, w, w, h * w,
+                                                       flat.ctypes.data if flat is not None else None,
+                                                       offs.ctypes.data_as(_ffi.szp) if offs is not None else None,
+                                                       ctypes.byref(self._opt), lv.ctypes.data, lv.size, out.ctypes.data,
+                                                       counts.ctypes.data_as(_ffi.szp), ctypes.byref(failed))
+            ctx.check(rc)
+        res = [[(int(lvl), out[k, j]) for j, lvl in enumerate(lv)] for k in range(n)]
+        return res if seeds is not None else (res, counts[:n].astype(np.int64))
+
 
 class SegmentingWatershed(_Transform):
     """lib.rs:1609-1849"""

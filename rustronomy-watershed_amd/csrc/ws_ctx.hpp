@@ -48,8 +48,8 @@ struct ws_ctx {
 
   wsapi::DevBuf img, keys, labels, labels2, stamps, flags, seeds, seeds64, out64, counts, aux, seed_stack, min_counts, min_nibbles;
   wsapi::DevBuf uf_parent, uf_size, uf_hooked, uf_death, uf_sd, alive, px_items, edge_items, mflags, lakes, refs, seed_tab, tile_list;
-  // ws_transform_to_list_batch(_device) / ws_merge_batch_device: the stack's labels, its lake records before the split into
-  // slices (16 B a record), the split's bins, the host form's cube and seeds
+  // ws_transform_to_list_batch(_device) / ws_merge_batch_device / ws_transform_history_batch(_device): the stack's labels, its
+  // lake records before the split into slices (16 B a record), the split's bins, the host forms' cube and seeds
   wsapi::DevBuf stack_labels, stack_records, stack_bins, batch_cube, batch_seeds;
   // ws_transform_history(_device): the hook parent of every colour of the stamped merge forest (its death levels: uf_death), and
   // the host form's u32 planes before they cross the bus

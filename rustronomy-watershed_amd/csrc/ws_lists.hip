@@ -564,6 +564,150 @@ int render_levels(ws_ctx *c, bool merging, const HistoryTable &tab, uint32_t *d_
   return WS_OK;
 }
 
+// ---- transform_history of a cube of slices (ws_transform_history_batch(_device)) ---------------------------------------------------
+
+// The transform of slices [k_first, k_first + g) of a batch, left on the context for rendering: a stack (labels restart at 1 in every
+// slice; colour c of slice k_first + k is c + base[k] in the merge forest) or one slice of the loop (g == 1, base null)
+struct HistoryGroup {
+  size_t k_first, g;
+  const uint32_t *keys, *labels, *base;
+};
+
+// slices [ka, kb) of the group (plane pixels each), tab's levels, into out: slice ka + r's plane of slot j at out + (r * per_slice + j) * plane_stride
+int render_group(ws_ctx *c, bool merging, const HistoryGroup &grp, size_t plane, size_t ka, size_t kb, const HistoryTable &tab, uint32_t *out,
+                 size_t per_slice, size_t plane_stride) {
+  if (!grp.base) return render_levels(c, merging, tab, out, plane_stride, plane);
+  const HistoryStack st{grp.base + ka, (uint32_t)plane, (uint32_t)per_slice};
+  HIP_TRY(c, render_history_stack(c->stream, merging, grp.keys + ka * plane, grp.labels + ka * plane, (const uint32_t *)c->uf_death.p,
+                                  (const uint32_t *)c->uf_hook.p, tab, out, plane_stride, (kb - ka) * plane, st));
+  return WS_OK;
+}
+
+// The transforms of a batch for transform_history, each handed to emit(HistoryGroup) while its planes can be rendered.  Slices
+// that stack run per group of slices as one flood (flood_stack) and, merging, ONE run of the stamping per-level driver over the
+// stack's numbering of colours (merge_host, arrival form, history: no pair crosses a slice border, so no lake either); anything
+// else -- and a stack that fails or mispredicts, which the loop repeats and whose failing slice it names -- as the single-field
+// transform of ws_transform_history_device slice by slice.  Statistics are summed.
+template <class F>
+int history_batch_run(ws_ctx *c, bool merging, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w, size_t stride, size_t slice_stride,
+                      const uint32_t *d_seeds_rc, const size_t *seed_offsets, const ws_options *opt, size_t *failed_slice, F emit) {
+  size_t ph, pw, per_group = 0;
+  int rc = check_plane(c, h, w, stride, opt, &ph, &pw);
+  if (rc) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t plane = ph * pw;
+  ws_stats acc{};
+  if (n_slices > 1 && slice_stride == h * stride && d_cube && d_seeds_rc && stackable(c, n_slices, h, w, stride, ph, pw, seed_offsets, opt, &per_group)) {
+    bool stacked = true;
+    std::vector<uint32_t> first;
+    for (size_t k0 = 0; k0 < n_slices && stacked; k0 += per_group) {
+      const size_t g = std::min(per_group, n_slices - k0);
+      const size_t s0 = seed_offsets[k0], ns = seed_offsets[k0 + g] - s0;
+      if ((rc = ensure(c, c->stack_labels, g * plane * sizeof(uint32_t)))) return rc;
+      first.resize(g + 1);
+      for (size_t k = 0; k <= g; ++k) first[k] = (uint32_t)(seed_offsets[k0 + k] - s0);
+      stats_begin(c);
+      bool mispredicted = false;
+      uint32_t *labels = (uint32_t *)c->stack_labels.p;
+      rc = flood_stack(c, d_cube + k0 * h * stride, stride, g, ph, pw, d_seeds_rc + 2 * s0, first.data(), opt, labels, &mispredicted);
+      c->have_keys = false;      // the stamps are those of a stack, not of an image
+      if (rc != WS_OK || mispredicted) {      // the loop repeats the work and names the slice
+        (void)stats_end(c);
+        c->err.clear();
+        stacked = false;
+        break;
+      }
+      if ((rc = stats_end(c))) return rc;
+      stats_add(acc, c->stats);
+      const uint32_t *d_base = stacked_first(c, ns);
+      if (merging) {
+        DeviceLists dev{nullptr, nullptr, nullptr};
+        dev.d_keys = (const uint32_t *)c->keys.p;
+        dev.d_seg = labels;
+        dev.slice_h = (int)ph;
+        dev.d_slice_base = d_base;
+        if ((rc = merge_host(c, true, nullptr, g * ph, pw, pw, nullptr, ns, opt, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
+                             &dev, true)))
+          return rc;
+        stats_add(acc, c->stats);
+      }
+      if ((rc = emit(HistoryGroup{k0, g, (const uint32_t *)c->keys.p, labels, d_base}))) return rc;
+    }
+    if (stacked) {
+      c->stats = acc;
+      return WS_OK;
+    }
+    acc = ws_stats{};
+  }
+  for (size_t k = 0; k < n_slices; ++k) {
+    const size_t ns = seed_offsets[k + 1] - seed_offsets[k];
+    const DeviceLists dev{d_cube + k * slice_stride, ns ? d_seeds_rc + 2 * seed_offsets[k] : nullptr, nullptr};
+    rc = merge_host(c, merging, nullptr, h, w, stride, nullptr, ns, opt, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, &dev, true);
+    if (rc == WS_OK) {
+      stats_add(acc, c->stats);
+      rc = emit(HistoryGroup{k, 1, (const uint32_t *)c->keys.p, (const uint32_t *)c->labels.p, nullptr});
+    }
+    if (rc != WS_OK) { if (failed_slice) *failed_slice = k; return rc; }
+  }
+  c->stats = acc;
+  c->have_keys = false;      // as after a stacked batch: the stamps are no single slice's business
+  return WS_OK;
+}
+
+// what both batch forms check before anything runs: the batch as ws_transform_to_list_batch(_device), the levels as
+// ws_transform_history(_device); *n_px: pixels of a (padded) slice
+int check_history_batch(ws_ctx *c, size_t n_slices, size_t h, size_t w, size_t row_stride, size_t slice_stride, const size_t *seed_offsets,
+                        const ws_options *opt, const uint8_t *levels, size_t n_levels, size_t *n_px) {
+  if (int rc = check_batch(c, n_slices, h, row_stride, slice_stride, seed_offsets, opt)) return rc;
+  return check_history(c, h, w, row_stride, opt, levels, n_levels, n_px);
+}
+
+// The host form's inputs on the device, as the device forms take them: the cube as contiguous slices (c->batch_cube) and the
+// seeds as u32 pairs (c->batch_seeds) -- seeds_rc == NULL: every slice's own find_local_minima (lib.rs:1178-1197), its seeds
+// behind the previous slices'.  offs (n_slices + 1): the seed offsets into c->batch_seeds; n_seeds (nullable): the counts.
+int upload_batch(ws_ctx *c, const uint8_t *cube, size_t n_slices, size_t h, size_t w, size_t row_stride, size_t slice_stride,
+                 const uint64_t *seeds_rc, const size_t *seed_offsets, std::vector<size_t> &offs, size_t *n_seeds, size_t *failed_slice) {
+  int rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t hw = h * w;
+  if ((rc = ensure(c, c->batch_cube, std::max<size_t>(n_slices * hw, 1)))) return rc;
+  uint8_t *d_cube = (uint8_t *)c->batch_cube.p;
+  if (hw && row_stride == w && (n_slices == 1 || slice_stride == hw)) {      // a contiguous cube: one copy
+    HIP_TRY(c, hipMemcpyAsync(d_cube, cube, n_slices * hw, hipMemcpyHostToDevice, c->stream));
+  } else if (hw) {
+    for (size_t k = 0; k < n_slices; ++k)
+      HIP_TRY(c, hipMemcpy2DAsync(d_cube + k * hw, w, cube + k * slice_stride, row_stride, w, h, hipMemcpyHostToDevice, c->stream));
+  }
+  offs.assign(n_slices + 1, 0);
+  if (seeds_rc) {
+    // the u64 pairs cross whole and are narrowed on the device, as stage_inputs does (k_narrow_seeds: the host loop it replaced
+    // took 5 ms for 7.3 M seeds); a coordinate past u32 is out of bounds either way: its pair becomes ~0 and stays so
+    const size_t s0 = seed_offsets[0], total = seed_offsets[n_slices] - s0;
+    if ((rc = ensure(c, c->batch_seeds, std::max<size_t>(total, 1) * 2 * sizeof(uint32_t)))) return rc;
+    if (total) {
+      if ((rc = ensure(c, c->seeds64, total * 2 * sizeof(uint64_t)))) return rc;
+      HIP_TRY(c, hipMemcpyAsync(c->seeds64.p, seeds_rc + 2 * s0, total * 2 * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(c, narrow_seeds(c->stream, (const uint64_t *)c->seeds64.p, total, 0xFFFFFFFFull, 0xFFFFFFFFull, (uint32_t *)c->batch_seeds.p));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (size_t k = 0; k <= n_slices; ++k) offs[k] = seed_offsets[k] - s0;
+  } else {
+    const size_t bound = h >= 3 && w >= 3 ? ((h - 1) / 2 + 1) * ((w - 1) / 2 + 1) : 0;
+    if ((rc = ensure(c, c->batch_seeds, std::max<size_t>(n_slices * bound, 1) * 2 * sizeof(uint32_t)))) return rc;
+    for (size_t k = 0; k < n_slices; ++k) {
+      size_t found = 0;
+      if (bound && (rc = ws_find_local_minima_device(c, d_cube + k * hw, h, w, w, (uint32_t *)c->batch_seeds.p + 2 * offs[k], bound, &found))) {
+        if (failed_slice) *failed_slice = k;
+        return rc;
+      }
+      offs[k + 1] = offs[k] + found;
+    }
+  }
+  if (n_seeds)
+    for (size_t k = 0; k < n_slices; ++k) n_seeds[k] = offs[k + 1] - offs[k];
+  return WS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -812,38 +956,11 @@ int ws_transform_to_list_batch(ws_ctx *c, int merging, const uint8_t *cube, size
   size_t ph, pw;
   int rc = check_plane(c, h, w, row_stride, opt, &ph, &pw);
   if (rc) return rc;
-  HIP_TRY(c, hipSetDevice(c->device));
   const size_t hw = h * w, plane = ph * pw;
   // the cube as contiguous slices, the seeds as u32 pairs (the device form's inputs), then the records back as ws_transform_to_list's are
-  if ((rc = ensure(c, c->batch_cube, std::max<size_t>(n_slices * hw, 1)))) return rc;
+  std::vector<size_t> offs;
+  if ((rc = upload_batch(c, cube, n_slices, h, w, row_stride, slice_stride, seeds_rc, seed_offsets, offs, n_seeds, failed_slice))) return rc;
   uint8_t *d_cube = (uint8_t *)c->batch_cube.p;
-  if (hw)
-    for (size_t k = 0; k < n_slices; ++k)
-      HIP_TRY(c, hipMemcpy2DAsync(d_cube + k * hw, w, cube + k * slice_stride, row_stride, w, h, hipMemcpyHostToDevice, c->stream));
-  std::vector<size_t> offs(n_slices + 1, 0);
-  if (seeds_rc) {
-    const size_t s0 = seed_offsets[0], total = seed_offsets[n_slices] - s0;
-    std::vector<uint32_t> s32(2 * total);
-    for (size_t i = 0; i < 2 * total; ++i)      // (a coordinate past u32 is out of bounds either way: it stays so)
-      s32[i] = (uint32_t)std::min<uint64_t>(seeds_rc[2 * s0 + i], 0xFFFFFFFFull);
-    if ((rc = ensure(c, c->batch_seeds, std::max<size_t>(total, 1) * 2 * sizeof(uint32_t)))) return rc;
-    if (total) HIP_TRY(c, hipMemcpyAsync(c->batch_seeds.p, s32.data(), 2 * total * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (size_t k = 0; k <= n_slices; ++k) offs[k] = seed_offsets[k] - s0;
-  } else {      // every slice's own find_local_minima (lib.rs:1178-1197), its seeds behind the previous slices'
-    const size_t bound = h >= 3 && w >= 3 ? ((h - 1) / 2 + 1) * ((w - 1) / 2 + 1) : 0;
-    if ((rc = ensure(c, c->batch_seeds, std::max<size_t>(n_slices * bound, 1) * 2 * sizeof(uint32_t)))) return rc;
-    for (size_t k = 0; k < n_slices; ++k) {
-      size_t found = 0;
-      if (bound && (rc = ws_find_local_minima_device(c, d_cube + k * hw, h, w, w, (uint32_t *)c->batch_seeds.p + 2 * offs[k], bound, &found))) {
-        if (failed_slice) *failed_slice = k;
-        return rc;
-      }
-      offs[k + 1] = offs[k] + found;
-    }
-  }
-  if (n_seeds)
-    for (size_t k = 0; k < n_slices; ++k) n_seeds[k] = offs[k + 1] - offs[k];
   if ((rc = ensure(c, c->lakes, std::max<size_t>(cap, 1) * sizeof(ws_lake)))) return rc;
   if ((rc = ensure(c, c->out64, std::max<size_t>(plane, 1) * sizeof(uint64_t)))) return rc;      // (the narrowed records' staging)
   rc = ws_transform_to_list_batch_device(c, merging, d_cube, n_slices, h, w, w, hw, (const uint32_t *)c->batch_seeds.p, offs.data(), opt,
@@ -879,6 +996,78 @@ int ws_merge_batch_device(ws_ctx *c, const uint8_t *d_cube, size_t n_slices, siz
   c->stats = acc;
   c->have_keys = false;
   return WS_OK;
+}
+
+int ws_transform_history_batch_device(ws_ctx *c, int merging, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w, size_t row_stride,
+                                      size_t slice_stride, const uint32_t *d_seeds_rc, const size_t *seed_offsets, const ws_options *opt,
+                                      const uint8_t *levels, size_t n_levels, uint32_t *d_out, size_t plane_stride, size_t *failed_slice) {
+  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
+  if (!c) return WS_ERR_BAD_ARG;
+  if (failed_slice) *failed_slice = 0;
+  size_t n = 0;
+  if (int rc = check_history_batch(c, n_slices, h, w, row_stride, slice_stride, seed_offsets, opt, levels, n_levels, &n)) return rc;
+  if (plane_stride < n) return fail(c, WS_ERR_BAD_ARG, "plane_stride is shorter than the plane");
+  if (n_levels == 0 || n_slices == 0) return WS_OK;
+  if ((!d_cube && h * w) || (!d_seeds_rc && seed_offsets[n_slices] > seed_offsets[0]) || (!d_out && n)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  // every slice's planes at once, straight into the caller's buffer
+  const HistoryTable tab = history_table(levels, 0, n_levels);
+  return history_batch_run(c, merging != 0, d_cube, n_slices, h, w, row_stride, slice_stride, d_seeds_rc, seed_offsets, opt, failed_slice,
+                           [&](const HistoryGroup &grp) {
+                             return render_group(c, merging != 0, grp, n, 0, grp.g, tab, d_out + grp.k_first * n_levels * plane_stride, n_levels,
+                                                 plane_stride);
+                           });
+}
+
+int ws_transform_history_batch(ws_ctx *c, int merging, const uint8_t *cube, size_t n_slices, size_t h, size_t w, size_t row_stride,
+                               size_t slice_stride, const uint64_t *seeds_rc, const size_t *seed_offsets, const ws_options *opt,
+                               const uint8_t *levels, size_t n_levels, uint64_t *out, size_t *n_seeds, size_t *failed_slice) {
+  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
+  if (!c) return WS_ERR_BAD_ARG;
+  if (failed_slice) *failed_slice = 0;
+  size_t n = 0;
+  if (int rc = check_history_batch(c, seeds_rc ? n_slices : 0, h, w, row_stride, slice_stride, seed_offsets, opt, levels, n_levels, &n)) return rc;
+  if (n_levels == 0 || n_slices == 0) return WS_OK;
+  if ((!cube && h * w) || (!out && n)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  std::vector<size_t> offs;
+  int rc = upload_batch(c, cube, n_slices, h, w, row_stride, slice_stride, seeds_rc, seed_offsets, offs, n_seeds, failed_slice);
+  if (rc) return rc;
+  if (n == 0)      // (no pixel: the transforms still run, for their errors)
+    return history_batch_run(c, merging != 0, (const uint8_t *)c->batch_cube.p, n_slices, h, w, w, h * w, (const uint32_t *)c->batch_seeds.p,
+                             offs.data(), opt, failed_slice, [](const HistoryGroup &) { return (int)WS_OK; });
+  // The planes are rendered into bounded scratch and cross the bus chunk by chunk.  Where a slice's planes fit, a chunk is a run
+  // of whole slices -- contiguous in `out` as in the scratch, so it crosses in ONE labels_to_host_u64 (u32 words widened by the
+  // host threads); where they do not, a chunk is a run of one slice's levels, as in ws_transform_history.
+  const size_t scratch_words = HISTORY_SCRATCH_BYTES / sizeof(uint32_t), slice_words = n_levels * n;
+  const size_t slices_per = slice_words <= scratch_words ? std::min(n_slices, scratch_words / slice_words) : 0;
+  const size_t levels_per = std::max<size_t>(1, std::min(n_levels, scratch_words / n));
+  if ((rc = ensure(c, c->history_planes, (slices_per ? slices_per * slice_words : levels_per * n) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, c->out64, n * sizeof(uint64_t)))) return rc;      // (the plane-by-plane copy widens there)
+  uint32_t *planes = (uint32_t *)c->history_planes.p;
+  auto to_host = [&](uint64_t *dst, size_t n_planes) -> int {
+    if (host_copy_in_chunks(c, n_planes * n)) return labels_to_host_u64(c, planes, dst, n_planes * n);
+    for (size_t i = 0; i < n_planes; ++i)
+      if (int rc_copy = labels_to_host_u64(c, planes + i * n, dst + i * n, n)) return rc_copy;
+    return (int)WS_OK;
+  };
+  const HistoryTable all = history_table(levels, 0, n_levels);
+  return history_batch_run(c, merging != 0, (const uint8_t *)c->batch_cube.p, n_slices, h, w, w, h * w, (const uint32_t *)c->batch_seeds.p,
+                           offs.data(), opt, failed_slice, [&](const HistoryGroup &grp) -> int {
+                             if (slices_per) {
+                               for (size_t ka = 0; ka < grp.g; ka += slices_per) {
+                                 const size_t kb = std::min(ka + slices_per, grp.g);
+                                 if (int rc_r = render_group(c, merging != 0, grp, n, ka, kb, all, planes, n_levels, n)) return rc_r;
+                                 if (int rc_c = to_host(out + (grp.k_first + ka) * slice_words, (kb - ka) * n_levels)) return rc_c;
+                               }
+                               return (int)WS_OK;
+                             }
+                             for (size_t k = 0; k < grp.g; ++k)
+                               for (size_t j0 = 0; j0 < n_levels; j0 += levels_per) {
+                                 const size_t j1 = std::min(j0 + levels_per, n_levels);
+                                 if (int rc_r = render_group(c, merging != 0, grp, n, k, k + 1, history_table(levels, j0, j1), planes, 0, n)) return rc_r;
+                                 if (int rc_c = to_host(out + (grp.k_first + k) * slice_words + j0 * n, j1 - j0)) return rc_c;
+                               }
+                             return (int)WS_OK;
+                           });
 }
 
 }  // extern "C"

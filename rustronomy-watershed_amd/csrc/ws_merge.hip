@@ -1281,21 +1281,32 @@ hipError_t union_stamped_ranged(hipStream_t s, const uint2 *edge_items, const u6
 // and every plane gets its four pixels as one 16-byte store.  The merging colour follows the stamped forest up as L grows:
 // the walk only ever moves on, and death[] of the colour it stands on is kept in a register, so a level at which the lake did
 // not merge costs no load.
-template <bool MERGING>
+// STACKED (ws_transform_history_batch_device): keys / labels are slices of st.plane pixels, labels in each slice's own colours;
+// slice kr's colour c is c + st.base[kr] in the forest, and its planes start at out + kr * st.per_slice * plane_stride.
+// st.plane % 4 == 0, so a quad never straddles two slices.
+template <bool MERGING, bool STACKED>
 __global__ __launch_bounds__(256) void k_render_history(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ labels,
                                                         const uint32_t *__restrict__ death, const uint32_t *__restrict__ hook,
-                                                        HistoryTable tab, uint32_t *out, size_t plane_stride, size_t n) {
+                                                        HistoryTable tab, uint32_t *out, size_t plane_stride, size_t n, HistoryStack st) {
   const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, step = (size_t)gridDim.x * blockDim.x;
   const bool vec = ((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(labels) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0 &&
-                   (plane_stride & 3u) == 0;
+                   (plane_stride & 3u) == 0 && (!STACKED || (st.plane & 3u) == 0);
   const size_t nq = vec ? n / 4 : 0;
   for (size_t q = tid; q < nq; q += step) {
     const u32x4_m k = reinterpret_cast<const u32x4_m *>(keys)[q], l = reinterpret_cast<const u32x4_m *>(labels)[q];
     uint32_t arr[4] = {k.x >> 24, k.y >> 24, k.z >> 24, k.w >> 24};      // arrival level; KEY_INF: 255, above every level
     uint32_t col[4] = {l.x, l.y, l.z, l.w}, d[4];
+    size_t o = 0;      // (STACKED) the quad's word in its slice's first plane
+    uint32_t b = 0;    // (STACKED, MERGING) the slice's colour base
+    if constexpr (STACKED) {
+      const uint32_t i = (uint32_t)(4 * q), kr = i / st.plane;
+      o = (size_t)kr * st.per_slice * plane_stride + (i - kr * st.plane);
+      if constexpr (MERGING) b = st.base[kr];
+    }
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       if (col[p] == 0u) arr[p] = 0xFFu;
+      if constexpr (STACKED && MERGING) col[p] += b;      // (colour 0 is never shown: arr = 0xFF)
       d[p] = MERGING && arr[p] != 0xFFu ? death[col[p]] : 0xFFFFFFFFu;
     }
     for (uint32_t j = 0; j < tab.n; ++j) {
@@ -1305,20 +1316,31 @@ __global__ __launch_bounds__(256) void k_render_history(const uint32_t *__restri
       for (int p = 0; p < 4; ++p) {
         if (MERGING && arr[p] <= L)
           while (d[p] <= L) { col[p] = hook[col[p]]; d[p] = death[col[p]]; }
-        v[p] = arr[p] <= L ? col[p] : 0u;
+        v[p] = arr[p] <= L ? col[p] - b : 0u;
       }
-      reinterpret_cast<u32x4_m *>(out + (size_t)(e >> 8) * plane_stride)[q] = u32x4_m{v[0], v[1], v[2], v[3]};
+      if constexpr (STACKED)
+        *reinterpret_cast<u32x4_m *>(out + (size_t)(e >> 8) * plane_stride + o) = u32x4_m{v[0], v[1], v[2], v[3]};
+      else
+        reinterpret_cast<u32x4_m *>(out + (size_t)(e >> 8) * plane_stride)[q] = u32x4_m{v[0], v[1], v[2], v[3]};
     }
   }
   for (size_t i = nq * 4 + tid; i < n; i += step) {      // the tail (all of the plane when a pointer or the stride is not 16-byte aligned)
     uint32_t a = keys[i] >> 24, c = labels[i];
     if (c == 0u) a = 0xFFu;
+    size_t o = i;
+    uint32_t b = 0;
+    if constexpr (STACKED) {
+      const uint32_t kr = (uint32_t)i / st.plane;
+      o = (size_t)kr * st.per_slice * plane_stride + ((uint32_t)i - kr * st.plane);
+      if constexpr (MERGING) b = st.base[kr];
+      c += b;
+    }
     uint32_t dc = MERGING && a != 0xFFu ? death[c] : 0xFFFFFFFFu;
     for (uint32_t j = 0; j < tab.n; ++j) {
       const uint32_t e = tab.e[j], L = e & 0xFFu;
       if (MERGING && a <= L)
         while (dc <= L) { c = hook[c]; dc = death[c]; }
-      out[(size_t)(e >> 8) * plane_stride + i] = a <= L ? c : 0u;
+      out[(size_t)(e >> 8) * plane_stride + o] = a <= L ? c - b : 0u;
     }
   }
 }
@@ -1327,8 +1349,19 @@ hipError_t render_history(hipStream_t s, bool merging, const uint32_t *keys, con
                           const HistoryTable &tab, uint32_t *out, size_t plane_stride, size_t n) {
   if (n == 0 || tab.n == 0) return hipSuccess;
   const unsigned blocks = (unsigned)std::min<size_t>((n / 4 + 255) / 256 + 1, 16384);
-  if (merging) k_render_history<true><<<blocks, 256, 0, s>>>(keys, labels, death, hook, tab, out, plane_stride, n);
-  else k_render_history<false><<<blocks, 256, 0, s>>>(keys, labels, nullptr, nullptr, tab, out, plane_stride, n);
+  if (merging) k_render_history<true, false><<<blocks, 256, 0, s>>>(keys, labels, death, hook, tab, out, plane_stride, n, HistoryStack{});
+  else k_render_history<false, false><<<blocks, 256, 0, s>>>(keys, labels, nullptr, nullptr, tab, out, plane_stride, n, HistoryStack{});
+  return hipGetLastError();
+}
+
+hipError_t render_history_stack(hipStream_t s, bool merging, const uint32_t *keys, const uint32_t *labels, const uint32_t *death,
+                                const uint32_t *hook, const HistoryTable &tab, uint32_t *out, size_t plane_stride, size_t n,
+                                const HistoryStack &st) {
+  if (n == 0 || tab.n == 0) return hipSuccess;
+  if (st.plane == 0 || n % st.plane != 0 || n > 0xFFFFFFFFull) return hipErrorInvalidValue;      // (slice indices are u32 divisions)
+  const unsigned blocks = (unsigned)std::min<size_t>((n / 4 + 255) / 256 + 1, 16384);
+  if (merging) k_render_history<true, true><<<blocks, 256, 0, s>>>(keys, labels, death, hook, tab, out, plane_stride, n, st);
+  else k_render_history<false, true><<<blocks, 256, 0, s>>>(keys, labels, nullptr, nullptr, tab, out, plane_stride, n, st);
   return hipGetLastError();
 }
 

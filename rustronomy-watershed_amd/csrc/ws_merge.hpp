@@ -110,6 +110,16 @@ struct HistoryTable {
 // being the segmenting one or (merging) the lake's canonical id at L found up the stamped forest
 hipError_t render_history(hipStream_t s, bool merging, const uint32_t *keys, const uint32_t *labels, const uint32_t *death, const uint32_t *hook,
                           const HistoryTable &tab, uint32_t *out, size_t plane_stride, size_t n);
+// the same over slices [k0, k1) of a stack (ws_transform_history_batch_device): keys / labels from slice k0 on, n = (k1 - k0) *
+// plane pixels (below 2^32), labels in each slice's own colours; base: the colour bases of slices k0 .. k1 in the forest's
+// numbering (merging only); plane kr * per_slice + slot of out is slice k0 + kr's plane of the table's slot
+struct HistoryStack {
+  const uint32_t *base;
+  uint32_t plane, per_slice;
+};
+hipError_t render_history_stack(hipStream_t s, bool merging, const uint32_t *keys, const uint32_t *labels, const uint32_t *death,
+                                const uint32_t *hook, const HistoryTable &tab, uint32_t *out, size_t plane_stride, size_t n,
+                                const HistoryStack &st);
 
 // A stack of n_slices slices of slice_h x w pixels flooded as one plane (labels restart at 1 in every slice; base: n_slices + 1
 // words, colour c of slice k is c + base[k] in the stack's numbering).

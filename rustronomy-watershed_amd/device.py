@@ -269,5 +269,30 @@ class DeviceEngine:
                                                               lv.ctypes.data, lv.size, out.data_ptr(), ph * pw))
         return out
 
+    def transform_history_batch(self, cube, seeds, seed_offsets, levels=None, merging=False, max_level=254, edge=False, out=None):
+        """transform_history of every slice of a cube for the water levels in `levels` (any order, repeats allowed, at most 256;
+        None: 0..=max_level) with everything in HBM (ws_transform_history_batch_device); cube, seeds and seed_offsets as
+        transform_to_list_batch.  Returns an (S, K, H', W') int32 tensor: out[k, j] is transform_history(cube[k], its seeds,
+        levels)[j], in the slice's own colours.  `out`: a reusable (S, K, H', W') int32 device tensor."""
+        from .api import _history_levels
+        lv = _history_levels(levels, max_level)
+        offs = self._batch_args(cube, seeds, seed_offsets)
+        s, h, w = cube.shape
+        e = 2 if edge else 0
+        shape = (s, lv.size, h + e, w + e)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int32, device=self.device)
+        elif out.dtype != torch.int32 or not out.is_contiguous() or tuple(out.shape) != shape:
+            raise ValueError(f"out must be a contiguous int32 tensor of shape {shape}")
+        if lv.size == 0 or s == 0:
+            return out
+        opt = self.options(max_level, edge)
+        failed = ctypes.c_size_t(0)
+        self.ctx.check(_ffi.lib().ws_transform_history_batch_device(self.ctx.handle, int(merging), cube.data_ptr(), s, h, w, w, h * w,
+                                                                    seeds.data_ptr() if seeds.numel() else None, offs, ctypes.byref(opt),
+                                                                    lv.ctypes.data, lv.size, out.data_ptr(), (h + e) * (w + e),
+                                                                    ctypes.byref(failed)))
+        return out
+
     def stats(self):
         return self.ctx.stats()
