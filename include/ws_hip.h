@@ -140,6 +140,15 @@ typedef struct ws_lake {
   uint64_t area;
 } ws_lake;
 
+/* One record of the merging transform's lake hierarchy (ws_merge_tree): record c belongs to seed colour c. */
+#define WS_TREE_ALIVE 0xFFFFFFFFu
+typedef struct ws_tree_node {
+  uint32_t parent;       /* canonical id of the lake that swallowed this one; 0 if none */
+  uint32_t death_level;  /* first water level after which this colour is no lake of its own; WS_TREE_ALIVE if none */
+  uint32_t area;         /* pixels of the lake while it was last its own */
+  uint32_t n_leaves;     /* seed colours in the lake at that moment, itself included */
+} ws_tree_node;
+
 /* ---- context ------------------------------------------------------------------------- */
 
 int ws_abi_version(void);
@@ -401,6 +410,31 @@ int ws_transform_history_device(ws_ctx *ctx, int merging, const uint8_t *d_img, 
 int ws_transform_history(ws_ctx *ctx, int merging, const uint8_t *img, size_t h, size_t w, size_t row_stride,
                          const uint64_t *seeds_rc, size_t n_seeds, const ws_options *opt,
                          const uint8_t *levels, size_t n_levels, uint64_t *out);
+/* The merging transform's lake hierarchy -- which lake swallowed which, after what water level, and how big each was -- as one
+ * record per seed colour, from one flood and one run of the stamping per-level unions of ws_transform_history_device(merging);
+ * no plane is written.  d_tree: n_seeds + 1 records in HBM, record c for colour c (the c-th seed, from 1).  With P_L the
+ * canonical merging plane after level L (ws_transform_history_device's) and "c exists" meaning that c's seed pixel carries c
+ * right after seeding (a later seed on the same pixel overwrites, lib.rs:1670-1677):
+ *   death_level  the first L in 0 ..= max_water_level with P_L[seed pixel of c] != c, WS_TREE_ALIVE if there is none;
+ *   parent       that value, the canonical id (smallest seed colour) of the lake c went into: 0 < parent < c, and the parent
+ *                dies strictly later or never; 0 if c never died;
+ *   area         pixels equal to c in P_(death_level - 1) (in P_max if c never died; 1 if death_level == 0: the seed alone);
+ *   n_leaves     existing colours whose seed pixel shows c in that plane (1 if death_level == 0).
+ * A colour that does not exist is (0, WS_TREE_ALIVE, 0, 0); record 0 is (0, WS_TREE_ALIVE, pixels of the padded plane still
+ * uncoloured after the last level, 0).  Following `parent` from c while death_level <= L gives P_L at c's seed pixel, so with
+ * the segmenting labels the plane of any level is a table lookup.  d_labels (nullable): receives those labels, the padded h * w
+ * plane of u32 the tree's colours refer to.  Image, strides, seeds, edge correction, seed_shift and duplicate seeds as
+ * ws_merge_device; n_seeds == 0 writes record 0 only.  Null pointers with non-zero sizes, bad options and a context that holds
+ * a begun transform are refused before anything runs.  Returns with the records complete; afterwards ws_last_arrival_device
+ * reports this transform's stamps.  Workspace kept by the context: the merge forest (8 B a colour, as transform_history), the
+ * unions' buckets (at most 20 B a pixel, as transform_to_list), 4 B a colour for the colours ordered by death level and 6 KB of
+ * counters; the records themselves are the accumulators. */
+int ws_merge_tree_device(ws_ctx *ctx, const uint8_t *d_img, size_t h, size_t w, size_t row_stride, const uint32_t *d_seeds_rc,
+                         size_t n_seeds, const ws_options *opt, ws_tree_node *d_tree, uint32_t *d_labels);
+/* The same from and into HOST memory: u64 (row, col) seed pairs, the records into `tree` (n_seeds + 1), the segmenting labels
+ * (nullable) as a u64 plane of the padded shape.  Keeps 16 B a colour more on the device (the records before they cross). */
+int ws_merge_tree(ws_ctx *ctx, const uint8_t *img, size_t h, size_t w, size_t row_stride, const uint64_t *seeds_rc, size_t n_seeds,
+                  const ws_options *opt, ws_tree_node *tree, uint64_t *labels);
 /* transform_history of every slice of a cube for a list of water levels (tests/integration.rs:267,356 take a cube apart slice by
  * slice), everything in HBM.  Slices, seeds, seed_offsets (n_slices + 1 entries, on the HOST), edge correction, duplicate seeds
  * and *failed_slice as ws_transform_to_list_batch_device; levels, n_levels (0: nothing runs, nothing is written), merging and the

@@ -372,6 +372,31 @@ class MergingWatershed : public Watershed<T> {        // lib.rs:1297-1562
     this->template run<int>(input, seeds, nullptr, &out);
     return out;
   }
+  // not in the reference: the lake hierarchy of the merging transform, one record per seed colour (index 0 .. seeds.size()) from
+  // one flood, no plane written (ws_merge_tree): which lake swallowed which, after what water level, how big each was
+  struct MergeTree {
+    static constexpr std::uint32_t ALIVE = WS_TREE_ALIVE;
+    std::vector<ws_tree_node> nodes;
+    Array2<usize> labels;      // the segmenting labels the colours refer to (0 x 0 unless asked for)
+    // colour -> canonical id of its lake after water level `level`: follow `parent` while death_level <= level
+    std::vector<std::uint32_t> roots_at(std::uint32_t level) const {
+      std::vector<std::uint32_t> root(nodes.size());
+      for (std::size_t c = 0; c < nodes.size(); ++c) {
+        std::uint32_t x = std::uint32_t(c);
+        while (nodes[x].death_level <= level) x = nodes[x].parent;
+        root[c] = x;
+      }
+      return root;
+    }
+  };
+  MergeTree merge_tree(ArrayView2<std::uint8_t> input, const std::vector<Seed> &seeds, bool want_labels = false) const {
+    const std::size_t e = this->opt_.edge_correction ? 2 : 0;
+    MergeTree t{std::vector<ws_tree_node>(seeds.size() + 1), Array2<usize>(want_labels ? input.rows + e : 0, want_labels ? input.cols + e : 0)};
+    auto packed = detail::pack(seeds);
+    this->ctx_->check(ws_merge_tree(this->ctx_->get(), input.ptr, input.rows, input.cols, input.row_stride, packed.data(), seeds.size(),
+                                    &this->opt_, t.nodes.data(), want_labels ? t.labels.data.data() : nullptr));
+    return t;
+  }
 
  private:
   template <class U> friend class TransformBuilder;

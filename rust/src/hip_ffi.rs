@@ -30,6 +30,18 @@ pub struct ws_lake {
     pub area: u64,
 }
 
+pub const WS_TREE_ALIVE: u32 = 0xFFFF_FFFF;
+
+/// One record of the merging transform's lake hierarchy (ws_merge_tree); record c belongs to seed colour c.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct ws_tree_node {
+    pub parent: u32,
+    pub death_level: u32,
+    pub area: u32,
+    pub n_leaves: u32,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct ws_stats {
@@ -226,6 +238,10 @@ extern "C" {
         plane_stride: usize) -> c_int;
     pub fn ws_transform_history(ctx: *mut ws_ctx, merging: c_int, img: *const u8, h: usize, w: usize, row_stride: usize,
         seeds_rc: *const u64, n_seeds: usize, opt: *const ws_options, levels: *const u8, n_levels: usize, out: *mut u64) -> c_int;
+    pub fn ws_merge_tree_device(ctx: *mut ws_ctx, d_img: *const u8, h: usize, w: usize, row_stride: usize, d_seeds_rc: *const u32,
+        n_seeds: usize, opt: *const ws_options, d_tree: *mut ws_tree_node, d_labels: *mut u32) -> c_int;
+    pub fn ws_merge_tree(ctx: *mut ws_ctx, img: *const u8, h: usize, w: usize, row_stride: usize, seeds_rc: *const u64,
+        n_seeds: usize, opt: *const ws_options, tree: *mut ws_tree_node, labels: *mut u64) -> c_int;
     pub fn ws_pre_processor_device(ctx: *mut ws_ctx, d_data: *const c_void, dtype: c_int, n_elems: usize,
         max_value: u8, d_out: *mut u8) -> c_int;
     pub fn ws_random_field_device(ctx: *mut ws_ctx, d_img: *mut u8, h: usize, w: usize, row_stride: usize,

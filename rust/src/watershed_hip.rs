@@ -527,6 +527,28 @@ impl<T> Watershed<T> for MergingWatershed<T> {
     }
 }
 
+/// The merging transform's lake hierarchy (`MergingWatershed::merge_tree`): `nodes[c]` is seed colour c's record.
+pub struct MergeTree {
+    pub nodes: Vec<hip_ffi::ws_tree_node>,
+    pub labels: Option<nd::Array2<usize>>,
+}
+
+impl MergeTree {
+    pub const ALIVE: u32 = hip_ffi::WS_TREE_ALIVE;
+    /// colour -> canonical id of its lake after water level `level`: follow `parent` while `death_level <= level`.
+    pub fn roots_at(&self, level: u32) -> Vec<u32> {
+        (0..self.nodes.len() as u32)
+            .map(|c| {
+                let mut x = c;
+                while self.nodes[x as usize].death_level <= level {
+                    x = self.nodes[x as usize].parent;
+                }
+                x
+            })
+            .collect()
+    }
+}
+
 impl<T> MergingWatershed<T> {
     /// Not in the reference: the merging `transform_to_list(cube[k], &find_local_minima(cube[k]))` of every slice of a cube as one
     /// call; as `SegmentingWatershed::transform_to_list_cube`.
@@ -537,6 +559,26 @@ impl<T> MergingWatershed<T> {
     /// of canonical ids); as `SegmentingWatershed::transform_history_cube`.
     pub fn transform_history_cube(&self, cube: nd::ArrayView3<u8>, levels: &[u8]) -> (Vec<HistoryPlanes>, Vec<usize>) {
         run_history_cube(true, &self.opt, cube, levels)
+    }
+    /// Not in the reference: the lake hierarchy of the merging transform -- which lake swallowed which, after what water level,
+    /// how big each was -- as one record per seed colour (index 0 ..= seeds.len()) from one flood; no plane is written
+    /// (`ws_merge_tree`).  With `want_labels` also the segmenting label plane the colours refer to.
+    pub fn merge_tree(&self, input: nd::ArrayView2<u8>, seeds: &[(usize, usize)], want_labels: bool) -> MergeTree {
+        let (h, w) = input.dim();
+        let (std_img, stride) = shim::standard(&input);
+        let packed = shim::pack_seeds(seeds);
+        let o = self.opt.ffi();
+        let mut nodes = vec![hip_ffi::ws_tree_node::default(); seeds.len() + 1];
+        let mut labels = if want_labels { Some(nd::Array2::<usize>::zeros(self.opt.plane(h, w))) } else { None };
+        let lab_ptr = match labels.as_mut() {
+            Some(a) => a.as_slice_mut().expect("standard layout").as_mut_ptr() as *mut u64,
+            None => std::ptr::null_mut(),
+        };
+        shim::with_ctx(|ctx| unsafe {
+            let rc = hip_ffi::ws_merge_tree(ctx, std_img.as_ptr(), h, w, stride, packed.as_ptr(), seeds.len(), &o, nodes.as_mut_ptr(), lab_ptr);
+            shim::check(ctx, rc, "ws_merge_tree");
+        });
+        MergeTree { nodes, labels }
     }
     /// Not in the reference: the merged label plane after the last level (canonical ids: the smallest seed colour of
     /// every lake).  The reference's own `transform` is the stub above.

@@ -67,6 +67,14 @@ class Lake(ctypes.Structure):
     _fields_ = [("colour", ctypes.c_uint64), ("area", ctypes.c_uint64)]
 
 
+WS_TREE_ALIVE = 0xFFFFFFFF
+
+
+class TreeNode(ctypes.Structure):
+    """ws_tree_node: one record of the merging transform's lake hierarchy (ws_merge_tree)."""
+    _fields_ = [("parent", ctypes.c_uint32), ("death_level", ctypes.c_uint32), ("area", ctypes.c_uint32), ("n_leaves", ctypes.c_uint32)]
+
+
 class TileBlock(ctypes.Structure):
     """ws_tile_block: one rank's row block of a tiled field, device resident."""
     _fields_ = [("d_img", vp), ("d_seeds_rc", vp), ("d_colours", vp), ("n_seeds", sz),
@@ -142,6 +150,8 @@ SIGNATURES = {
                                                          vp, sz, vp, sz, szp]),
     "ws_transform_history_batch": (ctypes.c_int, [vp, ctypes.c_int, vp, sz, sz, sz, sz, sz, vp, szp, ctypes.POINTER(Options),
                                                   vp, sz, vp, szp, szp]),
+    "ws_merge_tree_device": (ctypes.c_int, [vp, vp, sz, sz, sz, vp, sz, ctypes.POINTER(Options), vp, vp]),
+    "ws_merge_tree": (ctypes.c_int, [vp, vp, sz, sz, sz, vp, sz, ctypes.POINTER(Options), vp, vp]),
     "ws_pre_processor": (ctypes.c_int, [vp, vp, ctypes.c_int, sz, ctypes.c_uint8, vp]),
     "ws_pre_processor_device": (ctypes.c_int, [vp, vp, ctypes.c_int, sz, ctypes.c_uint8, vp]),
     "ws_block_init": (ctypes.c_int, [vp, sz, sz, vp, vp, sz, vp, vp]),

@@ -164,6 +164,39 @@ def _history_levels(levels, max_level):
     return np.ascontiguousarray(lv, dtype=np.uint8)
 
 
+class MergeTree:
+    """The merging transform's lake hierarchy (ws_merge_tree): numpy arrays indexed by seed colour, 0 .. n_seeds.
+    `parent`: canonical id of the lake that swallowed the colour (0: none); `death_level`: the first water level after which the
+    colour is no lake of its own (ALIVE: none); `area`, `n_leaves`: pixels and seed colours of the lake while it was last its
+    own.  `labels`: the segmenting label plane the colours refer to, when it was asked for."""
+    ALIVE = _ffi.WS_TREE_ALIVE
+    __slots__ = ("parent", "death_level", "area", "n_leaves", "labels")
+
+    def __init__(self, parent, death_level, area, n_leaves, labels=None):
+        self.parent = np.asarray(parent, dtype=np.uint32)
+        self.death_level = np.asarray(death_level, dtype=np.uint32)
+        self.area = np.asarray(area, dtype=np.uint32)
+        self.n_leaves = np.asarray(n_leaves, dtype=np.uint32)
+        self.labels = labels
+
+    def roots_at(self, level):
+        """colour -> canonical id of its lake after water level `level`: follow `parent` while death_level <= level.
+        roots_at(L)[labels] is the merging label plane of level L wherever that plane is coloured."""
+        root = np.arange(self.parent.size, dtype=np.uint32)
+        dead = self.death_level[root] <= level
+        while dead.any():          # parents die strictly later: at most one step per level
+            root[dead] = self.parent[root[dead]]
+            dead = self.death_level[root] <= level
+        return root
+
+    def children(self):
+        """{colour: sorted array of the colours it swallowed}, for the colours that swallowed any."""
+        dying = np.flatnonzero(self.death_level != self.ALIVE)
+        order = dying[np.argsort(self.parent[dying], kind="stable")]
+        keys, first = np.unique(self.parent[order], return_index=True)
+        return {int(k): part for k, part in zip(keys, np.split(order, first[1:]))}
+
+
 class TransformBuilder:
     """lib.rs:908-1047.  `TransformBuilder()` is both `new()` and `default()`."""
 
@@ -578,3 +611,16 @@ class MergingWatershed(_Transform):
     def transform_final(self, input, seeds):
         """Not in the reference: the merged label plane after the last level."""
         return self._run_with_hook(input, seeds, None, True)[1]
+
+    def merge_tree(self, input, seeds, want_labels=False):
+        """Not in the reference: the lake hierarchy of the merging transform as a MergeTree -- one record per seed colour from one
+        flood, no plane written (ws_merge_tree).  want_labels: also the segmenting label plane (u64) the colours refer to."""
+        a, stride = _as_image(input)
+        s, ns = _as_seeds(seeds)
+        h, w = a.shape
+        tree = np.empty((ns + 1, 4), dtype=np.uint32)
+        labels = np.empty(self._shape(a), dtype=np.uint64) if want_labels else None
+        ctx = self._ctx()
+        ctx.check(_ffi.lib().ws_merge_tree(ctx.handle, a.ctypes.data, h, w, stride, s.ctypes.data, ns, ctypes.byref(self._opt),
+                                           tree.ctypes.data, labels.ctypes.data if want_labels else None))
+        return MergeTree(tree[:, 0].copy(), tree[:, 1].copy(), tree[:, 2].copy(), tree[:, 3].copy(), labels)

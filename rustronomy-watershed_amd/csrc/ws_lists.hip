@@ -564,6 +564,43 @@ int render_levels(ws_ctx *c, bool merging, const HistoryTable &tab, uint32_t *d_
   return WS_OK;
 }
 
+// ---- merge_tree: the hierarchy of the merging transform -----------------------------------------------------
+
+static_assert(sizeof(ws_tree_node) == sizeof(TreeRec) && WS_TREE_ALIVE == TREE_ALIVE, "ws_tree_node is the kernels' TreeRec");
+
+// what both forms check before anything runs
+int check_tree(ws_ctx *c, size_t h, size_t w, size_t stride, const ws_options *opt, size_t n_seeds, size_t *ph, size_t *pw) {
+  if (int rc = check_plane(c, h, w, stride, opt, ph, pw)) return rc;
+  if (n_seeds >= 0xFFFFFFFFull) return fail(c, WS_ERR_TOO_LARGE, "too many seeds");
+  return WS_OK;
+}
+
+// every buffer the tree needs, BEFORE the transform: a buffer that moves bumps the context's generation, and the level loop's
+// captured graphs are keyed by it
+int ensure_tree(ws_ctx *c, size_t n_seeds, bool host_records) {
+  int rc;
+  if ((rc = ensure(c, c->tree_order, (n_seeds + 1) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, c->tree_ws, TREE_WS_WORDS * sizeof(u64c)))) return rc;
+  if (host_records && (rc = ensure(c, c->tree_out, (n_seeds + 1) * sizeof(ws_tree_node)))) return rc;
+  return WS_OK;
+}
+
+// the records from the transform merge_host(merging, history) has just run on this context
+int build_tree(ws_ctx *c, const uint32_t *d_seeds, size_t n_seeds, const ws_options *opt, size_t ph, size_t pw, ws_tree_node *d_tree) {
+  const uint32_t levels = (uint32_t)opt->max_water_level + 1;
+  const uint32_t *death = (const uint32_t *)c->uf_death.p, *hook = (const uint32_t *)c->uf_hook.p;
+  const uint32_t *keys = (const uint32_t *)c->keys.p, *seg = (const uint32_t *)c->labels.p;
+  u64c *ws = (u64c *)c->tree_ws.p;
+  TreeRec *tree = reinterpret_cast<TreeRec *>(d_tree);
+  Span sp(c, KC_OTHER);
+  HIP_TRY(c, hipMemsetAsync(ws, 0, TREE_WS_WORDS * sizeof(u64c), c->stream));
+  // (MF_OFF_PX + levels: the pixels that arrived at levels 0 .. max_water_level)
+  HIP_TRY(c, tree_init(c->stream, death, hook, d_seeds, seg, (int)ph, (int)pw, (const u64c *)c->mflags.p + MF_OFF_PX + levels, tree, n_seeds + 1, ws));
+  HIP_TRY(c, tree_own_counts(c->stream, keys, seg, death, hook, tree, ph * pw));
+  HIP_TRY(c, tree_fold(c->stream, tree, n_seeds + 1, levels, ws, (uint32_t *)c->tree_order.p));
+  return WS_OK;
+}
+
 // ---- transform_history of a cube of slices (ws_transform_history_batch(_device)) ---------------------------------------------------
 
 // The transform of slices [k_first, k_first + g) of a batch, left on the context for rendering: a stack (labels restart at 1 in every
@@ -760,6 +797,48 @@ int ws_transform_history(ws_ctx *c, int merging, const uint8_t *img, size_t h, s
         if (int rc = labels_to_host_u64(c, planes + (k - k0) * n, out + k * n, n)) return rc;
     }
   }
+  return WS_OK;
+}
+
+int ws_merge_tree_device(ws_ctx *c, const uint8_t *d_img, size_t h, size_t w, size_t stride, const uint32_t *d_seeds_rc, size_t n_seeds,
+                         const ws_options *opt, ws_tree_node *d_tree, uint32_t *d_labels) {
+  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
+  if (!c) return WS_ERR_BAD_ARG;
+  if (!opt || !d_tree || (!d_img && h * w) || (!d_seeds_rc && n_seeds)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  size_t ph = 0, pw = 0;
+  if (int rc = check_tree(c, h, w, stride, opt, n_seeds, &ph, &pw)) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (int rc = ensure_tree(c, n_seeds, false)) return rc;
+  const DeviceLists dev{d_img, d_seeds_rc, nullptr};
+  if (int rc = merge_host(c, true, nullptr, h, w, stride, nullptr, n_seeds, opt, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
+                          &dev, true))
+    return rc;
+  // the seed pairs as the flood took them: the caller's, or (shifted_seeds) moved into the padded plane in the context's buffer
+  const uint32_t *seeds = seed_shift_of(opt) && n_seeds ? (const uint32_t *)c->seeds.p : d_seeds_rc;
+  if (int rc = build_tree(c, seeds, n_seeds, opt, ph, pw, d_tree)) return rc;
+  if (d_labels && ph * pw) HIP_TRY(c, hipMemcpyAsync(d_labels, c->labels.p, ph * pw * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return WS_OK;
+}
+
+int ws_merge_tree(ws_ctx *c, const uint8_t *img, size_t h, size_t w, size_t stride, const uint64_t *seeds_rc, size_t n_seeds,
+                  const ws_options *opt, ws_tree_node *tree, uint64_t *labels) {
+  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
+  if (!c) return WS_ERR_BAD_ARG;
+  if (!opt || !tree || (!img && h * w) || (!seeds_rc && n_seeds)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  size_t ph = 0, pw = 0;
+  if (int rc = check_tree(c, h, w, stride, opt, n_seeds, &ph, &pw)) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (int rc = ensure_tree(c, n_seeds, true)) return rc;
+  if (int rc = merge_host(c, true, img, h, w, stride, seeds_rc, n_seeds, opt, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
+                          nullptr, true))
+    return rc;
+  const uint32_t *seeds = (const uint32_t *)c->seeds.p;      // stage_inputs: narrowed, shifted where the options say so
+  if (int rc = build_tree(c, seeds, n_seeds, opt, ph, pw, (ws_tree_node *)c->tree_out.p)) return rc;
+  HIP_TRY(c, hipMemcpyAsync(tree, c->tree_out.p, (n_seeds + 1) * sizeof(ws_tree_node), hipMemcpyDeviceToHost, c->stream));
+  if (labels && ph * pw)
+    if (int rc = labels_to_host_u64(c, (const uint32_t *)c->labels.p, labels, ph * pw)) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
   return WS_OK;
 }
 

@@ -1365,6 +1365,237 @@ hipError_t render_history_stack(hipStream_t s, bool merging, const uint32_t *key
   return hipGetLastError();
 }
 
+// ---- merge tree (ws_merge_tree_device) ----------------------------------------------------------------------------------------------
+//
+// The stamped forest of a merging transform_history run IS the lake hierarchy, up to two things: hook[b] is whatever root the racing
+// CAS read, not the canonical id, and nothing has counted pixels.  Three steps turn it into one record per colour:
+// canonical parents (one walk per colour), own counts (one pass over the stamps), and a fold up the tree in ascending death level.
+
+constexpr int TREE_PER_THREAD = 16;      // colours per thread of the per-colour kernels: a workgroup adds once per level to 256 shared counters
+constexpr int TREE_CHUNK = 256 * TREE_PER_THREAD;
+
+__global__ __launch_bounds__(256) void k_tree_init(const uint32_t *__restrict__ death, const uint32_t *__restrict__ hook,
+                                                   const uint32_t *__restrict__ seeds_rc, const uint32_t *__restrict__ seg, int H, int W,
+                                                   const u64c *__restrict__ arrived, TreeRec *tree, size_t n_colours, u64c *hist) {
+  __shared__ uint32_t s_h[NLEVELS];
+  s_h[threadIdx.x] = 0;
+  __syncthreads();
+  for (int k = 0; k < TREE_PER_THREAD; ++k) {
+    const size_t c = (size_t)blockIdx.x * TREE_CHUNK + (size_t)k * 256 + threadIdx.x;
+    if (c >= n_colours) break;
+    TreeRec r{0u, TREE_ALIVE, 0u, 0u};
+    if (c == 0) {
+      r.area = (uint32_t)((u64c)H * (u64c)W - arrived[0]);      // what the last level left uncoloured
+    } else {
+      const uint32_t y = seeds_rc[2 * (c - 1)], x = seeds_rc[2 * (c - 1) + 1];
+      // a later seed on the same pixel overwrites (lib.rs:1670-1677): such a colour never was
+      r.n_leaves = y < (uint32_t)H && x < (uint32_t)W && seg[(size_t)y * W + x] == (uint32_t)c ? 1u : 0u;
+      const uint32_t d = death[c];
+      if (d != TREE_ALIVE) {
+        uint32_t p = hook[c];
+        while (death[p] <= d) p = hook[p];      // <=: a colour that dies at the same level is not that level's root
+        r.parent = p;
+        r.death_level = d;
+        atomicAdd(&s_h[d & (NLEVELS - 1)], 1u);
+      }
+    }
+    tree[c] = r;
+  }
+  __syncthreads();
+  if (s_h[threadIdx.x]) atomicAdd(&hist[threadIdx.x], (u64c)s_h[threadIdx.x]);
+}
+
+hipError_t tree_init(hipStream_t s, const uint32_t *death, const uint32_t *hook, const uint32_t *seeds_rc, const uint32_t *seg_labels, int h, int w,
+                     const u64c *arrived, TreeRec *tree, size_t n_colours, u64c *ws) {
+  if (n_colours == 0) return hipSuccess;
+  k_tree_init<<<(unsigned)((n_colours + TREE_CHUNK - 1) / TREE_CHUNK), 256, 0, s>>>(death, hook, seeds_rc, seg_labels, h, w, arrived, tree, n_colours, ws);
+  return hipGetLastError();
+}
+
+// Own counts.  Around the percolation level most pixels of the plane land on ONE root, and a same-address atomic retires every ~12 ns:
+// a workgroup takes a contiguous run of pixels, counts in an LDS table keyed by root (a wave first adds up the lanes that agree with
+// its first lane) and adds to memory once per root it met.  A root that finds no slot within OWN_PROBES adds for itself: exact either way.
+constexpr int OWN_SLOTS = 2048, OWN_PROBES = 4;
+constexpr uint32_t OWN_EMPTY = 0xFFFFFFFFu;
+
+__device__ __forceinline__ void own_add(uint32_t *s_key, uint32_t *s_cnt, TreeRec *tree, uint32_t r, uint32_t k) {
+  const uint32_t h0 = (r * 2654435761u) >> 21;      // 11 bits
+  for (int j = 0; j < OWN_PROBES; ++j) {
+    const uint32_t slot = (h0 + (uint32_t)j) & (OWN_SLOTS - 1);
+    const uint32_t old = atomicCAS(&s_key[slot], OWN_EMPTY, r);
+    if (old == OWN_EMPTY || old == r) { atomicAdd(&s_cnt[slot], k); return; }
+  }
+  atomicAdd(&tree[r].area, k);
+}
+
+__global__ __launch_bounds__(256) void k_tree_own(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ labels,
+                                                  const uint32_t *__restrict__ death, const uint32_t *__restrict__ hook, TreeRec *tree,
+                                                  size_t n, size_t steps) {
+  __shared__ uint32_t s_key[OWN_SLOTS], s_cnt[OWN_SLOTS];
+  for (int j = threadIdx.x; j < OWN_SLOTS; j += 256) { s_key[j] = OWN_EMPTY; s_cnt[j] = 0; }
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const bool vec = ((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(labels)) & 15u) == 0;
+  for (size_t st = 0; st < steps; ++st) {      // workgroup uniform
+    const size_t i0 = (((size_t)blockIdx.x * steps + st) * 256 + threadIdx.x) * 4;
+    uint32_t arr[4], col[4];
+    if (vec && i0 + 3 < n) {
+      const u32x4_m k = *reinterpret_cast<const u32x4_m *>(keys + i0), l = *reinterpret_cast<const u32x4_m *>(labels + i0);
+      arr[0] = k.x >> 24; arr[1] = k.y >> 24; arr[2] = k.z >> 24; arr[3] = k.w >> 24;
+      col[0] = l.x; col[1] = l.y; col[2] = l.z; col[3] = l.w;
+    } else {
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        const bool in = i0 + p < n;
+        arr[p] = in ? keys[i0 + p] >> 24 : 0xFFu;
+        col[p] = in ? labels[i0 + p] : 0u;
+      }
+    }
+    // the four walks side by side (a walk is a chain of dependent gathers: one after the other they were most of the kernel)
+    uint32_t r[4], d[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      r[p] = col[p];
+      d[p] = col[p] != 0u && arr[p] != 0xFFu ? death[col[p]] : TREE_ALIVE;      // (as k_render_history: KEY_INF and colour 0 are never shown)
+    }
+    for (;;) {      // the root at the pixel's arrival level
+      bool go[4];
+#pragma unroll
+      for (int p = 0; p < 4; ++p) go[p] = d[p] <= arr[p];
+      if (!(go[0] || go[1] || go[2] || go[3])) break;
+#pragma unroll
+      for (int p = 0; p < 4; ++p) if (go[p]) r[p] = hook[r[p]];
+#pragma unroll
+      for (int p = 0; p < 4; ++p) if (go[p]) d[p] = death[r[p]];
+    }
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const bool active = col[p] != 0u && arr[p] != 0xFFu;
+      const unsigned long long todo = __builtin_amdgcn_ballot_w64(active);
+      if (todo == 0) continue;      // wave uniform
+      const int leader = (int)__builtin_ctzll(todo);
+      const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)r[p], leader);
+      const unsigned long long same = __builtin_amdgcn_ballot_w64(active && r[p] == r0);
+      if (lane == leader) own_add(s_key, s_cnt, tree, r0, (uint32_t)__popcll(same));
+      else if (active && r[p] != r0) own_add(s_key, s_cnt, tree, r[p], 1u);
+    }
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < OWN_SLOTS; j += 256)
+    if (s_cnt[j]) atomicAdd(&tree[s_key[j]].area, s_cnt[j]);
+}
+
+hipError_t tree_own_counts(hipStream_t s, const uint32_t *keys, const uint32_t *labels, const uint32_t *death, const uint32_t *hook, TreeRec *tree, size_t n) {
+  if (n == 0) return hipSuccess;
+  // at most two thousand workgroups on a large plane (that many adds reach the surviving lake's word), 1024 pixels a step
+  const size_t quads = (n + 1023) / 1024;
+  const size_t steps = std::max<size_t>((quads + 2047) / 2048, 1);
+  k_tree_own<<<(unsigned)((quads + steps - 1) / steps), 256, 0, s>>>(keys, labels, death, hook, tree, n, steps);
+  return hipGetLastError();
+}
+
+// bounds of the death levels' buckets (ws + NLEVELS + 1: NLEVELS + 1 words) and the scatter's cursors (behind them), from the counts
+__global__ __launch_bounds__(NLEVELS) void k_tree_offsets(u64c *ws) {
+  __shared__ u64c s_a[NLEVELS];
+  const int t = threadIdx.x;
+  const u64c a0 = ws[t];
+  s_a[t] = a0;
+  __syncthreads();
+  for (int o = 1; o < NLEVELS; o <<= 1) {
+    const u64c a = t >= o ? s_a[t - o] : 0ull;
+    __syncthreads();
+    s_a[t] += a;
+    __syncthreads();
+  }
+  u64c *off = ws + NLEVELS + 1, *cur = off + NLEVELS + 1;
+  off[t] = cur[t] = s_a[t] - a0;
+  if (t == NLEVELS - 1) off[NLEVELS] = s_a[t];
+}
+
+// order[]: the dying colours by death level; a workgroup reserves once per level for its TREE_CHUNK colours
+__global__ __launch_bounds__(256) void k_tree_scatter(const TreeRec *__restrict__ tree, size_t n_colours, u64c *cursor, uint32_t *order) {
+  __shared__ uint32_t s_n[NLEVELS];
+  __shared__ u64c s_base[NLEVELS];
+  s_n[threadIdx.x] = 0;
+  __syncthreads();
+  uint32_t d[TREE_PER_THREAD];
+#pragma unroll
+  for (int k = 0; k < TREE_PER_THREAD; ++k) {
+    const size_t c = (size_t)blockIdx.x * TREE_CHUNK + (size_t)k * 256 + threadIdx.x;
+    d[k] = c < n_colours ? tree[c].death_level : TREE_ALIVE;
+    if (d[k] != TREE_ALIVE) atomicAdd(&s_n[d[k] & (NLEVELS - 1)], 1u);
+  }
+  __syncthreads();
+  {
+    const uint32_t cnt = s_n[threadIdx.x];
+    s_base[threadIdx.x] = cnt ? atomicAdd(&cursor[threadIdx.x], (u64c)cnt) : 0ull;
+  }
+  __syncthreads();
+  s_n[threadIdx.x] = 0;
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < TREE_PER_THREAD; ++k) {
+    if (d[k] == TREE_ALIVE) continue;
+    const uint32_t l = d[k] & (NLEVELS - 1);
+    order[s_base[l] + atomicAdd(&s_n[l], 1u)] = (uint32_t)((size_t)blockIdx.x * TREE_CHUNK + (size_t)k * 256 + threadIdx.x);
+  }
+}
+
+// One death level: every colour of the bucket hands its area and its leaves to its parent.  Late levels hand thousands of lakes to ONE
+// parent: a wave adds up the lanes that share a parent (two rounds of leader election) before it adds, as k_fold_and_add_sd does.
+// A colour that dies at level 0 never was a lake after a flood: it hands on no pixel (its seed pixel was counted for the root of
+// level 0) and keeps area 1, the seed alone.
+__global__ __launch_bounds__(256) void k_tree_fold(TreeRec *tree, const uint32_t *__restrict__ order, const u64c *__restrict__ range, uint32_t level) {
+  const u64c first = range[0];
+  const size_t n = (size_t)(range[1] - first);
+  const int lane = threadIdx.x & 63;
+  order += first;
+  for (size_t base = (size_t)blockIdx.x * 256; base < n; base += (size_t)gridDim.x * 256) {      // uniform trip count per wave
+    const size_t i = base + threadIdx.x;
+    const bool active = i < n;
+    const uint32_t c = active ? order[i] : 0u;
+    uint32_t p = 0xFFFFFFFFu, area = 0, leaves = 0;
+    if (active) {
+      const TreeRec r = tree[c];
+      p = r.parent; area = r.area; leaves = r.n_leaves;
+      if (level == 0) tree[c].area = 1u;
+    }
+    unsigned long long todo = __builtin_amdgcn_ballot_w64(active);
+    for (int round = 0; round < 2 && todo != 0; ++round) {
+      const int leader = (int)__builtin_ctzll(todo);
+      const uint32_t p0 = (uint32_t)__builtin_amdgcn_readlane((int)p, leader);
+      const bool same = active && p == p0;
+      const uint32_t sa = wave_sum_u32(same ? area : 0u), sl = wave_sum_u32(same ? leaves : 0u);
+      if (lane == leader) {
+        if (sa) atomicAdd(&tree[p0].area, sa);
+        if (sl) atomicAdd(&tree[p0].n_leaves, sl);
+      }
+      todo &= ~__builtin_amdgcn_ballot_w64(same);
+    }
+    if ((todo >> lane) & 1ull) {
+      if (area) atomicAdd(&tree[p].area, area);
+      if (leaves) atomicAdd(&tree[p].n_leaves, leaves);
+    }
+  }
+}
+
+hipError_t tree_fold(hipStream_t s, TreeRec *tree, size_t n_colours, uint32_t levels, u64c *ws, uint32_t *order) {
+  if (n_colours <= 1) return hipSuccess;
+  k_tree_offsets<<<1, NLEVELS, 0, s>>>(ws);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  u64c *off = ws + NLEVELS + 1;
+  k_tree_scatter<<<(unsigned)((n_colours + TREE_CHUNK - 1) / TREE_CHUNK), 256, 0, s>>>(tree, n_colours, off + NLEVELS + 1, order);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  // a level's bucket is known on the device only: a fixed grid that strides (an even spread would be colours / levels per level)
+  const unsigned grid = (unsigned)std::min<size_t>(std::max<size_t>(n_colours / (256 * 64), 1), 128);
+  for (uint32_t l = 0; l < levels; ++l) {
+    k_tree_fold<<<grid, 256, 0, s>>>(tree, order, off + l, l);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
 // ---- a stack of slices (ws_transform_to_list_batch_device, ws_merge_batch_device) --------------------------------------------
 //
 // The slices of a cube flooded as ONE plane of g x slice_h rows (ws_segment.hip, segment_batch_stacked): labels restart at 1 in

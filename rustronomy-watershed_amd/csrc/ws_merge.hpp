@@ -133,4 +133,22 @@ hipError_t split_records(hipStream_t s, bool scatter, const uint64_t *rec, size_
 hipError_t merge_stack(hipStream_t s, uint32_t *labels, int slice_h, int w, size_t n_slices, const uint32_t *base, uint32_t *parent,
                        size_t n_colours);
 
+// merge tree (ws_merge_tree_device): one record per seed colour from the stamped forest (death / hook) of a merging transform_history
+// run, the flood's stamps and segmenting colours.  The records are their own accumulators: area and n_leaves are added to in place.
+constexpr uint32_t TREE_ALIVE = 0xFFFFFFFFu;
+struct TreeRec {      // == ws_tree_node
+  uint32_t parent, death_level, area, n_leaves;
+};
+constexpr int TREE_WS_WORDS = 3 * (NLEVELS + 1);      // u64 words of scratch: deaths per level, their prefix sums, the scatter's cursors
+// every record: death level, canonical parent (the walk from hook[c] while death[x] <= death[c]), n_leaves = 1 where the seed pixel
+// of c carries c (seeds_rc: n_colours - 1 pairs in the plane's own coordinates), area 0; record 0: n - arrived[0] uncoloured pixels.
+// ws: TREE_WS_WORDS zeroed words; ws[l] += colours that die at level l
+hipError_t tree_init(hipStream_t s, const uint32_t *death, const uint32_t *hook, const uint32_t *seeds_rc, const uint32_t *seg_labels, int h, int w,
+                     const u64c *arrived, TreeRec *tree, size_t n_colours, u64c *ws);
+// tree[r].area += 1 for every coloured pixel, r = the root of its colour at its arrival level
+hipError_t tree_own_counts(hipStream_t s, const uint32_t *keys, const uint32_t *labels, const uint32_t *death, const uint32_t *hook, TreeRec *tree, size_t n);
+// order[]: the colours that die, bucketed by death level (bounds: ws[NLEVELS + 1 + l]); then level by level, ascending, every dying
+// colour hands area and n_leaves to its parent (children die strictly before their parents)
+hipError_t tree_fold(hipStream_t s, TreeRec *tree, size_t n_colours, uint32_t levels, u64c *ws, uint32_t *order);
+
 }  // namespace wsk

@@ -294,5 +294,24 @@ class DeviceEngine:
                                                                     ctypes.byref(failed)))
         return out
 
+    def merge_tree(self, img, seeds, max_level=254, edge=False, seed_shift=False, want_labels=False, out=None):
+        """The merging transform's lake hierarchy with everything in HBM (ws_merge_tree_device): an (n_seeds + 1, 4) int32 tensor
+        whose row c is colour c's (parent, death_level, area, n_leaves) -- uint32 bits, death_level -1 = never died.  With
+        want_labels also the segmenting (H', W') int32 label plane the colours refer to: returns (tree, labels).  `out`: a
+        reusable contiguous (n_seeds + 1, 4) int32 device tensor."""
+        assert img.dtype == torch.uint8 and img.dim() == 2 and img.is_contiguous() and img.is_cuda
+        assert seeds.dtype == torch.int32 and seeds.is_cuda and (seeds.numel() == 0 or seeds.is_contiguous())
+        h, w = img.shape
+        ns = seeds.shape[0] if seeds.dim() == 2 else 0
+        if out is None:
+            out = torch.empty((ns + 1, 4), dtype=torch.int32, device=self.device)
+        elif out.dtype != torch.int32 or not out.is_contiguous() or tuple(out.shape) != (ns + 1, 4):
+            raise ValueError(f"out must be a contiguous int32 tensor of shape {(ns + 1, 4)}")
+        labels = torch.empty(self._plane(img, edge), dtype=torch.int32, device=self.device) if want_labels else None
+        opt = self.options(max_level, edge, None, seed_shift)
+        self.ctx.check(_ffi.lib().ws_merge_tree_device(self.ctx.handle, img.data_ptr(), h, w, w, seeds.data_ptr() if ns else None, ns,
+                                                       ctypes.byref(opt), out.data_ptr(), labels.data_ptr() if want_labels else None))
+        return (out, labels) if want_labels else out
+
     def stats(self):
         return self.ctx.stats()
