@@ -459,6 +459,33 @@ int ws_transform_history_batch(ws_ctx *ctx, int merging, const uint8_t *cube, si
                                size_t row_stride, size_t slice_stride, const uint64_t *seeds_rc, const size_t *seed_offsets,
                                const ws_options *opt, const uint8_t *levels, size_t n_levels,
                                uint64_t *out, size_t *n_seeds, size_t *failed_slice);
+/* ws_merge_tree_device of every slice of a cube in one call, everything in HBM.  Slices, seeds, seed_offsets (n_slices + 1 entries,
+ * on the HOST), edge correction, seed_shift, duplicate seeds and *failed_slice as ws_transform_history_batch_device.  Records,
+ * slice-major: slice k with its n_k seeds owns n_k + 1 records from index (seed_offsets[k] - seed_offsets[0]) + k on, record c of
+ * them colour c of the slice's own colours 1 .. n_k, `parent` in those colours too; seed count + n_slices records in all, and no
+ * other word of d_tree is written.  Every record is bit-identical to what ws_merge_tree_device writes for that slice alone: a
+ * slice's record 0 is (0, WS_TREE_ALIVE, pixels of that slice's padded plane still uncoloured after the last level, 0), and a
+ * slice without seeds owns that one record.  d_labels (nullable): the segmenting labels of every slice, n_slices padded planes of
+ * u32 in the slices' own colours (ws_segment_batch_device's).  Null pointers with non-zero sizes, bad options, offsets that
+ * decrease, 0xFFFFFFFF seeds or more and a context that holds a begun transform are refused before anything runs; n_slices == 0
+ * writes nothing.  When the slices stack (as ws_transform_history_batch_device) every group of slices runs as one flood and ONE run
+ * of the stamping per-level unions over the stack's colours -- the captured graphs are those of the stacked history loop -- and
+ * the tree kernels run once over the group: one fold launch per level for all of its slices.  Anything else, and a stack that
+ * fails or mispredicts, runs as a loop of ws_merge_tree_device, which names the failing slice.  Scratch of the stacked form, kept
+ * by the context: as ws_transform_history_batch_device, 16 B a colour of the largest group (its records in the stack's numbering)
+ * and 2 KB a slice of arrival counts.  Statistics are summed over the call's transforms; afterwards ws_last_arrival_device reports
+ * "unsupported". */
+int ws_merge_tree_batch_device(ws_ctx *ctx, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w, size_t row_stride,
+                               size_t slice_stride, const uint32_t *d_seeds_rc, const size_t *seed_offsets, const ws_options *opt,
+                               ws_tree_node *d_tree, uint32_t *d_labels, size_t *failed_slice);
+/* The same from and into HOST memory: the cube and the u64 (row, col) seed pairs as ws_transform_history_batch takes them (seeds_rc
+ * == NULL: every slice's own find_local_minima, n_seeds[k], nullable, receives how many, and the records' offsets are the running
+ * sum of those counts).  `tree` holds `cap` records; *n_records (nullable) receives the total, seed count + n_slices.  cap smaller
+ * than that: WS_ERR_CAPACITY once the minima are found or counted and before any flood -- only *n_records and n_seeds[] are
+ * meaningful then, `tree` and `labels` are untouched.  labels (nullable): n_slices padded planes of u64. */
+int ws_merge_tree_batch(ws_ctx *ctx, const uint8_t *cube, size_t n_slices, size_t h, size_t w, size_t row_stride, size_t slice_stride,
+                        const uint64_t *seeds_rc, const size_t *seed_offsets, const ws_options *opt, ws_tree_node *tree, size_t cap,
+                        size_t *n_records, uint64_t *labels, size_t *n_seeds, size_t *failed_slice);
 
 /* ---- input preparation (first "next" row) ---------------------------------------
  *

@@ -397,6 +397,50 @@ class MergingWatershed : public Watershed<T> {        // lib.rs:1297-1562
                                     &this->opt_, t.nodes.data(), want_labels ? t.labels.data.data() : nullptr));
     return t;
   }
+  // not in the reference: merge_tree of every slice of a contiguous cube (n_slices x rows x cols) as ONE call of the library
+  // (ws_merge_tree_batch: slices that stack share one flood, one set of per-level unions and one fold launch per level).
+  // seeds: one list per slice, or nullptr for every slice's own find_local_minima (n_seeds, nullable, receives the counts).
+  std::vector<MergeTree> merge_tree_cube(const std::uint8_t *cube, std::size_t n_slices, std::size_t rows, std::size_t cols,
+                                         const std::vector<std::vector<Seed>> *seeds = nullptr, bool want_labels = false,
+                                         std::vector<std::size_t> *n_seeds = nullptr) const {
+    if (seeds && seeds->size() != n_slices) throw std::invalid_argument("one seed list per slice");
+    const std::size_t e = this->opt_.edge_correction ? 2 : 0, prow = rows + e, pcol = cols + e, npx = prow * pcol;
+    std::vector<std::uint64_t> packed;
+    std::vector<std::size_t> offs(n_slices + 1, 0), counts(n_slices, 0);
+    if (seeds)
+      for (std::size_t k = 0; k < n_slices; ++k) {
+        const auto one = detail::pack((*seeds)[k]);
+        packed.insert(packed.end(), one.begin(), one.end());
+        offs[k + 1] = offs[k] + (*seeds)[k].size();
+      }
+    // own minima: rarely denser than one pixel in eight; a too small guess is answered before any flood with the count
+    std::size_t cap = seeds ? offs[n_slices] + n_slices : n_slices * (rows * cols / 8 + 1), total = 0, failed = 0;
+    std::vector<ws_tree_node> flat(cap);
+    std::vector<usize> labels(want_labels ? n_slices * npx : 0);
+    for (int attempt = 0; attempt < 2; ++attempt) {
+      const int rc = ws_merge_tree_batch(this->ctx_->get(), cube, n_slices, rows, cols, cols, rows * cols, seeds ? packed.data() : nullptr,
+                                         seeds ? offs.data() : nullptr, &this->opt_, flat.data(), cap, &total,
+                                         want_labels ? labels.data() : nullptr, counts.data(), &failed);
+      if (rc == WS_ERR_CAPACITY && total > cap && attempt == 0) {
+        cap = total;
+        flat.resize(cap);
+        continue;
+      }
+      this->ctx_->check(rc);
+      break;
+    }
+    std::vector<MergeTree> out;
+    std::size_t at = 0;
+    for (std::size_t k = 0; k < n_slices; ++k) {
+      const std::size_t n = counts[k] + 1;
+      MergeTree t{std::vector<ws_tree_node>(flat.begin() + at, flat.begin() + at + n), Array2<usize>(want_labels ? prow : 0, want_labels ? pcol : 0)};
+      if (want_labels) std::copy(labels.begin() + k * npx, labels.begin() + (k + 1) * npx, t.labels.data.begin());
+      out.push_back(std::move(t));
+      at += n;
+    }
+    if (n_seeds) *n_seeds = counts;
+    return out;
+  }
 
  private:
   template <class U> friend class TransformBuilder;

@@ -580,6 +580,47 @@ impl<T> MergingWatershed<T> {
         });
         MergeTree { nodes, labels }
     }
+    /// Not in the reference: `merge_tree(cube[k], &find_local_minima(cube[k]), want_labels)` of every slice of a cube as one call
+    /// (`ws_merge_tree_batch`: slices that stack share one flood, one set of per-level unions and one fold launch per level).
+    /// Returns the trees, in the slices' own colours, and the number of minima of every slice.
+    pub fn merge_tree_cube(&self, cube: nd::ArrayView3<u8>, want_labels: bool) -> (Vec<MergeTree>, Vec<usize>) {
+        let (n, h, w) = cube.dim();
+        let std_cube = cube.as_standard_layout();
+        let o = self.opt.ffi();
+        let (ph, pw) = self.opt.plane(h, w);
+        // minima are rarely denser than one pixel in eight; a too small guess is answered with the count before any flood
+        let mut cap = n * (h * w / 8 + 1);
+        let mut flat = vec![hip_ffi::ws_tree_node::default(); cap];
+        let mut labels = if want_labels { Some(nd::Array3::<usize>::zeros((n, ph, pw))) } else { None };
+        let lab_ptr = match labels.as_mut() {
+            Some(a) => a.as_slice_mut().expect("standard layout").as_mut_ptr() as *mut u64,
+            None => std::ptr::null_mut(),
+        };
+        let mut n_seeds = vec![0usize; n];
+        let (mut total, mut failed) = (0usize, 0usize);
+        shim::with_ctx(|ctx| unsafe {
+            for attempt in 0..2 {
+                let rc = hip_ffi::ws_merge_tree_batch(ctx, std_cube.as_ptr(), n, h, w, w, h * w, std::ptr::null(), std::ptr::null(), &o,
+                                                      flat.as_mut_ptr(), cap, &mut total, lab_ptr, n_seeds.as_mut_ptr(), &mut failed);
+                if rc == hip_ffi::WS_ERR_CAPACITY && total > cap && attempt == 0 {
+                    cap = total;
+                    flat.resize(cap, hip_ffi::ws_tree_node::default());
+                    continue;
+                }
+                shim::check(ctx, rc, "ws_merge_tree_batch");
+                break;
+            }
+        });
+        let mut at = 0usize;
+        let trees = (0..n)
+            .map(|k| {
+                let nodes = flat[at..at + n_seeds[k] + 1].to_vec();
+                at += n_seeds[k] + 1;
+                MergeTree { nodes, labels: labels.as_ref().map(|a| a.slice(nd::s![k, .., ..]).to_owned()) }
+            })
+            .collect();
+        (trees, n_seeds)
+    }
     /// Not in the reference: the merged label plane after the last level (canonical ids: the smallest seed colour of
     /// every lake).  The reference's own `transform` is the stub above.
     pub fn transform_final(&self, input: nd::ArrayView2<u8>, seeds: &[(usize, usize)]) -> nd::Array2<usize> {

@@ -56,6 +56,8 @@ struct ws_ctx {
   wsapi::DevBuf uf_hook, history_planes;
   // ws_merge_tree(_device): the dying colours bucketed by death level and the buckets' counters; the host form's records
   wsapi::DevBuf tree_order, tree_ws, tree_out;
+  // ws_merge_tree_batch(_device): a stack's records in the forest's numbering before they move to the caller's layout
+  wsapi::DevBuf tree_forest;
   uint32_t *pinned = nullptr;      // FLAG_WORDS words of pinned host memory: the host's mirror of the flag block
   uint32_t *pinned_dev = nullptr;  // the same words as the device sees them (nullptr: not mapped, copies only)
   hipEvent_t ring_ev[wsk::COUNTER_RING]{};   // flag slot copied to the host

@@ -745,6 +745,66 @@ int upload_batch(ws_ctx *c, const uint8_t *cube, size_t n_slices, size_t h, size
   return WS_OK;
 }
 
+// ---- merge_tree of a cube of slices (ws_merge_tree_batch(_device)) ----------------------------------------
+
+// the records of a stacked group from the transform history_batch_run has just run on this context, into the caller's layout at d_tree
+int build_tree_stack(ws_ctx *c, const HistoryGroup &grp, size_t ns, const ws_options *opt, size_t ph, size_t pw, ws_tree_node *d_tree) {
+  const uint32_t levels = (uint32_t)opt->max_water_level + 1;
+  const size_t plane = ph * pw;
+  const uint32_t *death = (const uint32_t *)c->uf_death.p, *hook = (const uint32_t *)c->uf_hook.p;
+  u64c *ws = (u64c *)c->tree_ws.p, *hist = ws + TREE_WS_WORDS;      // (behind the fold's counters: arrivals per (slice, level))
+  TreeRec *forest = (TreeRec *)c->tree_forest.p;
+  const TreeStack st{grp.base, (uint32_t)grp.g, (uint32_t)plane};
+  Span sp(c, KC_OTHER);
+  HIP_TRY(c, hipMemsetAsync(ws, 0, (TREE_WS_WORDS + grp.g * NLEVELS) * sizeof(u64c), c->stream));
+  HIP_TRY(c, slice_arrivals(c->stream, grp.keys, plane, grp.g, hist));
+  HIP_TRY(c, tree_init_stack(c->stream, death, hook, (const uint32_t *)c->seed_stack.p, grp.labels, (int)(grp.g * ph), (int)pw, forest, ns + 1, ws, st));
+  HIP_TRY(c, tree_own_counts_stack(c->stream, grp.keys, grp.labels, death, hook, forest, grp.g * plane, st));
+  HIP_TRY(c, tree_fold(c->stream, forest, ns + 1, levels, ws, (uint32_t *)c->tree_order.p));      // ONE launch per level for the group
+  HIP_TRY(c, tree_unstack(c->stream, forest, ns, grp.base, grp.g, hist, levels, plane, reinterpret_cast<TreeRec *>(d_tree)));
+  return WS_OK;
+}
+
+// The trees of a batch into d_tree (device; slice k's n_k + 1 records from (seed_offsets[k] - seed_offsets[0]) + k on), every group's
+// segmenting labels handed to labels(HistoryGroup) while they are on the context.  Every buffer the tree kernels need is sized for
+// the largest group BEFORE the first transform (as ensure_tree: nothing moves under the level loop's captured graphs).
+template <class F>
+int tree_batch_run(ws_ctx *c, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w, size_t stride, size_t slice_stride,
+                   const uint32_t *d_seeds_rc, const size_t *seed_offsets, const ws_options *opt, size_t ph, size_t pw, ws_tree_node *d_tree,
+                   size_t *failed_slice, F labels) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  size_t per_group = 0, most = 0, most_group = 0;
+  for (size_t k = 0; k < n_slices; ++k) most = std::max(most, seed_offsets[k + 1] - seed_offsets[k]);
+  const bool stack = n_slices > 1 && slice_stride == h * stride && d_cube && d_seeds_rc &&
+                     stackable(c, n_slices, h, w, stride, ph, pw, seed_offsets, opt, &per_group);
+  if (!stack) per_group = 0;
+  if (stack) {
+    per_group = std::min(per_group, n_slices);
+    for (size_t k0 = 0; k0 < n_slices; k0 += per_group) most_group = std::max(most_group, seed_offsets[std::min(k0 + per_group, n_slices)] - seed_offsets[k0]);
+  }
+  int rc;
+  if ((rc = ensure(c, c->tree_order, (std::max(most, most_group) + 1) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, c->tree_ws, (TREE_WS_WORDS + per_group * NLEVELS) * sizeof(u64c)))) return rc;
+  if (stack) {
+    if ((rc = ensure(c, c->tree_forest, (most_group + 1) * sizeof(TreeRec)))) return rc;
+    if ((rc = ensure(c, c->seed_stack, (most_group * 2 + per_group + 1) * sizeof(uint32_t)))) return rc;      // (flood_stack's, for its largest group)
+  }
+  const size_t s0 = seed_offsets[0];
+  return history_batch_run(c, true, d_cube, n_slices, h, w, stride, slice_stride, d_seeds_rc, seed_offsets, opt, failed_slice,
+                           [&](const HistoryGroup &grp) -> int {
+                             const size_t k = grp.k_first, ns = seed_offsets[k + grp.g] - seed_offsets[k];
+                             ws_tree_node *out = d_tree + (seed_offsets[k] - s0) + k;
+                             if (grp.base) {
+                               if (int rc_t = build_tree_stack(c, grp, ns, opt, ph, pw, out)) return rc_t;
+                             } else {
+                               // the seed pairs as the flood took them: the caller's, or (shifted_seeds) moved into the padded plane
+                               const uint32_t *seeds = seed_shift_of(opt) && ns ? (const uint32_t *)c->seeds.p : d_seeds_rc + 2 * seed_offsets[k];
+                               if (int rc_t = build_tree(c, seeds, ns, opt, ph, pw, out)) return rc_t;
+                             }
+                             return labels(grp);
+                           });
+}
+
 }  // namespace
 
 extern "C" {
@@ -1147,6 +1207,70 @@ int ws_transform_history_batch(ws_ctx *c, int merging, const uint8_t *cube, size
                                }
                              return (int)WS_OK;
                            });
+}
+
+int ws_merge_tree_batch_device(ws_ctx *c, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w, size_t row_stride, size_t slice_stride,
+                               const uint32_t *d_seeds_rc, const size_t *seed_offsets, const ws_options *opt, ws_tree_node *d_tree,
+                               uint32_t *d_labels, size_t *failed_slice) {
+  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
+  if (!c) return WS_ERR_BAD_ARG;
+  if (failed_slice) *failed_slice = 0;
+  if (int rc = check_batch(c, n_slices, h, row_stride, slice_stride, seed_offsets, opt)) return rc;
+  size_t ph = 0, pw = 0;
+  if (int rc = check_plane(c, h, w, row_stride, opt, &ph, &pw)) return rc;
+  if (n_slices == 0) return WS_OK;
+  const size_t total = seed_offsets[n_slices] - seed_offsets[0], plane = ph * pw;
+  if (total >= 0xFFFFFFFFull) return fail(c, WS_ERR_TOO_LARGE, "too many seeds");
+  if (!d_tree || (!d_cube && h * w) || (!d_seeds_rc && total)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  if (int rc = tree_batch_run(c, d_cube, n_slices, h, w, row_stride, slice_stride, d_seeds_rc, seed_offsets, opt, ph, pw, d_tree, failed_slice,
+                              [&](const HistoryGroup &grp) -> int {
+                                if (d_labels && plane)
+                                  HIP_TRY(c, hipMemcpyAsync(d_labels + grp.k_first * plane, grp.labels, grp.g * plane * sizeof(uint32_t),
+                                                            hipMemcpyDeviceToDevice, c->stream));
+                                return (int)WS_OK;
+                              }))
+    return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return WS_OK;
+}
+
+int ws_merge_tree_batch(ws_ctx *c, const uint8_t *cube, size_t n_slices, size_t h, size_t w, size_t row_stride, size_t slice_stride,
+                        const uint64_t *seeds_rc, const size_t *seed_offsets, const ws_options *opt, ws_tree_node *tree, size_t cap,
+                        size_t *n_records, uint64_t *labels, size_t *n_seeds, size_t *failed_slice) {
+  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
+  if (!c) return WS_ERR_BAD_ARG;
+  if (failed_slice) *failed_slice = 0;
+  if (int rc = check_batch(c, seeds_rc ? n_slices : 0, h, row_stride, slice_stride, seed_offsets, opt)) return rc;
+  size_t ph = 0, pw = 0;
+  int rc = check_plane(c, h, w, row_stride, opt, &ph, &pw);
+  if (rc) return rc;
+  if (n_slices == 0) {
+    if (n_records) *n_records = 0;
+    return WS_OK;
+  }
+  if ((!cube && h * w) || (!tree && cap)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  if (seeds_rc && seed_offsets[n_slices] - seed_offsets[0] >= 0xFFFFFFFFull) return fail(c, WS_ERR_TOO_LARGE, "too many seeds");
+  std::vector<size_t> offs;
+  if ((rc = upload_batch(c, cube, n_slices, h, w, row_stride, slice_stride, seeds_rc, seed_offsets, offs, n_seeds, failed_slice))) return rc;
+  const size_t total = offs[n_slices] + n_slices, plane = ph * pw;
+  if (n_records) *n_records = total;
+  if (offs[n_slices] >= 0xFFFFFFFFull) return fail(c, WS_ERR_TOO_LARGE, "too many seeds");
+  if (cap < total) return fail(c, WS_ERR_CAPACITY, "tree buffer too small");      // counted, nothing flooded: the caller learns how many records to make room for
+  if ((rc = ensure(c, c->tree_out, total * sizeof(ws_tree_node)))) return rc;
+  if (labels && (rc = ensure(c, c->out64, std::max<size_t>(plane, 1) * sizeof(uint64_t)))) return rc;      // (the plane-by-plane copy widens there)
+  rc = tree_batch_run(c, (const uint8_t *)c->batch_cube.p, n_slices, h, w, w, h * w, (const uint32_t *)c->batch_seeds.p, offs.data(), opt, ph, pw,
+                      (ws_tree_node *)c->tree_out.p, failed_slice, [&](const HistoryGroup &grp) -> int {
+                        if (!labels || !plane) return (int)WS_OK;
+                        uint64_t *dst = labels + grp.k_first * plane;
+                        if (host_copy_in_chunks(c, grp.g * plane)) return labels_to_host_u64(c, grp.labels, dst, grp.g * plane);
+                        for (size_t k = 0; k < grp.g; ++k)
+                          if (int rc_copy = labels_to_host_u64(c, grp.labels + k * plane, dst + k * plane, plane)) return rc_copy;
+                        return (int)WS_OK;
+                      });
+  if (rc) return rc;
+  HIP_TRY(c, hipMemcpyAsync(tree, c->tree_out.p, total * sizeof(ws_tree_node), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return WS_OK;
 }
 
 }  // extern "C"

@@ -1374,9 +1374,15 @@ hipError_t render_history_stack(hipStream_t s, bool merging, const uint32_t *key
 constexpr int TREE_PER_THREAD = 16;      // colours per thread of the per-colour kernels: a workgroup adds once per level to 256 shared counters
 constexpr int TREE_CHUNK = 256 * TREE_PER_THREAD;
 
+__device__ __forceinline__ uint32_t slice_of_colour(const uint32_t *base, uint32_t g, uint32_t c);      // (with the stack's kernels, below)
+
+// STACKED (ws_merge_tree_batch_device): the forest is that of a stack of st.g slices of st.plane pixels (H = g x slice rows); colour
+// c of the forest is colour c - st.base[k] of its slice k, seeds_rc are the stacked seed pairs (flood_stack) and seg holds every
+// slice's own colours.  Record 0 of the forest belongs to nobody: every slice's own comes from k_tree_unstack.
+template <bool STACKED>
 __global__ __launch_bounds__(256) void k_tree_init(const uint32_t *__restrict__ death, const uint32_t *__restrict__ hook,
                                                    const uint32_t *__restrict__ seeds_rc, const uint32_t *__restrict__ seg, int H, int W,
-                                                   const u64c *__restrict__ arrived, TreeRec *tree, size_t n_colours, u64c *hist) {
+                                                   const u64c *__restrict__ arrived, TreeRec *tree, size_t n_colours, u64c *hist, TreeStack st) {
   __shared__ uint32_t s_h[NLEVELS];
   s_h[threadIdx.x] = 0;
   __syncthreads();
@@ -1385,11 +1391,13 @@ __global__ __launch_bounds__(256) void k_tree_init(const uint32_t *__restrict__ 
     if (c >= n_colours) break;
     TreeRec r{0u, TREE_ALIVE, 0u, 0u};
     if (c == 0) {
-      r.area = (uint32_t)((u64c)H * (u64c)W - arrived[0]);      // what the last level left uncoloured
+      if constexpr (!STACKED) r.area = (uint32_t)((u64c)H * (u64c)W - arrived[0]);      // what the last level left uncoloured
     } else {
       const uint32_t y = seeds_rc[2 * (c - 1)], x = seeds_rc[2 * (c - 1) + 1];
+      uint32_t own = (uint32_t)c;      // the colour in the plane's own numbering
+      if constexpr (STACKED) own -= st.base[slice_of_colour(st.base, st.g, (uint32_t)c)];
       // a later seed on the same pixel overwrites (lib.rs:1670-1677): such a colour never was
-      r.n_leaves = y < (uint32_t)H && x < (uint32_t)W && seg[(size_t)y * W + x] == (uint32_t)c ? 1u : 0u;
+      r.n_leaves = y < (uint32_t)H && x < (uint32_t)W && seg[(size_t)y * W + x] == own ? 1u : 0u;
       const uint32_t d = death[c];
       if (d != TREE_ALIVE) {
         uint32_t p = hook[c];
@@ -1408,7 +1416,16 @@ __global__ __launch_bounds__(256) void k_tree_init(const uint32_t *__restrict__ 
 hipError_t tree_init(hipStream_t s, const uint32_t *death, const uint32_t *hook, const uint32_t *seeds_rc, const uint32_t *seg_labels, int h, int w,
                      const u64c *arrived, TreeRec *tree, size_t n_colours, u64c *ws) {
   if (n_colours == 0) return hipSuccess;
-  k_tree_init<<<(unsigned)((n_colours + TREE_CHUNK - 1) / TREE_CHUNK), 256, 0, s>>>(death, hook, seeds_rc, seg_labels, h, w, arrived, tree, n_colours, ws);
+  k_tree_init<false><<<(unsigned)((n_colours + TREE_CHUNK - 1) / TREE_CHUNK), 256, 0, s>>>(death, hook, seeds_rc, seg_labels, h, w, arrived, tree, n_colours, ws,
+                                                                                           TreeStack{});
+  return hipGetLastError();
+}
+
+hipError_t tree_init_stack(hipStream_t s, const uint32_t *death, const uint32_t *hook, const uint32_t *stacked_rc, const uint32_t *seg_labels, int h, int w,
+                           TreeRec *tree, size_t n_colours, u64c *ws, const TreeStack &st) {
+  if (n_colours == 0) return hipSuccess;
+  if (st.g == 0 || st.plane == 0 || (size_t)h * (size_t)w != (size_t)st.g * st.plane) return hipErrorInvalidValue;
+  k_tree_init<true><<<(unsigned)((n_colours + TREE_CHUNK - 1) / TREE_CHUNK), 256, 0, s>>>(death, hook, stacked_rc, seg_labels, h, w, nullptr, tree, n_colours, ws, st);
   return hipGetLastError();
 }
 
@@ -1428,9 +1445,12 @@ __device__ __forceinline__ void own_add(uint32_t *s_key, uint32_t *s_cnt, TreeRe
   atomicAdd(&tree[r].area, k);
 }
 
+// STACKED: labels hold every slice's own colours; a quad's slice is i0 / stack.plane (stack.plane % 4 == 0: a quad never straddles two
+// slices, a workgroup's runs may) and its colours move to the forest's numbering before the walk, so the table is keyed by forest root.
+template <bool STACKED>
 __global__ __launch_bounds__(256) void k_tree_own(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ labels,
                                                   const uint32_t *__restrict__ death, const uint32_t *__restrict__ hook, TreeRec *tree,
-                                                  size_t n, size_t steps) {
+                                                  size_t n, size_t steps, TreeStack stack) {
   __shared__ uint32_t s_key[OWN_SLOTS], s_cnt[OWN_SLOTS];
   for (int j = threadIdx.x; j < OWN_SLOTS; j += 256) { s_key[j] = OWN_EMPTY; s_cnt[j] = 0; }
   __syncthreads();
@@ -1450,6 +1470,11 @@ __global__ __launch_bounds__(256) void k_tree_own(const uint32_t *__restrict__ k
         arr[p] = in ? keys[i0 + p] >> 24 : 0xFFu;
         col[p] = in ? labels[i0 + p] : 0u;
       }
+    }
+    if constexpr (STACKED) {
+      const uint32_t b = i0 < n ? stack.base[(uint32_t)i0 / stack.plane] : 0u;      // (n < 2^32: tree_own_counts_stack)
+#pragma unroll
+      for (int p = 0; p < 4; ++p) col[p] += col[p] != 0u ? b : 0u;
     }
     // the four walks side by side (a walk is a chain of dependent gathers: one after the other they were most of the kernel)
     uint32_t r[4], d[4];
@@ -1490,7 +1515,17 @@ hipError_t tree_own_counts(hipStream_t s, const uint32_t *keys, const uint32_t *
   // at most two thousand workgroups on a large plane (that many adds reach the surviving lake's word), 1024 pixels a step
   const size_t quads = (n + 1023) / 1024;
   const size_t steps = std::max<size_t>((quads + 2047) / 2048, 1);
-  k_tree_own<<<(unsigned)((quads + steps - 1) / steps), 256, 0, s>>>(keys, labels, death, hook, tree, n, steps);
+  k_tree_own<false><<<(unsigned)((quads + steps - 1) / steps), 256, 0, s>>>(keys, labels, death, hook, tree, n, steps, TreeStack{});
+  return hipGetLastError();
+}
+
+hipError_t tree_own_counts_stack(hipStream_t s, const uint32_t *keys, const uint32_t *labels, const uint32_t *death, const uint32_t *hook, TreeRec *tree,
+                                 size_t n, const TreeStack &st) {
+  if (n == 0) return hipSuccess;
+  if (st.plane == 0 || (st.plane & 3u) != 0 || n != (size_t)st.g * st.plane || n > 0xFFFFFFFFull) return hipErrorInvalidValue;      // (slice indices are u32 divisions)
+  const size_t quads = (n + 1023) / 1024;
+  const size_t steps = std::max<size_t>((quads + 2047) / 2048, 1);
+  k_tree_own<true><<<(unsigned)((quads + steps - 1) / steps), 256, 0, s>>>(keys, labels, death, hook, tree, n, steps, st);
   return hipGetLastError();
 }
 
@@ -1643,6 +1678,34 @@ hipError_t slice_arrivals(hipStream_t s, const uint32_t *keys, size_t plane, siz
   if (plane == 0 || n_slices == 0) return hipSuccess;
   const unsigned bx = (unsigned)std::min<size_t>(std::max<size_t>(plane / (4 * 256 * 16), 1), 256);      // ~16 words a thread
   k_slice_arrivals<<<dim3(bx, (unsigned)n_slices), 256, 0, s>>>(keys, plane, hist);
+  return hipGetLastError();
+}
+
+// The forest's tree records (ws_merge_tree_batch_device) into the caller's slice-major layout in the slices' own colours: record c
+// of the forest (1 .. n_seeds) is record c - base[k] of its slice k, at out[c + k] (every slice before it owns one record 0), its
+// parent -- same slice: no pair crosses a slice border -- less the slice's base.  Thread n_seeds + k writes slice k's record 0 at
+// out[base[k] + k]: the pixels of its plane that no level up to the last coloured (hist: k_slice_arrivals').
+__global__ __launch_bounds__(256) void k_tree_unstack(const TreeRec *__restrict__ forest, size_t n_seeds, const uint32_t *__restrict__ base, uint32_t g,
+                                                      const u64c *__restrict__ hist, uint32_t levels, uint32_t plane, TreeRec *out) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n_seeds) {
+    const uint32_t c = (uint32_t)i + 1u, k = slice_of_colour(base, g, c);
+    TreeRec r = forest[c];
+    if (r.death_level != TREE_ALIVE) r.parent -= base[k];
+    out[(size_t)c + k] = r;
+  } else if (i < n_seeds + g) {
+    const uint32_t k = (uint32_t)(i - n_seeds);
+    u64c arrived = 0;
+    for (uint32_t l = 0; l < levels; ++l) arrived += hist[(size_t)k * NLEVELS + l];
+    out[(size_t)base[k] + k] = TreeRec{0u, TREE_ALIVE, (uint32_t)((u64c)plane - arrived), 0u};
+  }
+}
+
+hipError_t tree_unstack(hipStream_t s, const TreeRec *forest, size_t n_seeds, const uint32_t *base, size_t g, const u64c *hist, uint32_t levels,
+                        size_t plane, TreeRec *out) {
+  if (g == 0) return hipSuccess;
+  if (levels > (uint32_t)NLEVELS || plane > 0xFFFFFFFFull || g > 0xFFFFFFFFull) return hipErrorInvalidValue;
+  k_tree_unstack<<<(unsigned)((n_seeds + g + 255) / 256), 256, 0, s>>>(forest, n_seeds, base, (uint32_t)g, hist, levels, (uint32_t)plane, out);
   return hipGetLastError();
 }
 

@@ -150,5 +150,20 @@ hipError_t tree_own_counts(hipStream_t s, const uint32_t *keys, const uint32_t *
 // order[]: the colours that die, bucketed by death level (bounds: ws[NLEVELS + 1 + l]); then level by level, ascending, every dying
 // colour hands area and n_leaves to its parent (children die strictly before their parents)
 hipError_t tree_fold(hipStream_t s, TreeRec *tree, size_t n_colours, uint32_t levels, u64c *ws, uint32_t *order);
+// The same over the forest of a stack of slices (ws_merge_tree_batch_device): g slices of `plane` pixels (plane % 4 == 0), colour c
+// of the forest = colour c - base[k] of its slice k (base: g + 1 words on the device, sorted).  tree_init_stack / tree_own_counts_stack
+// fill `tree` in the FOREST's numbering (n_colours = the stack's seeds + 1; parents too), tree_fold folds it as it is -- one launch per
+// level for the whole stack -- and tree_unstack writes the caller's layout: slice k's records at out[base[k] + k ...], own colours,
+// record 0 = plane - the slice's arrivals of levels 0 .. levels - 1 (hist: slice_arrivals').
+struct TreeStack {
+  const uint32_t *base;
+  uint32_t g, plane;
+};
+hipError_t tree_init_stack(hipStream_t s, const uint32_t *death, const uint32_t *hook, const uint32_t *stacked_rc, const uint32_t *seg_labels, int h, int w,
+                           TreeRec *tree, size_t n_colours, u64c *ws, const TreeStack &st);
+hipError_t tree_own_counts_stack(hipStream_t s, const uint32_t *keys, const uint32_t *labels, const uint32_t *death, const uint32_t *hook, TreeRec *tree,
+                                 size_t n, const TreeStack &st);
+hipError_t tree_unstack(hipStream_t s, const TreeRec *forest, size_t n_seeds, const uint32_t *base, size_t g, const u64c *hist, uint32_t levels,
+                        size_t plane, TreeRec *out);
 
 }  // namespace wsk

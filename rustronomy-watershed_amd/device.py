@@ -313,5 +313,29 @@ class DeviceEngine:
                                                        ctypes.byref(opt), out.data_ptr(), labels.data_ptr() if want_labels else None))
         return (out, labels) if want_labels else out
 
+    def merge_tree_batch(self, cube, seeds, seed_offsets, max_level=254, edge=False, seed_shift=False, want_labels=False, out=None):
+        """merge_tree of every slice of a cube with everything in HBM (ws_merge_tree_batch_device); cube, seeds and seed_offsets as
+        transform_to_list_batch.  Returns an (n_seeds_total + S, 4) int32 tensor: slice k's n_k + 1 rows start at
+        (seed_offsets[k] - seed_offsets[0]) + k, row c of them colour c of the slice's own colours as merge_tree's.  With
+        want_labels also the segmenting (S, H', W') int32 labels: returns (tree, labels).  `out`: a reusable contiguous int32
+        device tensor of that shape."""
+        offs = self._batch_args(cube, seeds, seed_offsets)
+        s, h, w = cube.shape
+        e = 2 if edge else 0
+        shape = (int(seed_offsets[-1]) - int(seed_offsets[0]) + s, 4)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int32, device=self.device)
+        elif out.dtype != torch.int32 or not out.is_contiguous() or tuple(out.shape) != shape:
+            raise ValueError(f"out must be a contiguous int32 tensor of shape {shape}")
+        labels = torch.empty((s, h + e, w + e), dtype=torch.int32, device=self.device) if want_labels else None
+        if s:
+            opt = self.options(max_level, edge, None, seed_shift)
+            failed = ctypes.c_size_t(0)
+            self.ctx.check(_ffi.lib().ws_merge_tree_batch_device(self.ctx.handle, cube.data_ptr(), s, h, w, w, h * w,
+                                                                 seeds.data_ptr() if seeds.numel() else None, offs, ctypes.byref(opt),
+                                                                 out.data_ptr(), labels.data_ptr() if want_labels else None,
+                                                                 ctypes.byref(failed)))
+        return (out, labels) if want_labels else out
+
     def stats(self):
         return self.ctx.stats()
