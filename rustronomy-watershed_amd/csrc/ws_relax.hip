@@ -428,7 +428,7 @@ __device__ __forceinline__ void scan_cols_both(patch_t &T, const patch_t &B, uin
 // Exactness does not rest on any of this: stamps only ever fall, by relaxation steps from upper bounds (a stale read is an
 // older, larger stamp: less progress, never a wrong value), and the pass AFTER this launch runs every tile once from an
 // all-tiles list -- the flood is at its fixpoint when the ordinary passes that follow say so.
-template <int NW, bool CHUNKED, bool SCAN, bool LITE, bool SPLIT = false, int SEAM = 0, int PERSIST = 0>
+template <int NW, bool CHUNKED, bool SCAN, bool LITE, bool SPLIT = false, int SEAM = 0, int PERSIST = 0, int SEAM_PITCH = 32>
 __global__ __launch_bounds__(64 * NW, SCAN ? 4 : 6) void k_relax(      // the scan variant trades occupancy (few tiles run there) for registers
 const uint8_t *__restrict__ img, size_t img_stride, uint32_t *keys,
                                                       int H, int W, int tilesX, int tilesY, int otherX, int otherY,
@@ -454,7 +454,10 @@ const uint8_t *__restrict__ img, size_t img_stride, uint32_t *keys,
   //           32 tile_x + j + 1 (x = 256 times that), and no stamp crosses from one lane PAIR to the next.
   // A seam tile iterates to its fixpoint and raises, in the stamp word that the next pass of the anchored grid reads, the
   // flag of every 256 x 32 tile that holds a pixel next to a changed outer row or column of it.  (otherX: that array's pitch.)
+  // (SEAM_PITCH, SEAM 1: rows between two horizontal seams -- 64 after pass 0 on 256 x 64 tiles, k_relax0_tall.  The flags
+  // stay those of the 256 x 32 tiles: seam row 64 (ty + 1) is the border between tile rows seam_fy and seam_fy + 1.)
   constexpr int SEAM_PY = 32, SEAM_PX = 256, SEAM_HALF = SEAM == 1 ? TH / 2 : 4;
+  static_assert(SEAM_PITCH % SEAM_PY == 0, "a seam is a border of the 256 x 32 grid");
   // row 0: halo above the tile; rows 1+2w / 2+2w: top / bottom row of band w; last row: halo below
   __shared__ __attribute__((aligned(16))) uint32_t sRow[2 * NB + 2][TW];
   // the tile border as loaded (top row, bottom row, left column, right column): compared with the
@@ -538,10 +541,11 @@ const uint8_t *__restrict__ img, size_t img_stride, uint32_t *keys,
     // (a seam whose tiles on both sides have asked for a re-run already -- pass 0 stopped at its round cap there: a smooth
     // map -- is left to them: on such maps the repair would be 64 us of sweeps that the re-runs undo)
     if (SEAM == 1) {
-      if (tx * TW >= W || (ty + 1) * SEAM_PY >= H) return;
+      if (tx * TW >= W || (ty + 1) * SEAM_PITCH >= H) return;
       // (a tile that asked for its re-run is work for pass 2: this pass must not look like a fixpoint to the host -- pass 0
       // cannot say so itself, its launch clears this pass's convergence slot)
-      const bool fa = stamps_cur[((size_t)ty * otherX + tx + 1) * 4 + 2] == pass + 1, fb = stamps_cur[((size_t)(ty + 1) * otherX + tx + 1) * 4 + 2] == pass + 1;
+      const int fy = (ty + 1) * (SEAM_PITCH / SEAM_PY) - 1;
+      const bool fa = stamps_cur[((size_t)fy * otherX + tx + 1) * 4 + 2] == pass + 1, fb = stamps_cur[((size_t)(fy + 1) * otherX + tx + 1) * 4 + 2] == pass + 1;
       if ((fa || fb) && threadIdx.x == 0) pf.edge_changed[(pass % COUNTER_RING) * FLAG_SLOT + (blockIdx.x % NSTRIPE) * STRIPE_STRIDE] = 1u;
       if (fa && fb) return;
     } else if (SEAM == 2) {
@@ -729,7 +733,8 @@ const uint8_t *__restrict__ img, size_t img_stride, uint32_t *keys,
                            : (CHUNKED ? (use_list ? (int)(entry == blockIdx.x ? first_entry : tile_list[RL_HDR + (pass & 1u) * list_cap + entry]) : first + (int)__builtin_ctzll(todo) * stride) : first);
   const int tile_x = tile % tilesX, tile_y = tile / tilesX;
   const int x0 = SEAM ? tile_x * TW : tile_x * TW - (shifted ? TW / 2 : 0);
-  const int y0 = SEAM == 1 ? (tile_y + 1) * SEAM_PY - SEAM_HALF : tile_y * TH - (shifted ? TH / 2 : 0);
+  const int y0 = SEAM == 1 ? (tile_y + 1) * SEAM_PITCH - SEAM_HALF : tile_y * TH - (shifted ? TH / 2 : 0);
+  const int seam_fy = (tile_y + 1) * (SEAM_PITCH / SEAM_PY) - 1;      // SEAM 1: the 256 x 32 tile row above the seam
   const int seam_x = (tile_x * 32 + (lane >> 1) + 1) * SEAM_PX;      // SEAM 2: this lane pair's seam (outside the plane: no seam)
 
   WS_STAMP(0);
@@ -1132,8 +1137,8 @@ const uint8_t *__restrict__ img, size_t img_stride, uint32_t *keys,
       // have stored their flags themselves.)
       bool any = SEAM == 2 && (ed & 1u) != 0u;
       if (SEAM == 1) {      // (bit 5: the band stopped at its round cap)
-        if (ed & (64u | 32u)) { stamps_cur[((size_t)tile_y * otherX + tile_x) * 4 + 3] = pass + 1; any = true; }
-        if (ed & (128u | 32u)) { stamps_cur[((size_t)(tile_y + 1) * otherX + tile_x) * 4 + 3] = pass + 1; any = true; }
+        if (ed & (64u | 32u)) { stamps_cur[((size_t)seam_fy * otherX + tile_x) * 4 + 3] = pass + 1; any = true; }
+        if (ed & (128u | 32u)) { stamps_cur[((size_t)(seam_fy + 1) * otherX + tile_x) * 4 + 3] = pass + 1; any = true; }
       }
       if (any) pf.edge_changed[(pass % COUNTER_RING) * FLAG_SLOT + stripe] = 1u;
       if (ed) pf.any_change[stripe] = 1u;
@@ -1464,6 +1469,277 @@ hipError_t block_flag_border_tiles(hipStream_t s, uint32_t *stamps, int h, int w
   return hipGetLastError();
 }
 
+// ---- pass 0 of the seam-repair flow on 256 x 64 tiles --------------------------------------------------------------------
+//
+// Pass 0 of a transform that starts from its seeds and repairs its seams with bands and strips (relax_pass, seam_flow) has
+// its own kernel: the same sweeps as k_relax, but a lane owns 4 columns x 8 rows -- two stacked 4 x 4 patches -- so the
+// tile is 256 x 64 with the same eight waves.  What a tile run pays outside its sweeps (image bytes to bases, seed bits to
+// stamps, addresses, the band rows' way through LDS) is paid once per 32 pixels of a lane instead of once per 16, rows 3
+// and 4 of a patch are neighbours in registers, and the plane has half as many horizontal seams for the bands to repair.
+// None of this fits k_relax's 80 registers, and none of that template's other nine variants needs it.
+//   * only the fast path: W % 4 == 0, image rows readable as aligned dwords, seeds as a bit plane (relax_pass asks);
+//   * the stamp plane is created here (every patch is written), so there is no "did my patch change" sum;
+//   * nobody reads pass 0's quadrant flags in this flow -- bands and strips look at every seam whatever they say -- so the
+//     tile border as loaded is not kept.  "A border pixel changed and matters across the border" (the pass's convergence
+//     word) needs no copy either: a border pixel starts as a seed (0, for ever) or at KEY_INF, so it changed iff it is
+//     neither now, and what lies across the border is still in the halo row of LDS / the halo column registers;
+//   * a tile that stops at its round cap marks BOTH 256 x 32 tiles it covers, in the words the bands, the strips and pass 2
+//     read, and all their quadrant flags, as k_relax does for its one.
+constexpr int RX0_PH = 2 * RX_P;              // rows of a lane's patch
+constexpr int RX0_TH = RX_NW * RX0_PH;        // tile height: 64
+typedef uint32_t tall_t[RX0_PH][RX_P];
+
+template <bool TRACK, bool DOWN>
+__device__ __forceinline__ void tall_sweep_rows(tall_t &T, const tall_t &B, const uint32_t (&up)[RX_P], const uint32_t (&dn)[RX_P],
+                                                const uint32_t (&L)[RX0_PH], const uint32_t (&R)[RX0_PH], bool &changed) {
+#pragma unroll
+  for (int k = 0; k < RX0_PH; ++k) {
+    const int r = DOWN ? k : RX0_PH - 1 - k;
+#pragma unroll
+    for (int c = 0; c < RX_P; ++c)
+      relax_px<TRACK>(T[r][c], B[r][c], r == 0 ? up[c] : T[r - 1][c], r == RX0_PH - 1 ? dn[c] : T[r + 1][c],
+                      c == 0 ? L[r] : T[r][c - 1], c == RX_P - 1 ? R[r] : T[r][c + 1], changed);
+  }
+}
+template <bool TRACK, bool RIGHT>
+__device__ __forceinline__ void tall_sweep_cols(tall_t &T, const tall_t &B, const uint32_t (&up)[RX_P], const uint32_t (&dn)[RX_P],
+                                                const uint32_t (&L)[RX0_PH], const uint32_t (&R)[RX0_PH], bool &changed) {
+#pragma unroll
+  for (int k = 0; k < RX_P; ++k) {
+    const int c = RIGHT ? k : RX_P - 1 - k;
+#pragma unroll
+    for (int r = 0; r < RX0_PH; ++r)
+      relax_px<TRACK>(T[r][c], B[r][c], r == 0 ? up[c] : T[r - 1][c], r == RX0_PH - 1 ? dn[c] : T[r + 1][c],
+                      c == 0 ? L[r] : T[r][c - 1], c == RX_P - 1 ? R[r] : T[r][c + 1], changed);
+  }
+}
+
+// (flagAX / flagSX: tile columns of the anchored / shifted 256 x 32 grid, the pitches of stamps_own / stamps_rerun)
+__global__ __launch_bounds__(64 * RX_NW, 4) void k_relax0_tall(const uint8_t *__restrict__ img, uint32_t stride32, uint32_t *keys, int H, int W,
+                                                               int tilesX, int flagAX, int flagSX, uint32_t max_level, uint32_t *stamps_own,
+                                                               uint32_t *stamps_rerun, PassFlags pf, uint32_t max_iters,
+                                                               const uint32_t *__restrict__ seed_mask, int SH, int check_carry, uint32_t *tile_list) {
+  constexpr int NB = RX_NW, TW = RX_TW, TH = RX0_TH;
+  constexpr uint32_t pass = 0;
+  // row 0: halo above the tile; rows 1+2w / 2+2w: top / bottom row of band w; last row: halo below
+  __shared__ __attribute__((aligned(16))) uint32_t sRow[2 * NB + 2][TW];
+  __shared__ uint32_t s_flag[3];      // "some lane changed in round k" in slot k % 3 (k_relax)
+
+  // the first wave of workgroup 0 clears the next pass's convergence slot, and the tile list length that pass 2 counts from
+  if (blockIdx.x == 0 && threadIdx.x < NSTRIPE)
+    pf.edge_changed[((pass + 1) % COUNTER_RING) * FLAG_SLOT + threadIdx.x * STRIPE_STRIDE] = 0;
+  if (tile_list && blockIdx.x == 0 && threadIdx.x == 0) { tile_list[(pass + 2) & 3u] = 0u; tile_list[4 + ((pass + 2) & 3u)] = 0u; }
+  const int tile = (int)xcd_span_index(blockIdx.x, gridDim.x);      // (XCD-aware: consecutive workgroups go to different XCDs)
+  const int tile_x = tile % tilesX, tile_y = tile / tilesX;
+  const int x0 = tile_x * TW, y0 = tile_y * TH;
+  if (x0 >= W || y0 >= H) return;
+  const int tid = threadIdx.x, lane = tid & 63, band = tid >> 6;
+  const int gx0 = x0 + lane * RX_P, gyb = y0 + band * RX0_PH;
+  if (tid == 0) { s_flag[0] = 0; s_flag[1] = 0; s_flag[2] = 0; }
+
+  // ---- load phase: unconditional loads on clamped addresses; a patch (W % 4 == 0) is wholly inside the plane or wholly outside
+  tall_t T, B;
+  uint32_t Lh[RX0_PH], Rh[RX0_PH];
+  const bool dims24 = (uint32_t)W < (1u << 24) && (uint32_t)H < (1u << 24);      // kernel uniform: row * W as v_mul_u32_u24
+  const uint32_t gxc0 = (uint32_t)min(gx0, W - RX_P);
+  // tile halo columns: the left half of the lanes fetch the column left of the tile, the right half the one right of it;
+  // only lane 0 / lane 63 ever use the value (as the DPP `old` operand)
+  const int xh_raw = lane < 32 ? x0 - 1 : x0 + TW;
+  const uint32_t xh = (uint32_t)min(max(xh_raw, 0), W - 1);
+  const bool xh_ok = lane < 32 ? x0 > 0 : x0 + TW < W;
+  const int gy_halo_raw = band == 0 ? y0 - 1 : y0 + TH;
+  const uint32_t gy_halo = (uint32_t)min(max(gy_halo_raw, 0), H - 1);
+  u32x4_t halo_row;
+  {
+    uint32_t iv[RX0_PH];
+#pragma unroll
+    for (int r = 0; r < RX0_PH; ++r) {
+      const uint32_t gyc = (uint32_t)min(gyb + r, H - 1);
+      // (a bit plane exists only for planes of fewer than 2^31 pixels: pixel indices fit 32 bits)
+      const uint32_t ro = dims24 ? __umul24(gyc, (uint32_t)W) : gyc * (uint32_t)W;
+      const uint32_t p = ro + gxc0, ph_ = ro + xh;
+      const uint32_t nib = seed_mask[p >> 5] >> (p & 31u);
+      iv[r] = *reinterpret_cast<const uint32_t *>(img + ((unsigned long long)gyc * stride32 + gxc0));
+      Lh[r] = (seed_mask[ph_ >> 5] >> (ph_ & 31u)) & 1u;
+      T[r][0] = nib & 1u; T[r][1] = nib & 2u; T[r][2] = nib & 4u; T[r][3] = nib & 8u;
+    }
+    const uint32_t p = (dims24 ? __umul24(gy_halo, (uint32_t)W) : gy_halo * (uint32_t)W) + gxc0;
+    const uint32_t nib = seed_mask[p >> 5] >> (p & 31u);
+    halo_row = u32x4_t{nib & 1u, nib & 2u, nib & 4u, nib & 8u};
+    // image bytes -> bases, as patch_bases: the one (kernel uniform) branch outside the loop that loads the rows
+    if (max_level == 254u) {
+#pragma unroll
+      for (int r = 0; r < RX0_PH; ++r) {
+        B[r][0] = (iv[r] << 24) | 1u;
+        B[r][1] = ((iv[r] << 16) & 0xFF000000u) | 1u;
+        B[r][2] = ((iv[r] << 8) & 0xFF000000u) | 1u;
+        B[r][3] = (iv[r] & 0xFF000000u) | 1u;
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < RX0_PH; ++r)
+#pragma unroll
+        for (int c = 0; c < RX_P; ++c) {
+          const uint32_t v = (iv[r] >> (8 * c)) & 0xFFu;
+          B[r][c] = v <= max_level ? ((v << 24) | 1u) : KEY_INF;
+        }
+    }
+  }
+  // seed = stamp 0, everything else never coloured
+#pragma unroll
+  for (int r = 0; r < RX0_PH; ++r) {
+#pragma unroll
+    for (int c = 0; c < RX_P; ++c) T[r][c] = T[r][c] ? 0u : KEY_INF;
+    Lh[r] = Lh[r] ? 0u : KEY_INF;
+  }
+  halo_row.x = halo_row.x ? 0u : KEY_INF; halo_row.y = halo_row.y ? 0u : KEY_INF;
+  halo_row.z = halo_row.z ? 0u : KEY_INF; halo_row.w = halo_row.w ? 0u : KEY_INF;
+  // Workgroup uniform: the tile and its halo ring lie strictly inside the image (and the image is not a stack of slices) --
+  // none of the masks below can bite (k_relax)
+  const bool inner = SH == H && x0 >= 1 && x0 + TW <= W - 1 && y0 >= 1 && y0 + TH <= H - 1;
+  if (!inner) {
+    int ry = SH == H ? gyb : gyb % SH;      // row inside its slice (a patch of eight rows may hold the walls of several slices)
+#pragma unroll
+    for (int r = 0; r < RX0_PH; ++r) {
+      const int gy = gyb + r;
+      const bool row_ok = gy < H, row_int = ry >= 1 && ry < SH - 1 && gy < H;
+#pragma unroll
+      for (int c = 0; c < RX_P; ++c) {
+        const int gx = gx0 + c;
+        if (!(row_ok && gx < W)) T[r][c] = KEY_INF;
+        if (!(row_int && gx >= 1 && gx < W - 1)) B[r][c] = KEY_INF;
+      }
+      if (!(row_ok && xh_ok)) Lh[r] = KEY_INF;
+      if (++ry == SH) ry = 0;
+    }
+    const bool ok = gy_halo_raw >= 0 && gy_halo_raw < H;
+    if (!(ok && gx0 + 0 < W)) halo_row.x = KEY_INF;
+    if (!(ok && gx0 + 1 < W)) halo_row.y = KEY_INF;
+    if (!(ok && gx0 + 2 < W)) halo_row.z = KEY_INF;
+    if (!(ok && gx0 + 3 < W)) halo_row.w = KEY_INF;
+  }
+#pragma unroll
+  for (int r = 0; r < RX0_PH; ++r) {
+#pragma unroll
+    for (int c = 0; c < RX_P; ++c) B[r][c] = min(B[r][c], T[r][c]);      // b <= t: seeds and everything that can never change are pinned
+    Rh[r] = Lh[r];
+  }
+  // the columns left / right of the patch, persistent: lane 0 / lane 63 keep the tile's halo column (k_relax)
+  auto refresh_columns = [&]() {
+#pragma unroll
+    for (int r = 0; r < RX0_PH; ++r) {
+      Lh[r] = lane_left(Lh[r], T[r][3]);
+      Rh[r] = lane_right(Rh[r], T[r][0]);
+    }
+  };
+  auto publish_rows = [&]() {
+    *reinterpret_cast<u32x4_t *>(&sRow[1 + 2 * band][lane * RX_P]) = u32x4_t{T[0][0], T[0][1], T[0][2], T[0][3]};
+    *reinterpret_cast<u32x4_t *>(&sRow[2 + 2 * band][lane * RX_P]) = u32x4_t{T[RX0_PH - 1][0], T[RX0_PH - 1][1], T[RX0_PH - 1][2], T[RX0_PH - 1][3]};
+  };
+  if (band == 0) *reinterpret_cast<u32x4_t *>(&sRow[0][lane * RX_P]) = halo_row;
+  if (band == NB - 1) *reinterpret_cast<u32x4_t *>(&sRow[2 * NB + 1][lane * RX_P]) = halo_row;
+  publish_rows();
+  __syncthreads();
+
+  // ---- relaxation: k_relax's rounds (three free sweeps, the band rows published, one checked sweep), its round cap, and
+  // from the third round on the checked sweep alone
+  uint32_t iters = 0;
+  bool unfinished = max_iters == 0;
+  uint32_t up[RX_P], dn[RX_P];
+  auto fetch_rows = [&]() {
+    const u32x4_t up4 = *reinterpret_cast<const u32x4_t *>(&sRow[2 * band][lane * RX_P]);
+    const u32x4_t dn4 = *reinterpret_cast<const u32x4_t *>(&sRow[2 * band + 3][lane * RX_P]);
+    up[0] = up4.x; up[1] = up4.y; up[2] = up4.z; up[3] = up4.w;
+    dn[0] = dn4.x; dn[1] = dn4.y; dn[2] = dn4.z; dn[3] = dn4.w;
+  };
+  for (; max_iters != 0;) {
+    ++iters;
+    if (iters <= 2) {
+      bool untracked = false;
+      fetch_rows();
+      refresh_columns();
+      tall_sweep_rows<false, true>(T, B, up, dn, Lh, Rh, untracked);       // down
+      refresh_columns();
+      tall_sweep_cols<false, true>(T, B, up, dn, Lh, Rh, untracked);       // right
+      refresh_columns();
+      tall_sweep_rows<false, false>(T, B, up, dn, Lh, Rh, untracked);      // up
+      publish_rows();
+      __syncthreads();
+    }
+    bool changed = false;
+    fetch_rows();
+    refresh_columns();
+    tall_sweep_cols<true, false>(T, B, up, dn, Lh, Rh, changed);           // left, checked
+    const uint32_t slot = (iters - 1) % 3;
+    if (__builtin_amdgcn_ballot_w64(changed) != 0) {
+      publish_rows();      // a neighbour band reads these rows only if another round follows, i.e. only if someone changed
+      if (lane == 0) s_flag[slot] = 1;
+    }
+    __syncthreads();
+    const bool again = s_flag[slot] != 0;
+    if (tid == 0) s_flag[(slot + 2) % 3] = 0;
+    if (!again) break;
+    if (iters >= max_iters) { unfinished = true; break; }
+  }
+
+  // ---- write every patch back (16 B per lane and row), ring-carry check, flags
+  uint32_t ovf = 0;
+  if (gx0 < W) {
+#pragma unroll
+    for (int r = 0; r < RX0_PH; ++r) {
+      const int gy = gyb + r;
+      if (gy < H) *reinterpret_cast<u32x4_t *>(keys + (size_t)gy * W + gx0) = u32x4_t{T[r][0], T[r][1], T[r][2], T[r][3]};
+      if (check_carry) {               // kernel uniform
+#pragma unroll
+        for (int c = 0; c < RX_P; ++c)   // a finite non-seed stamp with ring 0 can only come from a carry out of the ring field
+          ovf |= (T[r][c] != 0u && T[r][c] < KEY_INF && (T[r][c] & RING_MASK) == 0u);
+      }
+    }
+  }
+  if (ovf) atomicExch(pf.overflow, 1u);      // never taken on sane inputs
+  const uint32_t stripe = (blockIdx.x % NSTRIPE) * STRIPE_STRIDE;
+  // A changed border pixel matters to the tile across the border when it can lower the pixel it touches there, which this
+  // tile holds as its halo (k_relax).  Changed: neither a seed (0) nor still KEY_INF, which `now + 1 < across` implies.
+  auto matters = [](uint32_t now, uint32_t across) { return now != 0u && now + 1u < across; };
+  bool edge = false;
+  if (band == 0) {
+    const u32x4_t a = *reinterpret_cast<const u32x4_t *>(&sRow[0][lane * RX_P]);      // the halo row above, as loaded
+    edge |= matters(T[0][0], a.x) || matters(T[0][1], a.y) || matters(T[0][2], a.z) || matters(T[0][3], a.w);
+  }
+  if (band == NB - 1) {
+    const u32x4_t a = *reinterpret_cast<const u32x4_t *>(&sRow[2 * NB + 1][lane * RX_P]);      // the halo row below
+    constexpr int l = RX0_PH - 1;
+    edge |= matters(T[l][0], a.x) || matters(T[l][1], a.y) || matters(T[l][2], a.z) || matters(T[l][3], a.w);
+  }
+  if (lane == 0 || lane == 63) {
+#pragma unroll
+    for (int r = 0; r < RX0_PH; ++r) edge |= matters(T[r][lane == 0 ? 0 : 3], lane == 0 ? Lh[r] : Rh[r]);      // (Lh of lane 0, Rh of lane 63: the halo column)
+  }
+  // plain, idempotent stores into striped words: no same-address atomics on the tile path
+  if (edge) pf.edge_changed[(pass % COUNTER_RING) * FLAG_SLOT + stripe] = 1u;
+  if (tid == 0) {
+    if (unfinished) {
+      // Stopped at the round cap: not a fixpoint of its own pixels.  Both 256 x 32 tiles ask for their re-run where pass 2
+      // will look -- word 2 of entry (x + 1, y) of the stamp array the bands and strips write (k_relax, chunk == 3) -- and
+      // raise all their quadrant flags.
+#pragma unroll
+      for (int k = 0; k < RX0_TH / (RX_NW * RX_P); ++k) {
+        const int fy = tile_y * (RX0_TH / (RX_NW * RX_P)) + k;
+        if (fy * (RX_NW * RX_P) >= H) break;
+        stamps_rerun[((size_t)fy * flagSX + tile_x + 1) * 4 + 2] = pass + 2;
+        uint32_t *own = stamps_own + ((size_t)fy * flagAX + tile_x) * 4;
+        own[0] = pass + 1; own[1] = pass + 1; own[2] = pass + 1; own[3] = pass + 1;
+      }
+      pf.edge_changed[(pass % COUNTER_RING) * FLAG_SLOT + stripe] = 1u;
+    }
+    pf.any_change[stripe] = 1u;
+    if (pf.stats) {            // profiling only: a 256 x 64 run counts as two tile runs (eight quarter tiles) of `iters` rounds each
+      atomicAdd(&pf.stats[stripe], (uint32_t)(TW * TH / 2048));
+      atomicAdd(&pf.stats[FLAG_SLOT + stripe], 2u * iters);
+    }
+  }
+}
+
 // Does a transform of this plane, started from its seeds, repair pass 0's seams with bands and strips (relax_pass)?
 bool relax_uses_seam_repair(int h, int w, bool seed_bits, int slice_h, bool padded, size_t seam_min_px) {
   const int ax = (w + RX_TW - 1) / RX_TW, ay = (h + RX_NW * RX_P - 1) / (RX_NW * RX_P);
@@ -1580,11 +1856,35 @@ hipError_t relax_pass(hipStream_t s, const uint8_t *img, size_t img_stride, uint
   // do); a tile, band or strip slice of a smooth map that is still moving then asks for a re-run in pass 2 instead of
   // carrying a flood across its 256 columns sweep by sweep.
   constexpr uint32_t SEAM_REPAIR_ROUNDS = 4;
-  if (seam_flow && pass == 1) {
-    // Rows each side of a seam (tuning knob, tools/ only).  What pass 0 leaves wrong thins out fourfold per pixel of distance from
-    // the seam, and a band raises a flag when its first or last row changes: with 4 rows a side 41 % of the tiles are flagged
-    // (pass 2: 52 us), with 6 a tile in eight (25 us), with 8 one in eleven (23 us) -- and the bands cost 35 / 50 / 59 us.
-    static const int seam_band = [] { const char *e = tuning_env("WS_RELAX_SEAM_BAND"); return e ? atoi(e) : 6; }();
+  // Rows each side of a seam (tuning knob, tools/ only).  What pass 0 leaves wrong thins out fourfold per pixel of distance from
+  // the seam, and a band raises a flag when its first or last row changes: with 4 rows a side 41 % of the tiles are flagged
+  // (pass 2: 52 us), with 6 a tile in eight (25 us), with 8 one in eleven (23 us) -- and the bands cost 35 / 50 / 59 us.
+  static const int seam_band = [] { const char *e = tuning_env("WS_RELAX_SEAM_BAND"); return e ? atoi(e) : 6; }();
+  // Pass 0 of that flow on 256 x 64 tiles (k_relax0_tall) wherever its one load path applies -- image rows that can be read
+  // as aligned dwords -- and the plane has a seam at a multiple of 64 rows for the bands to repair.  Pass 1 asks the same
+  // question of the same arguments, so the bands know which seams pass 0 left.
+  // Why the flags are still a superset of the pixels whose equation can be violated: a pass-0 tile that did not stop at its
+  // round cap is a fixpoint of its own pixels against the halo it loaded, so an equation can only be violated next to a
+  // border of a 256 x 64 tile -- the horizontal seams at rows 64 k, the vertical ones at columns 256 k.  The bands lie
+  // astride every row 64 k, the strips astride every column 256 k in ALL rows (they have not moved), each iterates to its
+  // own fixpoint on fresh stamps and flags the 256 x 32 tile that holds a pixel next to a changed outer row or column of
+  // it, exactly as before.  The rows 64 k + 32, seams of the old geometry, are interior rows of a pass-0 tile now: nothing
+  // is left violated there unless the tile stopped at its cap -- and then it has marked both 256 x 32 tiles it covers for
+  // pass 2, all of whose pixels that pass examines again.  Stamps start from an upper bound and only fall, as ever.
+  static const bool no_tall = tuning_env("WS_RELAX_NO_TALL") != nullptr;      // A/B knob, tools/ only
+  const bool tall0 = seam_flow && !no_tall && seam_band == 6 && h > RX0_TH && w >= RX_P &&
+                     ((reinterpret_cast<uintptr_t>(img) | img_stride) & 3u) == 0 && img_stride <= 0xFFFFFFFFull;
+  const int ay_tall = (h + RX0_TH - 1) / RX0_TH;
+  if (tall0 && pass == 0) {
+    k_relax0_tall<<<ax * ay_tall, 64 * RX_NW, 0, s>>>(img, (uint32_t)img_stride, keys, h, w, ax, ax, sx, max_level, cur, const_cast<uint32_t *>(prev), pf,
+                                                     max_iters, seed_labels, sh, check_carry, tile_list);
+    return hipGetLastError();
+  }
+  if (tall0 && pass == 1) {
+    // bands only where pass 0 has seams: rows 64 k (half the workgroups, the same twelve rows each); the strips as ever
+    k_relax<3, false, false, false, false, 1, 0, RX0_TH><<<ax * (ay_tall - 1), 192, 0, s>>>(img, img_stride, keys, h, w, ax, ay_tall - 1, sx, sy, 0, 1, max_level, pass, prev, cur,
+                                                                                          pf, SEAM_REPAIR_ROUNDS, nullptr, 0, sh, check_carry, pad, tile_list, 0, 0, 0, list_cap, 0);
+  } else if (seam_flow && pass == 1) {
     if (seam_band == 4)
       k_relax<2, false, false, false, false, 1><<<ax * (ay - 1), 128, 0, s>>>(img, img_stride, keys, h, w, ax, ay - 1, sx, sy, 0, 1, max_level, pass, prev, cur,
                                                                             pf, SEAM_REPAIR_ROUNDS, nullptr, 0, sh, check_carry, pad, tile_list, 0, 0, 0, list_cap, 0);
@@ -1594,6 +1894,8 @@ hipError_t relax_pass(hipStream_t s, const uint8_t *img, size_t img_stride, uint
     else
       k_relax<4, false, false, false, false, 1><<<ax * (ay - 1), 256, 0, s>>>(img, img_stride, keys, h, w, ax, ay - 1, sx, sy, 0, 1, max_level, pass, prev, cur,
                                                                             pf, SEAM_REPAIR_ROUNDS, nullptr, 0, sh, check_carry, pad, tile_list, 0, 0, 0, list_cap, 0);
+  }
+  if (seam_flow && pass == 1) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const int strips_x = (ax - 1 + 31) / 32;
