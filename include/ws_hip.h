@@ -149,6 +149,20 @@ typedef struct ws_tree_node {
   uint32_t n_leaves;     /* seed colours in the lake at that moment, itself included */
 } ws_tree_node;
 
+/* One lake of that hierarchy measured (ws_merge_tree_stats): record c belongs to seed colour c, over the pixels `area` counts.
+ * v(p) is the weight of pixel p; rows and columns are those of the padded plane.  72 bytes. */
+typedef struct ws_lake_stats {
+  uint64_t sum_w;    /* sum of v(p) over the lake's pixels */
+  uint64_t sum_wr;   /* sum of v(p) * row(p) */
+  uint64_t sum_wc;   /* sum of v(p) * col(p) */
+  uint64_t sum_r;    /* sum of row(p) */
+  uint64_t sum_c;    /* sum of col(p) */
+  uint32_t r_min, r_max, c_min, c_max; /* bounding box, inclusive */
+  uint32_t w_min, w_max;               /* smallest / largest v(p) */
+  uint32_t peak_pixel; /* row-major index, in the padded plane, of the FIRST pixel in row-major order with v == w_max */
+  uint32_t reserved;   /* 0 */
+} ws_lake_stats;
+
 /* ---- context ------------------------------------------------------------------------- */
 
 int ws_abi_version(void);
@@ -435,6 +449,28 @@ int ws_merge_tree_device(ws_ctx *ctx, const uint8_t *d_img, size_t h, size_t w, 
  * (nullable) as a u64 plane of the padded shape.  Keeps 16 B a colour more on the device (the records before they cross). */
 int ws_merge_tree(ws_ctx *ctx, const uint8_t *img, size_t h, size_t w, size_t row_stride, const uint64_t *seeds_rc, size_t n_seeds,
                   const ws_options *opt, ws_tree_node *tree, uint64_t *labels);
+/* ws_merge_tree_device and a catalogue of its lakes from the same flood: d_tree receives exactly what ws_merge_tree_device writes,
+ * d_stats n_seeds + 1 records, record c for colour c.  For an existing colour c let M_c be the pixels equal to c in
+ * P_(death_level - 1) (P_max if c never died; the seed pixel alone if death_level == 0): the set whose size is `area`.  Record c
+ * holds the sums, the extrema and the box of M_c; record 0 those of the pixels still uncoloured after the last level.  row and col
+ * are coordinates of the padded plane (shifted by one under edge correction).  v(p) comes from the weight plane: h x w elements,
+ * unpadded, weight_row_stride ELEMENTS a row, weight_dtype WS_U8 or WS_U16 (anything else: WS_ERR_UNSUPPORTED); under edge
+ * correction weight pixel (r, x) sits at padded (r + 1, x + 1) and the ring weighs 0.  d_weight == NULL: the image itself as u8
+ * (dtype and stride are ignored).  A colour that does not exist, and record 0 when nothing is uncoloured, get the identity of the
+ * fold: every sum 0, r_min = c_min = w_min = peak_pixel = 0xFFFFFFFF, r_max = c_max = w_max = 0; reserved is always 0.
+ * n_seeds == 0 writes record 0 of both arrays only.  Null pointers with non-zero sizes, bad options, a short image or weight
+ * stride and a context that holds a begun transform are refused before anything runs and leave the outputs untouched, and so is
+ * (WS_ERR_TOO_LARGE) a plane for which wmax(dtype) * pixels * max(padded h, padded w) does not fit in 64 bits.  Everything is
+ * integer and every record reproducible to the bit; float data is quantised by the caller (ws_pre_processor).  d_labels
+ * (nullable) as ws_merge_tree_device.  Workspace kept by the context on top of ws_merge_tree_device's: 68 B a colour. */
+int ws_merge_tree_stats_device(ws_ctx *ctx, const uint8_t *d_img, size_t h, size_t w, size_t row_stride, const uint32_t *d_seeds_rc,
+                               size_t n_seeds, const ws_options *opt, const void *d_weight, int weight_dtype,
+                               size_t weight_row_stride, ws_tree_node *d_tree, ws_lake_stats *d_stats, uint32_t *d_labels);
+/* The same from and into HOST memory, as ws_merge_tree: the weight plane is uploaded (contiguous, on the context) and the records
+ * come back into `tree` and `stats` (n_seeds + 1 each).  Keeps 88 B a colour more on the device and the weight plane. */
+int ws_merge_tree_stats(ws_ctx *ctx, const uint8_t *img, size_t h, size_t w, size_t row_stride, const uint64_t *seeds_rc,
+                        size_t n_seeds, const ws_options *opt, const void *weight, int weight_dtype, size_t weight_row_stride,
+                        ws_tree_node *tree, ws_lake_stats *stats, uint64_t *labels);
 /* transform_history of every slice of a cube for a list of water levels (tests/integration.rs:267,356 take a cube apart slice by
  * slice), everything in HBM.  Slices, seeds, seed_offsets (n_slices + 1 entries, on the HOST), edge correction, duplicate seeds
  * and *failed_slice as ws_transform_to_list_batch_device; levels, n_levels (0: nothing runs, nothing is written), merging and the

@@ -397,6 +397,35 @@ class MergingWatershed : public Watershed<T> {        // lib.rs:1297-1562
                                     &this->opt_, t.nodes.data(), want_labels ? t.labels.data.data() : nullptr));
     return t;
   }
+  // not in the reference: merge_tree and a catalogue of its lakes from the same flood (ws_merge_tree_stats): stats[c] holds the
+  // weighted and plain first moments, the box, the extrema and the first peak pixel of the pixels nodes[c].area counts, stats[0]
+  // those of the pixels never coloured; rows and columns are those of the padded plane.  Weights: a u8 or u16 plane of the image's
+  // shape; without one the image itself weighs.
+  struct LakeCatalogue {
+    MergeTree tree;
+    std::vector<ws_lake_stats> stats;
+    // the weighted centroid (row, col) of record c in the padded plane; false where the record weighs nothing
+    bool centroid(std::size_t c, double *row, double *col) const {
+      const ws_lake_stats &r = stats[c];
+      if (r.sum_w == 0) return false;
+      *row = double(r.sum_wr) / double(r.sum_w);
+      *col = double(r.sum_wc) / double(r.sum_w);
+      return true;
+    }
+  };
+  LakeCatalogue merge_tree_stats(ArrayView2<std::uint8_t> input, const std::vector<Seed> &seeds, bool want_labels = false) const {
+    return lake_catalogue(input, seeds, nullptr, 0, 0, want_labels);
+  }
+  LakeCatalogue merge_tree_stats(ArrayView2<std::uint8_t> input, const std::vector<Seed> &seeds, ArrayView2<std::uint8_t> weights,
+                                 bool want_labels = false) const {
+    if (weights.rows != input.rows || weights.cols != input.cols) throw std::invalid_argument("weights must have the image's shape");
+    return lake_catalogue(input, seeds, weights.ptr, WS_U8, weights.row_stride, want_labels);
+  }
+  LakeCatalogue merge_tree_stats(ArrayView2<std::uint8_t> input, const std::vector<Seed> &seeds, ArrayView2<std::uint16_t> weights,
+                                 bool want_labels = false) const {
+    if (weights.rows != input.rows || weights.cols != input.cols) throw std::invalid_argument("weights must have the image's shape");
+    return lake_catalogue(input, seeds, weights.ptr, WS_U16, weights.row_stride, want_labels);
+  }
   // not in the reference: merge_tree of every slice of a contiguous cube (n_slices x rows x cols) as ONE call of the library
   // (ws_merge_tree_batch: slices that stack share one flood, one set of per-level unions and one fold launch per level).
   // seeds: one list per slice, or nullptr for every slice's own find_local_minima (n_seeds, nullable, receives the counts).
@@ -443,6 +472,18 @@ class MergingWatershed : public Watershed<T> {        // lib.rs:1297-1562
   }
 
  private:
+  LakeCatalogue lake_catalogue(ArrayView2<std::uint8_t> input, const std::vector<Seed> &seeds, const void *weights, int dtype,
+                               std::size_t weight_stride, bool want_labels) const {
+    const std::size_t e = this->opt_.edge_correction ? 2 : 0;
+    LakeCatalogue cat{MergeTree{std::vector<ws_tree_node>(seeds.size() + 1),
+                                Array2<usize>(want_labels ? input.rows + e : 0, want_labels ? input.cols + e : 0)},
+                      std::vector<ws_lake_stats>(seeds.size() + 1)};
+    auto packed = detail::pack(seeds);
+    this->ctx_->check(ws_merge_tree_stats(this->ctx_->get(), input.ptr, input.rows, input.cols, input.row_stride, packed.data(), seeds.size(),
+                                          &this->opt_, weights, dtype, weight_stride, cat.tree.nodes.data(), cat.stats.data(),
+                                          want_labels ? cat.tree.labels.data.data() : nullptr));
+    return cat;
+  }
   template <class U> friend class TransformBuilder;
   using Watershed<T>::Watershed;
 };

@@ -42,6 +42,28 @@ pub struct ws_tree_node {
     pub n_leaves: u32,
 }
 
+/// One lake of that hierarchy measured (ws_merge_tree_stats), 72 bytes; record c belongs to seed colour c.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct ws_lake_stats {
+    pub sum_w: u64,
+    pub sum_wr: u64,
+    pub sum_wc: u64,
+    pub sum_r: u64,
+    pub sum_c: u64,
+    pub r_min: u32,
+    pub r_max: u32,
+    pub c_min: u32,
+    pub c_max: u32,
+    pub w_min: u32,
+    pub w_max: u32,
+    pub peak_pixel: u32,
+    pub reserved: u32,
+}
+
+pub const WS_U16: c_int = 3;
+pub const WS_U8: c_int = 5;
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct ws_stats {
@@ -242,6 +264,12 @@ extern "C" {
         n_seeds: usize, opt: *const ws_options, d_tree: *mut ws_tree_node, d_labels: *mut u32) -> c_int;
     pub fn ws_merge_tree(ctx: *mut ws_ctx, img: *const u8, h: usize, w: usize, row_stride: usize, seeds_rc: *const u64,
         n_seeds: usize, opt: *const ws_options, tree: *mut ws_tree_node, labels: *mut u64) -> c_int;
+    pub fn ws_merge_tree_stats_device(ctx: *mut ws_ctx, d_img: *const u8, h: usize, w: usize, row_stride: usize, d_seeds_rc: *const u32,
+        n_seeds: usize, opt: *const ws_options, d_weight: *const c_void, weight_dtype: c_int, weight_row_stride: usize,
+        d_tree: *mut ws_tree_node, d_stats: *mut ws_lake_stats, d_labels: *mut u32) -> c_int;
+    pub fn ws_merge_tree_stats(ctx: *mut ws_ctx, img: *const u8, h: usize, w: usize, row_stride: usize, seeds_rc: *const u64,
+        n_seeds: usize, opt: *const ws_options, weight: *const c_void, weight_dtype: c_int, weight_row_stride: usize,
+        tree: *mut ws_tree_node, stats: *mut ws_lake_stats, labels: *mut u64) -> c_int;
     pub fn ws_merge_tree_batch_device(ctx: *mut ws_ctx, d_cube: *const u8, n_slices: usize, h: usize, w: usize, row_stride: usize,
         slice_stride: usize, d_seeds_rc: *const u32, seed_offsets: *const usize, opt: *const ws_options, d_tree: *mut ws_tree_node,
         d_labels: *mut u32, failed_slice: *mut usize) -> c_int;

@@ -75,6 +75,14 @@ class TreeNode(ctypes.Structure):
     _fields_ = [("parent", ctypes.c_uint32), ("death_level", ctypes.c_uint32), ("area", ctypes.c_uint32), ("n_leaves", ctypes.c_uint32)]
 
 
+class LakeStats(ctypes.Structure):
+    """ws_lake_stats: one lake of the hierarchy measured (ws_merge_tree_stats), 72 bytes."""
+    _fields_ = [("sum_w", ctypes.c_uint64), ("sum_wr", ctypes.c_uint64), ("sum_wc", ctypes.c_uint64), ("sum_r", ctypes.c_uint64),
+                ("sum_c", ctypes.c_uint64), ("r_min", ctypes.c_uint32), ("r_max", ctypes.c_uint32), ("c_min", ctypes.c_uint32),
+                ("c_max", ctypes.c_uint32), ("w_min", ctypes.c_uint32), ("w_max", ctypes.c_uint32), ("peak_pixel", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
 class TileBlock(ctypes.Structure):
     """ws_tile_block: one rank's row block of a tiled field, device resident."""
     _fields_ = [("d_img", vp), ("d_seeds_rc", vp), ("d_colours", vp), ("n_seeds", sz),
@@ -152,6 +160,8 @@ SIGNATURES = {
                                                   vp, sz, vp, szp, szp]),
     "ws_merge_tree_device": (ctypes.c_int, [vp, vp, sz, sz, sz, vp, sz, ctypes.POINTER(Options), vp, vp]),
     "ws_merge_tree": (ctypes.c_int, [vp, vp, sz, sz, sz, vp, sz, ctypes.POINTER(Options), vp, vp]),
+    "ws_merge_tree_stats_device": (ctypes.c_int, [vp, vp, sz, sz, sz, vp, sz, ctypes.POINTER(Options), vp, ctypes.c_int, sz, vp, vp, vp]),
+    "ws_merge_tree_stats": (ctypes.c_int, [vp, vp, sz, sz, sz, vp, sz, ctypes.POINTER(Options), vp, ctypes.c_int, sz, vp, vp, vp]),
     "ws_merge_tree_batch_device": (ctypes.c_int, [vp, vp, sz, sz, sz, sz, sz, vp, szp, ctypes.POINTER(Options), vp, vp, szp]),
     "ws_merge_tree_batch": (ctypes.c_int, [vp, vp, sz, sz, sz, sz, sz, vp, szp, ctypes.POINTER(Options), vp, sz, szp, vp, szp, szp]),
     "ws_pre_processor": (ctypes.c_int, [vp, vp, ctypes.c_int, sz, ctypes.c_uint8, vp]),

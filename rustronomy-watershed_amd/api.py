@@ -164,6 +164,36 @@ def _history_levels(levels, max_level):
     return np.ascontiguousarray(lv, dtype=np.uint8)
 
 
+LAKE_STATS_DTYPE = np.dtype([("sum_w", "<u8"), ("sum_wr", "<u8"), ("sum_wc", "<u8"), ("sum_r", "<u8"), ("sum_c", "<u8"),
+                             ("r_min", "<u4"), ("r_max", "<u4"), ("c_min", "<u4"), ("c_max", "<u4"), ("w_min", "<u4"), ("w_max", "<u4"),
+                             ("peak_pixel", "<u4"), ("reserved", "<u4")])      # ws_lake_stats, 72 bytes
+
+
+def _as_weights(weights, shape):
+    """(array or None, ws_dtype, row stride in elements) of a weight plane for ws_merge_tree_stats: u8 or u16, the image's shape."""
+    if weights is None:
+        return None, 0, 0
+    a = np.asarray(weights)
+    if a.dtype not in (np.uint8, np.uint16) or a.ndim != 2:
+        raise TypeError("weights must be a 2-D uint8 or uint16 array (quantise float data first: pre_processor_with_max)")
+    if a.shape != tuple(shape):
+        raise ValueError(f"weights must have the image's shape {tuple(shape)}, not {a.shape}")
+    item = a.dtype.itemsize
+    if a.size and (a.strides[1] != item or a.strides[0] % item or a.strides[0] < a.shape[1] * item):
+        a = np.ascontiguousarray(a)
+    return a, _ffi.WS_DTYPES[a.dtype.name], (a.strides[0] // item if a.size else a.shape[1])
+
+
+def centroids(stats):
+    """(row, col) float64 arrays: the weighted centroid sum_wr / sum_w, sum_wc / sum_w of every record of merge_tree_stats, in the
+    coordinates of the padded plane; nan where sum_w == 0."""
+    sw = stats["sum_w"].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        row = np.where(sw > 0, stats["sum_wr"].astype(np.float64) / sw, np.nan)
+        col = np.where(sw > 0, stats["sum_wc"].astype(np.float64) / sw, np.nan)
+    return row, col
+
+
 class MergeTree:
     """The merging transform's lake hierarchy (ws_merge_tree): numpy arrays indexed by seed colour, 0 .. n_seeds.
     `parent`: canonical id of the lake that swallowed the colour (0: none); `death_level`: the first water level after which the
@@ -624,6 +654,25 @@ class MergingWatershed(_Transform):
         ctx.check(_ffi.lib().ws_merge_tree(ctx.handle, a.ctypes.data, h, w, stride, s.ctypes.data, ns, ctypes.byref(self._opt),
                                            tree.ctypes.data, labels.ctypes.data if want_labels else None))
         return MergeTree(tree[:, 0].copy(), tree[:, 1].copy(), tree[:, 2].copy(), tree[:, 3].copy(), labels)
+
+    def merge_tree_stats(self, input, seeds, weights=None, want_labels=False):
+        """Not in the reference: merge_tree and a catalogue of its lakes from the same flood (ws_merge_tree_stats).  Returns
+        (MergeTree, stats): stats is a numpy structured array (LAKE_STATS_DTYPE) of n_seeds + 1 records, record c the weighted
+        and plain first moments, the box, the extrema and the first peak pixel of the pixels `area[c]` counts, record 0 those of
+        the pixels never coloured; rows and columns are those of the padded plane.  weights: a u8 or u16 plane of the image's
+        shape (None: the image itself).  centroids(stats) gives the weighted centroids."""
+        a, stride = _as_image(input)
+        s, ns = _as_seeds(seeds)
+        h, w = a.shape
+        wt, dtype, wstride = _as_weights(weights, a.shape)
+        tree = np.empty((ns + 1, 4), dtype=np.uint32)
+        stats = np.empty(ns + 1, dtype=LAKE_STATS_DTYPE)
+        labels = np.empty(self._shape(a), dtype=np.uint64) if want_labels else None
+        ctx = self._ctx()
+        ctx.check(_ffi.lib().ws_merge_tree_stats(ctx.handle, a.ctypes.data, h, w, stride, s.ctypes.data, ns, ctypes.byref(self._opt),
+                                                 wt.ctypes.data if wt is not None else None, dtype, wstride, tree.ctypes.data,
+                                                 stats.ctypes.data, labels.ctypes.data if want_labels else None))
+        return MergeTree(tree[:, 0].copy(), tree[:, 1].copy(), tree[:, 2].copy(), tree[:, 3].copy(), labels), stats
 
     def merge_tree_cube(self, cube, seeds=None, want_labels=False):
         """merge_tree of every slice cube[k] of a 3-D u8 array with seeds[k] -- or, with seeds None, the slice's own

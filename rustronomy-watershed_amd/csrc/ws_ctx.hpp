@@ -58,6 +58,8 @@ struct ws_ctx {
   wsapi::DevBuf tree_order, tree_ws, tree_out;
   // ws_merge_tree_batch(_device): a stack's records in the forest's numbering before they move to the caller's layout
   wsapi::DevBuf tree_forest;
+  // ws_merge_tree_stats(_device): the accumulator planes (68 B a colour); the host form's records and its weight plane on the device
+  wsapi::DevBuf lake_acc, lake_out, lake_weight;
   uint32_t *pinned = nullptr;      // FLAG_WORDS words of pinned host memory: the host's mirror of the flag block
   uint32_t *pinned_dev = nullptr;  // the same words as the device sees them (nullptr: not mapped, copies only)
   hipEvent_t ring_ev[wsk::COUNTER_RING]{};   // flag slot copied to the host

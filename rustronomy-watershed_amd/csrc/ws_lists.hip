@@ -601,6 +601,41 @@ int build_tree(ws_ctx *c, const uint32_t *d_seeds, size_t n_seeds, const ws_opti
   return WS_OK;
 }
 
+// ---- merge_tree_stats: the lakes of the hierarchy measured ---------------------------------------------------
+
+static_assert(sizeof(ws_lake_stats) == 72 && sizeof(ws_lake_stats) == sizeof(LakeRec), "ws_lake_stats is the kernels' LakeRec");
+
+// what both forms check, after check_tree and before anything runs: the weights' type and stride, and that no sum can pass 64 bits
+int check_lake_weights(ws_ctx *c, size_t w, size_t ph, size_t pw, const void *weight, int dtype, size_t weight_stride) {
+  uint64_t wmax = 0xFFull;
+  if (weight) {
+    if (dtype != WS_U8 && dtype != WS_U16) return fail(c, WS_ERR_UNSUPPORTED, "weights are u8 or u16");
+    if (weight_stride < w) return fail(c, WS_ERR_BAD_ARG, "weight_row_stride < w");
+    if (dtype == WS_U16) wmax = 0xFFFFull;
+  }
+  const uint64_t pixels = (uint64_t)ph * pw, longest = std::max(ph, pw);
+  if (longest && pixels > UINT64_MAX / wmax / longest) return fail(c, WS_ERR_TOO_LARGE, "the weighted moments do not fit in 64 bits");
+  return WS_OK;
+}
+
+int ensure_lake(ws_ctx *c, size_t n_seeds, bool host_records) {
+  int rc;
+  if ((rc = ensure(c, c->lake_acc, (n_seeds + 1) * LAKE_ACC_BYTES))) return rc;
+  if (host_records && (rc = ensure(c, c->lake_out, (n_seeds + 1) * sizeof(ws_lake_stats)))) return rc;
+  return WS_OK;
+}
+
+// the statistics of the tree build_tree has just finished at d_tree, from the same transform
+int build_lake_stats(ws_ctx *c, const uint32_t *d_seeds, size_t n_seeds, const ws_options *opt, size_t ph, size_t pw, const ws_tree_node *d_tree,
+                     const LakeWeights &wt, ws_lake_stats *d_stats) {
+  Span sp(c, KC_OTHER);
+  HIP_TRY(c, lake_stats(c->stream, (const uint32_t *)c->keys.p, (const uint32_t *)c->labels.p, (const uint32_t *)c->uf_death.p,
+                        (const uint32_t *)c->uf_hook.p, reinterpret_cast<const TreeRec *>(d_tree), d_seeds, n_seeds + 1,
+                        (uint32_t)opt->max_water_level + 1, (const u64c *)c->tree_ws.p, (const uint32_t *)c->tree_order.p, wt, (int)ph, (int)pw,
+                        c->lake_acc.p, reinterpret_cast<LakeRec *>(d_stats)));
+  return WS_OK;
+}
+
 // ---- transform_history of a cube of slices (ws_transform_history_batch(_device)) ---------------------------------------------------
 
 // The transform of slices [k_first, k_first + g) of a batch, left on the context for rendering: a stack (labels restart at 1 in every
@@ -896,6 +931,68 @@ int ws_merge_tree(ws_ctx *c, const uint8_t *img, size_t h, size_t w, size_t stri
   const uint32_t *seeds = (const uint32_t *)c->seeds.p;      // stage_inputs: narrowed, shifted where the options say so
   if (int rc = build_tree(c, seeds, n_seeds, opt, ph, pw, (ws_tree_node *)c->tree_out.p)) return rc;
   HIP_TRY(c, hipMemcpyAsync(tree, c->tree_out.p, (n_seeds + 1) * sizeof(ws_tree_node), hipMemcpyDeviceToHost, c->stream));
+  if (labels && ph * pw)
+    if (int rc = labels_to_host_u64(c, (const uint32_t *)c->labels.p, labels, ph * pw)) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return WS_OK;
+}
+
+int ws_merge_tree_stats_device(ws_ctx *c, const uint8_t *d_img, size_t h, size_t w, size_t stride, const uint32_t *d_seeds_rc, size_t n_seeds,
+                               const ws_options *opt, const void *d_weight, int weight_dtype, size_t weight_stride, ws_tree_node *d_tree,
+                               ws_lake_stats *d_stats, uint32_t *d_labels) {
+  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
+  if (!c) return WS_ERR_BAD_ARG;
+  if (!opt || !d_tree || !d_stats || (!d_img && h * w) || (!d_seeds_rc && n_seeds)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  size_t ph = 0, pw = 0;
+  if (int rc = check_tree(c, h, w, stride, opt, n_seeds, &ph, &pw)) return rc;
+  if (int rc = check_lake_weights(c, w, ph, pw, d_weight, weight_dtype, weight_stride)) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (int rc = ensure_tree(c, n_seeds, false)) return rc;
+  if (int rc = ensure_lake(c, n_seeds, false)) return rc;
+  const DeviceLists dev{d_img, d_seeds_rc, nullptr};
+  if (int rc = merge_host(c, true, nullptr, h, w, stride, nullptr, n_seeds, opt, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
+                          &dev, true))
+    return rc;
+  const uint32_t *seeds = seed_shift_of(opt) && n_seeds ? (const uint32_t *)c->seeds.p : d_seeds_rc;
+  if (int rc = build_tree(c, seeds, n_seeds, opt, ph, pw, d_tree)) return rc;
+  const uint32_t off = opt->edge_correction ? 1u : 0u;
+  const LakeWeights wt = d_weight ? LakeWeights{d_weight, weight_stride, (uint32_t)h, (uint32_t)w, off, weight_dtype == WS_U16}
+                                  : LakeWeights{d_img, stride, (uint32_t)h, (uint32_t)w, off, 0};
+  if (int rc = build_lake_stats(c, seeds, n_seeds, opt, ph, pw, d_tree, wt, d_stats)) return rc;
+  if (d_labels && ph * pw) HIP_TRY(c, hipMemcpyAsync(d_labels, c->labels.p, ph * pw * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return WS_OK;
+}
+
+int ws_merge_tree_stats(ws_ctx *c, const uint8_t *img, size_t h, size_t w, size_t stride, const uint64_t *seeds_rc, size_t n_seeds,
+                        const ws_options *opt, const void *weight, int weight_dtype, size_t weight_stride, ws_tree_node *tree,
+                        ws_lake_stats *stats, uint64_t *labels) {
+  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
+  if (!c) return WS_ERR_BAD_ARG;
+  if (!opt || !tree || !stats || (!img && h * w) || (!seeds_rc && n_seeds)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  size_t ph = 0, pw = 0;
+  if (int rc = check_tree(c, h, w, stride, opt, n_seeds, &ph, &pw)) return rc;
+  if (int rc = check_lake_weights(c, w, ph, pw, weight, weight_dtype, weight_stride)) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (int rc = ensure_tree(c, n_seeds, true)) return rc;
+  if (int rc = ensure_lake(c, n_seeds, true)) return rc;
+  const size_t elem = weight && weight_dtype == WS_U16 ? 2 : 1;
+  const bool own_plane = weight && h * w;
+  if (own_plane) {      // contiguous on the context, before the transform: nothing moves under the level loop's graphs
+    if (int rc = ensure(c, c->lake_weight, h * w * elem)) return rc;
+    HIP_TRY(c, hipMemcpy2DAsync(c->lake_weight.p, w * elem, weight, weight_stride * elem, w * elem, h, hipMemcpyHostToDevice, c->stream));
+  }
+  if (int rc = merge_host(c, true, img, h, w, stride, seeds_rc, n_seeds, opt, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
+                          nullptr, true))
+    return rc;
+  const uint32_t *seeds = (const uint32_t *)c->seeds.p;      // stage_inputs: narrowed, shifted where the options say so
+  ws_tree_node *d_tree = (ws_tree_node *)c->tree_out.p;
+  if (int rc = build_tree(c, seeds, n_seeds, opt, ph, pw, d_tree)) return rc;
+  // (no weights: the image as stage_inputs left it on the device, w bytes a row)
+  const LakeWeights wt{own_plane ? c->lake_weight.p : c->img.p, w, (uint32_t)h, (uint32_t)w, opt->edge_correction ? 1u : 0u, elem == 2};
+  if (int rc = build_lake_stats(c, seeds, n_seeds, opt, ph, pw, d_tree, wt, (ws_lake_stats *)c->lake_out.p)) return rc;
+  HIP_TRY(c, hipMemcpyAsync(tree, d_tree, (n_seeds + 1) * sizeof(ws_tree_node), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(stats, c->lake_out.p, (n_seeds + 1) * sizeof(ws_lake_stats), hipMemcpyDeviceToHost, c->stream));
   if (labels && ph * pw)
     if (int rc = labels_to_host_u64(c, (const uint32_t *)c->labels.p, labels, ph * pw)) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));

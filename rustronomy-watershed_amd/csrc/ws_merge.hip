@@ -1631,6 +1631,286 @@ hipError_t tree_fold(hipStream_t s, TreeRec *tree, size_t n_colours, uint32_t le
   return hipSuccess;
 }
 
+// ---- lake statistics (ws_merge_tree_stats_device) ------------------------------------------------------------
+//
+// What carries `area` up the tree carries any commutative per-pixel quantity: five u64 sums, a box, the smallest weight and the
+// packed peak (weight << 32 | 0xFFFFFFFF - pixel: its maximum is the FIRST pixel in row-major order that holds the largest weight).
+// Sums, minima and maxima of integers do not depend on the order the atomics arrive in: every record is reproducible to the bit.
+// The accumulators are planes of n_colours entries (sum: w, wr, wc, r, c, peak; box: r_min, r_max, c_min, c_max, w_min), so that the
+// lanes of a wave that update neighbouring colours touch neighbouring words; k_lake_write turns them into the 72-byte records.
+
+constexpr int LAKE_SLOTS = 512, LAKE_PROBES = 4;      // 72 B a slot: 36 KB a workgroup, four workgroups (16 waves) a CU of 160 KB
+constexpr uint32_t LAKE_EMPTY = 0xFFFFFFFFu;
+
+struct LakePart {
+  u64c w, wr, wc, r, c, peak;
+  uint32_t r_min, r_max, c_min, c_max, w_min;
+};
+
+__device__ __forceinline__ LakePart lake_none() { return LakePart{0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u, 0xFFFFFFFFu}; }
+
+__device__ __forceinline__ LakePart lake_pixel(uint32_t v, uint32_t y, uint32_t x, uint32_t i) {
+  return LakePart{(u64c)v, (u64c)v * y, (u64c)v * x, (u64c)y, (u64c)x, (u64c)v << 32 | (u64c)(0xFFFFFFFFu - i), y, y, x, x, v};
+}
+
+__device__ __forceinline__ void lake_join(LakePart &a, const LakePart &b) {
+  a.w += b.w; a.wr += b.wr; a.wc += b.wc; a.r += b.r; a.c += b.c;
+  a.peak = a.peak > b.peak ? a.peak : b.peak;
+  a.r_min = min(a.r_min, b.r_min); a.r_max = max(a.r_max, b.r_max);
+  a.c_min = min(a.c_min, b.c_min); a.c_max = max(a.c_max, b.c_max);
+  a.w_min = min(a.w_min, b.w_min);
+}
+
+__device__ __forceinline__ LakePart lake_wave_total(LakePart a) {      // the join over the wave, in every lane
+  for (int o = 32; o > 0; o >>= 1) {
+    LakePart b;
+    b.w = __shfl_xor(a.w, o, 64); b.wr = __shfl_xor(a.wr, o, 64); b.wc = __shfl_xor(a.wc, o, 64);
+    b.r = __shfl_xor(a.r, o, 64); b.c = __shfl_xor(a.c, o, 64); b.peak = __shfl_xor(a.peak, o, 64);
+    b.r_min = __shfl_xor(a.r_min, o, 64); b.r_max = __shfl_xor(a.r_max, o, 64);
+    b.c_min = __shfl_xor(a.c_min, o, 64); b.c_max = __shfl_xor(a.c_max, o, 64);
+    b.w_min = __shfl_xor(a.w_min, o, 64);
+    lake_join(a, b);
+  }
+  return a;
+}
+
+// entry i of accumulator planes of n entries each (LDS table or memory) takes a part: one atomic a field, none for a sum of 0
+__device__ __forceinline__ void lake_apply(u64c *sum, uint32_t *box, size_t n, size_t i, const LakePart &a) {
+  if (a.w) atomicAdd(&sum[i], a.w);
+  if (a.wr) atomicAdd(&sum[n + i], a.wr);
+  if (a.wc) atomicAdd(&sum[2 * n + i], a.wc);
+  if (a.r) atomicAdd(&sum[3 * n + i], a.r);
+  if (a.c) atomicAdd(&sum[4 * n + i], a.c);
+  atomicMax(&sum[5 * n + i], a.peak);
+  atomicMin(&box[i], a.r_min);
+  atomicMax(&box[n + i], a.r_max);
+  atomicMin(&box[2 * n + i], a.c_min);
+  atomicMax(&box[3 * n + i], a.c_max);
+  atomicMin(&box[4 * n + i], a.w_min);
+}
+
+__device__ __forceinline__ LakePart lake_load(const u64c *sum, const uint32_t *box, size_t n, size_t i) {
+  return LakePart{sum[i], sum[n + i], sum[2 * n + i], sum[3 * n + i], sum[4 * n + i], sum[5 * n + i],
+                  box[i], box[n + i], box[2 * n + i], box[3 * n + i], box[4 * n + i]};
+}
+
+__device__ __forceinline__ void lake_store(u64c *sum, uint32_t *box, size_t n, size_t i, const LakePart &a) {
+  sum[i] = a.w; sum[n + i] = a.wr; sum[2 * n + i] = a.wc; sum[3 * n + i] = a.r; sum[4 * n + i] = a.c; sum[5 * n + i] = a.peak;
+  box[i] = a.r_min; box[n + i] = a.r_max; box[2 * n + i] = a.c_min; box[3 * n + i] = a.c_max; box[4 * n + i] = a.w_min;
+}
+
+template <typename T>
+__device__ __forceinline__ uint32_t lake_weight(const LakeWeights &wt, uint32_t y, uint32_t x) {
+  const uint32_t yy = y - wt.off, xx = x - wt.off;      // (the ring wraps to far above h and w)
+  return yy < wt.h && xx < wt.w ? (uint32_t)reinterpret_cast<const T *>(wt.p)[(size_t)yy * wt.stride + xx] : 0u;
+}
+
+__global__ __launch_bounds__(256) void k_lake_init(u64c *sum, uint32_t *box, size_t n) {
+  const size_t c = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (c < n) lake_store(sum, box, n, c, lake_none());
+}
+
+// a root's part into the workgroup's table; a root that finds no slot within LAKE_PROBES updates memory itself: exact either way
+__device__ __forceinline__ void lake_add(uint32_t *s_key, u64c *s_sum, uint32_t *s_box, uint32_t *s_used, u64c *sum, uint32_t *box, size_t n_colours,
+                                         uint32_t r, const LakePart &a) {
+  const uint32_t h0 = (r * 2654435761u) >> 23;      // 9 bits
+  for (int j = 0; j < LAKE_PROBES; ++j) {
+    const uint32_t slot = (h0 + (uint32_t)j) & (LAKE_SLOTS - 1);
+    const uint32_t old = atomicCAS(&s_key[slot], LAKE_EMPTY, r);
+    if (old == LAKE_EMPTY) atomicAdd(s_used, 1u);
+    if (old == LAKE_EMPTY || old == r) { lake_apply(s_sum, s_box, LAKE_SLOTS, slot, a); return; }
+  }
+  lake_apply(sum, box, n_colours, r, a);
+}
+
+// the table into memory, one visit per root it holds, and empty again
+__device__ __forceinline__ void lake_flush(uint32_t *s_key, u64c *s_sum, uint32_t *s_box, u64c *sum, uint32_t *box, size_t n_colours) {
+  for (int j = threadIdx.x; j < LAKE_SLOTS; j += 256) {
+    if (s_key[j] == LAKE_EMPTY) continue;
+    lake_apply(sum, box, n_colours, s_key[j], lake_load(s_sum, s_box, LAKE_SLOTS, j));
+    s_key[j] = LAKE_EMPTY;
+    lake_store(s_sum, s_box, LAKE_SLOTS, j, lake_none());
+  }
+}
+
+// Own statistics: every pixel to the root of its colour at its arrival level (the walks of k_tree_own), an uncoloured pixel to
+// record 0.  Around the percolation level most of the plane lands on ONE root and a pixel brings eleven atomics, not one: a lane
+// first joins those of its four pixels that share a root, a wave joins the lanes that agree with its first lane, the workgroup's
+// table takes the rest, and memory is touched once per root and workgroup.  The table lives across the workgroup's steps (the big
+// lake keeps its slot) until a step leaves it more than half full: below the percolation level a long run meets thousands of small
+// roots, and a table they have filled sends every newcomer to memory field by field; it is written out and starts again empty.
+template <typename T>
+__global__ __launch_bounds__(256) void k_lake_own(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ labels,
+                                                  const uint32_t *__restrict__ death, const uint32_t *__restrict__ hook, LakeWeights wt,
+                                                  uint32_t W, u64c *sum, uint32_t *box, size_t n_colours, size_t n, size_t steps) {
+  __shared__ u64c s_sum[6 * LAKE_SLOTS];
+  __shared__ uint32_t s_box[5 * LAKE_SLOTS], s_key[LAKE_SLOTS], s_used;
+  for (int j = threadIdx.x; j < LAKE_SLOTS; j += 256) {
+    s_key[j] = LAKE_EMPTY;
+    lake_store(s_sum, s_box, LAKE_SLOTS, j, lake_none());
+  }
+  if (threadIdx.x == 0) s_used = 0;
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const bool vec = ((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(labels)) & 15u) == 0;
+  uint32_t flushed_at = 0;      // slots taken, over the run, when the table was last written out
+  for (size_t st = 0; st < steps; ++st) {      // workgroup uniform
+    const size_t i0 = (((size_t)blockIdx.x * steps + st) * 256 + threadIdx.x) * 4;
+    uint32_t arr[4], col[4];
+    if (vec && i0 + 3 < n) {
+      const u32x4_m k = *reinterpret_cast<const u32x4_m *>(keys + i0), l = *reinterpret_cast<const u32x4_m *>(labels + i0);
+      arr[0] = k.x >> 24; arr[1] = k.y >> 24; arr[2] = k.z >> 24; arr[3] = k.w >> 24;
+      col[0] = l.x; col[1] = l.y; col[2] = l.z; col[3] = l.w;
+    } else {
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        const bool in = i0 + p < n;
+        arr[p] = in ? keys[i0 + p] >> 24 : 0xFFu;
+        col[p] = in ? labels[i0 + p] : 0u;
+      }
+    }
+    uint32_t r[4], d[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const bool coloured = col[p] != 0u && arr[p] != 0xFFu;      // (as k_tree_own)
+      r[p] = coloured ? col[p] : 0u;
+      d[p] = coloured ? death[col[p]] : TREE_ALIVE;
+    }
+    for (;;) {      // the root at the pixel's arrival level, four walks side by side
+      bool go[4];
+#pragma unroll
+      for (int p = 0; p < 4; ++p) go[p] = d[p] <= arr[p];
+      if (!(go[0] || go[1] || go[2] || go[3])) break;
+#pragma unroll
+      for (int p = 0; p < 4; ++p) if (go[p]) r[p] = hook[r[p]];
+#pragma unroll
+      for (int p = 0; p < 4; ++p) if (go[p]) d[p] = death[r[p]];
+    }
+    uint32_t y = i0 < n ? (uint32_t)i0 / W : 0u, x = i0 < n ? (uint32_t)i0 % W : 0u;      // (n < 2^32)
+    LakePart part[4];
+    bool live[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      live[p] = i0 + p < n;
+      part[p] = lake_pixel(live[p] ? lake_weight<T>(wt, y, x) : 0u, y, x, (uint32_t)(i0 + p));
+      if (++x == W) { x = 0; ++y; }
+    }
+#pragma unroll
+    for (int p = 1; p < 4; ++p)
+#pragma unroll
+      for (int q = 0; q < p; ++q)
+        if (live[p] && live[q] && r[p] == r[q]) { lake_join(part[q], part[p]); live[p] = false; }
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const unsigned long long todo = __builtin_amdgcn_ballot_w64(live[p]);
+      if (todo == 0) continue;      // wave uniform
+      const int leader = (int)__builtin_ctzll(todo);
+      const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)r[p], leader);
+      const bool same = live[p] && r[p] == r0;
+      if (__popcll(__builtin_amdgcn_ballot_w64(same)) > 1) {      // wave uniform
+        const LakePart total = lake_wave_total(same ? part[p] : lake_none());
+        if (lane == leader) lake_add(s_key, s_sum, s_box, &s_used, sum, box, n_colours, r0, total);
+        else if (live[p] && !same) lake_add(s_key, s_sum, s_box, &s_used, sum, box, n_colours, r[p], part[p]);
+      } else if (live[p]) {
+        lake_add(s_key, s_sum, s_box, &s_used, sum, box, n_colours, r[p], part[p]);
+      }
+    }
+    __syncthreads();
+    const uint32_t used = s_used;      // (nobody inserts between the two barriers: workgroup uniform)
+    const bool full = used - flushed_at > LAKE_SLOTS / 2;
+    if (full || st + 1 == steps) lake_flush(s_key, s_sum, s_box, sum, box, n_colours);
+    if (full) flushed_at = used;
+    __syncthreads();
+  }
+}
+
+// One death level from 1 up: every colour of the bucket joins its record into its parent's (children die strictly before their
+// parents: nobody reads a record another lane is adding to).  Lanes that share a parent are joined in the wave first, as k_tree_fold.
+__global__ __launch_bounds__(256) void k_lake_fold(const TreeRec *__restrict__ tree, u64c *sum, uint32_t *box, size_t n_colours,
+                                                   const uint32_t *__restrict__ order, const u64c *__restrict__ range) {
+  const u64c first = range[0];
+  const size_t n = (size_t)(range[1] - first);
+  const int lane = threadIdx.x & 63;
+  order += first;
+  for (size_t base = (size_t)blockIdx.x * 256; base < n; base += (size_t)gridDim.x * 256) {      // uniform trip count per wave
+    const size_t i = base + threadIdx.x;
+    const bool active = i < n;
+    uint32_t p = 0xFFFFFFFFu;
+    LakePart part = lake_none();
+    if (active) {
+      const uint32_t c = order[i];
+      p = tree[c].parent;
+      part = lake_load(sum, box, n_colours, c);
+    }
+    unsigned long long todo = __builtin_amdgcn_ballot_w64(active);
+    for (int round = 0; round < 2 && todo != 0; ++round) {
+      const int leader = (int)__builtin_ctzll(todo);
+      const uint32_t p0 = (uint32_t)__builtin_amdgcn_readlane((int)p, leader);
+      const bool same = active && p == p0;
+      const unsigned long long with = __builtin_amdgcn_ballot_w64(same);
+      if (__popcll(with) > 1) {      // wave uniform
+        const LakePart total = lake_wave_total(same ? part : lake_none());
+        if (lane == leader) lake_apply(sum, box, n_colours, p0, total);
+      } else if (lane == leader) {
+        lake_apply(sum, box, n_colours, p0, part);
+      }
+      todo &= ~with;
+    }
+    if ((todo >> lane) & 1ull) lake_apply(sum, box, n_colours, p, part);
+  }
+}
+
+// The records.  A colour that dies at level 0 handed on nothing and was never the root of a pixel: it takes its seed pixel alone.
+template <typename T>
+__global__ __launch_bounds__(256) void k_lake_write(const TreeRec *__restrict__ tree, const uint32_t *__restrict__ seeds_rc, LakeWeights wt, uint32_t W,
+                                                    const u64c *__restrict__ sum, const uint32_t *__restrict__ box, size_t n_colours, LakeRec *out) {
+  const size_t c = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (c >= n_colours) return;
+  LakePart a = lake_load(sum, box, n_colours, c);
+  if (c != 0) {
+    const TreeRec t = tree[c];
+    if (t.death_level == 0u && t.n_leaves != 0u) {
+      const uint32_t y = seeds_rc[2 * (c - 1)], x = seeds_rc[2 * (c - 1) + 1];
+      a = lake_pixel(lake_weight<T>(wt, y, x), y, x, y * W + x);
+    }
+  }
+  out[c] = LakeRec{a.w, a.wr, a.wc, a.r, a.c, a.r_min, a.r_max, a.c_min, a.c_max, a.w_min, (uint32_t)(a.peak >> 32),
+                   0xFFFFFFFFu - (uint32_t)a.peak, 0u};
+}
+
+hipError_t lake_stats(hipStream_t s, const uint32_t *keys, const uint32_t *labels, const uint32_t *death, const uint32_t *hook, const TreeRec *tree,
+                      const uint32_t *seeds_rc, size_t n_colours, uint32_t levels, const u64c *ws, const uint32_t *order, const LakeWeights &wt, int h,
+                      int w, void *acc, LakeRec *out) {
+  if (n_colours == 0) return hipSuccess;
+  const size_t n = (size_t)h * (size_t)w;
+  if (n > 0xFFFFFFFFull || (reinterpret_cast<uintptr_t>(acc) & 7u) != 0) return hipErrorInvalidValue;      // (rows and columns are u32 divisions)
+  u64c *sum = (u64c *)acc;
+  uint32_t *box = (uint32_t *)(sum + 6 * n_colours);
+  const unsigned per_colour = (unsigned)((n_colours + 255) / 256);
+  k_lake_init<<<per_colour, 256, 0, s>>>(sum, box, n_colours);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (n) {      // the grid of tree_own_counts: at most two thousand workgroups, 1024 pixels a step
+    const size_t quads = (n + 1023) / 1024;
+    const size_t steps = std::max<size_t>((quads + 2047) / 2048, 1);
+    const unsigned grid = (unsigned)((quads + steps - 1) / steps);
+    if (wt.u16) k_lake_own<uint16_t><<<grid, 256, 0, s>>>(keys, labels, death, hook, wt, (uint32_t)w, sum, box, n_colours, n, steps);
+    else k_lake_own<uint8_t><<<grid, 256, 0, s>>>(keys, labels, death, hook, wt, (uint32_t)w, sum, box, n_colours, n, steps);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  if (n_colours > 1) {      // (tree_fold built order[] and its bounds under the same condition)
+    const u64c *off = ws + NLEVELS + 1;
+    const unsigned grid = (unsigned)std::min<size_t>(std::max<size_t>(n_colours / (256 * 64), 1), 128);
+    for (uint32_t l = 1; l < levels; ++l) {
+      k_lake_fold<<<grid, 256, 0, s>>>(tree, sum, box, n_colours, order, off + l);
+      if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+  }
+  if (wt.u16) k_lake_write<uint16_t><<<per_colour, 256, 0, s>>>(tree, seeds_rc, wt, (uint32_t)w, sum, box, n_colours, out);
+  else k_lake_write<uint8_t><<<per_colour, 256, 0, s>>>(tree, seeds_rc, wt, (uint32_t)w, sum, box, n_colours, out);
+  return hipGetLastError();
+}
+
 // ---- a stack of slices (ws_transform_to_list_batch_device, ws_merge_batch_device) --------------------------------------------
 //
 // The slices of a cube flooded as ONE plane of g x slice_h rows (ws_segment.hip, segment_batch_stacked): labels restart at 1 in

@@ -166,4 +166,26 @@ hipError_t tree_own_counts_stack(hipStream_t s, const uint32_t *keys, const uint
 hipError_t tree_unstack(hipStream_t s, const TreeRec *forest, size_t n_seeds, const uint32_t *base, size_t g, const u64c *hist, uint32_t levels,
                         size_t plane, TreeRec *out);
 
+// lake statistics (ws_merge_tree_stats_device): per colour the weighted and plain first moments, the box,
+// the extrema of the weight and the first pixel that holds the largest, over the pixels `area` counts.  Integers only.
+struct LakeRec {      // == ws_lake_stats
+  u64c sum_w, sum_wr, sum_wc, sum_r, sum_c;
+  uint32_t r_min, r_max, c_min, c_max, w_min, w_max, peak_pixel, reserved;
+};
+// the weight plane: h x w elements of u8 or u16 (u16 != 0), `stride` elements a row; pixel (r, x) of it sits at (r + off, x + off)
+// of the padded plane and every other pixel of that plane weighs 0
+struct LakeWeights {
+  const void *p;
+  size_t stride;
+  uint32_t h, w, off;
+  int u16;
+};
+constexpr size_t LAKE_ACC_BYTES = 6 * sizeof(u64c) + 5 * sizeof(uint32_t);      // per colour: five sums and the packed peak, then the box and w_min
+// After tree_init / tree_own_counts / tree_fold of the same transform (tree: finished records; ws, order: tree_fold's buckets, left
+// as they are): own statistics in one pass over the stamps, the segmenting labels and the weights, one fold launch per death level
+// from 1 up, and the records into out (n_colours of them).  acc: n_colours * LAKE_ACC_BYTES of scratch, 8-byte aligned.
+hipError_t lake_stats(hipStream_t s, const uint32_t *keys, const uint32_t *labels, const uint32_t *death, const uint32_t *hook, const TreeRec *tree,
+                      const uint32_t *seeds_rc, size_t n_colours, uint32_t levels, const u64c *ws, const uint32_t *order, const LakeWeights &wt, int h,
+                      int w, void *acc, LakeRec *out);
+
 }  // namespace wsk

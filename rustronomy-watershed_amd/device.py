@@ -313,6 +313,43 @@ class DeviceEngine:
                                                        ctypes.byref(opt), out.data_ptr(), labels.data_ptr() if want_labels else None))
         return (out, labels) if want_labels else out
 
+    def merge_tree_stats(self, img, seeds, weights=None, max_level=254, edge=False, seed_shift=False, want_labels=False, out=None,
+                         out_stats=None):
+        """merge_tree and a catalogue of its lakes from the same flood with everything in HBM (ws_merge_tree_stats_device): the
+        tree tensor of merge_tree and an (n_seeds + 1, 9) int64 tensor of raw ws_lake_stats records -- row c, the bits of colour
+        c's 72 bytes: sum_w, sum_wr, sum_wc, sum_r, sum_c (uint64 bits), then r_min | r_max << 32, c_min | c_max << 32,
+        w_min | w_max << 32, peak_pixel | reserved << 32.  weights: a 2-D uint8 or int16 / uint16 (taken as u16 bits) device
+        tensor of the image's shape whose rows are contiguous (a row stride in elements is honoured), None: the image itself.
+        With want_labels returns (tree, stats, labels).  `out`, `out_stats`: reusable contiguous tensors of those shapes."""
+        assert img.dtype == torch.uint8 and img.dim() == 2 and img.is_contiguous() and img.is_cuda
+        assert seeds.dtype == torch.int32 and seeds.is_cuda and (seeds.numel() == 0 or seeds.is_contiguous())
+        h, w = img.shape
+        ns = seeds.shape[0] if seeds.dim() == 2 else 0
+        dtype, wstride = 0, 0
+        if weights is not None:
+            u16 = {torch.int16, getattr(torch, "uint16", torch.int16)}
+            if weights.dtype != torch.uint8 and weights.dtype not in u16:
+                raise TypeError("weights must be a uint8, uint16 or int16 (u16 bits) tensor")
+            if not weights.is_cuda or weights.dim() != 2 or tuple(weights.shape) != (h, w) or (w > 1 and weights.stride(1) != 1):
+                raise ValueError(f"weights must be a device tensor of shape {(h, w)} with contiguous rows")
+            dtype = _ffi.WS_DTYPES["uint8" if weights.dtype == torch.uint8 else "uint16"]
+            wstride = weights.stride(0) if h > 1 else w
+        if out is None:
+            out = torch.empty((ns + 1, 4), dtype=torch.int32, device=self.device)
+        elif out.dtype != torch.int32 or not out.is_contiguous() or tuple(out.shape) != (ns + 1, 4):
+            raise ValueError(f"out must be a contiguous int32 tensor of shape {(ns + 1, 4)}")
+        if out_stats is None:
+            out_stats = torch.empty((ns + 1, 9), dtype=torch.int64, device=self.device)
+        elif out_stats.dtype != torch.int64 or not out_stats.is_contiguous() or tuple(out_stats.shape) != (ns + 1, 9):
+            raise ValueError(f"out_stats must be a contiguous int64 tensor of shape {(ns + 1, 9)}")
+        labels = torch.empty(self._plane(img, edge), dtype=torch.int32, device=self.device) if want_labels else None
+        opt = self.options(max_level, edge, None, seed_shift)
+        self.ctx.check(_ffi.lib().ws_merge_tree_stats_device(self.ctx.handle, img.data_ptr(), h, w, w, seeds.data_ptr() if ns else None, ns,
+                                                             ctypes.byref(opt), weights.data_ptr() if weights is not None else None, dtype,
+                                                             wstride, out.data_ptr(), out_stats.data_ptr(),
+                                                             labels.data_ptr() if want_labels else None))
+        return (out, out_stats, labels) if want_labels else (out, out_stats)
+
     def merge_tree_batch(self, cube, seeds, seed_offsets, max_level=254, edge=False, seed_shift=False, want_labels=False, out=None):
         """merge_tree of every slice of a cube with everything in HBM (ws_merge_tree_batch_device); cube, seeds and seed_offsets as
         transform_to_list_batch.  Returns an (n_seeds_total + S, 4) int32 tensor: slice k's n_k + 1 rows start at
