@@ -529,7 +529,15 @@ int ws_merge_tree_batch(ws_ctx *ctx, const uint8_t *cube, size_t n_slices, size_
  * array (any dimension, passed flattened) -> u8 in [0, MAX].  Quirks reproduced as coded: min and
  * max folds are seeded with 0; values that are not `is_normal` in f64 -- NaN, -inf, subnormals AND
  * exact 0 -- become NEVER_FILL (255); +inf becomes ALWAYS_FILL (0); the rest is
- * trunc((x - min) / (max - min) * MAX) in f64.  max_value must be in 1..=254 (the reference asserts). */
+ * trunc((x - min) / (max - min) * MAX) in f64.  max_value must be in 1..=254 (the reference asserts).
+ *
+ * Range overflow: when max - min is not finite -- WS_F64 data only, e.g. {-1e308, 1e308} -- the element equal to max is
+ * inf / inf = NaN and the reference panics (`to_u8().unwrap()` on None, lib.rs:1164).  Both functions then return
+ * WS_ERR_UNSUPPORTED, ws_last_error names that line, and the contents of `out` / `d_out` are unspecified.  To decide this
+ * ws_pre_processor_device reads (min, max) back between its two kernels: for WS_F64 it waits for the context's stream once per
+ * call (every other dtype stays asynchronous; the host form waits for its result anyway).
+ *
+ * n_elems == 0 writes nothing (null pointers allowed).  A context that holds a begun transform refuses both calls. */
 typedef enum ws_dtype { WS_F32 = 0, WS_F64 = 1, WS_I32 = 2, WS_U16 = 3, WS_I16 = 4, WS_U8 = 5 } ws_dtype;
 int ws_pre_processor(ws_ctx *ctx, const void *data, int dtype, size_t n_elems, uint8_t max_value, uint8_t *out);
 int ws_pre_processor_device(ws_ctx *ctx, const void *d_data, int dtype, size_t n_elems, uint8_t max_value,

@@ -645,8 +645,8 @@ static double pre_get(const void *data, int dtype, size_t i) {
   }
 }
 
-/* dtype: 0 f32, 1 f64, 2 i32, 3 u16, 4 i16, 5 u8.  Returns 0, or -1 when max_value is not in
- * 1..=254 (the reference asserts, lib.rs:1143-1144). */
+/* dtype: 0 f32, 1 f64, 2 i32, 3 u16, 4 i16, 5 u8.  Returns 0; -1 when max_value is not in 1..=254 (the reference
+ * asserts, lib.rs:1143-1144); -2 when the reference panics at lib.rs:1164 (below) -- `out` is partly written then. */
 int ws_or_pre_processor(const void *data, int dtype, size_t n, uint8_t max_value, uint8_t *out) {
   if (max_value >= WS_OR_NEVER_FILL || max_value <= WS_OR_ALWAYS_FILL) return -1;
   double mn = 0.0, mx = 0.0;                               /* lib.rs:1149, 1154: folds seeded with zero */
@@ -659,11 +659,14 @@ int ws_or_pre_processor(const void *data, int dtype, size_t n, uint8_t max_value
     const double v = pre_get(data, dtype, i);
     if (isnormal(v)) {                                     /* lib.rs:1161 */
       const double normal = (v - mn) / (mx - mn);          /* lib.rs:1163 */
-      /* lib.rs:1164: `(normal * MAX).to_u8().unwrap()` truncates toward zero and PANICS outside 0..=255.  With the
-       * zero-seeded folds mn <= 0 <= mx, and for finite v: mn <= v <= mx, so 0 <= normal <= 1 and the product lies
-       * in [0, MAX] (MAX <= 254): the cast below is the reference's value wherever the reference returns one.  The only
-       * inputs outside that are mx == mn (all values 0 / non-finite: no `normal` branch is taken) -- asserted, so that
-       * an out-of-range product is an error here too instead of an undefined C conversion. */
+      /* lib.rs:1164: `(normal * MAX).to_u8().unwrap()` truncates toward zero and PANICS outside 0..=255 and on NaN.
+       * With the zero-seeded folds mn <= 0 <= mx, and for finite v: mn <= v <= mx.  Two kinds of input leave [0, MAX]:
+       *  - mx == mn (all values 0 / non-finite): no element is normal, this branch is never taken;
+       *  - mx - mn == +inf (f64 data whose finite values span more than DBL_MAX, e.g. {-1e308, 1e308}): mx is then a
+       *    normal element and (mx - mn) / (mx - mn) = inf / inf = NaN -- the reference panics, so does this (-2).
+       * Everywhere else 0 <= normal <= 1 and the product lies in [0, MAX] (MAX <= 254), so the cast below is the
+       * reference's value wherever the reference returns one; the test keeps an out-of-range product an error here
+       * instead of an undefined C conversion. */
       const double scaled = normal * (double)max_value;
       if (!(scaled >= 0.0 && scaled < 256.0)) return -2;    /* the reference would panic (unwrap on None) */
       out[i] = (uint8_t)scaled;

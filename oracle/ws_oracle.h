@@ -124,7 +124,8 @@ size_t ws_or_canonicalise(uint64_t *labels, size_t h, size_t w, const uint64_t *
                           size_t n_seeds);
 
 /* lib.rs:1081-1173: pre_processor / pre_processor_with_max.  dtype: 0 f32, 1 f64, 2 i32, 3 u16, 4 i16,
- * 5 u8.  Returns 0, or -1 when max_value is outside 1..=254 (the reference asserts). */
+ * 5 u8.  Returns 0, -1 when max_value is outside 1..=254 (the reference asserts), or -2 when max - min of the data is not
+ * finite (f64 only): the reference panics at lib.rs:1164. */
 int ws_or_pre_processor(const void *data, int dtype, size_t n, uint8_t max_value, uint8_t *out);
 
 /* ---- second, independent restatement: the arrival-time form ------------------

@@ -4,6 +4,8 @@
 // WS_ERR_HIP otherwise.
 #include "ws_ctx.hpp"
 
+#include <cmath>
+
 namespace wsapi {
 
 PassFlags make_pf(ws_ctx *c) {
@@ -394,7 +396,18 @@ int ws_pre_processor_device(ws_ctx *c, const void *d_data, int dtype, size_t n, 
   HIP_TRY(c, hipSetDevice(c->device));
   int rc;
   if ((rc = ensure(c, c->counts, 2 * PREPROC_BLOCKS * sizeof(double)))) return rc;
-  HIP_TRY(c, preprocess(c->stream, d_data, dtype, n, max_value, (double *)c->counts.p, d_out));
+  if (n == 0) return WS_OK;
+  HIP_TRY(c, preprocess_minmax(c->stream, d_data, dtype, n, (double *)c->counts.p));
+  if (dtype == WS_F64) {
+    // only f64 data can span more than DBL_MAX (every other type's range is exact and small in f64): max - min = +inf makes
+    // the element equal to max inf / inf = NaN, on which the reference panics (lib.rs:1164).  The two doubles are read here.
+    double mm[2] = {0.0, 0.0};
+    HIP_TRY(c, hipMemcpyAsync(mm, c->counts.p, sizeof mm, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (!(fabs(mm[1] - mm[0]) <= 1.7976931348623157e308))
+      return fail(c, WS_ERR_UNSUPPORTED, "max - min of the data is not finite: the reference panics (to_u8().unwrap() on NaN, lib.rs:1164)");
+  }
+  HIP_TRY(c, preprocess_quantise(c->stream, d_data, dtype, n, max_value, (const double *)c->counts.p, d_out));
   return WS_OK;
 }
 

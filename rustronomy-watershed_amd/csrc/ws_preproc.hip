@@ -11,6 +11,10 @@
 //     anything else           -> NEVER_FILL (255)    (NaN, -inf, subnormals and exact 0)
 // f64 add/sub/mul/div are IEEE correctly rounded on gfx950 in the default (non fast-math) build, so
 // the result is bit-identical to the reference's f64 arithmetic.
+//
+// f64 data whose finite values span more than DBL_MAX make max - min = +inf: the element equal to max is inf / inf = NaN and
+// the reference panics (`to_u8().unwrap()` on None, lib.rs:1164).  The fold and the quantiser are therefore two calls: the
+// caller (ws_pre_processor_device) reads (min, max) between them and refuses that input instead of casting a NaN.
 #include "ws_common.hpp"
 #include "ws_preproc.hpp"
 
@@ -81,7 +85,7 @@ __global__ __launch_bounds__(256) void k_quantise(const T *__restrict__ data, si
     uint8_t q;
     if (a >= 2.2250738585072014e-308 && a <= 1.7976931348623157e308) {      // f64::is_normal
       const double normal = (v - mn) / range;                               // lib.rs:1163
-      q = (uint8_t)(normal * maxv);                                         // lib.rs:1164: to_u8 truncates; in [0, MAX] by construction
+      q = (uint8_t)(normal * maxv);                                         // lib.rs:1164: to_u8 truncates; in [0, MAX] while `range` is finite
     } else if (v == INFINITY) {
       q = 0;                                                                // lib.rs:1165-1167
     } else {
@@ -92,15 +96,19 @@ __global__ __launch_bounds__(256) void k_quantise(const T *__restrict__ data, si
 }
 
 template <typename T>
-static hipError_t run(hipStream_t s, const void *data, size_t n, uint8_t maxv, double *scratch, uint8_t *out) {
+static hipError_t run_minmax(hipStream_t s, const void *data, size_t n, double *scratch) {
   if (n == 0) return hipSuccess;
   const int blocks = (int)((n + 2047) / 2048 < PREPROC_BLOCKS ? (n + 2047) / 2048 : PREPROC_BLOCKS);
   k_minmax<T><<<blocks, 256, 0, s>>>((const T *)data, n, scratch);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   k_minmax_final<<<1, 256, 0, s>>>(scratch, blocks);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
+  return hipGetLastError();
+}
+
+template <typename T>
+static hipError_t run_quantise(hipStream_t s, const void *data, size_t n, uint8_t maxv, const double *scratch, uint8_t *out) {
+  if (n == 0) return hipSuccess;
   const int qblocks = (int)((n + 1023) / 1024 < 16384 ? (n + 1023) / 1024 : 16384);
   k_quantise<T><<<qblocks, 256, 0, s>>>((const T *)data, n, scratch, (double)maxv, out);
   return hipGetLastError();
@@ -118,14 +126,26 @@ size_t preproc_elem_size(int dtype) {
   }
 }
 
-hipError_t preprocess(hipStream_t s, const void *data, int dtype, size_t n, uint8_t maxv, double *scratch, uint8_t *out) {
+hipError_t preprocess_minmax(hipStream_t s, const void *data, int dtype, size_t n, double *scratch) {
   switch (dtype) {
-    case 0: return run<float>(s, data, n, maxv, scratch, out);
-    case 1: return run<double>(s, data, n, maxv, scratch, out);
-    case 2: return run<int32_t>(s, data, n, maxv, scratch, out);
-    case 3: return run<uint16_t>(s, data, n, maxv, scratch, out);
-    case 4: return run<int16_t>(s, data, n, maxv, scratch, out);
-    case 5: return run<uint8_t>(s, data, n, maxv, scratch, out);
+    case 0: return run_minmax<float>(s, data, n, scratch);
+    case 1: return run_minmax<double>(s, data, n, scratch);
+    case 2: return run_minmax<int32_t>(s, data, n, scratch);
+    case 3: return run_minmax<uint16_t>(s, data, n, scratch);
+    case 4: return run_minmax<int16_t>(s, data, n, scratch);
+    case 5: return run_minmax<uint8_t>(s, data, n, scratch);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+hipError_t preprocess_quantise(hipStream_t s, const void *data, int dtype, size_t n, uint8_t maxv, const double *scratch, uint8_t *out) {
+  switch (dtype) {
+    case 0: return run_quantise<float>(s, data, n, maxv, scratch, out);
+    case 1: return run_quantise<double>(s, data, n, maxv, scratch, out);
+    case 2: return run_quantise<int32_t>(s, data, n, maxv, scratch, out);
+    case 3: return run_quantise<uint16_t>(s, data, n, maxv, scratch, out);
+    case 4: return run_quantise<int16_t>(s, data, n, maxv, scratch, out);
+    case 5: return run_quantise<uint8_t>(s, data, n, maxv, scratch, out);
     default: return hipErrorInvalidValue;
   }
 }

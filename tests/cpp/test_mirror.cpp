@@ -230,6 +230,14 @@ static int shim_sequence_checks() {
   CHECK(ws_pre_processor(ctx, f.data(), WS_F32, f.size(), 200, q.data()) == WS_OK);
   CHECK(ws_or_pre_processor(f.data(), 0, f.size(), 200, qw.data()) == 0);
   CHECK(q == qw);
+  // max - min = +inf: the reference panics (lib.rs:1164); the engine refuses, the oracle reports -2, the next call works
+  const double wide[4] = {-1e308, 1e308, 1.0, -3.0};
+  CHECK(ws_pre_processor(ctx, wide, WS_F64, 4, 254, q.data()) == WS_ERR_UNSUPPORTED);
+  CHECK(std::strstr(ws_last_error(ctx), "lib.rs:1164") != nullptr);
+  CHECK(ws_or_pre_processor(wide, 1, 4, 254, qw.data()) == -2);
+  CHECK(ws_pre_processor(ctx, f.data(), WS_F32, f.size(), 200, q.data()) == WS_OK);
+  CHECK(ws_or_pre_processor(f.data(), 0, f.size(), 200, qw.data()) == 0);
+  CHECK(q == qw);
 
   // shim::check: WS_ERR_SEED_OOB becomes the reference's index panic (lib.rs:1676)
   const uint64_t bad[2] = {H, 0};

@@ -313,6 +313,10 @@ def canonicalise(labels, seeds):
     return lab, int(n)
 
 
+class ReferencePanics(Exception):
+    """the reference panics on this input where no more specific exception of this module applies (pre_processor: lib.rs:1164)"""
+
+
 DTYPES = {"float32": 0, "float64": 1, "int32": 2, "uint16": 3, "int16": 4, "uint8": 5}
 
 
@@ -320,6 +324,8 @@ def pre_processor(arr, max_value=254):
     a = np.ascontiguousarray(arr)
     out = np.empty(a.shape, dtype=np.uint8)
     rc = lib().ws_or_pre_processor(a.ctypes.data, DTYPES[a.dtype.name], a.size, max_value, _p(out, _u8p))
+    if rc == -2:
+        raise ReferencePanics("max - min is not finite: to_u8().unwrap() on NaN (lib.rs:1164)")
     if rc != 0:
         raise AssertionError("MAX must be in 1..=254 (lib.rs:1143-1144)")
     return out
@@ -331,10 +337,15 @@ def pre_processor_numpy(arr, max_value=254):
     fin = np.isfinite(x)
     mn = min(0.0, float(x[fin].min())) if fin.any() else 0.0
     mx = max(0.0, float(x[fin].max())) if fin.any() else 0.0
+    with np.errstate(all="ignore"):
+        rng = np.float64(mx) - np.float64(mn)
+    if not np.isfinite(rng):      # mx is then a normal element: inf / inf = NaN, to_u8() is None (lib.rs:1164)
+        raise ReferencePanics("max - min is not finite: to_u8().unwrap() on NaN (lib.rs:1164)")
     out = np.full(x.shape, 255, dtype=np.uint8)
     normal = fin & (np.abs(x) >= np.finfo(np.float64).tiny)
+    q = np.zeros(x.shape, dtype=np.float64)
     with np.errstate(all="ignore"):
-        q = ((x - mn) / (mx - mn)) * float(max_value)
+        q[normal] = ((x[normal] - mn) / rng) * float(max_value)
     out[normal] = np.trunc(q[normal]).astype(np.uint8)
     out[np.isposinf(x)] = 0
     return out
