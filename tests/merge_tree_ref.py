@@ -81,7 +81,9 @@ def expected_tree(img, seeds, max_level=254, edge=False, seed_shift=False):
 
 
 def roots_at(parent, death, level):
-    """colour -> the end of the walk along `parent` while death_level <= level."""
+    """colour -> the end of the walk along `parent` while death_level <= level.  The cap of 258 steps is enough for every valid
+    tree: death levels strictly increase along `parent` and there are at most 255 levels, so no chain holds more than 255
+    hooks -- the staircase of tests/merging_cases.py, 254 deep, comes within one of that (tests/test_merging_cases_cpu.py)."""
     root = np.arange(parent.size, dtype=np.int64)
     for _ in range(258):
         dead = death[root] <= level
