@@ -1740,6 +1740,285 @@ __global__ __launch_bounds__(64 * RX_NW, 4) void k_relax0_tall(const uint8_t *__
   }
 }
 
+// ---- the strips of that flow on 64-row slices ----------------------------------------------------------------------------
+//
+// After pass 0 on 256 x 64 tiles the horizontal seams, and the bands that repair them, lie at rows 64 k.  A strip slice of 32
+// rows (k_relax, SEAM 2) then has every other end on a row 64 k + 32 that no band has touched: the vertical seam is as wrong
+// there as anywhere, the two slices that meet run side by side on each other's stale rows, both change their outer rows and
+// both flag -- tools/sim_tile_schedule.c (SIM_REPAIR_GEOM): 31 % of the 256 x 32 tiles flagged for pass 2, 26 % of them by a
+// slice's first / last row, against 9 % / 4 % when pass 0 ran on 256 x 32 tiles.  Slices of 64 rows end on rows 64 k only,
+// where the bands have run: 7 % / 2 %.
+// The layout is k_relax0_tall's: eight waves, a lane holds 4 columns x 8 rows; and SEAM 2's across: lanes 2 j and 2 j + 1 hold
+// the 8 columns astride seam 32 tile_x + j + 1 (x = 256 times that), and a select after each DPP shift keeps stamps from
+// crossing from one lane PAIR to the next.  Sweep order and round cap are those of the 32-row strips.
+//   * only the fast path (W % 4 == 0, image rows readable as aligned dwords: k_relax0_tall's conditions, relax_pass asks);
+//   * of the slice as loaded only what the flag rule reads is kept: every lane's outer column, the first and the last row;
+//   * the flags are those of SEAM 2, in the same words, by the same "changed and matters" rule: a lane flags the 256 x 32 tile
+//     that holds its eight rows (a slice spans two tile rows), on its own side of the seam, when its outer column changed;
+//     the tile above / below the slice when the slice's first / last row (rows 64 k and 64 k + 63) changed; a slice that stops
+//     at its round cap marks both tile rows on both sides of each of its seams.
+__global__ __launch_bounds__(64 * RX_NW, 4) void k_relax_strips_tall(const uint8_t *__restrict__ img, uint32_t stride32, uint32_t *keys, int H, int W,
+                                                                     int stripsX, int flagSX, uint32_t max_level, uint32_t pass, uint32_t *stamps_cur,
+                                                                     PassFlags pf, uint32_t max_iters, int SH, int check_carry, uint32_t *tile_list) {
+  constexpr int NB = RX_NW, TW = RX_TW, TH = RX0_TH;
+  constexpr int SEAM_PY = RX_NW * RX_P, SEAM_PX = RX_TW;      // the grid whose tiles are flagged: 256 x 32
+  // row 0: halo above the slice; rows 1+2w / 2+2w: top / bottom row of band w; last row: halo below
+  __shared__ __attribute__((aligned(16))) uint32_t sRow[2 * NB + 2][TW];
+  __shared__ __attribute__((aligned(16))) uint32_t sInitRow[2][TW];      // the slice's first and last row as loaded
+  __shared__ uint32_t s_flag[3];      // "some lane changed in round k" in slot k % 3 (k_relax)
+  __shared__ uint32_t s_edges;
+  __shared__ uint64_t s_sum[64 * NB];      // per-lane patch checksum taken at load time (k_relax)
+  __shared__ uint32_t sInitCol[RX0_PH][64 * NB];      // every lane's outer column as loaded (parked: the sweeps need the registers)
+
+  // as every launch of k_relax: the next pass's convergence slot and the tile list length that pass + 2 counts from
+  if (blockIdx.x == 0 && threadIdx.x < NSTRIPE)
+    pf.edge_changed[((pass + 1) % COUNTER_RING) * FLAG_SLOT + threadIdx.x * STRIPE_STRIDE] = 0;
+  if (tile_list && blockIdx.x == 0 && threadIdx.x == 0) { tile_list[(pass + 2) & 3u] = 0u; tile_list[4 + ((pass + 2) & 3u)] = 0u; }
+  const int tile = (int)xcd_span_index(blockIdx.x, gridDim.x);
+  const int tile_x = tile % stripsX, tile_y = tile / stripsX;
+  const int y0 = tile_y * TH;
+  if (y0 >= H || (tile_x * 32 + 1) * SEAM_PX >= W) return;
+  const int tid = threadIdx.x, lane = tid & 63, band = tid >> 6;
+  const int seam_x = (tile_x * 32 + (lane >> 1) + 1) * SEAM_PX;      // this lane pair's seam (outside the plane: no seam)
+  const bool has_seam = seam_x < W;
+  const int fx = seam_x / SEAM_PX - 1 + (lane & 1);      // the tile column this lane's columns lie in
+  {
+    // A 256 x 32 tile that pass 0 gave up on (word 2 of entry (x + 1, y): k_relax0_tall) is left to its re-run: when that is
+    // every tile this slice touches -- a smooth map -- the slice does not run.  Per 32-row half, as the marks are.
+    bool settled = true;
+#pragma unroll
+    for (int k = 0; k < TH / SEAM_PY; ++k) {
+      const int fy = tile_y * (TH / SEAM_PY) + k;
+      const bool there = has_seam && fy * SEAM_PY < H;
+      const uint32_t word = stamps_cur[there ? ((size_t)fy * flagSX + fx + 1) * 4 + 2 : 2];
+      settled &= !there || word == pass + 1;
+    }
+    if (__builtin_amdgcn_ballot_w64(settled) == ~0ull) return;      // (workgroup uniform: every wave asks the same 64 questions)
+  }
+  const int gx0 = has_seam ? seam_x - RX_P + (lane & 1) * RX_P : W, gyb = y0 + band * RX0_PH;
+  if (tid == 0) { s_edges = 0; s_flag[0] = 0; s_flag[1] = 0; s_flag[2] = 0; }
+
+  // ---- load phase: unconditional loads on clamped addresses; a patch (W % 4 == 0) is wholly inside the plane or wholly outside
+  tall_t T, B;
+  uint32_t halo[RX0_PH];      // the column outside this lane's side of the strip: left of the even lane, right of the odd one
+  const uint32_t gxc0 = (uint32_t)min(gx0, W - RX_P);
+  const int xh_raw = (lane & 1) ? gx0 + RX_P : gx0 - 1;
+  const uint32_t xh = (uint32_t)min(max(xh_raw, 0), W - 1);
+  const bool xh_ok = has_seam && xh_raw < W;
+  const int gy_halo_raw = band == 0 ? y0 - 1 : y0 + TH;
+  const uint32_t gy_halo = (uint32_t)min(max(gy_halo_raw, 0), H - 1);
+  u32x4_t halo_row;
+  {
+    u32x4_t kv[RX0_PH];
+    uint32_t iv[RX0_PH];
+#pragma unroll
+    for (int r = 0; r < RX0_PH; ++r) {
+      const uint32_t gyc = (uint32_t)min(gyb + r, H - 1);
+      iv[r] = *reinterpret_cast<const uint32_t *>(img + ((unsigned long long)gyc * stride32 + gxc0));
+      kv[r] = *reinterpret_cast<const u32x4_t *>(keys + (size_t)gyc * W + gxc0);
+      halo[r] = keys[(size_t)gyc * W + xh];
+    }
+    halo_row = *reinterpret_cast<const u32x4_t *>(keys + (size_t)gy_halo * W + gxc0);
+#pragma unroll
+    for (int r = 0; r < RX0_PH; ++r) { T[r][0] = kv[r].x; T[r][1] = kv[r].y; T[r][2] = kv[r].z; T[r][3] = kv[r].w; }
+    // image bytes -> bases, as patch_bases: the one (kernel uniform) branch outside the loop that loads the rows
+    if (max_level == 254u) {
+#pragma unroll
+      for (int r = 0; r < RX0_PH; ++r) {
+        B[r][0] = (iv[r] << 24) | 1u;
+        B[r][1] = ((iv[r] << 16) & 0xFF000000u) | 1u;
+        B[r][2] = ((iv[r] << 8) & 0xFF000000u) | 1u;
+        B[r][3] = (iv[r] & 0xFF000000u) | 1u;
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < RX0_PH; ++r)
+#pragma unroll
+        for (int c = 0; c < RX_P; ++c) {
+          const uint32_t v = (iv[r] >> (8 * c)) & 0xFFu;
+          B[r][c] = v <= max_level ? ((v << 24) | 1u) : KEY_INF;
+        }
+    }
+  }
+  {
+    // pixels outside the plane never hold a stamp, pixels of the image border and of a slice wall never change (k_relax)
+    int ry = SH == H ? gyb : gyb % SH;      // row inside its slice of a stack (a patch of eight rows may hold the walls of several)
+#pragma unroll
+    for (int r = 0; r < RX0_PH; ++r) {
+      const int gy = gyb + r;
+      const bool row_ok = gy < H, row_int = ry >= 1 && ry < SH - 1 && gy < H;
+#pragma unroll
+      for (int c = 0; c < RX_P; ++c) {
+        const int gx = gx0 + c;
+        if (!(row_ok && gx < W)) T[r][c] = KEY_INF;
+        if (!(row_int && gx >= 1 && gx < W - 1)) B[r][c] = KEY_INF;
+      }
+      if (!(row_ok && xh_ok)) halo[r] = KEY_INF;
+      if (++ry == SH) ry = 0;
+    }
+    const bool ok = gy_halo_raw >= 0 && gy_halo_raw < H;
+    if (!(ok && gx0 + 0 < W)) halo_row.x = KEY_INF;
+    if (!(ok && gx0 + 1 < W)) halo_row.y = KEY_INF;
+    if (!(ok && gx0 + 2 < W)) halo_row.z = KEY_INF;
+    if (!(ok && gx0 + 3 < W)) halo_row.w = KEY_INF;
+  }
+  uint32_t Lh[RX0_PH], Rh[RX0_PH];
+  {
+    uint64_t sum_before = 0;      // stamps only ever decrease: a 64-bit patch sum tells "changed" exactly
+#pragma unroll
+    for (int r = 0; r < RX0_PH; ++r) {
+#pragma unroll
+      for (int c = 0; c < RX_P; ++c) {
+        B[r][c] = min(B[r][c], T[r][c]);      // b <= t: seeds and everything that can never change are pinned
+        sum_before += T[r][c];
+      }
+      Lh[r] = halo[r];
+      Rh[r] = halo[r];
+      sInitCol[r][tid] = (lane & 1) ? T[r][RX_P - 1] : T[r][0];
+    }
+    s_sum[tid] = sum_before;
+  }
+  // The columns left / right of the patch, persistent (k_relax): the even lane's right column is the odd lane's first, the
+  // odd lane's left column the even lane's last, and the select puts the strip's halo column back where the shift has
+  // brought in a stamp of the next lane pair.
+  auto refresh_columns = [&]() {
+#pragma unroll
+    for (int r = 0; r < RX0_PH; ++r) {
+      Lh[r] = lane_left(Lh[r], T[r][RX_P - 1]);
+      Rh[r] = lane_right(Rh[r], T[r][0]);
+      Lh[r] = (lane & 1) ? Lh[r] : halo[r];
+      Rh[r] = (lane & 1) ? halo[r] : Rh[r];
+    }
+  };
+  auto publish_rows = [&]() {
+    *reinterpret_cast<u32x4_t *>(&sRow[1 + 2 * band][lane * RX_P]) = u32x4_t{T[0][0], T[0][1], T[0][2], T[0][3]};
+    *reinterpret_cast<u32x4_t *>(&sRow[2 + 2 * band][lane * RX_P]) = u32x4_t{T[RX0_PH - 1][0], T[RX0_PH - 1][1], T[RX0_PH - 1][2], T[RX0_PH - 1][3]};
+  };
+  if (band == 0) {
+    *reinterpret_cast<u32x4_t *>(&sRow[0][lane * RX_P]) = halo_row;
+    *reinterpret_cast<u32x4_t *>(&sInitRow[0][lane * RX_P]) = u32x4_t{T[0][0], T[0][1], T[0][2], T[0][3]};
+  }
+  if (band == NB - 1) {
+    *reinterpret_cast<u32x4_t *>(&sRow[2 * NB + 1][lane * RX_P]) = halo_row;
+    *reinterpret_cast<u32x4_t *>(&sInitRow[1][lane * RX_P]) = u32x4_t{T[RX0_PH - 1][0], T[RX0_PH - 1][1], T[RX0_PH - 1][2], T[RX0_PH - 1][3]};
+  }
+  publish_rows();
+  __syncthreads();
+
+  // ---- relaxation: the strips' rounds -- three free sweeps, the band rows published, one checked sweep -- to the slice's
+  // fixpoint or the round cap
+  uint32_t iters = 0;
+  bool unfinished = max_iters == 0;
+  uint32_t up[RX_P], dn[RX_P];
+  auto fetch_rows = [&]() {
+    const u32x4_t up4 = *reinterpret_cast<const u32x4_t *>(&sRow[2 * band][lane * RX_P]);
+    const u32x4_t dn4 = *reinterpret_cast<const u32x4_t *>(&sRow[2 * band + 3][lane * RX_P]);
+    up[0] = up4.x; up[1] = up4.y; up[2] = up4.z; up[3] = up4.w;
+    dn[0] = dn4.x; dn[1] = dn4.y; dn[2] = dn4.z; dn[3] = dn4.w;
+  };
+  for (; max_iters != 0;) {
+    ++iters;
+    {
+      bool untracked = false;
+      fetch_rows();
+      refresh_columns();
+      tall_sweep_rows<false, true>(T, B, up, dn, Lh, Rh, untracked);       // down
+      refresh_columns();
+      tall_sweep_cols<false, true>(T, B, up, dn, Lh, Rh, untracked);       // right
+      refresh_columns();
+      tall_sweep_rows<false, false>(T, B, up, dn, Lh, Rh, untracked);      // up
+      publish_rows();
+      __syncthreads();
+    }
+    bool changed = false;
+    fetch_rows();
+    refresh_columns();
+    tall_sweep_cols<true, false>(T, B, up, dn, Lh, Rh, changed);           // left, checked
+    const uint32_t slot = (iters - 1) % 3;
+    if (__builtin_amdgcn_ballot_w64(changed) != 0) {
+      publish_rows();      // a neighbour band reads these rows only if another round follows, i.e. only if someone changed
+      if (lane == 0) s_flag[slot] = 1;
+    }
+    __syncthreads();
+    const bool again = s_flag[slot] != 0;
+    if (tid == 0) s_flag[(slot + 2) % 3] = 0;
+    if (!again) break;
+    if (iters >= max_iters) { unfinished = true; break; }
+  }
+
+  // ---- write back the patches that changed (16 B per lane and row), ring-carry check, flags
+  uint64_t sum_after = 0;
+#pragma unroll
+  for (int r = 0; r < RX0_PH; ++r)
+#pragma unroll
+    for (int c = 0; c < RX_P; ++c) sum_after += T[r][c];
+  uint32_t e = 0, ovf = 0;
+  if (has_seam && sum_after != s_sum[tid]) {      // (a seam inside the plane: gx0 + RX_P <= W)
+#pragma unroll
+    for (int r = 0; r < RX0_PH; ++r) {
+      const int gy = gyb + r;
+      if (gy < H) *reinterpret_cast<u32x4_t *>(keys + (size_t)gy * W + gx0) = u32x4_t{T[r][0], T[r][1], T[r][2], T[r][3]};
+      if (check_carry) {               // kernel uniform
+#pragma unroll
+        for (int c = 0; c < RX_P; ++c)   // a finite non-seed stamp with ring 0 can only come from a carry out of the ring field
+          ovf |= (T[r][c] != 0u && T[r][c] < KEY_INF && (T[r][c] & RING_MASK) == 0u);
+      }
+    }
+    e |= 16u;
+  }
+  if (ovf) atomicExch(pf.overflow, 1u);      // never taken on sane inputs
+  // Flags: the word that pass 2 reads for anchored tile (x, y), word 3 of entry (x, y) of the shifted grid's stamps.
+  // Why they are a superset of the pixels whose equation can be violated, on slices of 64 rows: when the strips start, an
+  // equation can only be violated next to a vertical seam (pass 0's tiles and the bands are fixpoints of their own pixels, and
+  // what a band changed in its outer rows it has flagged, save in the columns that lie inside a strip).  A slice that did
+  // not stop at its cap is a fixpoint of its 8 x 64 pixels per seam against the halo it loaded, so what it leaves violated
+  // lies (a) across one of its outer columns, next to a pixel it lowered: in the 256 x 32 tile that holds that row, on that
+  // lane's side of the seam -- flagged by the lane; (b) across its first or last row, in the slice above or below, which
+  // lies in the tile above or below on the same side -- flagged by the lane of band 0 / band 7 that holds the pixel; (c) at
+  // its own first or last row, when the slice above or below lowered the halo row after this one had loaded it -- which is
+  // that slice's case (b).  The halo columns belong to no strip and do not change during the launch.  In each case the
+  // lowered pixel can only pull its neighbour down when it is at least two below what the neighbour held when the slice
+  // loaded it (`matters`; the neighbour can only have fallen since, so the test errs on the side of flagging).  A slice at
+  // its cap is no fixpoint: both tile rows on both sides of every seam of it run again and examine all its pixels.  Slice
+  // ends lie on rows 64 k and 64 k + 63 only -- the rows 64 k + 32 are interior rows now, as they are in pass 0's tiles.
+  auto matters = [](uint32_t before, uint32_t now, uint32_t across) { return before != now && now + 1u < across; };
+  if (has_seam) {
+    const uint32_t mark = pass + 1;
+    bool col = unfinished;
+#pragma unroll
+    for (int r = 0; r < RX0_PH; ++r) col |= matters(sInitCol[r][tid], (lane & 1) ? T[r][RX_P - 1] : T[r][0], halo[r]);
+    bool top = false, bottom = false;
+    if (band == 0) {
+      const u32x4_t o = *reinterpret_cast<const u32x4_t *>(&sInitRow[0][lane * RX_P]);
+      const u32x4_t a = *reinterpret_cast<const u32x4_t *>(&sRow[0][lane * RX_P]);      // the halo row above, as loaded
+      top = matters(o.x, T[0][0], a.x) || matters(o.y, T[0][1], a.y) || matters(o.z, T[0][2], a.z) || matters(o.w, T[0][3], a.w);
+    }
+    if (band == NB - 1) {
+      const u32x4_t o = *reinterpret_cast<const u32x4_t *>(&sInitRow[1][lane * RX_P]);
+      const u32x4_t a = *reinterpret_cast<const u32x4_t *>(&sRow[2 * NB + 1][lane * RX_P]);      // the halo row below
+      constexpr int l = RX0_PH - 1;
+      bottom = matters(o.x, T[l][0], a.x) || matters(o.y, T[l][1], a.y) || matters(o.z, T[l][2], a.z) || matters(o.w, T[l][3], a.w);
+    }
+    // (a lane's eight rows lie in one tile row of the 256 x 32 grid)
+    if (col && gyb < H) { stamps_cur[((size_t)(gyb / SEAM_PY) * flagSX + fx) * 4 + 3] = mark; e |= 1u; }
+    if (top && y0 > 0) { stamps_cur[((size_t)((y0 - 1) / SEAM_PY) * flagSX + fx) * 4 + 3] = mark; e |= 1u; }
+    if (bottom && y0 + TH < H) { stamps_cur[((size_t)((y0 + TH) / SEAM_PY) * flagSX + fx) * 4 + 3] = mark; e |= 1u; }
+  }
+  if (e) atomicOr(&s_edges, e);
+  __syncthreads();
+  if (tid == 0) {
+    const uint32_t ed = s_edges;
+    const uint32_t stripe = (blockIdx.x % NSTRIPE) * STRIPE_STRIDE;
+    // plain, idempotent stores into striped words: no same-address atomics on the tile path
+    if (ed & 1u) pf.edge_changed[(pass % COUNTER_RING) * FLAG_SLOT + stripe] = 1u;
+    if (ed) pf.any_change[stripe] = 1u;
+    if (pf.stats) {            // profiling only: a 64-row slice counts as two of 32 rows (eight quarter tiles) of `iters` rounds each
+      atomicAdd(&pf.stats[stripe], (uint32_t)(TW * TH / 2048));
+      atomicAdd(&pf.stats[FLAG_SLOT + stripe], 2u * iters);
+    }
+  }
+}
+
 // Does a transform of this plane, started from its seeds, repair pass 0's seams with bands and strips (relax_pass)?
 bool relax_uses_seam_repair(int h, int w, bool seed_bits, int slice_h, bool padded, size_t seam_min_px) {
   const int ax = (w + RX_TW - 1) / RX_TW, ay = (h + RX_NW * RX_P - 1) / (RX_NW * RX_P);
@@ -1866,7 +2145,8 @@ hipError_t relax_pass(hipStream_t s, const uint8_t *img, size_t img_stride, uint
   // Why the flags are still a superset of the pixels whose equation can be violated: a pass-0 tile that did not stop at its
   // round cap is a fixpoint of its own pixels against the halo it loaded, so an equation can only be violated next to a
   // border of a 256 x 64 tile -- the horizontal seams at rows 64 k, the vertical ones at columns 256 k.  The bands lie
-  // astride every row 64 k, the strips astride every column 256 k in ALL rows (they have not moved), each iterates to its
+  // astride every row 64 k, the strips astride every column 256 k in ALL rows (in slices of 64 rows whose ends lie on the
+  // bands' rows: k_relax_strips_tall, where the argument is spelt out for them), each iterates to its
   // own fixpoint on fresh stamps and flags the 256 x 32 tile that holds a pixel next to a changed outer row or column of
   // it, exactly as before.  The rows 64 k + 32, seams of the old geometry, are interior rows of a pass-0 tile now: nothing
   // is left violated there unless the tile stopped at its cap -- and then it has marked both 256 x 32 tiles it covers for
@@ -1899,6 +2179,14 @@ hipError_t relax_pass(hipStream_t s, const uint8_t *img, size_t img_stride, uint
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const int strips_x = (ax - 1 + 31) / 32;
+    // After pass 0 on 256 x 64 tiles the strips run on slices of 64 rows, whose ends lie where the bands have run
+    // (k_relax_strips_tall); every other flow keeps its 32-row slices.
+    static const bool no_tall_strips = tuning_env("WS_RELAX_NO_TALL_STRIPS") != nullptr;      // A/B knob, tools/ only
+    if (tall0 && !no_tall_strips) {
+      k_relax_strips_tall<<<strips_x * ay_tall, 64 * RX_NW, 0, s>>>(img, (uint32_t)img_stride, keys, h, w, strips_x, sx, max_level, pass, cur, pf,
+                                                                  SEAM_REPAIR_ROUNDS, sh, check_carry, tile_list);
+      return hipGetLastError();
+    }
     k_relax<RX_NW, false, false, false, false, 2><<<strips_x * ay, 64 * RX_NW, 0, s>>>(img, img_stride, keys, h, w, strips_x, ay, sx, sy, 0, 1, max_level, pass,
                                                                                        prev, cur, pf, SEAM_REPAIR_ROUNDS, nullptr, 0, sh, check_carry, pad, tile_list, 0, 0,
                                                                                        0, list_cap, 0);

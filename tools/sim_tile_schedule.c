@@ -31,6 +31,8 @@ static long g_rounds, g_ops[128];
 static long g_chg_hist[12], g_chg_runs, g_bbox_rows_hist[9], g_bbox_cols_hist[9];      /* SIM_CHANGED: changed pixels per tile run (log2 bins), height / width of their bounding box in eighths of the tile */
 static int g_matters;
 static int g_skip_l, g_skip_r;      /* columns at the left / right end of a tile whose changes do not count as a changed first / last row */
+static int g_fh;              /* SIM_REPAIR: rows of a flagged tile; a run reports its changed side columns per block of g_fh rows */
+static unsigned g_lcol, g_rcol;      /* bit k: the left / right column changed (and matters) in rows k * g_fh ... of the run */
 static uint32_t g_side_min[5]; /* smallest new key among the changed pixels of the top / bottom / left / right border, and of the tile */
 
 static inline uint32_t med3(uint32_t lo, uint32_t x, uint32_t hi) { return x < lo ? lo : (x > hi ? hi : x); }
@@ -154,6 +156,7 @@ static int run_tile(int x0, int y0, int tw, int th, int cap, const char *recipe)
     if (cap && round >= cap) { res |= 32; break; }
   }
   for (int k = 0; k < 5; ++k) g_side_min[k] = 0xFFFFFFFFu;
+  g_lcol = g_rcol = 0;
   {
     long nchg = 0; int ymin = th, ymax = -1, xmin = tw, xmax = -1;
     for (int y = 0; y < th && y0 + y < N; ++y)
@@ -181,8 +184,8 @@ static int run_tile(int x0, int y0, int tw, int th, int cap, const char *recipe)
 #define MATTERS(off) MATTERS2(off, (off) == -1 ? -1 : ((off) == 1 ? 1 : 0), (off) == -P ? -1 : ((off) == P ? 1 : 0))
         if (y == 0 && row_counts && MATTERS(-P)) { res |= 1; if (n < g_side_min[0]) g_side_min[0] = n; }
         if ((y == th - 1 || y0 + y == N - 1) && row_counts && MATTERS(P)) { res |= 2; if (n < g_side_min[1]) g_side_min[1] = n; }
-        if (x == 0 && MATTERS(-1)) { res |= 4; if (n < g_side_min[2]) g_side_min[2] = n; }
-        if ((x == tw - 1 || x0 + x == N - 1) && MATTERS(1)) { res |= 8; if (n < g_side_min[3]) g_side_min[3] = n; }
+        if (x == 0 && MATTERS(-1)) { res |= 4; if (g_fh) g_lcol |= 1u << (y / g_fh); if (n < g_side_min[2]) g_side_min[2] = n; }
+        if ((x == tw - 1 || x0 + x == N - 1) && MATTERS(1)) { res |= 8; if (g_fh) g_rcol |= 1u << (y / g_fh); if (n < g_side_min[3]) g_side_min[3] = n; }
       }
     }
   return res;
@@ -331,26 +334,39 @@ int main(int argc, char **argv) {
   }
   if (getenv("SIM_REPAIR")) {
     /* The seam repair of ws_relax.hip, replayed: pass 0 (every tile to its own fixpoint), then bands of +-kb rows along the
-     * horizontal seams (tiles tw wide), then strips of +-ks columns along the vertical seams (slices th tall), every launch
-     * with the halo as the launch found it; which regular tiles get flagged, and why.  SIM_REPAIR="kb,ks[,order]" with order
+     * horizontal seams (tiles tw wide), then strips of +-ks columns along the vertical seams, every launch with the halo as
+     * the launch found it; which regular tiles (tw x th) get flagged, and why.  SIM_REPAIR="kb,ks[,order]" with order
      * 0 = bands then strips (the engine), 1 = strips then bands, 2 = bands, strips, then a second strip launch half a
-     * slice higher, 3 = as 2 plus a second band launch half a tile to the right. */
-    int kb = 4, ks = 4, order = 0;
+     * slice higher, 3 = as 2 plus a second band launch half a tile to the right.
+     * SIM_REPAIR_GEOM="p0h,sh": pass 0 on tiles p0h rows high (a multiple of th; bands astride the rows k * p0h only) and
+     * strip slices sh rows high (a multiple of th); both th when not given.  The flags stay those of the tw x th tiles: a
+     * strip's side column flags the tile that holds the changed row, its first / last row the tile above / below the slice.
+     * SIM_REPAIR_CAPS="p0,rep": round caps of pass 0 and of the bands and strips (0: none); who stops at its cap flags every
+     * tile it covers (pass 0) or touches (a band: above and below; a slice: both sides, every row block). */
+    int kb = 4, ks = 4, order = 0, p0h = th, sh = th, p0cap = 0, repcap = 0;
     sscanf(getenv("SIM_REPAIR"), "%d,%d,%d", &kb, &ks, &order);
+    if (getenv("SIM_REPAIR_GEOM")) sscanf(getenv("SIM_REPAIR_GEOM"), "%d,%d", &p0h, &sh);
+    if (getenv("SIM_REPAIR_CAPS")) sscanf(getenv("SIM_REPAIR_CAPS"), "%d,%d", &p0cap, &repcap);
+    if (p0h % th || sh % th) { fprintf(stderr, "SIM_REPAIR_GEOM: multiples of TH\n"); return 2; }
     uint32_t *truth = malloc(n * 4);
     memcpy(truth, key, n * 4);
     for (size_t p = 0; p < n; ++p) key[p] = KEY_INF;
     for (size_t i = 0; i < ns; ++i) key[seeds[i]] = 0;
     memcpy(snap, key, n * 4);
-    for (int j = 0; j < ty; ++j)
-      for (int i = 0; i < tx; ++i) run_tile(i * tw, j * th, tw, th, 0, recipe);
-    uint8_t *flag = calloc((size_t)tx * ty, 1);
-    long why[4] = {0, 0, 0, 0};      /* band rows, strip columns, strip slice rows, band columns (only when no strips follow) */
     /* scratch tiles for other shapes */
     free(cur); free(beg); free(bar); free(bs);
-    const size_t big = (size_t)(th + 2 * kb + 2 + 64) * (tw + 2 * ks + 2 + 64);
+    const int maxh = p0h > sh ? p0h : sh;
+    const size_t big = (size_t)(maxh + 2 * kb + 2 + 64) * (tw + 2 * ks + 2 + 64);
     cur = malloc(big * 4); beg = malloc(big * 4); bar = malloc(big * 4); bs = malloc(big * 4);
+    uint8_t *flag = calloc((size_t)tx * ty, 1);
+    long why[5] = {0, 0, 0, 0, 0};      /* band rows, strip columns, strip slice rows, band columns (only when no strips follow), pass-0 cap */
 #define FLAG(i_, j_, w_) do { if ((i_) >= 0 && (i_) < tx && (j_) >= 0 && (j_) < ty) { if (!flag[(size_t)(j_) * tx + (i_)]) ++why[w_]; flag[(size_t)(j_) * tx + (i_)] = 1; } } while (0)
+    const int per0 = p0h / th, pers = sh / th;      /* flagged tile rows per pass-0 tile / per slice */
+    for (int j = 0; j * p0h < N; ++j)
+      for (int i = 0; i < tx; ++i) {
+        const int r = run_tile(i * tw, j * p0h, tw, p0h, p0cap, recipe);
+        if (r & 32) for (int k = 0; k < per0; ++k) FLAG(i, j * per0 + k, 4);
+      }
     for (int phase = 0; phase < 4; ++phase) {
       int what;      /* 0 bands, 1 strips, 2 strips shifted, 3 bands shifted, -1 nothing */
       if (order == 0) what = phase == 0 ? 0 : (phase == 1 ? 1 : -1);
@@ -362,32 +378,42 @@ int main(int argc, char **argv) {
       memcpy(snap, key, n * 4);
       if (what == 0 || what == 3) {
         const int xoff = what == 3 ? tw / 2 : 0;
-        for (int j = 1; j < ty; ++j)
+        for (int j = 1; j * p0h < N; ++j)
           for (int i = 0; i * tw - xoff < N; ++i) {
             const int x0 = i * tw - xoff;
             /* what a band changes in the columns a strip will look at again is the strip's business */
             if (getenv("SIM_REPAIR_SKIP") && !last_bands && what == 0) { g_skip_l = x0 > 0 ? ks : 0; g_skip_r = x0 + tw < N ? ks : 0; }
-            const int r = run_tile(x0 < 0 ? 0 : x0, j * th - kb, x0 < 0 ? tw + x0 : tw, 2 * kb, 0, recipe);
+            const int r = run_tile(x0 < 0 ? 0 : x0, j * p0h - kb, x0 < 0 ? tw + x0 : tw, 2 * kb, repcap, recipe);
             g_skip_l = g_skip_r = 0;
-            const int ti = (x0 < 0 ? 0 : x0) / tw;
-            if (r & 1) { FLAG(ti, j - 1, 0); if (xoff) FLAG(ti + 1, j - 1, 0); }
-            if (r & 2) { FLAG(ti, j, 0); if (xoff) FLAG(ti + 1, j, 0); }
-            if ((last_bands || what == 3) && (r & 4)) { FLAG((x0 - 1) / tw, j - 1, 3); FLAG((x0 - 1) / tw, j, 3); }
-            if ((last_bands || what == 3) && (r & 8)) { FLAG((x0 + tw) / tw, j - 1, 3); FLAG((x0 + tw) / tw, j, 3); }
+            const int ti = (x0 < 0 ? 0 : x0) / tw, fj = j * per0;      /* the seam lies between tile rows fj - 1 and fj */
+            if (r & (1 | 32)) { FLAG(ti, fj - 1, 0); if (xoff) FLAG(ti + 1, fj - 1, 0); }
+            if (r & (2 | 32)) { FLAG(ti, fj, 0); if (xoff) FLAG(ti + 1, fj, 0); }
+            if ((last_bands || what == 3) && (r & 4)) { FLAG((x0 - 1) / tw, fj - 1, 3); FLAG((x0 - 1) / tw, fj, 3); }
+            if ((last_bands || what == 3) && (r & 8)) { FLAG((x0 + tw) / tw, fj - 1, 3); FLAG((x0 + tw) / tw, fj, 3); }
           }
       } else {
-        const int yoff = what == 2 ? th / 2 : 0;
+        const int yoff = what == 2 ? sh / 2 : 0;
         for (int i = 1; i < tx; ++i)
-          for (int j = 0; j * th - yoff < N; ++j) {
-            const int y0 = j * th - yoff;
-            const int r = run_tile(i * tw - ks, y0 < 0 ? 0 : y0, 2 * ks, y0 < 0 ? th + y0 : th, 0, recipe);
-            const int tj = (y0 < 0 ? 0 : y0) / th;
-            if (r & 4) { FLAG(i - 1, tj, 1); if (yoff) FLAG(i - 1, tj + 1, 1); }
-            if (r & 8) { FLAG(i, tj, 1); if (yoff) FLAG(i, tj + 1, 1); }
+          for (int j = 0; j * sh - yoff < N; ++j) {
+            const int y0 = j * sh - yoff, ys = y0 < 0 ? 0 : y0;
+            g_fh = yoff ? sh : th;      /* (a shifted slice: one block, which flags the tile rows it straddles, as before) */
+            const int r = run_tile(i * tw - ks, ys, 2 * ks, y0 < 0 ? sh + y0 : sh, repcap, recipe);
+            g_fh = 0;
+            const int tj = ys / th;
+            const unsigned lc = (r & 32) ? ~0u : g_lcol, rc = (r & 32) ? ~0u : g_rcol;
+            if (yoff) {
+              if (lc) { FLAG(i - 1, tj, 1); FLAG(i - 1, tj + 1, 1); }
+              if (rc) { FLAG(i, tj, 1); FLAG(i, tj + 1, 1); }
+            } else {
+              for (int k = 0; k < pers && (tj + k) * th < N; ++k) {
+                if (lc >> k & 1u) FLAG(i - 1, tj + k, 1);
+                if (rc >> k & 1u) FLAG(i, tj + k, 1);
+              }
+            }
             /* a slice's first / last row: covered by what follows? bands after strips cover the rows at the seams */
             const int rows_covered = (order == 1 && what == 1) || (order >= 2 && what == 1);
-            if (!rows_covered && (r & 1)) { FLAG(i - 1, (y0 - 1) / th, 2); FLAG(i, (y0 - 1) / th, 2); }
-            if (!rows_covered && (r & 2)) { FLAG(i - 1, (y0 + th) / th, 2); FLAG(i, (y0 + th) / th, 2); }
+            if (!rows_covered && (r & 1) && y0 > 0) { FLAG(i - 1, (y0 - 1) / th, 2); FLAG(i, (y0 - 1) / th, 2); }
+            if (!rows_covered && (r & 2)) { FLAG(i - 1, (y0 + sh) / th, 2); FLAG(i, (y0 + sh) / th, 2); }
           }
       }
     }
@@ -396,9 +422,12 @@ int main(int argc, char **argv) {
     for (int y = 0; y < N; ++y)
       for (int x = 0; x < N; ++x)
         if (key[(size_t)y * N + x] != truth[(size_t)y * N + x]) { ++wrong; if (!flag[(size_t)(y / th) * tx + x / tw]) ++wrong_unflagged; }
-    printf("repair kb %d ks %d order %d: %ld of %d tiles flagged (%.1f %%): first flagged by band rows %ld, strip columns %ld, strip slice rows %ld, band columns %ld; "
+    const double T = (double)tx * ty;
+    printf("repair kb %d ks %d order %d, pass 0 on %d x %d, strip slices of %d rows: %ld of %d tiles (%d x %d) flagged (%.1f %%): first flagged by pass-0 cap %ld (%.1f %%), "
+           "band rows %ld (%.1f %%), strip columns %ld (%.1f %%), strip slice rows %ld (%.1f %%), band columns %ld; "
            "%ld stamps still wrong, %ld of them in tiles nobody flagged (those need a neighbour's flag: an equation next to them is violated)\n",
-           kb, ks, order, flagged, tx * ty, 100.0 * flagged / (tx * ty), why[0], why[1], why[2], why[3], wrong, wrong_unflagged);
+           kb, ks, order, tw, p0h, sh, flagged, tx * ty, tw, th, 100.0 * flagged / T, why[4], 100.0 * why[4] / T, why[0], 100.0 * why[0] / T, why[1], 100.0 * why[1] / T,
+           why[2], 100.0 * why[2] / T, why[3], wrong, wrong_unflagged);
     memcpy(key, truth, n * 4);
   }
   if (getenv("SIM_SEAM_REPORT")) {
