@@ -50,9 +50,10 @@ int ws_block_relax(ws_ctx *c, const uint8_t *d_img, size_t h, size_t w, size_t s
   PassFlags pf = make_pf(c);
   pf.stats = nullptr;
   uint32_t passes = 0;
-  rc = pass_loop(c, flags, relax_tiles((int)h, (int)w), &passes, [&](uint32_t pass) {
-    return relax_pass(c->stream, d_img, stride, d_keys, (int)h, (int)w, max_water_level, pass, stamps, pf, c->debug_max_iters, nullptr, false, 0, false, false, tile_list);
-  });
+  RelaxPlane plane;
+  plane.img = d_img; plane.img_stride = stride; plane.keys = d_keys; plane.h = (int)h; plane.w = (int)w; plane.max_level = max_water_level;
+  plane.stamps = stamps; plane.pf = pf; plane.max_iters = c->debug_max_iters; plane.tile_list = tile_list;
+  rc = pass_loop(c, flags, relax_tiles((int)h, (int)w), &passes, [&](uint32_t pass) { return relax_pass(c->stream, plane, pass); });
   if (rc) return rc;
   c->stats.relax_passes += passes;
   HIP_TRY(c, hipMemcpyAsync(&c->pinned[FLAG_OVERFLOW], flags + FLAG_OVERFLOW, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -159,10 +160,13 @@ int ws_block_begin(ws_ctx *c, const uint8_t *d_img, size_t h, size_t w, size_t s
   c->misc_clean = false;
   HIP_TRY(c, seed_tables(c->stream, d_seeds_rc, n_seeds, ph, pw, seed_mask, word_base, flags + FLAG_SEED_ERR, stamps,
                          relax_tiles(ph, pw) * 4 * 2, flags, FLAG_MISC, nullptr, 0, first_colour - 1u));
-  const PassFlags pf = make_pf(c);
+  RelaxPlane plane;
+  plane.img = d_img; plane.img_stride = stride; plane.keys = d_keys; plane.h = ph; plane.w = pw; plane.max_level = max_water_level;
+  plane.stamps = stamps; plane.pf = make_pf(c); plane.max_iters = c->debug_max_iters; plane.tile_list = tile_list;
+  plane.seed_labels = seed_mask; plane.seed_bits = true; plane.carry_checked_later = true;
   rc = pass_loop(c, flags, relax_tiles(ph, pw), &c->stats.relax_passes, [&](uint32_t pass) {
     Span sp(c, KC_RELAX);
-    return relax_pass(c->stream, d_img, stride, d_keys, ph, pw, max_water_level, pass, stamps, pf, c->debug_max_iters, seed_mask, true, 0, true, false, tile_list);
+    return relax_pass(c->stream, plane, pass);
   }, true, 5);
   if (rc) return rc;
   c->stats.launches_relax = c->stats.relax_passes;
@@ -194,11 +198,14 @@ int ws_block_relax_halo(ws_ctx *c, const uint8_t *d_img, size_t h, size_t w, siz
   uint32_t *tile_list = (uint32_t *)c->tile_list.p;      // sized by ws_block_begin
   constexpr uint32_t FIRST = 4;      // an even pass of the late kind: few tiles run (chunked launches, long-range scans)
   HIP_TRY(c, block_flag_border_tiles(c->stream, stamps, ph, pw, FIRST, halo));
-  const PassFlags pf = make_pf(c);
+  RelaxPlane plane;
+  plane.img = d_img; plane.img_stride = stride; plane.keys = d_keys; plane.h = ph; plane.w = pw; plane.max_level = max_water_level;
+  plane.stamps = stamps; plane.pf = make_pf(c); plane.max_iters = c->debug_max_iters; plane.tile_list = tile_list;
+  plane.carry_checked_later = true;
   uint32_t last = 0;
   int rc = pass_loop(c, flags, ntiles, &last, [&](uint32_t pass) {
     Span sp(c, KC_RELAX);
-    return relax_pass(c->stream, d_img, stride, d_keys, ph, pw, max_water_level, pass, stamps, pf, c->debug_max_iters, nullptr, false, 0, true, false, tile_list);
+    return relax_pass(c->stream, plane, pass);
   }, true, 2, nullptr, nullptr, FIRST);
   if (rc) return rc;
   c->stats.relax_passes = last - FIRST;

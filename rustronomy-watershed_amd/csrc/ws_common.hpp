@@ -115,18 +115,29 @@ hipError_t snapshot_level_u32(hipStream_t s, const uint32_t *keys, const uint32_
 
 // relaxation (ws_relax.hip): 4x4 register patches, 256 x 32 tiles, row/column sweeps
 size_t relax_tiles(int h, int w);
-hipError_t relax_pass(hipStream_t s, const uint8_t *img, size_t img_stride, uint32_t *keys, int h, int w,
-                      uint32_t max_level, uint32_t pass, uint32_t *stamps, PassFlags pf, uint32_t max_iters,
-                      const uint32_t *seed_labels = nullptr,    // non-null: pass 0 derives the stamps from this label plane
-                      bool seed_bits = false,                   // ... which is one bit per pixel (seed_tables) instead
-                      int slice_h = 0,                          // > 0: the plane is a stack of independent slices of this many rows
-                      bool carry_checked_later = false,         // the caller's resolve_two_launch(.., carry_flag) looks for ring carries
-                      bool padded = false,                      // edge correction: img is the caller's (h-2) x (w-2) image, the ring of zeros is virtual
-                      uint32_t *tile_list = nullptr,            // relax_list_words(h, w) words: late passes run from a compacted list of tiles
-                      size_t seam_min_px = (size_t)1 << 24,     // planes from this many pixels on repair pass 0's seams with bands and strips (ws_relax.hip)
-                      int persistent_pass = 0);                 // the late passes of a long-range flood as one persistent launch with a tile queue: 1 first come (from pass 7), 2 in flood order (from pass 3); the caller resolves "auto"
+// What a transform's relaxation passes have in common: everything but the pass number.
+struct RelaxPlane {
+  const uint8_t *img = nullptr;
+  size_t img_stride = 0;
+  uint32_t *keys = nullptr;
+  int h = 0, w = 0;
+  uint32_t max_level = 0;
+  uint32_t *stamps = nullptr;
+  PassFlags pf = {};
+  uint32_t max_iters = 0xFFFFFFFFu;
+  const uint32_t *seed_labels = nullptr;    // non-null: pass 0 derives the stamps from this label plane
+  bool seed_bits = false;                   // ... which is one bit per pixel (seed_tables) instead
+  int slice_h = 0;                          // > 0: the plane is a stack of independent slices of this many rows
+  bool carry_checked_later = false;         // the caller's resolve_two_launch(.., carry_flag) looks for ring carries
+  bool padded = false;                      // edge correction: img is the caller's (h-2) x (w-2) image, the ring of zeros is virtual
+  uint32_t *tile_list = nullptr;            // relax_list_words(h, w) words: late passes run from a compacted list of tiles
+  size_t seam_min_px = (size_t)1 << 24;     // planes from this many pixels on repair pass 0's seams with bands and strips (ws_relax_plan.hpp)
+  int persistent_pass = 0;                  // the late passes of a long-range flood as one persistent launch with a tile queue: 1 first come (from pass 7), 2 in flood order (from pass 3); the caller resolves "auto"
+};
+hipError_t relax_pass(hipStream_t s, const RelaxPlane &plane, uint32_t pass);
+struct RelaxPlan;
+RelaxPlan relax_plan_for(const RelaxPlane &plane, uint32_t pass);      // what relax_pass launches for that pass (ws_relax_plan.hpp)
 size_t relax_list_words(int h, int w);
-bool relax_uses_seam_repair(int h, int w, bool seed_bits, int slice_h, bool padded, size_t seam_min_px);      // pass 1 of such a transform is two launches
 
 // label resolve, iterative form (row blocks of a tiled field, planes >= 2^31 pixels): 64x64 tiles
 size_t resolve_tiles(int h, int w);

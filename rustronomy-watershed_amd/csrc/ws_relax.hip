@@ -32,6 +32,7 @@
 // words are plain stores of 1 into striped slots (idempotent), statistics are striped counters
 // that exist only when profiling is on.
 #include "ws_common.hpp"
+#include "ws_relax_plan.hpp"      // tile geometry, round caps and the schedule (relax_plan)
 
 #include <algorithm>
 #include <cstdio>
@@ -65,9 +66,6 @@ __device__ unsigned long long *g_diag = nullptr;
 #define WS_STAMP(slot) do {} while (0)
 #define WS_STAMP_VALUE(slot, v) do {} while (0)
 #endif
-
-constexpr int RX_TW = 256;   // tile width: 64 lanes x 4 columns
-constexpr int RX_P = 4;      // patch side
 
 __device__ __forceinline__ uint32_t lane_left(uint32_t old, uint32_t v) {     // lane i <- lane i-1, lane 0 keeps old
   return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)v, 0x138, 0xF, 0xF, false);
@@ -173,10 +171,6 @@ constexpr uint32_t RLQ_RUNS = 10, RLQ_WAIT = 11, RLQ_LIFE = 12, RLQ_POLLS = 13; 
 // A worker gives up -- and tells the others to -- when the launch has lasted this long (s_memrealtime ticks of 10 ns): no spin
 // of this kernel can outlive it, whatever goes wrong with the queue.  What is left undone is work for the passes that follow.
 constexpr unsigned long long RLQ_BUDGET_TICKS = 5000000ull;      // 50 ms; a smooth 8192^2 map needs 3
-// Rounds per tile run of the persistent pass.  The ordinary late passes stop a tile after three (a pass ends when its slowest
-// tile ends); without a pass barrier that reason is gone and a run's fixed costs (loads, stores, queue: ~10 us) are spread over
-// more rounds: 8192^2 smooth maps, correlation 16 px: 6.74 ms with three, 6.36 with six, 6.28 with twelve.
-constexpr uint32_t RLQ_ROUND_CAP = 6;
 // PERSIST == 2, the queue in flood order: a worker takes a tile from the LOWEST non-empty of PQ_B buckets; a tile's bucket is the
 // level (>> pq_shift) of the smallest stamp waiting at its borders.  tools/sim_tile_schedule.c (SIM_QUEUE=prio): on an 8192^2
 // map of correlation length 64 px first-come order needs 152 k tile runs, this order 87 k with 32 buckets (86 k with 256):
@@ -271,14 +265,8 @@ __device__ __forceinline__ unsigned long long relax_todo(int first, int stride, 
 // So the whole row is evaluated EXACTLY -- the same values the sequential sweep would give, pixel by
 // pixel, ring carries included -- by a 6-step inclusive scan over the lanes of the wave: each lane
 // reduces its 4 pixels to one (lo, hi, 4) triple, the scan composes triples, and every lane then knows
-// the value that enters it from its neighbour.  Used only from pass RX_SCAN_FROM_PASS on (the bench field
-// has converged by then; the scan costs registers, so the early passes run a variant without it).
-// (r2: scans from the first round on and a cap on the rounds per tile run in those passes -- 8192^2 smooth maps, correlation
-// length 16 / 64 / 256 px: 16.4 -> 13.1, 29.2 -> 22.2, 12.5 -> 10.7 ms with a cap of two (gpurun_out/r2e); three since the
-// rounds of those passes are scans only and the scans DPP shifts: 8.4 -> 7.2, 8.6 -> 8.3, 4.1 -> 4.0 ms, gpurun_out/r2w/dpp.log)
-constexpr uint32_t RX_SCAN_FROM_PASS = 4;
-constexpr uint32_t RX_EARLY_ROUND_CAP = 4;     // rounds per tile run in passes 1 .. RX_SCAN_FROM_PASS - 1 (0: no cap): smooth 8192^2, correlation 16 px: 12.4 -> 10.4 ms
-constexpr uint32_t RX_LATE_ROUND_CAP = 3;      // rounds per tile run from pass RX_SCAN_FROM_PASS on (0: no cap); see relax_pass
+// the value that enters it from its neighbour.  Used only from pass RX_SCAN_FROM_PASS on (ws_relax_plan.hpp, with the
+// round caps of those passes and what was measured for them).
 
 template <bool TRACK, bool RIGHT, int LX>
 __device__ __forceinline__ void scan_row(uint32_t (&t)[RX_P], const uint32_t (&b)[RX_P], uint32_t halo_in, int xl, bool &changed) {
@@ -1327,8 +1315,6 @@ const uint8_t *__restrict__ img, size_t img_stride, uint32_t *keys,
   }
 }
 
-constexpr int RX_NW = 8;   // 512 threads: tile 256 x 32
-
 // The tiles that have to run in `pass`, compacted: tile_list[pass & 3] = how many, entries from tile_list[RL_HDR + (pass & 1) *
 // list_cap] on (any order).  It also clears the tiles' "queued for pass" words, which the passes that append their
 // successors' lists themselves (k_relax, append_next) exchange: every transform that reaches those passes comes through here.
@@ -1336,12 +1322,6 @@ constexpr int RX_NW = 8;   // 512 threads: tile 256 x 32
 // smooth map a pass moves the flood fronts by one tile, a few hundred tiles out of thousands, and the chunked launch
 // (a workgroup per four tiles, most of them idle, some with two busy ones to run back to back) took twice as long as
 // the tiles themselves.
-// first pass that runs on the grid of the pass before it (odd; see relax_pass).  8192^2 smooth maps, correlation length
-// 64 / 256 px: 436 -> 260 and 516 -> 292 passes, 16.8 -> 12.6 and 11.0 -> 7.0 ms (gpurun_out/r2k, bit-exact)
-constexpr uint32_t RX_SAME_GRID_FROM = 7;
-constexpr uint32_t RX_LIST_FROM_PASS = 6;      // the bench field has converged by then (its passes 4 and 5 find nothing to do)
-constexpr unsigned RX_LIST_GRID = 512;       // two workgroups of the scan variant per CU: all resident, the tickets share the list out
-
 template <int TW, int TH>
 __global__ __launch_bounds__(256) void k_relax_list(int H, int W, int tilesX, int tilesY, int otherX, int otherY, int shifted,
                                                     uint32_t pass, const uint32_t *__restrict__ stamps_prev, uint32_t *tile_list,
@@ -1419,29 +1399,7 @@ size_t relax_list_words(int h, int w) {
   return pq_base(tiles) + PQ_HDR + (size_t)PQ_B * pq_words_per_bucket(tiles);
 }
 
-// capacity of ONE of the two edge-stamp arrays: the shifted grid has one more row and column; the 128 x 64 grid of the
-// same-grid passes has its own count
-#ifndef WS_SPLIT_NW
-#define WS_SPLIT_NW RX_NW
-#endif
-constexpr int RX_SNW = WS_SPLIT_NW;
-constexpr int RX_STW = RX_TW / 2, RX_STH = 2 * RX_SNW * RX_P;      // tile of the SPLIT kernel: 128 x 64
-// The queue in flood order runs on tiles of twice the height, 128 x 128 (sixteen waves): the launch is bound by the chain of
-// tile runs along the floods, and a flood crosses half as many of these vertically.  The ordinary same-grid passes are
-// slower on them (a pass lasts as long as its slowest tile); 8192^2 smooth maps, correlation 4 / 16 / 64 / 256 px, passes:
-// 3.06 / 6.04 / 6.94 / 3.73 ms on 128 x 64, 3.58 / 7.23 / 7.39 / 3.48 on 128 x 128; queue: 3.78 / 7.2 / 5.12 / 4.09 against
-// 3.69 / 6.75 / 4.69 / 3.65 (gpurun_out/r3am).
-#ifndef WS_QUEUE_NW
-#define WS_QUEUE_NW 16
-#endif
-constexpr int RX_QNW = WS_QUEUE_NW;
-constexpr int RX_QTH = 2 * RX_QNW * RX_P;
-size_t relax_tiles(int h, int w) {
-  const int th = RX_NW * RX_P;
-  const size_t a = (size_t)((w + RX_TW - 1) / RX_TW + 1) * ((h + th - 1) / th + 1);
-  const size_t b = (size_t)((w + RX_STW - 1) / RX_STW + 1) * ((h + RX_STH - 1) / RX_STH + 1);
-  return std::max(a, b);
-}
+size_t relax_tiles(int h, int w) { return relax_plan_tiles(h, w); }
 
 // Row block of a tiled field: the caller has rewritten the plane's halo rows (row 0 and / or row h - 1).  Only tiles that
 // hold those rows have anything new to look at: raise, in the stamp array that the EVEN pass `pass` reads (the shifted
@@ -1485,8 +1443,6 @@ hipError_t block_flag_border_tiles(hipStream_t s, uint32_t *stamps, int h, int w
 //     neither now, and what lies across the border is still in the halo row of LDS / the halo column registers;
 //   * a tile that stops at its round cap marks BOTH 256 x 32 tiles it covers, in the words the bands, the strips and pass 2
 //     read, and all their quadrant flags, as k_relax does for its one.
-constexpr int RX0_PH = 2 * RX_P;              // rows of a lane's patch
-constexpr int RX0_TH = RX_NW * RX0_PH;        // tile height: 64
 typedef uint32_t tall_t[RX0_PH][RX_P];
 
 template <bool TRACK, bool DOWN>
@@ -2019,293 +1975,161 @@ __global__ __launch_bounds__(64 * RX_NW, 4) void k_relax_strips_tall(const uint8
   }
 }
 
-// Does a transform of this plane, started from its seeds, repair pass 0's seams with bands and strips (relax_pass)?
-bool relax_uses_seam_repair(int h, int w, bool seed_bits, int slice_h, bool padded, size_t seam_min_px) {
-  const int ax = (w + RX_TW - 1) / RX_TW, ay = (h + RX_NW * RX_P - 1) / (RX_NW * RX_P);
-  // (a stack of slices takes it too: slice walls are rows of pinned pixels, wherever they fall in a band or a strip slice)
-  (void)slice_h;
-  return seed_bits && !padded && (w & 3) == 0 && ax >= 2 && ay >= 2 && (size_t)h * (size_t)w >= seam_min_px;
+// The tuning knobs (tools/README.md): a -DWS_TUNING build reads them here, once per process; the product's tuning_env
+// knows no environment and this returns the product's constants.
+static RelaxKnobs relax_knobs() {
+  RelaxKnobs k;
+  if (const char *e = tuning_env("WS_RELAX_SAME_GRID_FROM")) k.same_grid_from = (uint32_t)atoi(e);
+  if (const char *e = tuning_env("WS_RELAX_QUEUE_FROM")) k.queue_from = (uint32_t)atoi(e);
+  if (const char *e = tuning_env("WS_RELAX_PERSIST")) k.persist = atoi(e);
+  if (const char *e = tuning_env("WS_RELAX_P0_ROUNDS")) k.p0_rounds = (uint32_t)atoi(e);
+  k.no_seam = tuning_env("WS_RELAX_NO_SEAM") != nullptr;
+  if (const char *e = tuning_env("WS_RELAX_LATE_CAP")) k.late_cap = (uint32_t)atoi(e);
+  if (const char *e = tuning_env("WS_RELAX_SCAN_FROM")) k.scan_from = (uint32_t)atoi(e);
+  if (const char *e = tuning_env("WS_RELAX_WIDE_CAP")) {
+    if (sscanf(e, "%d,%d", &k.wide_cap_n, &k.wide_cap_c) != 2) k.wide_cap_n = k.wide_cap_c = 0;
+  }
+  if (const char *e = tuning_env("WS_RELAX_EARLY_CAP")) k.early_cap = (uint32_t)atoi(e);
+  if (const char *e = tuning_env("WS_RELAX_LITE_FROM")) k.lite_from = (uint32_t)atoi(e);
+  if (const char *e = tuning_env("WS_RELAX_CHUNK_FROM")) k.chunk_from = (uint32_t)atoi(e);
+  if (const char *e = tuning_env("WS_RELAX_SEAM_BAND")) k.seam_band = atoi(e);
+  k.no_tall = tuning_env("WS_RELAX_NO_TALL") != nullptr;
+  k.no_tall_strips = tuning_env("WS_RELAX_NO_TALL_STRIPS") != nullptr;
+  if (const char *e = tuning_env("WS_RELAX_LIST_FROM")) k.list_from = (uint32_t)atoi(e);
+  k.no_append = tuning_env("WS_RELAX_NO_APPEND") != nullptr;
+  k.no_split = tuning_env("WS_RELAX_NO_SPLIT") != nullptr;
+  if (const char *e = tuning_env("WS_RELAX_PERSIST_WORKERS")) k.persist_workers = (unsigned)atoi(e);
+  if (const char *e = tuning_env("WS_RELAX_PERSIST_CAP")) k.persist_cap = (uint32_t)atoi(e);
+  if (const char *e = tuning_env("WS_RELAX_PERSIST_MODE")) k.persist_queue_mode = atoi(e);
+  k.persist_diag = tuning_env("WS_RELAX_PERSIST_DIAG") != nullptr;
+  return k;
 }
 
-hipError_t relax_pass(hipStream_t s, const uint8_t *img, size_t img_stride, uint32_t *keys, int h, int w,
-                      uint32_t max_level, uint32_t pass, uint32_t *stamps, PassFlags pf, uint32_t max_iters,
-                      const uint32_t *seed_labels, bool seed_bits, int slice_h, bool carry_checked_later, bool padded,
-                      uint32_t *tile_list, size_t seam_min_px, int persistent_pass) {
-  const int th = RX_NW * RX_P;
-  const int pad = padded ? 1 : 0;
+static const RelaxKnobs &relax_knobs_once() {
+  static const RelaxKnobs knobs = relax_knobs();
+  return knobs;
+}
+
+RelaxPlan relax_plan_for(const RelaxPlane &p, uint32_t pass) {
+  RelaxGeom g;
+  g.h = p.h; g.w = p.w; g.slice_h = p.slice_h; g.padded = p.padded;
+  g.has_seeds = p.seed_labels != nullptr; g.seed_bits = p.seed_bits;
+  g.aligned4 = ((reinterpret_cast<uintptr_t>(p.img) | p.img_stride) & 3u) == 0;
+  g.stride32 = p.img_stride <= 0xFFFFFFFFull;
+  g.has_list = p.tile_list != nullptr;
+  g.seam_min_px = p.seam_min_px; g.persist_mode = p.persistent_pass; g.max_iters = p.max_iters;
+  return relax_plan(g, pass, relax_knobs_once());
+}
+
+namespace {
+
+// what every step of a pass is launched with
+struct RelaxLaunch {
+  hipStream_t s;
+  const RelaxPlane &p;
+  const uint32_t *prev;      // the edge stamps the pass before wrote
+  uint32_t *cur;             // ... and the ones this pass writes
+  uint32_t list_cap;         // entries per tile list
+  int sh;                    // rows per slice
   // A carry out of the 24-bit ring field leaves a finite stamp with ring 0 in the plane (and nothing ever lowers it: the
   // true stamp does not exist).  A transform that hands the finished plane to k_resolve_local lets that kernel look for
   // it, once, instead of every write-back of every pass here (5 VALU ops per pixel in kernels that are VALU-bound).
-  const int check_carry = carry_checked_later ? 0 : 1;
-  const int sh = slice_h > 0 ? slice_h : h;
-  const int ax = (w + RX_TW - 1) / RX_TW, ay = (h + th - 1) / th;     // grid anchored at (0, 0): even passes
-  const int sx = ax + 1, sy = ay + 1;                                 // grid shifted by half a tile: odd passes
-  // Passes from RX_SAME_GRID_FROM on all run on the anchored grid (relax_todo, read_same): in the long-range regime a tile
-  // that stops at its round cap goes on itself, instead of handing its area to the FOUR tiles of the other grid that
-  // cover it (each of which loads 8192 pixels to work on a quarter of them).
-  static const uint32_t same_from_passes = [] {
-    const char *e = tuning_env("WS_RELAX_SAME_GRID_FROM");      // tuning knob, tools/ only
-    const uint32_t v = e ? (uint32_t)atoi(e) : RX_SAME_GRID_FROM;
-    return v < 3u ? 3u : (v | 1u);                               // odd: the pass before it runs on the anchored grid
-  }();
-  // The queue in flood order (persistent_pass == 2: the caller has seen sparse seeds, or was told to) starts as early as the
-  // schedule allows -- pass 3, right behind the seam repair and one pass with scans: a flood that crosses hundreds of tiles
-  // gains six of them from passes 3 .. 6 and pays six launches and their host round trip for it (8192^2, 35 seeds: 0.3 of
-  // 4.2 ms).  Pass 4 is then the pass that looks at every tile again; when it finds nothing to change the transform ends
-  // inside the replayed graph (run_fused_form: passes 0 .. 4 and the gated resolve).
-  static const uint32_t queue_from = [] {
-    const char *e = tuning_env("WS_RELAX_QUEUE_FROM");           // tuning knob, tools/ only
-    const uint32_t v = e ? (uint32_t)atoi(e) : 3u;
-    return v < 3u ? 3u : (v | 1u);
-  }();
-  const int persist_mode = tuning_env("WS_RELAX_PERSIST") ? atoi(tuning_env("WS_RELAX_PERSIST")) : persistent_pass;      // (A/B knob, tools/ only)
-  const bool queue_plane = persist_mode == 2 && tile_list && !pad && (w & 3) == 0 && w >= RX_P &&
-                           ((reinterpret_cast<uintptr_t>(img) | img_stride) & 3u) == 0 && relax_tiles(h, w) < (1u << 24);
-  // ... and so do the passes themselves on maps of middling seed density (persist_mode 4: the caller has seen between one
-  // seed per two tiles and ~30 per tile): same grid from pass 3, scans from pass 2, lists from pass 3.  8192^2 smooth maps,
-  // correlation 6 / 8 / 10 / 12 / 16 px: 3.45 / 3.79 / 4.37 / 4.68 / 5.76 -> 3.37 / 3.59 / 4.13 / 4.38 / 5.26 ms; at 4 px
-  // (80 seeds per tile) the late schedule wins, 2.96 against 3.12, and a random field never gets that far (gpurun_out/r3ax, r3ay).
-  const bool early_queue = (queue_plane || (persist_mode == 4 && tile_list)) && queue_from < same_from_passes;
-  const uint32_t same_from = early_queue ? queue_from : same_from_passes;
-  const int read_same = pass >= same_from ? 1 : 0, write_same = pass + 1 >= same_from ? 1 : 0;
-  const uint32_t list_cap = (uint32_t)relax_tiles(h, w);      // entries per tile list
-  const int shifted = read_same ? 0 : (int)(pass & 1u);
-  const int tx = shifted ? sx : ax, ty = shifted ? sy : ay;
-  const size_t cap = relax_tiles(h, w) * 4;
-  const uint32_t *prev = stamps + ((pass + 1) & 1) * cap;
-  uint32_t *cur = stamps + (pass & 1) * cap;
-  const int ox_ = read_same ? ax : (shifted ? ax : sx), oy_ = read_same ? ay : (shifted ? ay : sy);        // the previous pass's grid
-  // Pass 0 only has to produce a good first guess: pass 1 re-examines every pixel on the shifted grid
-  // anyway (a capped tile raises all four of its quadrant flags), so its last round -- the one that
-  // finds nothing left to do, a third of its time on the bench field -- is not worth running.
-  static const uint32_t p0_rounds = [] {
-    const char *e = tuning_env("WS_RELAX_P0_ROUNDS");        // tuning knob, tools/ only
-    return e ? (uint32_t)atoi(e) : 2u;
-  }();
-  static const bool no_seam = tuning_env("WS_RELAX_NO_SEAM") != nullptr;      // A/B knob, tools/ only
-  const bool seam_flow = !no_seam && seed_labels != nullptr && relax_uses_seam_repair(h, w, seed_bits, slice_h, padded, seam_min_px);      // (below)
-  constexpr uint32_t SEAM_P0_ROUNDS = 6;      // two rounds of four sweeps, then up to four of one (k_relax, chunk == 3)
-  const uint32_t p0_cap = seam_flow ? SEAM_P0_ROUNDS : p0_rounds;
-  if (pass == 0 && p0_cap < max_iters) max_iters = p0_cap;
-  // Late passes (the long-range regime of smooth maps: a few hundred tiles along the flood fronts per pass) end when their
-  // SLOWEST tile ends, and a tile that the front is crossing diagonally can take a dozen rounds.  Capping the rounds lets a
-  // pass end after the typical tile's work: a capped tile raises all four quadrant flags (like a capped pass-0 tile), so
-  // the tiles of the other grid that cover it carry on in the next pass -- next to the front, which has moved on meanwhile.
-  static const uint32_t late_cap = [] {
-    const char *e = tuning_env("WS_RELAX_LATE_CAP");      // tuning knob, tools/ only
-    return e ? (uint32_t)atoi(e) : RX_LATE_ROUND_CAP;
-  }();
-  static const uint32_t scan_from_knob = [] {
-    const char *e = tuning_env("WS_RELAX_SCAN_FROM");     // tuning knob, tools/ only
-    return e ? (uint32_t)atoi(e) : RX_SCAN_FROM_PASS;
-  }();
-  const uint32_t scan_from = early_queue ? same_from - 1u : std::max(scan_from_knob, 1u);
-  if (pass >= scan_from && late_cap != 0 && late_cap < max_iters) max_iters = late_cap;
-  // (tuning knob, tools/ only: "n,c" -- the first n scan passes with c rounds instead)
-  if (const char *e = tuning_env("WS_RELAX_WIDE_CAP")) {
-    int n_ = 0, c_ = 0;
-    if (sscanf(e, "%d,%d", &n_, &c_) == 2 && pass >= scan_from && pass < scan_from + (uint32_t)n_) max_iters = (uint32_t)c_;
-  }
-  // Passes 1 .. 3 have no scans: on a smooth map a tile that iterates to its own fixpoint by sweeps alone takes up to 64
-  // rounds to carry a flood across its 256 columns, all 8192 tiles of them, in a pass that the scan passes then redo.
-  static const uint32_t early_cap = [] {
-    const char *e = tuning_env("WS_RELAX_EARLY_CAP");     // tuning knob, tools/ only
-    return e ? (uint32_t)atoi(e) : RX_EARLY_ROUND_CAP;
-  }();
-  if (pass >= 1 && pass < scan_from && early_cap != 0 && early_cap < max_iters) max_iters = early_cap;
-  static const uint32_t lite_from = [] {
-    const char *e = tuning_env("WS_RELAX_LITE_FROM");     // tuning knob, tools/ only
-    return e ? (uint32_t)atoi(e) : 2u;
-  }();
-  // passes 0 and 1 run every tile and pass 2 about half of them (bench field): one tile per workgroup
-  static const uint32_t chunk_from = [] {
-    const char *e = tuning_env("WS_RELAX_CHUNK_FROM");      // tuning knob, tools/ only
-    return e ? (uint32_t)atoi(e) : 3u;
-  }();
-  // Seam repair (k_relax, SEAM): a transform that starts from its seeds runs pass 0 to every tile's own fixpoint and then,
-  // as "pass 1", 8-row bands astride the horizontal seams of the 256 x 32 grid and 8-column strips astride the vertical
-  // ones -- a third of the pixels of the shifted grid's pass, which it replaces -- and those raise the flags that pass 2
-  // reads.  Planes it is not offered for (odd widths, stacks of slices, the virtual halo, planes of a tile or two) keep
-  // the alternating grids from pass 1 on.
-  // (8192^2 bench field: pass 0 141 -> 168 us, pass 1 117 us -> bands 34 + strips 30 us, the later passes as before: 0.622 ->
-  // 0.595 ms per transform; 2048^2: 0.131 -> 0.137 ms, one more launch in a transform that is all launch gaps -- hence the
-  // size threshold.  Wider bands, smaller strip slices and a second, shifted strip launch were measured too: no better,
-  // profiles/r2_v6_seam_ab.log.)
-  // Round caps of that flow: three rounds bring a tile of the bench field to its own fixpoint (the third finds nothing to
-  // do); a tile, band or strip slice of a smooth map that is still moving then asks for a re-run in pass 2 instead of
-  // carrying a flood across its 256 columns sweep by sweep.
-  constexpr uint32_t SEAM_REPAIR_ROUNDS = 4;
-  // Rows each side of a seam (tuning knob, tools/ only).  What pass 0 leaves wrong thins out fourfold per pixel of distance from
-  // the seam, and a band raises a flag when its first or last row changes: with 4 rows a side 41 % of the tiles are flagged
-  // (pass 2: 52 us), with 6 a tile in eight (25 us), with 8 one in eleven (23 us) -- and the bands cost 35 / 50 / 59 us.
-  static const int seam_band = [] { const char *e = tuning_env("WS_RELAX_SEAM_BAND"); return e ? atoi(e) : 6; }();
-  // Pass 0 of that flow on 256 x 64 tiles (k_relax0_tall) wherever its one load path applies -- image rows that can be read
-  // as aligned dwords -- and the plane has a seam at a multiple of 64 rows for the bands to repair.  Pass 1 asks the same
-  // question of the same arguments, so the bands know which seams pass 0 left.
-  // Why the flags are still a superset of the pixels whose equation can be violated: a pass-0 tile that did not stop at its
-  // round cap is a fixpoint of its own pixels against the halo it loaded, so an equation can only be violated next to a
-  // border of a 256 x 64 tile -- the horizontal seams at rows 64 k, the vertical ones at columns 256 k.  The bands lie
-  // astride every row 64 k, the strips astride every column 256 k in ALL rows (in slices of 64 rows whose ends lie on the
-  // bands' rows: k_relax_strips_tall, where the argument is spelt out for them), each iterates to its
-  // own fixpoint on fresh stamps and flags the 256 x 32 tile that holds a pixel next to a changed outer row or column of
-  // it, exactly as before.  The rows 64 k + 32, seams of the old geometry, are interior rows of a pass-0 tile now: nothing
-  // is left violated there unless the tile stopped at its cap -- and then it has marked both 256 x 32 tiles it covers for
-  // pass 2, all of whose pixels that pass examines again.  Stamps start from an upper bound and only fall, as ever.
-  static const bool no_tall = tuning_env("WS_RELAX_NO_TALL") != nullptr;      // A/B knob, tools/ only
-  const bool tall0 = seam_flow && !no_tall && seam_band == 6 && h > RX0_TH && w >= RX_P &&
-                     ((reinterpret_cast<uintptr_t>(img) | img_stride) & 3u) == 0 && img_stride <= 0xFFFFFFFFull;
-  const int ay_tall = (h + RX0_TH - 1) / RX0_TH;
-  if (tall0 && pass == 0) {
-    k_relax0_tall<<<ax * ay_tall, 64 * RX_NW, 0, s>>>(img, (uint32_t)img_stride, keys, h, w, ax, ax, sx, max_level, cur, const_cast<uint32_t *>(prev), pf,
-                                                     max_iters, seed_labels, sh, check_carry, tile_list);
-    return hipGetLastError();
-  }
-  if (tall0 && pass == 1) {
-    // bands only where pass 0 has seams: rows 64 k (half the workgroups, the same twelve rows each); the strips as ever
-    k_relax<3, false, false, false, false, 1, 0, RX0_TH><<<ax * (ay_tall - 1), 192, 0, s>>>(img, img_stride, keys, h, w, ax, ay_tall - 1, sx, sy, 0, 1, max_level, pass, prev, cur,
-                                                                                          pf, SEAM_REPAIR_ROUNDS, nullptr, 0, sh, check_carry, pad, tile_list, 0, 0, 0, list_cap, 0);
-  } else if (seam_flow && pass == 1) {
-    if (seam_band == 4)
-      k_relax<2, false, false, false, false, 1><<<ax * (ay - 1), 128, 0, s>>>(img, img_stride, keys, h, w, ax, ay - 1, sx, sy, 0, 1, max_level, pass, prev, cur,
-                                                                            pf, SEAM_REPAIR_ROUNDS, nullptr, 0, sh, check_carry, pad, tile_list, 0, 0, 0, list_cap, 0);
-    else if (seam_band == 6)
-      k_relax<3, false, false, false, false, 1><<<ax * (ay - 1), 192, 0, s>>>(img, img_stride, keys, h, w, ax, ay - 1, sx, sy, 0, 1, max_level, pass, prev, cur,
-                                                                            pf, SEAM_REPAIR_ROUNDS, nullptr, 0, sh, check_carry, pad, tile_list, 0, 0, 0, list_cap, 0);
-    else
-      k_relax<4, false, false, false, false, 1><<<ax * (ay - 1), 256, 0, s>>>(img, img_stride, keys, h, w, ax, ay - 1, sx, sy, 0, 1, max_level, pass, prev, cur,
-                                                                            pf, SEAM_REPAIR_ROUNDS, nullptr, 0, sh, check_carry, pad, tile_list, 0, 0, 0, list_cap, 0);
-  }
-  if (seam_flow && pass == 1) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    const int strips_x = (ax - 1 + 31) / 32;
-    // After pass 0 on 256 x 64 tiles the strips run on slices of 64 rows, whose ends lie where the bands have run
-    // (k_relax_strips_tall); every other flow keeps its 32-row slices.
-    static const bool no_tall_strips = tuning_env("WS_RELAX_NO_TALL_STRIPS") != nullptr;      // A/B knob, tools/ only
-    if (tall0 && !no_tall_strips) {
-      k_relax_strips_tall<<<strips_x * ay_tall, 64 * RX_NW, 0, s>>>(img, (uint32_t)img_stride, keys, h, w, strips_x, sx, max_level, pass, cur, pf,
-                                                                  SEAM_REPAIR_ROUNDS, sh, check_carry, tile_list);
-      return hipGetLastError();
-    }
-    k_relax<RX_NW, false, false, false, false, 2><<<strips_x * ay, 64 * RX_NW, 0, s>>>(img, img_stride, keys, h, w, strips_x, ay, sx, sy, 0, 1, max_level, pass,
-                                                                                       prev, cur, pf, SEAM_REPAIR_ROUNDS, nullptr, 0, sh, check_carry, pad, tile_list, 0, 0,
-                                                                                       0, list_cap, 0);
-    return hipGetLastError();
-  }
-  const int sb = pass == 0 && seed_labels && seed_bits ? 1 : 0;
-  const uint32_t *sl = pass == 0 ? seed_labels : nullptr;
-  // (pass 2 after a seam repair runs a tile in ten: a workgroup per four tiles, as in the later passes)
-  const uint32_t chunk_from_now = seam_flow ? std::min(chunk_from, 2u) : chunk_from;
-  if (pass < chunk_from_now && pass < lite_from) {
-    k_relax<RX_NW, false, false, false><<<tx * ty, 64 * RX_NW, 0, s>>>(img, img_stride, keys, h, w, tx, ty, ox_, oy_, shifted, seam_flow && pass == 0 ? 3 : 1, max_level, pass,
-                                                                       prev, cur, pf, max_iters, sl, sb, sh, check_carry, pad, tile_list, 0, read_same, write_same, list_cap, 0);
-  } else if (pass < chunk_from_now) {
-    k_relax<RX_NW, false, false, true><<<tx * ty, 64 * RX_NW, 0, s>>>(img, img_stride, keys, h, w, tx, ty, ox_, oy_, shifted, 1, max_level, pass,
-                                                                      prev, cur, pf, max_iters, sl, sb, sh, check_carry, pad, tile_list, 0, read_same, write_same, list_cap, 0);
-  } else {
-    const int chunk = 4;
-    const unsigned grid = (unsigned)((tx * ty + chunk - 1) / chunk);
-    static const uint32_t list_from_passes = [] {
-      const char *e = tuning_env("WS_RELAX_LIST_FROM");      // tuning knob, tools/ only
-      return e ? (uint32_t)atoi(e) : RX_LIST_FROM_PASS;
-    }();
-    const uint32_t list_from = early_queue ? same_from : list_from_passes;
-    if (pass < scan_from) {
-      k_relax<RX_NW, true, false, true><<<grid, 64 * RX_NW, 0, s>>>(img, img_stride, keys, h, w, tx, ty, ox_, oy_, shifted, chunk, max_level,
-                                                              pass, prev, cur, pf, max_iters, nullptr, 0, sh, check_carry, pad, tile_list, 0, read_same, write_same, list_cap, 0);
-    } else if (tile_list && pass >= list_from && pass >= scan_from + 1) {
-      // (two passes earlier a launch has cleared this pass's counter: every kernel variant does, given a list)
-      // From the second same-grid pass on the list is there already: the tiles of the pass before appended it.
-      static const bool no_append = tuning_env("WS_RELAX_NO_APPEND") != nullptr;      // A/B knob, tools/ only
-      const uint32_t first_list_pass = std::max(list_from, scan_from + 1);
-      const int append_next = !no_append && pass >= same_from && pass >= first_list_pass ? 1 : 0;
-      const bool appended = !no_append && pass >= 1 && pass - 1 >= same_from && pass - 1 >= first_list_pass;
-      // The same-grid passes run on 128 x 64 tiles (k_relax, SPLIT); the first of them builds its list from the stamps the
-      // 256 x 32 grid left behind.
-      static const bool no_split = tuning_env("WS_RELAX_NO_SPLIT") != nullptr;      // A/B knob, tools/ only
-      const bool split = !no_split && pass >= same_from && same_from >= first_list_pass;
-      const int gx = split ? (w + RX_STW - 1) / RX_STW : tx, gy = split ? (h + RX_STH - 1) / RX_STH : ty;
-      if (!appended) {
-        // (one thread per tile and a few more: the queued marks, dummy slot included, are cleared here)
-        const unsigned blocks = (unsigned)((std::max<size_t>((size_t)gx * gy, list_cap + 1) + 255) / 256);
-        // The first same-grid pass as ONE persistent launch (k_relax, PERSIST): workgroups pull tiles from a queue and a tile
-        // that changes something its neighbour must see queues that neighbour at once.  The pass after it runs every tile
-        // from an all-tiles list, so the fixpoint is certified by the ordinary machinery whatever the queue did.
-        // 8192^2 smooth maps, correlation length 4 / 16 / 64 / 256 px (profiles/r3_v1_persistent_ab.txt): 3.0 / 5.8 / 6.7 / 3.5 ms
-        // with the passes; first come (mode 1) 3.0 / 6.4 / 6.4 / 4.1 -- a tile run costs 13-17 us either way (4 us of loads past
-        // L2, 4-8 of scan rounds, 3 of write-through stores, 2 of queue atomics), the queue saves the launch gaps and the
-        // tails of the passes and pays for them with a sixth more tile runs (a tile runs on the first flag instead of on all
-        // flags of a pass); in flood order (mode 2, from pass 3, on 128 x 128 tiles) 4.2 / 5.8 / 3.9 / 3.0: a third of the
-        // tile runs, and a win where floods are long.  The context picks mode 2 by itself when seeds are sparse
-        // (run_fused_form); ws_ctx_set_persistent_pass forces or forbids.
-        const bool persist = (persist_mode == 1 || persist_mode == 2) && split && pass == same_from && !pad && (w & 3) == 0 && w >= RX_P &&
-                             ((reinterpret_cast<uintptr_t>(img) | img_stride) & 3u) == 0 && (size_t)gx * gy <= list_cap && list_cap < (1u << 24);
-        if (persist) {
-          const bool in_order = persist_mode == 2;      // buckets in flood order (PERSIST == 2) instead of the first-come ring
-          hipError_t e = hipMemsetAsync(tile_list + RL_HDR, 0, 2 * (size_t)list_cap * sizeof(uint32_t), s);      // the ring: no entry yet
-          if (e == hipSuccess) e = hipMemsetAsync(tile_list + 8, 0, (RL_HDR - 8) * sizeof(uint32_t), s);      // counters (and diagnostics)
-          if (e == hipSuccess && in_order)
-            e = hipMemsetAsync(tile_list + pq_base(list_cap), 0, (PQ_HDR + (size_t)PQ_B * pq_words_per_bucket(list_cap)) * sizeof(uint32_t), s);
-          if (e != hipSuccess) return e;
-          const int qy = (h + RX_QTH - 1) / RX_QTH;      // (flood order: the queue's own grid, 128 x 128)
-          if (in_order)
-            k_relax_list_regrid<RX_STW, RX_QTH, RX_TW, RX_NW * RX_P><<<blocks, 256, 0, s>>>(h, w, gx, qy, ax, ay, pass, prev, tile_list, list_cap, 2);
-          else
-            k_relax_list_regrid<RX_STW, RX_STH, RX_TW, RX_NW * RX_P><<<blocks, 256, 0, s>>>(h, w, gx, gy, ax, ay, pass, prev, tile_list, list_cap, 1);
-          if ((e = hipGetLastError()) != hipSuccess) return e;
-          // In flood order: one worker per CU.  Two (all that are resident) run twice as long each, the rounds too -- a
-          // workgroup is one wave per SIMD, and two share their vector issue -- so nothing is gained where all are busy, and
-          // where most are idle their looks at the counts are in the way: 8192^2 smooth maps, correlation 4 / 16 / 64 / 256 px,
-          // 3.89 / 7.75 / 5.73 / 4.14 ms with 512 workers, 3.82 / 7.22 / 4.98 / 3.98 with 256 (gpurun_out/r3z).
-          const unsigned workers = tuning_env("WS_RELAX_PERSIST_WORKERS") ? (unsigned)atoi(tuning_env("WS_RELAX_PERSIST_WORKERS"))
-                                                                          : std::min<unsigned>(in_order ? RX_LIST_GRID / 2 : RX_LIST_GRID * RX_NW / RX_SNW, (unsigned)(gx * (in_order ? qy : gy)));
-          const uint32_t cap = tuning_env("WS_RELAX_PERSIST_CAP") ? (uint32_t)atoi(tuning_env("WS_RELAX_PERSIST_CAP")) : RLQ_ROUND_CAP;
-          const int mode = tuning_env("WS_RELAX_PERSIST_MODE") ? atoi(tuning_env("WS_RELAX_PERSIST_MODE")) : 0;
-          if (in_order)
-            k_relax<RX_QNW, true, true, true, true, 0, 2><<<workers, 64 * RX_QNW, 0, s>>>(img, img_stride, keys, h, w, gx, qy, gx, qy, 0, chunk, max_level, pass, prev, cur, pf, cap,
-                                                                                         nullptr, 0, sh, check_carry, pad, tile_list, mode, 1, 1, list_cap, 1);
-          else
-            k_relax<RX_SNW, true, true, true, true, 0, 1><<<workers, 64 * RX_SNW, 0, s>>>(img, img_stride, keys, h, w, gx, gy, gx, gy, 0, chunk, max_level, pass, prev, cur, pf, cap,
-                                                                                         nullptr, 0, sh, check_carry, pad, tile_list, mode, 1, 1, list_cap, 1);
-          if ((e = hipGetLastError()) != hipSuccess) return e;
-          hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-          (void)hipStreamIsCapturing(s, &capturing);
-          if (tuning_env("WS_RELAX_PERSIST_DIAG") && capturing == hipStreamCaptureStatusNone) {      // tools/ only: what the workers did
-            uint32_t hd[RL_HDR];
-            (void)hipStreamSynchronize(s);
-            (void)hipMemcpy(hd, tile_list, sizeof hd, hipMemcpyDeviceToHost);
-            fprintf(stderr, "[ws] persistent pass %u: pushed %u popped %u pending %u done %u runs %u | workers wait %.1f us, life %.1f us (sums / 512), polls %u\n", pass,
-                    hd[RLQ_TAIL], hd[RLQ_HEAD], hd[RLQ_PENDING], hd[RLQ_DONE], hd[RLQ_RUNS], hd[RLQ_WAIT] / 100.0 / 512.0, hd[RLQ_LIFE] / 100.0 / 512.0, hd[RLQ_POLLS]);
-            const double runs = hd[RLQ_RUNS] ? hd[RLQ_RUNS] : 1;
-            fprintf(stderr, "[ws]   per tile run (us): load %.2f rounds %.2f epilogue %.2f hand-in %.2f; shader clock %.0f MHz\n", hd[RLQ_PHASE] / 100.0 / runs, hd[RLQ_PHASE + 1] / 100.0 / runs,
-                    hd[RLQ_PHASE + 2] / 100.0 / runs, hd[RLQ_PHASE + 3] / 100.0 / runs, hd[RLQ_LIFE] ? 256.0 * hd[RLQ_PHASE + 4] / hd[RLQ_LIFE] * 100.0 : 0.0);
-          }
-          k_relax_list_all<RX_STW, RX_STH><<<(unsigned)((std::max<size_t>((size_t)gx * gy, list_cap + 1) + 255) / 256), 256, 0, s>>>(h, w, gx, gy, pass + 1, tile_list, list_cap);
-          return hipGetLastError();
-        }
-        if (split && pass == same_from)
-          k_relax_list_regrid<RX_STW, RX_STH, RX_TW, RX_NW * RX_P><<<blocks, 256, 0, s>>>(h, w, gx, gy, ax, ay, pass, prev, tile_list, list_cap, 0);
-        else if (split)
-          k_relax_list<RX_STW, RX_STH><<<blocks, 256, 0, s>>>(h, w, gx, gy, gx, gy, 0, pass, prev, tile_list, 1, list_cap);
-        else
-          k_relax_list<RX_TW, RX_NW * RX_P><<<blocks, 256, 0, s>>>(h, w, tx, ty, ox_, oy_, shifted, pass, prev, tile_list, read_same, list_cap);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-      }
-      if (split)
-        k_relax<RX_SNW, true, true, true, true><<<std::min<unsigned>(RX_LIST_GRID * RX_NW / RX_SNW, (unsigned)(gx * gy)), 64 * RX_SNW, 0, s>>>(
-            img, img_stride, keys, h, w, gx, gy, gx, gy, 0, chunk, max_level, pass, prev, cur, pf, max_iters, nullptr, 0, sh,
-            check_carry, pad, tile_list, 1, 1, 1, list_cap, append_next);
+  int check_carry;
+};
+
+// k_relax's argument list
+template <int NW, bool CHUNKED, bool SCAN, bool LITE, bool SPLIT = false, int SEAM = 0, int PERSIST = 0, int SEAM_PITCH = 32>
+void launch_relax(const RelaxLaunch &l, const RelaxStep &st) {
+  const RelaxPlane &p = l.p;
+  const uint32_t *seeds = st.seeds ? p.seed_labels : nullptr;
+  k_relax<NW, CHUNKED, SCAN, LITE, SPLIT, SEAM, PERSIST, SEAM_PITCH><<<st.grid, st.block, 0, l.s>>>(
+      p.img, p.img_stride, p.keys, p.h, p.w, st.tilesX, st.tilesY, st.otherX, st.otherY, st.shifted, st.chunk, p.max_level, st.pass, l.prev, l.cur, p.pf,
+      st.max_iters, seeds, seeds && p.seed_bits ? 1 : 0, l.sh, l.check_carry, p.padded ? 1 : 0, p.tile_list, st.use_list, st.read_same, st.write_same,
+      l.list_cap, st.append_next);
+}
+
+// tools/ only (WS_RELAX_PERSIST_DIAG): what the workers of the queue pass did
+void print_queue_diagnostics(const RelaxLaunch &l, uint32_t pass) {
+  uint32_t hd[RL_HDR];
+  (void)hipStreamSynchronize(l.s);
+  (void)hipMemcpy(hd, l.p.tile_list, sizeof hd, hipMemcpyDeviceToHost);
+  fprintf(stderr, "[ws] persistent pass %u: pushed %u popped %u pending %u done %u runs %u | workers wait %.1f us, life %.1f us (sums / 512), polls %u\n", pass,
+          hd[RLQ_TAIL], hd[RLQ_HEAD], hd[RLQ_PENDING], hd[RLQ_DONE], hd[RLQ_RUNS], hd[RLQ_WAIT] / 100.0 / 512.0, hd[RLQ_LIFE] / 100.0 / 512.0, hd[RLQ_POLLS]);
+  const double runs = hd[RLQ_RUNS] ? hd[RLQ_RUNS] : 1;
+  fprintf(stderr, "[ws]   per tile run (us): load %.2f rounds %.2f epilogue %.2f hand-in %.2f; shader clock %.0f MHz\n", hd[RLQ_PHASE] / 100.0 / runs, hd[RLQ_PHASE + 1] / 100.0 / runs,
+          hd[RLQ_PHASE + 2] / 100.0 / runs, hd[RLQ_PHASE + 3] / 100.0 / runs, hd[RLQ_LIFE] ? 256.0 * hd[RLQ_PHASE + 4] / hd[RLQ_LIFE] * 100.0 : 0.0);
+}
+
+hipError_t launch_step(const RelaxLaunch &l, const RelaxStep &st) {
+  const RelaxPlane &p = l.p;
+  uint32_t *const list = p.tile_list;
+  switch (st.kind) {
+    case RelaxStep::TALL_PASS0:      // (the anchored grid's tile columns are this kernel's own)
+      k_relax0_tall<<<st.grid, st.block, 0, l.s>>>(p.img, (uint32_t)p.img_stride, p.keys, p.h, p.w, st.tilesX, st.tilesX, st.otherX, p.max_level, l.cur,
+                                                   const_cast<uint32_t *>(l.prev), p.pf, st.max_iters, p.seed_labels, l.sh, l.check_carry, list);
+      break;
+    case RelaxStep::BANDS:
+      if (st.seam_pitch == RX0_TH) launch_relax<3, false, false, false, false, 1, 0, RX0_TH>(l, st);
+      else if (st.nw == 2) launch_relax<2, false, false, false, false, 1>(l, st);
+      else if (st.nw == 3) launch_relax<3, false, false, false, false, 1>(l, st);
+      else launch_relax<4, false, false, false, false, 1>(l, st);
+      break;
+    case RelaxStep::STRIPS: launch_relax<RX_NW, false, false, false, false, 2>(l, st); break;
+    case RelaxStep::STRIPS_TALL:
+      k_relax_strips_tall<<<st.grid, st.block, 0, l.s>>>(p.img, (uint32_t)p.img_stride, p.keys, p.h, p.w, st.tilesX, st.otherX, p.max_level, st.pass, l.cur, p.pf,
+                                                         st.max_iters, l.sh, l.check_carry, list);
+      break;
+    case RelaxStep::FULL: launch_relax<RX_NW, false, false, false>(l, st); break;
+    case RelaxStep::FULL_LITE: launch_relax<RX_NW, false, false, true>(l, st); break;
+    case RelaxStep::CHUNKED: launch_relax<RX_NW, true, false, true>(l, st); break;
+    case RelaxStep::CHUNKED_SCAN:
+    case RelaxStep::LISTED: launch_relax<RX_NW, true, true, true>(l, st); break;
+    case RelaxStep::LISTED_SPLIT: launch_relax<RX_SNW, true, true, true, true>(l, st); break;
+    case RelaxStep::QUEUE_FIRST_COME: launch_relax<RX_SNW, true, true, true, true, 0, 1>(l, st); break;
+    case RelaxStep::QUEUE_FLOOD_ORDER: launch_relax<RX_QNW, true, true, true, true, 0, 2>(l, st); break;
+    case RelaxStep::LIST_BUILD:
+      k_relax_list<RX_TW, RX_NW * RX_P><<<st.grid, st.block, 0, l.s>>>(p.h, p.w, st.tilesX, st.tilesY, st.otherX, st.otherY, st.shifted, st.pass, l.prev, list, st.read_same, l.list_cap);
+      break;
+    case RelaxStep::LIST_BUILD_SPLIT:
+      k_relax_list<RX_STW, RX_STH><<<st.grid, st.block, 0, l.s>>>(p.h, p.w, st.tilesX, st.tilesY, st.otherX, st.otherY, st.shifted, st.pass, l.prev, list, st.read_same, l.list_cap);
+      break;
+    case RelaxStep::LIST_REGRID:
+      if (st.regrid == 2)
+        k_relax_list_regrid<RX_STW, RX_QTH, RX_TW, RX_NW * RX_P><<<st.grid, st.block, 0, l.s>>>(p.h, p.w, st.tilesX, st.tilesY, st.otherX, st.otherY, st.pass, l.prev, list, l.list_cap, st.regrid);
       else
-        k_relax<RX_NW, true, true, true><<<std::min<unsigned>(RX_LIST_GRID, (unsigned)(tx * ty)), 64 * RX_NW, 0, s>>>(
-            img, img_stride, keys, h, w, tx, ty, ox_, oy_, shifted, chunk, max_level, pass, prev, cur, pf, max_iters, nullptr, 0, sh,
-            check_carry, pad, tile_list, 1, read_same, write_same, list_cap, append_next);
-    } else {
-      k_relax<RX_NW, true, true, true><<<grid, 64 * RX_NW, 0, s>>>(img, img_stride, keys, h, w, tx, ty, ox_, oy_, shifted, chunk, max_level,
-                                                             pass, prev, cur, pf, max_iters, nullptr, 0, sh, check_carry, pad, tile_list, 0, read_same, write_same, list_cap, 0);
-    }
+        k_relax_list_regrid<RX_STW, RX_STH, RX_TW, RX_NW * RX_P><<<st.grid, st.block, 0, l.s>>>(p.h, p.w, st.tilesX, st.tilesY, st.otherX, st.otherY, st.pass, l.prev, list, l.list_cap, st.regrid);
+      break;
+    case RelaxStep::LIST_ALL:
+      k_relax_list_all<RX_STW, RX_STH><<<st.grid, st.block, 0, l.s>>>(p.h, p.w, st.tilesX, st.tilesY, st.pass, list, l.list_cap);
+      break;
+    case RelaxStep::CLEAR_RING: return hipMemsetAsync(list + RL_HDR, 0, 2 * (size_t)l.list_cap * sizeof(uint32_t), l.s);
+    case RelaxStep::CLEAR_COUNTERS: return hipMemsetAsync(list + 8, 0, (RL_HDR - 8) * sizeof(uint32_t), l.s);
+    case RelaxStep::CLEAR_BUCKETS:
+      return hipMemsetAsync(list + pq_base(l.list_cap), 0, (PQ_HDR + (size_t)PQ_B * pq_words_per_bucket(l.list_cap)) * sizeof(uint32_t), l.s);
   }
   return hipGetLastError();
+}
+
+}  // namespace
+
+// One relaxation pass: what relax_plan (ws_relax_plan.hpp) decides, launched step by step.
+hipError_t relax_pass(hipStream_t s, const RelaxPlane &p, uint32_t pass) {
+  const RelaxPlan plan = relax_plan_for(p, pass);
+  const size_t cap = relax_tiles(p.h, p.w) * 4;
+  const RelaxLaunch l{s, p, p.stamps + ((pass + 1) & 1) * cap, p.stamps + (pass & 1) * cap, (uint32_t)relax_tiles(p.h, p.w),
+                      p.slice_h > 0 ? p.slice_h : p.h, p.carry_checked_later ? 0 : 1};
+  for (int i = 0; i < plan.n; ++i) {
+    const RelaxStep &st = plan.steps[i];
+    const hipError_t e = launch_step(l, st);
+    if (e != hipSuccess) return e;
+    const bool queue = st.kind == RelaxStep::QUEUE_FIRST_COME || st.kind == RelaxStep::QUEUE_FLOOD_ORDER;
+    if (queue && relax_knobs_once().persist_diag) {
+      hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+      (void)hipStreamIsCapturing(s, &capturing);
+      if (capturing == hipStreamCaptureStatusNone) print_queue_diagnostics(l, pass);
+    }
+  }
+  return hipSuccess;
 }
 
 }  // namespace wsk

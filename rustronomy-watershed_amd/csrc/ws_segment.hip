@@ -1,6 +1,7 @@
 // ws_segment.hip -- the segmenting drivers: the reference's transform_with_hook body (lib.rs:1638-1808) restated as launch
 // sequences on one HIP stream, in the fused form (all levels at once) and the literal sweep form.
 #include "ws_ctx.hpp"
+#include "ws_relax_plan.hpp"
 
 #include <atomic>
 #include <mutex>
@@ -58,6 +59,12 @@ int run_fused_form(ws_ctx *c, const uint8_t *d_img, size_t stride, int ph, int p
   const int persist_mode = c->persistent_pass != 3 ? c->persistent_pass
                                                    : (n_for_auto >= 1 && n_for_auto <= relax_tiles(ph, pw) / 2 ? 2
                                                       : (n_for_auto >= 1 && n_for_auto <= relax_tiles(ph, pw) * 32 ? 4 : 0));      // (4: the passes, on the early schedule)
+  // What the relaxation passes of this transform have in common.  The captured passes always start from the seed tables and
+  // leave the ring-carry test to the resolve behind them; the ordinary loop below fills in its own seed plane.
+  RelaxPlane plane;
+  plane.img = d_img; plane.img_stride = stride; plane.keys = keys; plane.h = ph; plane.w = pw; plane.max_level = max_level;
+  plane.stamps = stamps; plane.max_iters = c->debug_max_iters; plane.slice_h = slice_h; plane.padded = padded;
+  plane.tile_list = tile_list; plane.seam_min_px = c->seam_min_px; plane.persistent_pass = persist_mode;
   // ---- graph replay -------------------------------------------------------------------------------
   // A transform that repeats the previous one's arguments exactly (same buffers, sizes and seed COUNT; the contents
   // are free to change: a pipeline that reuses its buffers) replays its optimistic part -- seed tables, the first
@@ -107,11 +114,11 @@ int run_fused_form(ws_ctx *c, const uint8_t *d_img, size_t stride, int ph, int p
     }
   }
   if (graph_mode == 2) {
-    const PassFlags gpf = make_pf(c);
+    RelaxPlane captured = plane;
+    captured.pf = make_pf(c); captured.seed_labels = seed_mask; captured.seed_bits = true; captured.carry_checked_later = true;
     hipGraph_t graph = nullptr;
     hipError_t e = make_tables();
-    for (uint32_t pass = 0; pass < GRAPH_PASSES && e == hipSuccess; ++pass)
-      e = relax_pass(c->stream, d_img, stride, keys, ph, pw, max_level, pass, stamps, gpf, c->debug_max_iters, seed_mask, true, slice_h, true, padded, tile_list, c->seam_min_px, persist_mode);
+    for (uint32_t pass = 0; pass < GRAPH_PASSES && e == hipSuccess; ++pass) e = relax_pass(c->stream, captured, pass);
     const uint32_t last = GRAPH_PASSES - 1;
     if (e == hipSuccess)
       e = resolve_two_launch(c->stream, keys, d_labels, ph, pw, (uint32_t *)c->refs.p, c->debug_max_iters, seed_mask, word_base,
@@ -188,10 +195,10 @@ int run_fused_form(ws_ctx *c, const uint8_t *d_img, size_t stride, int ph, int p
       speculated_after = last_pass;
       return resolve(edge_slot(flags, last_pass));
     };
+  plane.pf = pf; plane.seed_labels = tables ? seed_mask : d_labels; plane.seed_bits = tables; plane.carry_checked_later = two_launch;
   auto launch_pass = [&](uint32_t pass) {
     Span sp(c, KC_RELAX);
-    return relax_pass(c->stream, d_img, stride, keys, ph, pw, max_level, pass, stamps, pf, c->debug_max_iters,
-                      tables ? seed_mask : d_labels, tables, slice_h, two_launch, padded, tile_list, c->seam_min_px, persist_mode);
+    return relax_pass(c->stream, plane, pass);
   };
   if (graph_mode != 0) {
     // the graph ran seed tables, passes 0 .. GRAPH_PASSES - 1, the gated resolve and the read-backs
@@ -208,7 +215,7 @@ int run_fused_form(ws_ctx *c, const uint8_t *d_img, size_t stride, int ph, int p
     if (rc) return rc;
   }
   // (a seam repair is two launches for pass 1: bands, strips)
-  c->stats.launches_relax = c->stats.relax_passes + (c->stats.relax_passes >= 2 && relax_uses_seam_repair(ph, pw, tables, slice_h, padded, c->seam_min_px) ? 1u : 0u);
+  c->stats.launches_relax = c->stats.relax_passes + (c->stats.relax_passes >= 2 && relax_plan_for(plane, 1).seam_flow ? 1u : 0u);
 
   // no host round trip here: the error words are read once, after the resolve launches are queued
   if (two_launch) {

@@ -28,7 +28,7 @@ GRAPH_SHAPE = (200, 520)
 
 
 def test_every_shape_takes_the_seam_flow_and_the_tall_path():
-    # relax_uses_seam_repair (ws_relax.hip): two tile columns of 256, two tile rows of 32, a width that is a multiple of 4;
+    # relax_seam_flow (ws_relax_plan.hpp): two tile columns of 256, two tile rows of 32, a width that is a multiple of 4;
     # pass 0 on 256 x 64 tiles and the 64-row strips: more than 64 rows.  A stack is one plane of s * h rows.
     planes = NOISE_SHAPES + [SMOOTH_SHAPE, SEED_SHAPE, LEVEL_SHAPE, GRAPH_SHAPE] + [(s * h, w) for s, h, w in STACKS]
     for h, w in planes:

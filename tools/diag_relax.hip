@@ -29,8 +29,11 @@ int main() {
     CHECK(hipMemset(stamps, 0, (size_t)ntiles * 8 * 4)); CHECK(hipMemset(flags, 0, flag_words * 4)); CHECK(hipMemset(diag, 0, (size_t)ntiles * 64));
     CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_diag), &diag, sizeof(diag)));
     PassFlags pf{flags, flags + COUNTER_RING * FLAG_SLOT, flags + (COUNTER_RING + 3) * FLAG_SLOT, with_stats ? flags + (COUNTER_RING + 1) * FLAG_SLOT : nullptr};
+    RelaxPlane plane;
+    plane.img = img; plane.img_stride = W; plane.keys = keys; plane.h = H; plane.w = W; plane.max_level = 254;
+    plane.stamps = stamps; plane.pf = pf;
     hipEvent_t a, b; CHECK(hipEventCreate(&a)); CHECK(hipEventCreate(&b)); CHECK(hipEventRecord(a));
-    CHECK(relax_pass(0, img, W, keys, H, W, 254, 0, stamps, pf, 0xFFFFFFFFu));
+    CHECK(relax_pass(0, plane, 0));
     CHECK(hipEventRecord(b)); CHECK(hipEventSynchronize(b)); float ms; CHECK(hipEventElapsedTime(&ms, a, b));
     std::vector<unsigned long long> h((size_t)ntiles * 8); CHECK(hipMemcpy(h.data(), diag, h.size() * 8, hipMemcpyDeviceToHost));
     std::vector<double> load, loop, tail, life; std::vector<unsigned long long> it; unsigned long long t_first = ~0ull, t_last = 0;

@@ -42,6 +42,9 @@ int main(int argc, char **argv) {
   CHECK(hipMemset(stamps, 0, (size_t)ntiles * 8 * 4)); CHECK(hipMemset(flags, 0, flag_words * 4)); CHECK(hipMemset(tile_list, 0, relax_list_words(H, W) * 4));
   CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_diag), &diag, sizeof(diag)));
   PassFlags pf{flags, flags + COUNTER_RING * FLAG_SLOT, flags + (COUNTER_RING + 3) * FLAG_SLOT, flags + (COUNTER_RING + 1) * FLAG_SLOT};
+  RelaxPlane plane;
+  plane.img = img; plane.img_stride = W; plane.keys = keys; plane.h = H; plane.w = W; plane.max_level = 254;
+  plane.stamps = stamps; plane.pf = pf; plane.tile_list = tile_list;
   std::vector<uint32_t> slot(FLAG_SLOT), st(2 * FLAG_SLOT);
   std::vector<unsigned long long> h((size_t)ntiles * 8);
   hipEvent_t a, b; CHECK(hipEventCreate(&a)); CHECK(hipEventCreate(&b));
@@ -49,7 +52,7 @@ int main(int argc, char **argv) {
   for (uint32_t pass = 0; pass < 2000; ++pass) {
     CHECK(hipMemset(diag, 0, (size_t)ntiles * 64)); CHECK(hipMemset(flags + (COUNTER_RING + 1) * FLAG_SLOT, 0, 2 * FLAG_SLOT * 4));
     CHECK(hipEventRecord(a));
-    CHECK(relax_pass(0, img, W, keys, H, W, 254, pass, stamps, pf, 0xFFFFFFFFu, nullptr, false, 0, false, false, tile_list));
+    CHECK(relax_pass(0, plane, pass));
     CHECK(hipEventRecord(b)); CHECK(hipEventSynchronize(b)); float ms; CHECK(hipEventElapsedTime(&ms, a, b)); total += ms;
     CHECK(hipMemcpy(slot.data(), flags + (pass % COUNTER_RING) * FLAG_SLOT, FLAG_SLOT * 4, hipMemcpyDeviceToHost));
     CHECK(hipMemcpy(st.data(), flags + (COUNTER_RING + 1) * FLAG_SLOT, 2 * FLAG_SLOT * 4, hipMemcpyDeviceToHost));

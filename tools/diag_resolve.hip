@@ -31,7 +31,10 @@ int main() {
     CHECK(hipMemset(stamps, 0, (size_t)ntiles * 8 * 4)); CHECK(hipMemset(flags, 0, flag_words * 4));
     unsigned long long *none = nullptr; CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_diag), &none, sizeof(none)));
     PassFlags pf{flags, flags + COUNTER_RING * FLAG_SLOT, flags + (COUNTER_RING + 3) * FLAG_SLOT, nullptr};
-    for (uint32_t pass = 0; pass < 12; ++pass) CHECK(relax_pass(0, img, W, keys, H, W, 254, pass, stamps, pf, 0xFFFFFFFFu));   // 12 passes: converged on this field
+    RelaxPlane plane;
+    plane.img = img; plane.img_stride = W; plane.keys = keys; plane.h = H; plane.w = W; plane.max_level = 254;
+    plane.stamps = stamps; plane.pf = pf;
+    for (uint32_t pass = 0; pass < 12; ++pass) CHECK(relax_pass(0, plane, pass));   // 12 passes: converged on this field
     CHECK(hipMemset(diag, 0, (size_t)rtiles * 64));
     CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_diag), &diag, sizeof(diag)));
     hipEvent_t a, b; CHECK(hipEventCreate(&a)); CHECK(hipEventCreate(&b)); CHECK(hipEventRecord(a));
