@@ -1003,9 +1003,11 @@ static int segment_tiled_host(ws_group *g, const uint8_t *img, size_t h, size_t 
   const int world = g->world;
   if (ph < (size_t)world) return gfail(g, WS_ERR_BAD_ARG, "a field needs at least one row per rank");
   // the reference indexes the (padded) plane with the caller's coordinates and panics outside it (lib.rs:1675-1677)
+  // (the raw coordinate against ph - shift, as k_narrow_seeds does: coordinate + shift wraps to 0 at 2^64 - 1 and would pass; past
+  // this loop every coordinate + shift is below 2^31, so the search and the filters below never see a wrapped value)
   bool rows_sorted = true;
   for (size_t i = 0; i < n_seeds; ++i) {
-    if (seeds_rc[2 * i] + shift >= ph || seeds_rc[2 * i + 1] + shift >= pw) return gfail(g, WS_ERR_SEED_OOB, "seed outside the label plane (the reference panics: lib.rs:1676)");
+    if (seeds_rc[2 * i] >= ph - shift || seeds_rc[2 * i + 1] >= pw - shift) return gfail(g, WS_ERR_SEED_OOB, "seed outside the label plane (the reference panics: lib.rs:1676)");
     if (i && seeds_rc[2 * i] < seeds_rc[2 * i - 2]) rows_sorted = false;
   }
   ws_options plain = *opt;
@@ -1153,7 +1155,7 @@ int ws_segment_tiled2d(ws_group *g, const uint8_t *img, size_t h, size_t w, size
   if (ph < (size_t)py || pw < (size_t)px) return gfail(g, WS_ERR_BAD_ARG, "a field needs at least one row and one column per tile");
   if (exchange_rounds) *exchange_rounds = 0;
   for (size_t i = 0; i < n_seeds; ++i)      // the reference indexes the (padded) plane with the caller's coordinates and panics outside it (lib.rs:1675-1677)
-    if (seeds_rc[2 * i] + shift >= ph || seeds_rc[2 * i + 1] + shift >= pw) return gfail(g, WS_ERR_SEED_OOB, "seed outside the label plane (the reference panics: lib.rs:1676)");
+    if (seeds_rc[2 * i] >= ph - shift || seeds_rc[2 * i + 1] >= pw - shift) return gfail(g, WS_ERR_SEED_OOB, "seed outside the label plane (the reference panics: lib.rs:1676)");      // (raw coordinate: + shift wraps at 2^64 - 1)
   ws_options plain = *opt;
   plain.edge_correction = 0;      // the tiles hold the padded plane's own pixels
   plain.seed_shift = 0;
