@@ -33,14 +33,14 @@
 // that exist only when profiling is on.
 #include "ws_common.hpp"
 #include "ws_relax_plan.hpp"      // tile geometry, round caps and the schedule (relax_plan)
+#include "ws_relax_patch.hpp"     // the register patch: relax_px, the sweeps, patch_bases
+#include "ws_relax_queue.hpp"     // tile_list's layout; the tile queue of the persistent pass
 
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 
 namespace wsk {
-
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 
 // Diagnostic build only (tools/diag_relax.hip defines WS_DIAG_STAMPS): per-workgroup phase stamps.
 #ifdef WS_DIAG_STAMPS
@@ -67,143 +67,28 @@ __device__ unsigned long long *g_diag = nullptr;
 #define WS_STAMP_VALUE(slot, v) do {} while (0)
 #endif
 
-__device__ __forceinline__ uint32_t lane_left(uint32_t old, uint32_t v) {     // lane i <- lane i-1, lane 0 keeps old
-  return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)v, 0x138, 0xF, 0xF, false);
-}
-__device__ __forceinline__ uint32_t lane_right(uint32_t old, uint32_t v) {    // lane i <- lane i+1, lane 63 keeps old
-  return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)v, 0x130, 0xF, 0xF, false);
-}
-
-// one pixel: key <- min(key, max(base, 1 + min4)).  The kernel keeps b <= t for every pixel (pixels
-// that can never change -- seeds, the image border, halo copies -- carry b = t), and under b <= t
-// min(t, max(b, x)) is the median of (b, x, t): v_min_u32, v_min3_u32, v_add_u32, v_med3_u32.
-__device__ __forceinline__ uint32_t med3u(uint32_t a, uint32_t b, uint32_t c) {
-  return max(min(a, b), min(max(a, b), c));
-}
-template <bool TRACK>
-__device__ __forceinline__ void relax_px(uint32_t &t, uint32_t b, uint32_t u, uint32_t d, uint32_t l, uint32_t r, bool &changed) {
-  const uint32_t n = med3u(b, min(min(u, d), min(l, r)) + 1u, t);
-  if (TRACK) changed |= n != t;      // v_cmp + a scalar OR: the flag lives in an SGPR pair
-  t = n;
-}
+// -DWS_TUNING, the queue pass (k_relax, PERSIST): ticks of thread 0 per phase of a tile run, in the kernel's q_ph / q_tp
+#ifdef WS_TUNING
+#define WS_QPHASE(k) do { if (PERSIST && threadIdx.x == 0) { const unsigned long long n_ = __builtin_amdgcn_s_memrealtime(); q_ph[k] += (uint32_t)(n_ - q_tp); q_tp = n_; } } while (0)
+#define WS_QPHASE0 do { if (PERSIST && threadIdx.x == 0) q_tp = __builtin_amdgcn_s_memrealtime(); } while (0)
+#else
+#define WS_QPHASE(k) do {} while (0)
+#define WS_QPHASE0 do {} while (0)
+#endif
 
 // element p of a u32 plane, or bit p of a bit plane
 __device__ __forceinline__ uint32_t plane_or_bit(const uint32_t *src, size_t p, int bits) {
   return bits ? (src[p >> 5] >> (p & 31u)) & 1u : src[p];
 }
 
-typedef uint32_t patch_t[RX_P][RX_P];
-
-// The image bytes of a patch (one dword per row) -> the pixels' bases: (level << 24) | 1, or KEY_INF for a level that never
-// opens.  With the default maximum level, 254 (lib.rs:942), only byte 255 never opens, and (255 << 24) | 1 lies ABOVE every
-// stamp: the `b = min(b, t)` that follows every load pins such a pixel at its stamp by itself -- no compare, no select, and
-// the byte comes into place with one shift and one and-or (7 cycles per pixel instead of 16.5: these kernels are bound by
-// vector issue, profiles/r3_v0_issue_counters.json).  Called AFTER the loop that loads the rows, with its one (kernel
-// uniform) branch outside the row loop: a branch between two rows' loads makes every row a memory round trip of its own
-// (pass 0: 168 -> 189 us, measured).
-__device__ __forceinline__ void patch_bases(const uint32_t (&iv)[RX_P], patch_t &B, uint32_t max_level) {
-  if (max_level == 254u) {
-#pragma unroll
-    for (int r = 0; r < RX_P; ++r) {
-      B[r][0] = (iv[r] << 24) | 1u;
-      B[r][1] = ((iv[r] << 16) & 0xFF000000u) | 1u;
-      B[r][2] = ((iv[r] << 8) & 0xFF000000u) | 1u;
-      B[r][3] = (iv[r] & 0xFF000000u) | 1u;
-    }
-  } else {
-#pragma unroll
-    for (int r = 0; r < RX_P; ++r)
-#pragma unroll
-      for (int c = 0; c < RX_P; ++c) {
-        const uint32_t v = (iv[r] >> (8 * c)) & 0xFFu;
-        B[r][c] = v <= max_level ? ((v << 24) | 1u) : KEY_INF;
-      }
-  }
-}
-
-// A sweep walks the patch rows (or columns) in its direction and, inside a row, the pixels left to right
-// (top to bottom), every pixel seeing its neighbours as they are NOW -- Gauss-Seidel all the way.  (Any
-// order is a valid relaxation; taking a row's "old" left/right values instead cost 40 register copies
-// per round.)
-template <bool TRACK, bool DOWN>
-__device__ __forceinline__ void sweep_rows(patch_t &T, const patch_t &B, const uint32_t (&up)[RX_P], const uint32_t (&dn)[RX_P],
-                                           const uint32_t (&L)[RX_P], const uint32_t (&R)[RX_P], bool &changed) {
-#pragma unroll
-  for (int k = 0; k < RX_P; ++k) {
-    const int r = DOWN ? k : RX_P - 1 - k;
-#pragma unroll
-    for (int c = 0; c < RX_P; ++c)
-      relax_px<TRACK>(T[r][c], B[r][c], r == 0 ? up[c] : T[r - 1][c], r == RX_P - 1 ? dn[c] : T[r + 1][c],
-                      c == 0 ? L[r] : T[r][c - 1], c == RX_P - 1 ? R[r] : T[r][c + 1], changed);
-  }
-}
-template <bool TRACK, bool RIGHT>
-__device__ __forceinline__ void sweep_cols(patch_t &T, const patch_t &B, const uint32_t (&up)[RX_P], const uint32_t (&dn)[RX_P],
-                                           const uint32_t (&L)[RX_P], const uint32_t (&R)[RX_P], bool &changed) {
-#pragma unroll
-  for (int k = 0; k < RX_P; ++k) {
-    const int c = RIGHT ? k : RX_P - 1 - k;
-#pragma unroll
-    for (int r = 0; r < RX_P; ++r)
-      relax_px<TRACK>(T[r][c], B[r][c], r == 0 ? up[c] : T[r - 1][c], r == RX_P - 1 ? dn[c] : T[r + 1][c],
-                      c == 0 ? L[r] : T[r][c - 1], c == RX_P - 1 ? R[r] : T[r][c + 1], changed);
-  }
-}
+// Stamp words of the SAME-GRID passes (relax_todo, read_same): pass + 1 in the low bits, and
+constexpr uint32_t ST_BORDER = 0x40000000u;      // a border pixel of the tile inside this quadrant changed
+constexpr uint32_t ST_SELF = 0x80000000u;        // (word 0) the tile stopped at its round cap: it goes on itself
+constexpr uint32_t ST_PASS = 0x3FFFFFFFu;
 
 // Which tiles of the chunk starting at `first` have to run in this pass?  Lane k answers for tile
 // first + k; the ballot is the to-do list.  tilesX x tilesY is this pass's grid, otherX x otherY the
 // grid of the previous pass.
-// Stamp words of the SAME-GRID passes (below): pass + 1 in the low bits, and
-constexpr uint32_t ST_BORDER = 0x40000000u;      // a border pixel of the tile inside this quadrant changed
-constexpr uint32_t ST_SELF = 0x80000000u;        // (word 0) the tile stopped at its round cap: it goes on itself
-constexpr uint32_t ST_PASS = 0x3FFFFFFFu;
-constexpr uint32_t RX_CAND = 64;      // candidates a workgroup collects before it hands them in (k_relax, append_flush)
-// tile_list header: [0 .. 3] list lengths and [4 .. 7] entry tickets of pass & 3 (a launch clears the words of pass + 2)
-constexpr uint32_t RL_HDR = 192;
-// ... and, for the persistent tile-queue pass (k_relax, PERSIST): [8] tiles queued or running, [9] "the queue has run dry" (1) or
-// "a worker ran out of its time budget" (2), [10] tile runs (diagnostics)
-constexpr uint32_t RLQ_PHASE = 16;      // -DWS_TUNING: ticks of thread 0 per phase of a tile run, summed (load, rounds, epilogue, hand-in)
-// Every word that all workers hammer sits on a 128-byte line of its own: head, tail, pending and the end flag in ONE line
-// were ~100 atomics and polls per microsecond on one L2 channel, and an atomic round trip took 3 us (a tile run 49 us
-// instead of 15).
-constexpr uint32_t RLQ_HEAD = 32, RLQ_TAIL = 64, RLQ_PENDING = 96, RLQ_DONE = 128;
-constexpr uint32_t RLQ_RUNS = 10, RLQ_WAIT = 11, RLQ_LIFE = 12, RLQ_POLLS = 13;      // (11-13: all workers' waiting / life time in 10 ns ticks, polls)
-// A worker gives up -- and tells the others to -- when the launch has lasted this long (s_memrealtime ticks of 10 ns): no spin
-// of this kernel can outlive it, whatever goes wrong with the queue.  What is left undone is work for the passes that follow.
-constexpr unsigned long long RLQ_BUDGET_TICKS = 5000000ull;      // 50 ms; a smooth 8192^2 map needs 3
-// PERSIST == 2, the queue in flood order: a worker takes a tile from the LOWEST non-empty of PQ_B buckets; a tile's bucket is the
-// level (>> pq_shift) of the smallest stamp waiting at its borders.  tools/sim_tile_schedule.c (SIM_QUEUE=prio): on an 8192^2
-// map of correlation length 64 px first-come order needs 152 k tile runs, this order 87 k with 32 buckets (86 k with 256):
-// a tile that waits until the flood below it has passed runs once on final borders instead of once per arrival.
-//   state   one word per tile: bit 31 running; bits 0 .. 30 "a stamp of bucket b waits" (idle: 0).  A tile that is not running and
-//           has bits set is queued: its bit is set in the bitmap of its lowest bucket;
-//   bucket  a bitmap over the tiles (idempotent: no ring, no overflow, no lap) and a count of its set bits; the 31 counts and a
-//           copy of the end flag share ONE 128-byte line, so that a worker's look at all of them is one memory request (a line
-//           per count: 32 requests per look, and the idle workers' looks alone slowed every tile load from 4 us to 21).
-//           A stale bit (its tile runs, or has run from a lower bucket) costs a failed claim or one idle run.
-constexpr int PQ_B = 31;
-constexpr uint32_t PQ_RUNNING = 0x80000000u;
-constexpr uint32_t PQ_HDR = 32;      // the counts' line: [b] set bits of bucket b, [31] the end flag again
-__host__ __device__ inline size_t pq_base(uint32_t list_cap) { return (RL_HDR + 3 * (size_t)list_cap + 64 + 31) & ~(size_t)31; }
-__host__ __device__ inline uint32_t pq_words_per_bucket(uint32_t tiles) { return ((tiles + 31u) / 32u + 255u) & ~255u; }      // whole 1 KiB chunks: one load of a wave
-__host__ __device__ inline uint32_t pq_shift_of(uint32_t max_level) { return 24u + (max_level >= 124u ? 3u : max_level >= 62u ? 2u : max_level >= 31u ? 1u : 0u); }
-
-// Stamp accesses of the persistent pass: tiles hand their border pixels to each other INSIDE a launch, across CUs and XCDs,
-// so every stamp is stored write-through and loaded past L1 at agent scope (global_store / global_load ... sc1;
-// MI355X_MICROARCH.md, inter-workgroup visibility).  Inline assembly, because HIP's agent-scope atomic loads are 8 bytes at
-// most and each is waited for on its own: 24 dependent round trips per lane and tile run (52 us per run against 12).  The
-// loads below are issued back to back and waited for ONCE (the wait's operands tie the loaded registers to it, so that no use
-// can be scheduled in front of it).
-__device__ __forceinline__ void coh_load4(u32x4_t &v, const uint32_t *p) {
-  asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(v) : "v"(p) : "memory");
-}
-__device__ __forceinline__ void coh_load1(uint32_t &v, const uint32_t *p) {
-  asm volatile("global_load_dword %0, %1, off sc1" : "=v"(v) : "v"(p) : "memory");
-}
-__device__ __forceinline__ void coh_store4(uint32_t *p, u32x4_t v) {
-  asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(p), "v"(v) : "memory");
-}
-
 template <int TW, int TH>
 __device__ __forceinline__ unsigned long long relax_todo(int first, int stride, int chunk, int H, int W, int tilesX, int tilesY, int otherX,
                                                          int otherY, int shifted, uint32_t pass,
@@ -403,19 +288,111 @@ __device__ __forceinline__ void scan_cols_both(patch_t &T, const patch_t &B, uin
   // and the checked sweep's)
 }
 
-// PERSIST (the first same-grid pass of a long-range flood, relax_pass): ONE launch instead of a pass per step of the flood
-// front.  The workgroups -- all resident -- pull tiles from a queue; a tile run that changes a side that matters to a
-// neighbour, or stops at its round cap, puts that neighbour (itself) back into the queue, at once: no pass barrier, so the
-// critical path is the chain of tile runs along the flood instead of the slowest tile of each of ~180 launches.
-//   queue   a ring of (sequence number, tile) pairs in the two entry arrays of tile_list; head = the ticket word, tail = the
-//           length word of this pass; a worker draws a ticket and waits for ITS entry (the sequence number tells it from the
-//           ring's previous lap);
-//   state   one word per tile (the "queued" marks): bit 0 queued -- or, while bit 1 is set, "flagged again while running" --,
-//           bit 1 running.  A tile is in the queue at most once, and a tile flagged while it runs queues itself when it ends;
-//   end     [RLQ_PENDING] counts tiles queued or running; who brings it to zero raises [RLQ_DONE].
-// Exactness does not rest on any of this: stamps only ever fall, by relaxation steps from upper bounds (a stale read is an
-// older, larger stamp: less progress, never a wrong value), and the pass AFTER this launch runs every tile once from an
-// all-tiles list -- the flood is at its fixpoint when the ordinary passes that follow say so.
+// ---- the pieces of a tile run that k_relax, k_relax0_tall and k_relax_strips_tall share -------------------------------------
+//
+// PH: rows of a lane's patch (ws_relax_patch.hpp).  A vector that a piece changes goes in by value and comes back as its
+// result: as a u32x4_t & it changed what the callers compile to (the paragraph "Four blocks of a tile run are NOT here",
+// after seed_stamps, has the figures of everything that could not be shared).
+constexpr int SEAM_PY = RX_NW * RX_P, SEAM_PX = RX_TW;      // the grid whose seams are repaired and whose tiles are flagged: 256 x 32
+
+// What every launch does first: the first wave of workgroup 0 clears the next pass's convergence slot, and thread 0 the length
+// and the ticket of the tile list that pass + 2 counts up from (this launch reads the list of `pass` and may append to the
+// list of pass + 1; k_relax_list appends only after this launch has ended).
+__device__ __forceinline__ void launch_prologue(const PassFlags &pf, uint32_t *tile_list, uint32_t pass) {
+  if (blockIdx.x == 0 && threadIdx.x < NSTRIPE)
+    pf.edge_changed[((pass + 1) % COUNTER_RING) * FLAG_SLOT + threadIdx.x * STRIPE_STRIDE] = 0;
+  if (tile_list && blockIdx.x == 0 && threadIdx.x == 0) { tile_list[(pass + 2) & 3u] = 0u; tile_list[4 + ((pass + 2) & 3u)] = 0u; }
+}
+
+// Does tile (tx, ty) of a launch with one tile per workgroup have anything to do?  (Workgroup uniform.)
+template <int SEAM, int SEAM_PITCH, int TW, int TH>
+__device__ __forceinline__ bool tile_has_work(int tx, int ty, int H, int W, int shifted, int otherX, int otherY, uint32_t pass,
+                                              const uint32_t *stamps_prev, const uint32_t *stamps_cur, const PassFlags &pf) {
+  // (a seam whose tiles on both sides have asked for a re-run already -- pass 0 stopped at its round cap there: a smooth
+  // map -- is left to them: on such maps the repair would be 64 us of sweeps that the re-runs undo)
+  if (SEAM == 1) {
+    if (tx * TW >= W || (ty + 1) * SEAM_PITCH >= H) return false;
+    // (a tile that asked for its re-run is work for pass 2: this pass must not look like a fixpoint to the host -- pass 0
+    // cannot say so itself, its launch clears this pass's convergence slot)
+    const int fy = (ty + 1) * (SEAM_PITCH / SEAM_PY) - 1;
+    const bool fa = stamps_cur[((size_t)fy * otherX + tx + 1) * 4 + 2] == pass + 1, fb = stamps_cur[((size_t)(fy + 1) * otherX + tx + 1) * 4 + 2] == pass + 1;
+    if ((fa || fb) && threadIdx.x == 0) pf.edge_changed[(pass % COUNTER_RING) * FLAG_SLOT + (blockIdx.x % NSTRIPE) * STRIPE_STRIDE] = 1u;
+    if (fa && fb) return false;
+  } else if (SEAM == 2) {
+    if (ty * TH - (shifted ? TH / 2 : 0) >= H || (tx * 32 + 1) * SEAM_PX >= W) return false;
+    const int l = threadIdx.x & 63;
+    const int sxl = (tx * 32 + (l >> 1) + 1) * SEAM_PX;
+    const bool settled = sxl >= W || stamps_cur[((size_t)((ty * TH) / SEAM_PY) * otherX + (sxl / SEAM_PX - 1 + (l & 1)) + 1) * 4 + 2] == pass + 1;
+    if (__builtin_amdgcn_ballot_w64(settled) == ~0ull) return false;
+  }
+  else if (tx * TW - (shifted ? TW / 2 : 0) >= W || ty * TH - (shifted ? TH / 2 : 0) >= H) return false;
+  if (SEAM == 0 && pass != 0) {       // the same test as relax_todo, on scalars
+    bool run = false;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int qx = q & 1, qy = q >> 1;
+      const int oi = tx + qx - (shifted ? 1 : 0), oj = ty + qy - (shifted ? 1 : 0);
+      const bool ok = oi >= 0 && oi < otherX && oj >= 0 && oj < otherY;
+      const size_t ot = (size_t)(ok ? oj : 0) * otherX + (ok ? oi : 0);
+      const uint32_t st = stamps_prev[ot * 4 + (3 - q)];
+      run |= ok && st == pass;
+    }
+    if (!run) return false;
+  }
+  return true;
+}
+
+// Seed bits (or labels) as loaded -> stamps: seed = coloured pixel = stamp 0, everything else never coloured.
+// col: the lane's halo column; halo_row: its four pixels of the tile's halo row (returned).
+template <int PH>
+__device__ __forceinline__ u32x4_t seed_stamps(uint32_t (&T)[PH][RX_P], uint32_t (&col)[PH], u32x4_t halo_row) {
+#pragma unroll
+  for (int r = 0; r < PH; ++r) {
+#pragma unroll
+    for (int c = 0; c < RX_P; ++c) T[r][c] = T[r][c] ? 0u : KEY_INF;
+    col[r] = col[r] ? 0u : KEY_INF;
+  }
+  halo_row.x = halo_row.x ? 0u : KEY_INF; halo_row.y = halo_row.y ? 0u : KEY_INF;
+  halo_row.z = halo_row.z ? 0u : KEY_INF; halo_row.w = halo_row.w ? 0u : KEY_INF;
+  return halo_row;
+}
+
+// Four blocks of a tile run are NOT here and stay written out in each of the three kernels: the border and slice-wall masks,
+// the band rows' way through sRow (publish and fetch), the end-of-round vote on s_flag, and the patch write-back with its
+// ring-carry test.  As __forceinline__ functions over the patch by reference each of them changed the register allocation
+// of the kernels that call it (product build; profiles/relax_kernel_resources.txt has the parent's table):
+//   band rows + vote   plain k_relax variants 68 -> 80 VGPRs with 1 - 13 spilled, occupancy 7 -> 6; k_relax0_tall 109 -> 128
+//                      VGPRs with 51 - 54 spilled; k_relax_strips_tall 96 - 113 spilled;
+//   write-back         plain variants 75 - 80 VGPRs, the chunked variant 6 -> 18 spilled, k_relax0_tall 109 -> 121 VGPRs;
+//   masks              of the resources only SGPRs moved (+2 .. +10, SGPR spills -22 .. +15), but every variant's instruction
+//                      count did (-199 .. +143 over the forms tried); with the masks and a row form of `matters` shared,
+//                      the headline median of three alternating runs lay 1.0 % under the range of the parent's three.
+// Also tried for rows, vote and write-back: the rows passed by value as u32x4_t (k_relax0_tall 127 VGPRs; new spills in
+// the strips, the chunked and the scan variants), the patch by non-const reference, the vector built element by element.
+// In the tall kernels rows and vote ARE lambdas, as in the parent.  A macro -- the same tokens in the kernel, so the same
+// code in k_relax at least -- was not tried and is the obvious next attempt.  The optimised IR shows the
+// patch rows as <4 x i32> values from load to store in the failing forms (the 16-byte stores pull them together); why a
+// function brings that about and the same statements written in the kernel do not is not established.  A change to one
+// of the four is a change in three places until the kernels have registers to spare.
+
+// A changed border pixel only MATTERS to the tile across the border when it can lower the pixel it touches there:
+// new stamp + 1 < that pixel's stamp -- which this tile holds, as its halo.  (The halo is as old as the tile's load: the
+// pixel can only have fallen since, so the test errs on the side of flagging.)  On smooth maps a third to a half of the
+// late tile runs changed nothing at all (tools/sim_tile_schedule.c, SIM_CHANGED): flagged by a neighbour whose front
+// had not caught up with theirs.
+__device__ __forceinline__ bool matters(uint32_t before, uint32_t now, uint32_t across) { return before != now && now + 1u < across; }
+
+// profiling only: striped counters, one per 64-byte line -- tile runs in quarter tiles of 256 x 32 (a 256 x 8 band is one;
+// ws_segment.hip divides), and their rounds
+__device__ __forceinline__ void count_tile_run(const PassFlags &pf, uint32_t stripe, uint32_t quarter_tiles, uint32_t rounds) {
+  if (pf.stats) {
+    atomicAdd(&pf.stats[stripe], quarter_tiles);
+    atomicAdd(&pf.stats[FLAG_SLOT + stripe], rounds);
+  }
+}
+
+// ---- k_relax: the ordinary tile run, the bands (SEAM 1), the 32-row strips (SEAM 2), and the workers of the tile queue
+// (PERSIST 1: first come, PERSIST 2: in flood order; ws_relax_queue.hpp) ------------------------------------------------------
 template <int NW, bool CHUNKED, bool SCAN, bool LITE, bool SPLIT = false, int SEAM = 0, int PERSIST = 0, int SEAM_PITCH = 32>
 __global__ __launch_bounds__(64 * NW, SCAN ? 4 : 6) void k_relax(      // the scan variant trades occupancy (few tiles run there) for registers
 const uint8_t *__restrict__ img, size_t img_stride, uint32_t *keys,
@@ -444,7 +421,7 @@ const uint8_t *__restrict__ img, size_t img_stride, uint32_t *keys,
   // flag of every 256 x 32 tile that holds a pixel next to a changed outer row or column of it.  (otherX: that array's pitch.)
   // (SEAM_PITCH, SEAM 1: rows between two horizontal seams -- 64 after pass 0 on 256 x 64 tiles, k_relax0_tall.  The flags
   // stay those of the 256 x 32 tiles: seam row 64 (ty + 1) is the border between tile rows seam_fy and seam_fy + 1.)
-  constexpr int SEAM_PY = 32, SEAM_PX = 256, SEAM_HALF = SEAM == 1 ? TH / 2 : 4;
+  constexpr int SEAM_HALF = SEAM == 1 ? TH / 2 : 4;
   static_assert(SEAM_PITCH % SEAM_PY == 0, "a seam is a border of the 256 x 32 grid");
   // row 0: halo above the tile; rows 1+2w / 2+2w: top / bottom row of band w; last row: halo below
   __shared__ __attribute__((aligned(16))) uint32_t sRow[2 * NB + 2][TW];
@@ -467,15 +444,7 @@ const uint8_t *__restrict__ img, size_t img_stride, uint32_t *keys,
   // long-range columns (SCAN): every band's four rows of a column as one clamped increment (lo, hi)
   __shared__ __attribute__((aligned(16))) uint32_t sFn[2][SCAN ? NB : 1][2][SCAN ? TW : 4];
 
-
-  // the first wave of workgroup 0 clears the next pass's convergence slot
-  if (blockIdx.x == 0 && threadIdx.x < NSTRIPE)
-    pf.edge_changed[((pass + 1) % COUNTER_RING) * FLAG_SLOT + threadIdx.x * STRIPE_STRIDE] = 0;
-  // ... and the length of the next pass's tile list (k_relax_list appends to it after this launch has ended)
-  // (tile_list: [0..3] list lengths of pass & 3; [4 ...) entries of the even passes, then of the odd ones, then one
-  // "queued for pass" word per tile.  This launch reads the list of `pass`, may append to the list of pass + 1, and clears
-  // the length that pass + 2 will count up from.)
-  if (tile_list && blockIdx.x == 0 && threadIdx.x == 0) { tile_list[(pass + 2) & 3u] = 0u; tile_list[4 + ((pass + 2) & 3u)] = 0u; }
+  launch_prologue(pf, tile_list, pass);
   // (XCD-aware: consecutive workgroups go to different XCDs; see xcd_span_index)
   // A chunk is `chunk` tiles one grid size apart, not neighbours: on a smooth map the tiles that still
   // run line up along a front, and four neighbours in one workgroup ran one after the other.
@@ -485,35 +454,21 @@ const uint8_t *__restrict__ img, size_t img_stride, uint32_t *keys,
   // list mode (late passes of a long-range flood): the tiles to run were compacted by k_relax_list; workgroup b takes
   // entries b, b + gridDim.x, ... -- no workgroup is launched for a tile that has nothing to do, none owns two busy ones
   uint32_t entry = blockIdx.x, n_entries = 0, first_entry = 0, runs_done = 0;
-  // PERSIST: the queue (see above)
-  unsigned long long *q_ring = reinterpret_cast<unsigned long long *>(tile_list + RL_HDR);      // list_cap entries: (sequence + 1) << 32 | tile
-  uint32_t *q_state = tile_list + RL_HDR + 2 * (size_t)list_cap;
-  uint32_t *q_head = tile_list + RLQ_HEAD, *q_tail = tile_list + RLQ_TAIL;
-  uint32_t *q_pending = tile_list + RLQ_PENDING, *q_done = tile_list + RLQ_DONE;
+  // PERSIST: the queue (ws_relax_queue.hpp)
+  const RelaxQueue q = relax_queue(tile_list, list_cap, (uint32_t)(tilesX * tilesY), max_level);
   __shared__ uint32_t s_qtile, s_qbucket, s_handoff;
   __shared__ uint32_t s_sidemin[4];      // PERSIST == 2: the smallest new stamp that matters across the top / bottom / left / right border
-  uint32_t *pq_avail = tile_list + pq_base(list_cap);
-  const uint32_t pq_bw = pq_words_per_bucket((uint32_t)(tilesX * tilesY));
-  uint32_t *pq_bits = pq_avail + PQ_HDR;
-  const uint32_t pq_shift = pq_shift_of(max_level);
   unsigned long long q_t0 = 0;
   uint32_t q_wait = 0, q_polls = 0;
 #ifdef WS_TUNING
   uint32_t q_ph[4] = {0, 0, 0, 0};
-  unsigned long long q_tp = 0;
-#define WS_QPHASE(k) do { if (PERSIST && threadIdx.x == 0) { const unsigned long long n_ = __builtin_amdgcn_s_memrealtime(); q_ph[k] += (uint32_t)(n_ - q_tp); q_tp = n_; } } while (0)
-#define WS_QPHASE0 do { if (PERSIST && threadIdx.x == 0) q_tp = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define WS_QPHASE(k) do {} while (0)
-#define WS_QPHASE0 do {} while (0)
-#endif
-#ifdef WS_TUNING
+  unsigned long long q_tp = 0;      // (WS_QPHASE)
   const unsigned long long q_c0 = PERSIST ? __builtin_amdgcn_s_memtime() : 0ull;
 #endif
   if (PERSIST) {
     q_t0 = __builtin_amdgcn_s_memrealtime();
     // whatever this launch does, the passes after it look at every tile again: tell the host that they have to run
-    if (blockIdx.x == 0 && threadIdx.x == 0 && __hip_atomic_load(q_tail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)
+    if (blockIdx.x == 0 && threadIdx.x == 0 && __hip_atomic_load(q.q_tail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)
       pf.edge_changed[(pass % COUNTER_RING) * FLAG_SLOT] = 1u;
   } else if (CHUNKED && use_list) {
     // (the workgroup's first entry is asked for together with the list length, not after it: one memory round trip less
@@ -525,177 +480,14 @@ const uint8_t *__restrict__ img, size_t img_stride, uint32_t *keys,
     todo = relax_todo<TW, TH>(first, stride, chunk, H, W, tilesX, tilesY, otherX, otherY, shifted, pass, stamps_prev, read_same);
     if (todo == 0) return;
   } else if (!PERSIST) {
-    const int tx = first % tilesX, ty = first / tilesX;
-    // (a seam whose tiles on both sides have asked for a re-run already -- pass 0 stopped at its round cap there: a smooth
-    // map -- is left to them: on such maps the repair would be 64 us of sweeps that the re-runs undo)
-    if (SEAM == 1) {
-      if (tx * TW >= W || (ty + 1) * SEAM_PITCH >= H) return;
-      // (a tile that asked for its re-run is work for pass 2: this pass must not look like a fixpoint to the host -- pass 0
-      // cannot say so itself, its launch clears this pass's convergence slot)
-      const int fy = (ty + 1) * (SEAM_PITCH / SEAM_PY) - 1;
-      const bool fa = stamps_cur[((size_t)fy * otherX + tx + 1) * 4 + 2] == pass + 1, fb = stamps_cur[((size_t)(fy + 1) * otherX + tx + 1) * 4 + 2] == pass + 1;
-      if ((fa || fb) && threadIdx.x == 0) pf.edge_changed[(pass % COUNTER_RING) * FLAG_SLOT + (blockIdx.x % NSTRIPE) * STRIPE_STRIDE] = 1u;
-      if (fa && fb) return;
-    } else if (SEAM == 2) {
-      if (ty * TH - (shifted ? TH / 2 : 0) >= H || (tx * 32 + 1) * SEAM_PX >= W) return;
-      const int l = threadIdx.x & 63;
-      const int sxl = (tx * 32 + (l >> 1) + 1) * SEAM_PX;
-      const bool settled = sxl >= W || stamps_cur[((size_t)((ty * TH) / SEAM_PY) * otherX + (sxl / SEAM_PX - 1 + (l & 1)) + 1) * 4 + 2] == pass + 1;
-      if (__builtin_amdgcn_ballot_w64(settled) == ~0ull) return;
-    }
-    else if (tx * TW - (shifted ? TW / 2 : 0) >= W || ty * TH - (shifted ? TH / 2 : 0) >= H) return;
-    if (SEAM == 0 && pass != 0) {       // the same test as relax_todo, on scalars (workgroup uniform)
-      bool run = false;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int qx = q & 1, qy = q >> 1;
-        const int oi = tx + qx - (shifted ? 1 : 0), oj = ty + qy - (shifted ? 1 : 0);
-        const bool ok = oi >= 0 && oi < otherX && oj >= 0 && oj < otherY;
-        const size_t ot = (size_t)(ok ? oj : 0) * otherX + (ok ? oi : 0);
-        const uint32_t st = stamps_prev[ot * 4 + (3 - q)];
-        run |= ok && st == pass;
-      }
-      if (!run) return;
-    }
+    if (!tile_has_work<SEAM, SEAM_PITCH, TW, TH>(first % tilesX, first / tilesX, H, W, shifted, otherX, otherY, pass, stamps_prev, stamps_cur, pf)) return;
   }
   if (threadIdx.x == 0) { s_ncand = 0; if (PERSIST == 2) s_handoff = 0; }      // (read again only after the first tile's barriers)
-  // Wave 0, all lanes: one "queued for pass p" exchange per candidate (a tile enters a list once: whoever finds the old
-  // mark adds it), one ticket for the new entries of all of them.
-  auto append_flush = [&]() {
-    const int lane = threadIdx.x & 63;
-    const uint32_t n = s_ncand;
-    uint32_t *queued = tile_list + RL_HDR + 2 * (size_t)list_cap;
-    uint32_t *next = tile_list + RL_HDR + ((pass + 1) & 1u) * (size_t)list_cap;
-    const uint32_t mark = pass + 1;
-    const bool mine = (uint32_t)lane < n;
-    const uint32_t cand = mine ? s_cand[lane] : 0u;
-    const bool fresh = mine && atomicExch(&queued[cand], mark) != mark;
-    const unsigned long long fm = __builtin_amdgcn_ballot_w64(fresh);
-    if (fm) {
-      uint32_t at = 0;
-      if (lane == 0) at = atomicAdd(&tile_list[(pass + 1) & 3u], (uint32_t)__popcll(fm));
-      at = __shfl(at, 0, 64);
-      if (fresh) next[at + __popcll(fm & ((1ull << lane) - 1ull))] = cand;
-    }
-    if (lane == 0) s_ncand = 0;
-  };
   for (;;) {
+  // which tile
   uint32_t q_tile = 0;
-  if (PERSIST == 2) {
-    if (threadIdx.x < 64 && s_handoff != 0u) {      // (wave uniform) the run before this one took a tile it had announced itself
-      if (threadIdx.x == 0) { s_handoff = 0u; s_sidemin[0] = s_sidemin[1] = s_sidemin[2] = s_sidemin[3] = 0xFFFFFFFFu; }
-    } else if (threadIdx.x < 64) {
-      const int ln = (int)threadIdx.x;
-      const unsigned long long w0 = __builtin_amdgcn_s_memrealtime();
-      const uint32_t nchunk = pq_bw >> 8;
-      uint32_t got = 0, got_b = 0, idle = 0;
-      for (;;) {
-        // one look at every bucket's count (lane b) and at the end flag (lane 63)
-        uint32_t av = 0;
-        if (ln < 32) av = __hip_atomic_load(pq_avail + ln, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (__shfl((int)av, PQ_B, 64) != 0) break;
-        const unsigned long long m = __builtin_amdgcn_ballot_w64(ln < PQ_B && (int)av > 0);
-        // (every turn of this loop checks the clock: whatever goes wrong with counts or bits, the end flag is seen a turn later)
-        if (ln == 0 && __builtin_amdgcn_s_memrealtime() - q_t0 > RLQ_BUDGET_TICKS) {
-          __hip_atomic_store(q_done, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          __hip_atomic_store(pq_avail + PQ_B, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        // A look that ends without a tile -- nothing queued, or somebody else was quicker -- is followed by a pause that grows
-        // with the looks in a row: a thousand workers after the same few bits, each look nine memory requests to the same
-        // nine lines, held every load of the RUNNING tiles up behind them (a tile run 60 us instead of 15).  Work that
-        // appears is found by whoever looks next, so the delay is the pause divided by the number of idle workers.
-        auto pause = [&]() {
-          ++q_polls;
-          ++idle;
-          // ... and with the worker's number: sixteen look every 3 us, forty-eight every 14, the rest every 54 -- a front that
-          // is a chain of tile runs is followed by the worker that runs it (the hand-off at the end of a run), and a backlog
-          // that lasts is found by everybody within one long pause
-          const int reps = (use_list & 2) ? 1 : (blockIdx.x < 16u ? 1 : (blockIdx.x < 64u ? 4 : 16));
-          if (use_list & 4) __builtin_amdgcn_s_sleep(2);
-          else if (idle < 3u) __builtin_amdgcn_s_sleep(8);
-          else if (idle < 6u) __builtin_amdgcn_s_sleep(64);
-          else { for (int z = 0; z < reps; ++z) __builtin_amdgcn_s_sleep(127); }
-        };
-        if (m == 0) { pause(); continue; }
-        const uint32_t b = (uint32_t)__builtin_ctzll(m);
-        uint32_t *bm = pq_bits + (size_t)b * pq_bw;
-        for (uint32_t cc = 0; cc < nchunk; ++cc) {
-          const uint32_t c = (cc + blockIdx.x) % nchunk;      // (workers start in different chunks of a long bitmap)
-          u32x4_t v;
-          coh_load4(v, bm + c * 256u + (uint32_t)ln * 4u);
-          asm volatile("s_waitcnt vmcnt(0)" : "+v"(v) : : "memory");
-          unsigned long long mm = __builtin_amdgcn_ballot_w64((v.x | v.y | v.z | v.w) != 0u);
-          if (mm == 0) continue;
-          // workers that look at the same moment take different bits: the k-th lane that has any
-          int k = (int)(blockIdx.x % (uint32_t)__popcll(mm));
-          while (k-- > 0) mm &= mm - 1ull;
-          const int sel = (int)__builtin_ctzll(mm);
-          uint32_t t1 = 0, tb = 0;
-          if (ln == sel) {
-            const int j = v.x ? 0 : (v.y ? 1 : (v.z ? 2 : 3));
-            const uint32_t wv = j == 0 ? v.x : (j == 1 ? v.y : (j == 2 ? v.z : v.w));
-            const uint32_t bit = wv & (0u - wv);
-            const uint32_t wi = c * 256u + (uint32_t)ln * 4u + (uint32_t)j;
-            if (atomicAnd(bm + wi, ~bit) & bit) {      // the bit is mine
-              atomicSub(pq_avail + b, 1u);
-              const uint32_t t = (wi << 5) + (uint32_t)__builtin_ctz(bit);
-              // not running -> running, every waiting bit taken with it: what they announced was stored before they were set,
-              // and this run loads after this exchange.  Running already (a stale bit): that run's end looks at the bits.
-              const uint32_t so = atomicMax(&q_state[t], PQ_RUNNING);
-              if (!(so & PQ_RUNNING)) {
-                if (so == 0u) atomicAdd(q_pending, 1u);      // (a stale bit of an idle tile: it runs once for nothing)
-                t1 = t + 1u;
-                tb = so ? (uint32_t)__builtin_ctz(so) : b;
-              }
-            }
-          }
-          got = (uint32_t)__shfl((int)t1, sel, 64);
-          got_b = (uint32_t)__shfl((int)tb, sel, 64);
-          break;      // taken, or somebody else was quicker: look at the counts again
-        }
-        if (got) break;
-        pause();
-      }
-      if (ln == 0) {
-        q_wait += (uint32_t)(__builtin_amdgcn_s_memrealtime() - w0);
-        s_qtile = got;
-        s_qbucket = got_b;
-        s_sidemin[0] = s_sidemin[1] = s_sidemin[2] = s_sidemin[3] = 0xFFFFFFFFu;
-      }
-    }
-    __syncthreads();
-    q_tile = s_qtile;
-  } else if (PERSIST) {
-    if (threadIdx.x == 0) {
-      unsigned long long v = 0;
-      if (__hip_atomic_load(q_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
-        const unsigned long long w0 = __builtin_amdgcn_s_memrealtime();
-        const uint32_t my = atomicAdd(q_head, 1u);
-        unsigned long long *slot = q_ring + (my % list_cap);
-        for (;;) {
-          v = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if ((uint32_t)(v >> 32) == my + 1u) break;      // my entry (not one of the ring's previous lap)
-          v = 0;
-          ++q_polls;
-          if (__hip_atomic_load(q_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;
-          if (__builtin_amdgcn_s_memrealtime() - q_t0 > RLQ_BUDGET_TICKS) { __hip_atomic_store(q_done, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
-          // an idle worker must not cost the busy ones their memory bandwidth: the first polls come quickly (work usually
-          // arrives within a tile run), later ones every few microseconds
-          // Who is next in line polls quickly (the flood is often a chain of tile runs: this wait is on its critical path);
-          // who is far behind the tail sleeps longer -- an idle worker must not cost the busy ones their memory bandwidth.
-          const uint32_t behind = my - __hip_atomic_load(q_tail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // tickets drawn before mine and not yet filled
-          if (behind < 4u) __builtin_amdgcn_s_sleep(2);
-          else if (behind < 32u) __builtin_amdgcn_s_sleep(24);
-          else __builtin_amdgcn_s_sleep(127);
-        }
-        q_wait += (uint32_t)(__builtin_amdgcn_s_memrealtime() - w0);
-        if (v != 0) atomicExch(q_state + (uint32_t)v, 2u);      // queued -> running: whoever flags it from now on makes it run again
-      }
-      s_qtile = v != 0 ? (uint32_t)v + 1u : 0u;
-    }
-    __syncthreads();
-    q_tile = s_qtile;
-  }
+  if (PERSIST == 2) q_tile = queue_take_flood_order(q, q_t0, q_wait, q_polls, use_list, s_qtile, s_qbucket, s_handoff, s_sidemin);
+  else if (PERSIST) q_tile = queue_take_first_come(q, q_t0, q_wait, q_polls, s_qtile);
   if (PERSIST) {
     if (q_tile == 0) {           // workgroup uniform: the queue has run dry (or the time budget is spent)
       if (threadIdx.x == 0) {
@@ -710,8 +502,9 @@ const uint8_t *__restrict__ img, size_t img_stride, uint32_t *keys,
       break;
     }
   }
-  // re-derived per tile on purpose (the asm hides the value from loop-invariant hoisting): hoisted
-  // per-lane addresses pushed the chunked variant over the 80-VGPR cap and into scratch
+  // re-derived per tile on purpose (the asm hides the value from loop-invariant hoisting): hoisted per-lane addresses
+  // are more registers held across the tile loop, and the chunked variant is past the 80-VGPR cap as it is -- it spills
+  // 6 VGPRs to 28 B/lane of scratch (profiles/relax_kernel_resources.txt)
   int tid = threadIdx.x;
   if (CHUNKED) asm volatile("" : "+v"(tid));
   const int lane = tid & 63;
@@ -828,16 +621,7 @@ const uint8_t *__restrict__ img, size_t img_stride, uint32_t *keys,
     halo_row.z = plane_or_bit(ksrc, (size_t)gy_halo * W + min(max(gx0 + 2, 0), W - 1), seed_bits);
     halo_row.w = plane_or_bit(ksrc, (size_t)gy_halo * W + min(max(gx0 + 3, 0), W - 1), seed_bits);
   }
-  if (from_labels) {
-#pragma unroll
-    for (int r = 0; r < RX_P; ++r) {
-#pragma unroll
-      for (int c = 0; c < RX_P; ++c) T[r][c] = T[r][c] ? 0u : KEY_INF;
-      halo[r] = halo[r] ? 0u : KEY_INF;
-    }
-    halo_row.x = halo_row.x ? 0u : KEY_INF; halo_row.y = halo_row.y ? 0u : KEY_INF;
-    halo_row.z = halo_row.z ? 0u : KEY_INF; halo_row.w = halo_row.w ? 0u : KEY_INF;
-  }
+  if (from_labels) halo_row = seed_stamps(T, halo, halo_row);
   // (bases: only interior pixels with img <= max level can ever be flooded (lib.rs:220-224); everything else, and every
   // seed (stamp 0 < base), is pinned at its current stamp: b = t -- patch_bases above, the border masks and the min below)
   // Workgroup uniform: the tile and its halo ring lie strictly inside the image (and the image is not a stack of
@@ -1064,8 +848,7 @@ const uint8_t *__restrict__ img, size_t img_stride, uint32_t *keys,
     // pixel can only have fallen since, so the test errs on the side of flagging.)  On smooth maps a third to a half of the
     // late tile runs changed nothing at all (tools/sim_tile_schedule.c, SIM_CHANGED): flagged by a neighbour whose front
     // had not caught up with theirs.
-    auto matters = [](uint32_t before, uint32_t now, uint32_t across) { return before != now && now + 1u < across; };
-    auto least = [](uint32_t before, uint32_t now, uint32_t across) { return before != now && now + 1u < across ? now : 0xFFFFFFFFu; };      // (PERSIST == 2: the queue's order)
+    auto least = [](uint32_t before, uint32_t now, uint32_t across) { return matters(before, now, across) ? now : 0xFFFFFFFFu; };      // (PERSIST == 2: the queue's order)
     if (band == 0) {
       const u32x4_t o = *reinterpret_cast<const u32x4_t *>(&sInitRow[0][xl * RX_P]);
       const u32x4_t a = *reinterpret_cast<const u32x4_t *>(&sRow[0][xl * RX_P]);      // the halo row above, as loaded
@@ -1168,7 +951,7 @@ const uint8_t *__restrict__ img, size_t img_stride, uint32_t *keys,
           bk[0] = s_qbucket;
 #pragma unroll
           for (int k = 1; k < 5; ++k) {
-            bk[k] = min(s_sidemin[k - 1] >> pq_shift, (uint32_t)(PQ_B - 1));
+            bk[k] = min(s_sidemin[k - 1] >> q.pq_shift, (uint32_t)(PQ_B - 1));
             if (want[k]) bk[0] = min(bk[0], bk[k]);
           }
 #pragma unroll
@@ -1183,119 +966,18 @@ const uint8_t *__restrict__ img, size_t img_stride, uint32_t *keys,
       }
       pf.any_change[stripe] = 1u;
     }
-    if (pf.stats) {            // profiling only: striped counters, one per 64-byte line
-      atomicAdd(&pf.stats[stripe], (uint32_t)(TW * TH / 2048));      // in quarter tiles: a 256 x 8 band is one, every other tile four (ws_segment.hip divides)
-      atomicAdd(&pf.stats[FLAG_SLOT + stripe], iters);
-    }
+    count_tile_run(pf, stripe, (uint32_t)(TW * TH / 2048), iters);
   }
   WS_STAMP(3);
   WS_QPHASE(2);
+  // hand in (the queue), or the next tile
   if (PERSIST == 2) {
-    __syncthreads();      // thread 0's candidates (s_cand, s_ncand: the append_next block above) are there
-    if (tid < 64) {
-      const uint32_t self = (uint32_t)tile, n = s_ncand;
-      // my own entry (a run that stopped at its round cap) is lane 0's first business: its bit, then "not running any more"
-      // in one more exchange that tells me what was announced while I ran
-      const bool mine = (uint32_t)lane < n;
-      const uint32_t cw = mine ? s_cand[lane] : 0u;
-      const uint32_t cand = cw & 0x00FFFFFFu, cb = cw >> 24;      // (relax_pass: the queue is not used on planes of 2^24 tiles)
-      const bool other = mine && cand != self;
-      // Hand-off: the announced tile of the lowest bucket, if that is no higher than the bucket I ran from (the front I am
-      // following), is MY next tile -- one exchange "not running -> running" instead of its bit, its count, some worker's
-      // look, claim and exchange: five memory round trips off every hop of a flood that is a chain of tile runs.
-      // (Asking the counts instead -- "nothing waits below it", a look issued before the stores -- cost more than it found:
-      // one more request per run to the line every worker's counts live on, 4.98 -> 5.32 ms at correlation 64 px.)
-      uint32_t pick = other && (cb <= s_qbucket || (use_list & 16)) && !(use_list & 8) ? (cb << 8) | (uint32_t)lane : 0xFFFFu;
-#pragma unroll
-      for (int k = 1; k < 8; k <<= 1) pick = min(pick, (uint32_t)__shfl_xor((int)pick, k, 64));      // (candidates sit in lanes 0 .. 4)
-      pick = (uint32_t)__shfl((int)pick, 0, 64);
-      const bool hand = pick != 0xFFFFu && (pick & 0xFFu) == (uint32_t)lane;
-      uint32_t old = 0;
-      bool taken = false;
-      if (hand) {
-        old = atomicMax(&q_state[cand], PQ_RUNNING);
-        taken = !(old & PQ_RUNNING);      // idle (old == 0: mine to count) or queued (its bit goes stale): it is mine now
-      }
-      if (other && !taken) old = atomicOr(&q_state[cand], 1u << cb);
-      // idle: mine to queue (and to count); queued in a higher bucket: mine to queue lower, and its old bit goes;
-      // queued at or below mine: nothing; running: announced, its run's end queues it
-      bool push = other && !taken && !(old & PQ_RUNNING) && (old & ((2u << cb) - 1u)) == 0u;
-      const bool fresh = (push || taken) && old == 0u;
-      if (taken) { s_handoff = 1u; s_qtile = cand + 1u; s_qbucket = cb; }
-      uint32_t pb = cb, pt = cand;
-      uint32_t left = 0;
-      if (lane == 63) {      // (never a candidate's lane: a run announces five tiles at most)
-        const uint32_t c0 = s_cand[0];
-        if (n != 0u && (c0 & 0x00FFFFFFu) == self) atomicOr(&q_state[self], 1u << (c0 >> 24));
-        left = atomicAnd(&q_state[self], ~PQ_RUNNING) & ~PQ_RUNNING;
-        if (left) { push = true; pb = (uint32_t)__builtin_ctz(left); pt = self; }
-      }
-      const uint32_t n_fresh = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(fresh));
-      if (lane == 63) {
-        // counted before anyone can take them; my own run leaves the count in the same add
-        const int net = (int)n_fresh - (left ? 0 : 1);
-        if (net > 0) atomicAdd(q_pending, (uint32_t)net);
-        else if (net < 0 && atomicSub(q_pending, 1u) == 1u) {
-          __hip_atomic_store(q_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          __hip_atomic_store(pq_avail + PQ_B, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        s_ncand = 0;
-#ifdef WS_TUNING
-        atomicAdd(tile_list + RLQ_RUNS, 1u);
-#endif
-      }
-      if (push) {
-        const uint32_t bit = 1u << (pt & 31u);
-        if (!(atomicOr(pq_bits + (size_t)pb * pq_bw + (pt >> 5), bit) & bit)) atomicAdd(pq_avail + pb, 1u);
-        if (pt != self && old != 0u) {      // lowered: the bit of its former bucket
-          const uint32_t ob = (uint32_t)__builtin_ctz(old);
-          if (atomicAnd(pq_bits + (size_t)ob * pq_bw + (pt >> 5), ~bit) & bit) atomicSub(pq_avail + ob, 1u);
-        }
-      }
-    }
+    queue_hand_in_flood_order(q, (uint32_t)tile, tid, lane, use_list, s_cand, s_ncand, s_qtile, s_qbucket, s_handoff);
     WS_QPHASE(3);
     continue;
   }
   if (PERSIST) {
-    __syncthreads();      // thread 0's candidates (s_cand, s_ncand: the append_next block above) are there
-    if (tid < 64) {
-      const uint32_t self = (uint32_t)tile, n = s_ncand;
-      const bool mine = (uint32_t)lane < n;
-      const uint32_t cand = mine ? s_cand[lane] : 0u;
-      // idle -> queued: mine to push; queued already: nothing; running: flagged, it queues itself when it ends
-      const bool fresh = mine && atomicOr(&q_state[cand], 1u) == 0u;
-      const unsigned long long fm = __builtin_amdgcn_ballot_w64(fresh);
-      const uint32_t nf = (uint32_t)__popcll(fm);
-      // my run is over: running -> idle, or -> queued if somebody (I myself, at my round cap) flagged me meanwhile
-      uint32_t again = 0;
-      if (lane == 0) again = atomicAnd(&q_state[self], ~2u) & 1u;
-      again = (uint32_t)__shfl((int)again, 0, 64);
-      const uint32_t total = nf + again;
-      if (total) {
-        uint32_t at = 0;
-        if (lane == 0) {      // counted before anyone can take them; my own run leaves the count in the same add
-          if (total != 1u) atomicAdd(q_pending, total - 1u);
-          at = atomicAdd(q_tail, total);
-        }
-        at = (uint32_t)__shfl((int)at, 0, 64);
-        if (fresh) {
-          const uint32_t idx = at + (uint32_t)__popcll(fm & ((1ull << lane) - 1ull));
-          __hip_atomic_store(q_ring + (idx % list_cap), ((unsigned long long)(idx + 1u) << 32) | cand, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        if (lane == 0 && again) {
-          const uint32_t idx = at + nf;
-          __hip_atomic_store(q_ring + (idx % list_cap), ((unsigned long long)(idx + 1u) << 32) | self, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-      }
-      if (lane == 0) {
-        s_ncand = 0;
-        // nothing queued by me and my run is over: was mine the last tile queued or running?
-        if (total == 0u && atomicSub(q_pending, 1u) == 1u) __hip_atomic_store(q_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#ifdef WS_TUNING
-        atomicAdd(tile_list + RLQ_RUNS, 1u);
-#endif
-      }
-    }
+    queue_hand_in_first_come(q, (uint32_t)tile, tid, lane, s_cand, s_ncand);
     WS_QPHASE(3);
     continue;
   }
@@ -1306,7 +988,7 @@ const uint8_t *__restrict__ img, size_t img_stride, uint32_t *keys,
     ++runs_done;
     const bool last = entry >= n_entries;
     // wave 0 hands the candidates in: when this was the workgroup's last tile, or when another tile's five might not fit
-    if (append_next && tid < 64 && (last || s_ncand > RX_CAND - 5u)) append_flush();
+    if (append_next && tid < 64 && (last || s_ncand > RX_CAND - 5u)) append_flush(tile_list, list_cap, pass, s_cand, s_ncand);
     if (last) break;
   } else {
     todo &= todo - 1;
@@ -1430,7 +1112,7 @@ hipError_t block_flag_border_tiles(hipStream_t s, uint32_t *stamps, int h, int w
 // ---- pass 0 of the seam-repair flow on 256 x 64 tiles --------------------------------------------------------------------
 //
 // Pass 0 of a transform that starts from its seeds and repairs its seams with bands and strips (relax_pass, seam_flow) has
-// its own kernel: the same sweeps as k_relax, but a lane owns 4 columns x 8 rows -- two stacked 4 x 4 patches -- so the
+// its own kernel: the same sweeps and the same pieces as k_relax, but a lane owns 4 columns x 8 rows -- two stacked 4 x 4 patches -- so the
 // tile is 256 x 64 with the same eight waves.  What a tile run pays outside its sweeps (image bytes to bases, seed bits to
 // stamps, addresses, the band rows' way through LDS) is paid once per 32 pixels of a lane instead of once per 16, rows 3
 // and 4 of a patch are neighbours in registers, and the plane has half as many horizontal seams for the bands to repair.
@@ -1443,32 +1125,6 @@ hipError_t block_flag_border_tiles(hipStream_t s, uint32_t *stamps, int h, int w
 //     neither now, and what lies across the border is still in the halo row of LDS / the halo column registers;
 //   * a tile that stops at its round cap marks BOTH 256 x 32 tiles it covers, in the words the bands, the strips and pass 2
 //     read, and all their quadrant flags, as k_relax does for its one.
-typedef uint32_t tall_t[RX0_PH][RX_P];
-
-template <bool TRACK, bool DOWN>
-__device__ __forceinline__ void tall_sweep_rows(tall_t &T, const tall_t &B, const uint32_t (&up)[RX_P], const uint32_t (&dn)[RX_P],
-                                                const uint32_t (&L)[RX0_PH], const uint32_t (&R)[RX0_PH], bool &changed) {
-#pragma unroll
-  for (int k = 0; k < RX0_PH; ++k) {
-    const int r = DOWN ? k : RX0_PH - 1 - k;
-#pragma unroll
-    for (int c = 0; c < RX_P; ++c)
-      relax_px<TRACK>(T[r][c], B[r][c], r == 0 ? up[c] : T[r - 1][c], r == RX0_PH - 1 ? dn[c] : T[r + 1][c],
-                      c == 0 ? L[r] : T[r][c - 1], c == RX_P - 1 ? R[r] : T[r][c + 1], changed);
-  }
-}
-template <bool TRACK, bool RIGHT>
-__device__ __forceinline__ void tall_sweep_cols(tall_t &T, const tall_t &B, const uint32_t (&up)[RX_P], const uint32_t (&dn)[RX_P],
-                                                const uint32_t (&L)[RX0_PH], const uint32_t (&R)[RX0_PH], bool &changed) {
-#pragma unroll
-  for (int k = 0; k < RX_P; ++k) {
-    const int c = RIGHT ? k : RX_P - 1 - k;
-#pragma unroll
-    for (int r = 0; r < RX0_PH; ++r)
-      relax_px<TRACK>(T[r][c], B[r][c], r == 0 ? up[c] : T[r - 1][c], r == RX0_PH - 1 ? dn[c] : T[r + 1][c],
-                      c == 0 ? L[r] : T[r][c - 1], c == RX_P - 1 ? R[r] : T[r][c + 1], changed);
-  }
-}
 
 // (flagAX / flagSX: tile columns of the anchored / shifted 256 x 32 grid, the pitches of stamps_own / stamps_rerun)
 __global__ __launch_bounds__(64 * RX_NW, 4) void k_relax0_tall(const uint8_t *__restrict__ img, uint32_t stride32, uint32_t *keys, int H, int W,
@@ -1481,10 +1137,7 @@ __global__ __launch_bounds__(64 * RX_NW, 4) void k_relax0_tall(const uint8_t *__
   __shared__ __attribute__((aligned(16))) uint32_t sRow[2 * NB + 2][TW];
   __shared__ uint32_t s_flag[3];      // "some lane changed in round k" in slot k % 3 (k_relax)
 
-  // the first wave of workgroup 0 clears the next pass's convergence slot, and the tile list length that pass 2 counts from
-  if (blockIdx.x == 0 && threadIdx.x < NSTRIPE)
-    pf.edge_changed[((pass + 1) % COUNTER_RING) * FLAG_SLOT + threadIdx.x * STRIPE_STRIDE] = 0;
-  if (tile_list && blockIdx.x == 0 && threadIdx.x == 0) { tile_list[(pass + 2) & 3u] = 0u; tile_list[4 + ((pass + 2) & 3u)] = 0u; }
+  launch_prologue(pf, tile_list, pass);
   const int tile = (int)xcd_span_index(blockIdx.x, gridDim.x);      // (XCD-aware: consecutive workgroups go to different XCDs)
   const int tile_x = tile % tilesX, tile_y = tile / tilesX;
   const int x0 = tile_x * TW, y0 = tile_y * TH;
@@ -1494,7 +1147,7 @@ __global__ __launch_bounds__(64 * RX_NW, 4) void k_relax0_tall(const uint8_t *__
   if (tid == 0) { s_flag[0] = 0; s_flag[1] = 0; s_flag[2] = 0; }
 
   // ---- load phase: unconditional loads on clamped addresses; a patch (W % 4 == 0) is wholly inside the plane or wholly outside
-  tall_t T, B;
+  uint32_t T[RX0_PH][RX_P], B[RX0_PH][RX_P];
   uint32_t Lh[RX0_PH], Rh[RX0_PH];
   const bool dims24 = (uint32_t)W < (1u << 24) && (uint32_t)H < (1u << 24);      // kernel uniform: row * W as v_mul_u32_u24
   const uint32_t gxc0 = (uint32_t)min(gx0, W - RX_P);
@@ -1522,34 +1175,9 @@ __global__ __launch_bounds__(64 * RX_NW, 4) void k_relax0_tall(const uint8_t *__
     const uint32_t p = (dims24 ? __umul24(gy_halo, (uint32_t)W) : gy_halo * (uint32_t)W) + gxc0;
     const uint32_t nib = seed_mask[p >> 5] >> (p & 31u);
     halo_row = u32x4_t{nib & 1u, nib & 2u, nib & 4u, nib & 8u};
-    // image bytes -> bases, as patch_bases: the one (kernel uniform) branch outside the loop that loads the rows
-    if (max_level == 254u) {
-#pragma unroll
-      for (int r = 0; r < RX0_PH; ++r) {
-        B[r][0] = (iv[r] << 24) | 1u;
-        B[r][1] = ((iv[r] << 16) & 0xFF000000u) | 1u;
-        B[r][2] = ((iv[r] << 8) & 0xFF000000u) | 1u;
-        B[r][3] = (iv[r] & 0xFF000000u) | 1u;
-      }
-    } else {
-#pragma unroll
-      for (int r = 0; r < RX0_PH; ++r)
-#pragma unroll
-        for (int c = 0; c < RX_P; ++c) {
-          const uint32_t v = (iv[r] >> (8 * c)) & 0xFFu;
-          B[r][c] = v <= max_level ? ((v << 24) | 1u) : KEY_INF;
-        }
-    }
+    patch_bases(iv, B, max_level);
   }
-  // seed = stamp 0, everything else never coloured
-#pragma unroll
-  for (int r = 0; r < RX0_PH; ++r) {
-#pragma unroll
-    for (int c = 0; c < RX_P; ++c) T[r][c] = T[r][c] ? 0u : KEY_INF;
-    Lh[r] = Lh[r] ? 0u : KEY_INF;
-  }
-  halo_row.x = halo_row.x ? 0u : KEY_INF; halo_row.y = halo_row.y ? 0u : KEY_INF;
-  halo_row.z = halo_row.z ? 0u : KEY_INF; halo_row.w = halo_row.w ? 0u : KEY_INF;
+  halo_row = seed_stamps(T, Lh, halo_row);
   // Workgroup uniform: the tile and its halo ring lie strictly inside the image (and the image is not a stack of slices) --
   // none of the masks below can bite (k_relax)
   const bool inner = SH == H && x0 >= 1 && x0 + TW <= W - 1 && y0 >= 1 && y0 + TH <= H - 1;
@@ -1580,7 +1208,7 @@ __global__ __launch_bounds__(64 * RX_NW, 4) void k_relax0_tall(const uint8_t *__
     for (int c = 0; c < RX_P; ++c) B[r][c] = min(B[r][c], T[r][c]);      // b <= t: seeds and everything that can never change are pinned
     Rh[r] = Lh[r];
   }
-  // the columns left / right of the patch, persistent: lane 0 / lane 63 keep the tile's halo column (k_relax)
+  // the columns left / right of the patch, persistent: lane 0 / lane 63 keep the tile's halo column (k_relax, refresh_columns)
   auto refresh_columns = [&]() {
 #pragma unroll
     for (int r = 0; r < RX0_PH; ++r) {
@@ -1614,18 +1242,18 @@ __global__ __launch_bounds__(64 * RX_NW, 4) void k_relax0_tall(const uint8_t *__
       bool untracked = false;
       fetch_rows();
       refresh_columns();
-      tall_sweep_rows<false, true>(T, B, up, dn, Lh, Rh, untracked);       // down
+      sweep_rows<false, true>(T, B, up, dn, Lh, Rh, untracked);       // down
       refresh_columns();
-      tall_sweep_cols<false, true>(T, B, up, dn, Lh, Rh, untracked);       // right
+      sweep_cols<false, true>(T, B, up, dn, Lh, Rh, untracked);       // right
       refresh_columns();
-      tall_sweep_rows<false, false>(T, B, up, dn, Lh, Rh, untracked);      // up
+      sweep_rows<false, false>(T, B, up, dn, Lh, Rh, untracked);      // up
       publish_rows();
       __syncthreads();
     }
     bool changed = false;
     fetch_rows();
     refresh_columns();
-    tall_sweep_cols<true, false>(T, B, up, dn, Lh, Rh, changed);           // left, checked
+    sweep_cols<true, false>(T, B, up, dn, Lh, Rh, changed);           // left, checked
     const uint32_t slot = (iters - 1) % 3;
     if (__builtin_amdgcn_ballot_w64(changed) != 0) {
       publish_rows();      // a neighbour band reads these rows only if another round follows, i.e. only if someone changed
@@ -1655,21 +1283,21 @@ __global__ __launch_bounds__(64 * RX_NW, 4) void k_relax0_tall(const uint8_t *__
   if (ovf) atomicExch(pf.overflow, 1u);      // never taken on sane inputs
   const uint32_t stripe = (blockIdx.x % NSTRIPE) * STRIPE_STRIDE;
   // A changed border pixel matters to the tile across the border when it can lower the pixel it touches there, which this
-  // tile holds as its halo (k_relax).  Changed: neither a seed (0) nor still KEY_INF, which `now + 1 < across` implies.
-  auto matters = [](uint32_t now, uint32_t across) { return now != 0u && now + 1u < across; };
+  // tile holds as its halo (`matters`).  No copy of the border as loaded is kept: a border pixel starts as a seed (0, for ever) or at
+  // KEY_INF, so "before" is 0 -- changed: neither a seed nor still KEY_INF, which `now + 1 < across` implies.
   bool edge = false;
   if (band == 0) {
     const u32x4_t a = *reinterpret_cast<const u32x4_t *>(&sRow[0][lane * RX_P]);      // the halo row above, as loaded
-    edge |= matters(T[0][0], a.x) || matters(T[0][1], a.y) || matters(T[0][2], a.z) || matters(T[0][3], a.w);
+    edge |= matters(0u, T[0][0], a.x) || matters(0u, T[0][1], a.y) || matters(0u, T[0][2], a.z) || matters(0u, T[0][3], a.w);
   }
   if (band == NB - 1) {
     const u32x4_t a = *reinterpret_cast<const u32x4_t *>(&sRow[2 * NB + 1][lane * RX_P]);      // the halo row below
     constexpr int l = RX0_PH - 1;
-    edge |= matters(T[l][0], a.x) || matters(T[l][1], a.y) || matters(T[l][2], a.z) || matters(T[l][3], a.w);
+    edge |= matters(0u, T[l][0], a.x) || matters(0u, T[l][1], a.y) || matters(0u, T[l][2], a.z) || matters(0u, T[l][3], a.w);
   }
   if (lane == 0 || lane == 63) {
 #pragma unroll
-    for (int r = 0; r < RX0_PH; ++r) edge |= matters(T[r][lane == 0 ? 0 : 3], lane == 0 ? Lh[r] : Rh[r]);      // (Lh of lane 0, Rh of lane 63: the halo column)
+    for (int r = 0; r < RX0_PH; ++r) edge |= matters(0u, T[r][lane == 0 ? 0 : 3], lane == 0 ? Lh[r] : Rh[r]);      // (Lh of lane 0, Rh of lane 63: the halo column)
   }
   // plain, idempotent stores into striped words: no same-address atomics on the tile path
   if (edge) pf.edge_changed[(pass % COUNTER_RING) * FLAG_SLOT + stripe] = 1u;
@@ -1689,10 +1317,7 @@ __global__ __launch_bounds__(64 * RX_NW, 4) void k_relax0_tall(const uint8_t *__
       pf.edge_changed[(pass % COUNTER_RING) * FLAG_SLOT + stripe] = 1u;
     }
     pf.any_change[stripe] = 1u;
-    if (pf.stats) {            // profiling only: a 256 x 64 run counts as two tile runs (eight quarter tiles) of `iters` rounds each
-      atomicAdd(&pf.stats[stripe], (uint32_t)(TW * TH / 2048));
-      atomicAdd(&pf.stats[FLAG_SLOT + stripe], 2u * iters);
-    }
+    count_tile_run(pf, stripe, (uint32_t)(TW * TH / 2048), 2u * iters);      // a 256 x 64 run counts as two tile runs of `iters` rounds each
   }
 }
 
@@ -1717,7 +1342,6 @@ __global__ __launch_bounds__(64 * RX_NW, 4) void k_relax_strips_tall(const uint8
                                                                      int stripsX, int flagSX, uint32_t max_level, uint32_t pass, uint32_t *stamps_cur,
                                                                      PassFlags pf, uint32_t max_iters, int SH, int check_carry, uint32_t *tile_list) {
   constexpr int NB = RX_NW, TW = RX_TW, TH = RX0_TH;
-  constexpr int SEAM_PY = RX_NW * RX_P, SEAM_PX = RX_TW;      // the grid whose tiles are flagged: 256 x 32
   // row 0: halo above the slice; rows 1+2w / 2+2w: top / bottom row of band w; last row: halo below
   __shared__ __attribute__((aligned(16))) uint32_t sRow[2 * NB + 2][TW];
   __shared__ __attribute__((aligned(16))) uint32_t sInitRow[2][TW];      // the slice's first and last row as loaded
@@ -1726,10 +1350,7 @@ __global__ __launch_bounds__(64 * RX_NW, 4) void k_relax_strips_tall(const uint8
   __shared__ uint64_t s_sum[64 * NB];      // per-lane patch checksum taken at load time (k_relax)
   __shared__ uint32_t sInitCol[RX0_PH][64 * NB];      // every lane's outer column as loaded (parked: the sweeps need the registers)
 
-  // as every launch of k_relax: the next pass's convergence slot and the tile list length that pass + 2 counts from
-  if (blockIdx.x == 0 && threadIdx.x < NSTRIPE)
-    pf.edge_changed[((pass + 1) % COUNTER_RING) * FLAG_SLOT + threadIdx.x * STRIPE_STRIDE] = 0;
-  if (tile_list && blockIdx.x == 0 && threadIdx.x == 0) { tile_list[(pass + 2) & 3u] = 0u; tile_list[4 + ((pass + 2) & 3u)] = 0u; }
+  launch_prologue(pf, tile_list, pass);
   const int tile = (int)xcd_span_index(blockIdx.x, gridDim.x);
   const int tile_x = tile % stripsX, tile_y = tile / stripsX;
   const int y0 = tile_y * TH;
@@ -1755,7 +1376,7 @@ __global__ __launch_bounds__(64 * RX_NW, 4) void k_relax_strips_tall(const uint8
   if (tid == 0) { s_edges = 0; s_flag[0] = 0; s_flag[1] = 0; s_flag[2] = 0; }
 
   // ---- load phase: unconditional loads on clamped addresses; a patch (W % 4 == 0) is wholly inside the plane or wholly outside
-  tall_t T, B;
+  uint32_t T[RX0_PH][RX_P], B[RX0_PH][RX_P];
   uint32_t halo[RX0_PH];      // the column outside this lane's side of the strip: left of the even lane, right of the odd one
   const uint32_t gxc0 = (uint32_t)min(gx0, W - RX_P);
   const int xh_raw = (lane & 1) ? gx0 + RX_P : gx0 - 1;
@@ -1777,24 +1398,7 @@ __global__ __launch_bounds__(64 * RX_NW, 4) void k_relax_strips_tall(const uint8
     halo_row = *reinterpret_cast<const u32x4_t *>(keys + (size_t)gy_halo * W + gxc0);
 #pragma unroll
     for (int r = 0; r < RX0_PH; ++r) { T[r][0] = kv[r].x; T[r][1] = kv[r].y; T[r][2] = kv[r].z; T[r][3] = kv[r].w; }
-    // image bytes -> bases, as patch_bases: the one (kernel uniform) branch outside the loop that loads the rows
-    if (max_level == 254u) {
-#pragma unroll
-      for (int r = 0; r < RX0_PH; ++r) {
-        B[r][0] = (iv[r] << 24) | 1u;
-        B[r][1] = ((iv[r] << 16) & 0xFF000000u) | 1u;
-        B[r][2] = ((iv[r] << 8) & 0xFF000000u) | 1u;
-        B[r][3] = (iv[r] & 0xFF000000u) | 1u;
-      }
-    } else {
-#pragma unroll
-      for (int r = 0; r < RX0_PH; ++r)
-#pragma unroll
-        for (int c = 0; c < RX_P; ++c) {
-          const uint32_t v = (iv[r] >> (8 * c)) & 0xFFu;
-          B[r][c] = v <= max_level ? ((v << 24) | 1u) : KEY_INF;
-        }
-    }
+    patch_bases(iv, B, max_level);
   }
   {
     // pixels outside the plane never hold a stamp, pixels of the image border and of a slice wall never change (k_relax)
@@ -1878,18 +1482,18 @@ __global__ __launch_bounds__(64 * RX_NW, 4) void k_relax_strips_tall(const uint8
       bool untracked = false;
       fetch_rows();
       refresh_columns();
-      tall_sweep_rows<false, true>(T, B, up, dn, Lh, Rh, untracked);       // down
+      sweep_rows<false, true>(T, B, up, dn, Lh, Rh, untracked);       // down
       refresh_columns();
-      tall_sweep_cols<false, true>(T, B, up, dn, Lh, Rh, untracked);       // right
+      sweep_cols<false, true>(T, B, up, dn, Lh, Rh, untracked);       // right
       refresh_columns();
-      tall_sweep_rows<false, false>(T, B, up, dn, Lh, Rh, untracked);      // up
+      sweep_rows<false, false>(T, B, up, dn, Lh, Rh, untracked);      // up
       publish_rows();
       __syncthreads();
     }
     bool changed = false;
     fetch_rows();
     refresh_columns();
-    tall_sweep_cols<true, false>(T, B, up, dn, Lh, Rh, changed);           // left, checked
+    sweep_cols<true, false>(T, B, up, dn, Lh, Rh, changed);           // left, checked
     const uint32_t slot = (iters - 1) % 3;
     if (__builtin_amdgcn_ballot_w64(changed) != 0) {
       publish_rows();      // a neighbour band reads these rows only if another round follows, i.e. only if someone changed
@@ -1937,7 +1541,6 @@ __global__ __launch_bounds__(64 * RX_NW, 4) void k_relax_strips_tall(const uint8
   // loaded it (`matters`; the neighbour can only have fallen since, so the test errs on the side of flagging).  A slice at
   // its cap is no fixpoint: both tile rows on both sides of every seam of it run again and examine all its pixels.  Slice
   // ends lie on rows 64 k and 64 k + 63 only -- the rows 64 k + 32 are interior rows now, as they are in pass 0's tiles.
-  auto matters = [](uint32_t before, uint32_t now, uint32_t across) { return before != now && now + 1u < across; };
   if (has_seam) {
     const uint32_t mark = pass + 1;
     bool col = unfinished;
@@ -1968,10 +1571,7 @@ __global__ __launch_bounds__(64 * RX_NW, 4) void k_relax_strips_tall(const uint8
     // plain, idempotent stores into striped words: no same-address atomics on the tile path
     if (ed & 1u) pf.edge_changed[(pass % COUNTER_RING) * FLAG_SLOT + stripe] = 1u;
     if (ed) pf.any_change[stripe] = 1u;
-    if (pf.stats) {            // profiling only: a 64-row slice counts as two of 32 rows (eight quarter tiles) of `iters` rounds each
-      atomicAdd(&pf.stats[stripe], (uint32_t)(TW * TH / 2048));
-      atomicAdd(&pf.stats[FLAG_SLOT + stripe], 2u * iters);
-    }
+    count_tile_run(pf, stripe, (uint32_t)(TW * TH / 2048), 2u * iters);      // a 64-row slice counts as two of 32 rows of `iters` rounds each
   }
 }
 

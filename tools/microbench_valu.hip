@@ -5,12 +5,13 @@
 // measures, per instruction kind and per occupancy (1..8 waves per SIMD):
 //   * independent streams of v_add_u32 / v_min_u32 / v_min3_u32 / v_med3_u32 / v_mov_b32_dpp (wave_shr:1): lane-ops/s of the
 //     whole chip and cycles per wave-instruction per SIMD;
-//   * the relaxation's own inner loop (ws_relax.hip: relax_px on a 4 x 4 register patch, sweeps down / right / up / left
+//   * the relaxation's own inner loop (ws_relax_patch.hpp: relax_px on a 4 x 4 register patch, sweeps down / right / up / left
 //     with the DPP column refresh, Gauss-Seidel dependencies and all): pixel updates/s -- the ceiling a tile run's sweeps
 //     can reach when nothing else (loads, LDS rows, barriers, flags) is in the way.
-// Build: hipcc --offload-arch=gfx950 -O3 -o tools/_build/microbench_valu tools/microbench_valu.hip
+// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -Irustronomy-watershed_amd/csrc -o tools/_build/microbench_valu tools/microbench_valu.hip
 // Run (GPU box): tools/_build/microbench_valu > gpurun_out/valu.txt
 #include <hip/hip_runtime.h>
+#include "ws_relax_patch.hpp"
 #include <cstdio>
 #include <cstdlib>
 #include <cstdint>
@@ -54,37 +55,8 @@ __global__ __launch_bounds__(256) void k_stream(uint32_t *out, int iters, uint32
   if (s == 0x12345678u) out[threadIdx.x] = s;
 }
 
-// ---- the relaxation's inner loop, as in ws_relax.hip (relax_px, sweep_rows, sweep_cols, refresh_columns) -----------------
-__device__ __forceinline__ uint32_t med3u(uint32_t a, uint32_t b, uint32_t c) { return max(min(a, b), min(max(a, b), c)); }
-__device__ __forceinline__ uint32_t lane_left(uint32_t old, uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)v, 0x138, 0xF, 0xF, false); }
-__device__ __forceinline__ uint32_t lane_right(uint32_t old, uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)v, 0x130, 0xF, 0xF, false); }
-template <bool TRACK>
-__device__ __forceinline__ void relax_px(uint32_t &t, uint32_t b, uint32_t u, uint32_t d, uint32_t l, uint32_t r, bool &changed) {
-  const uint32_t n = med3u(b, min(min(u, d), min(l, r)) + 1u, t);
-  if (TRACK) changed |= n != t;
-  t = n;
-}
-typedef uint32_t patch_t[4][4];
-template <bool TRACK, bool DOWN>
-__device__ __forceinline__ void sweep_rows(patch_t &T, const patch_t &B, const uint32_t (&up)[4], const uint32_t (&dn)[4], const uint32_t (&L)[4], const uint32_t (&R)[4], bool &ch) {
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int r = DOWN ? k : 3 - k;
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-      relax_px<TRACK>(T[r][c], B[r][c], r == 0 ? up[c] : T[r - 1][c], r == 3 ? dn[c] : T[r + 1][c], c == 0 ? L[r] : T[r][c - 1], c == 3 ? R[r] : T[r][c + 1], ch);
-  }
-}
-template <bool TRACK, bool RIGHT>
-__device__ __forceinline__ void sweep_cols(patch_t &T, const patch_t &B, const uint32_t (&up)[4], const uint32_t (&dn)[4], const uint32_t (&L)[4], const uint32_t (&R)[4], bool &ch) {
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int c = RIGHT ? k : 3 - k;
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      relax_px<TRACK>(T[r][c], B[r][c], r == 0 ? up[c] : T[r - 1][c], r == 3 ? dn[c] : T[r + 1][c], c == 0 ? L[r] : T[r][c - 1], c == 3 ? R[r] : T[r][c + 1], ch);
-  }
-}
+// ---- the relaxation's inner loop: the engine's own relax_px, sweep_rows, sweep_cols and lane shifts (ws_relax_patch.hpp) ------
+using namespace wsk;
 
 // rounds of (down, right, up, checked left) on a register patch; `up` / `dn` stay what they were (in the engine they come
 // from LDS once per round): 64 pixel updates per lane and round
