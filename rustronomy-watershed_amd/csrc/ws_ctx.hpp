@@ -114,7 +114,8 @@ struct ws_ctx {
     }
   };
   GraphKey graph_key, seen_key;      // of graph_exec / of the previous transform
-  // the per-level loop of transform_to_list / the merging final labels, captured in groups of levels (merge_host)
+  // the per-level loop of transform_to_list / the merging final labels / transform_history, captured in groups of levels
+  // (level_run, a stage of merge_host: ws_lists.hip; the loop's mode: ws_level_plan.hpp)
   struct ListKey {
     bool merging = false, want_list = false;
     uint32_t levels = 0;

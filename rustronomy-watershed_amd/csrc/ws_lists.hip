@@ -1,6 +1,7 @@
 // ws_lists.hip -- the merging drivers (lib.rs:1328-1522) and transform_to_list (lib.rs:1551-1561, 1837-1847): per-level
 // unions over seed colours, lake areas and sparse lake records (kernels: ws_merge.hip).
 #include "ws_ctx.hpp"
+#include "ws_level_plan.hpp"
 
 using namespace wsapi;
 
@@ -62,79 +63,94 @@ int ensure_uf(ws_ctx *c, size_t n_colours) {
 // (an even spread would be pixels / 255 per level) and the kernels stride
 unsigned level_grid(size_t n_px) { return (unsigned)std::min<size_t>(std::max<size_t>(n_px / (256 * 64), 8), 2048); }
 
-// Levels [l0, l1) of the per-level driver shared by the merging hook and both transform_to_list flavours; launches only.
-//   merging: union this level's crossing edges (lib.rs:1449-1466 in closed form)
-//   want_sizes: keep per-lake areas (lib.rs:628-635)
-//   per_level(l): called after level l is queued (device state current on c->stream)
-//   fused (merging lists without a hook): the records of level l - 1 ride in the launch that joins level l's edges
-//   (k_union_emit; ws_merge.hip) -- two launches per level instead of three; the caller emits the last level
-struct FusedEmit {
-  bool on = false;
-  size_t n_colours = 0, cap = 0;
-  uint64_t *lakes = nullptr;
-  bool live = false;           // many colours: records from the list of LIVE lakes (ws_merge.hip) instead of a look at every colour per level
-  unsigned emit_grid = 0;      // workgroups of the live-list walk
+// A job that no entry point builds is refused before anything runs (level_job_refusal, ws_level_plan.hpp)
+int check_job(ws_ctx *c, const LevelJob &job) {
+  if (const char *why = level_job_refusal(job)) return fail(c, WS_ERR_BAD_ARG, why);
+  return WS_OK;
+}
+
+// What the stages of merge_host hand on to each other (one per call, never copied: opt may point into it)
+struct LevelRun {
+  ws_options plain{};                  // the arrival form's options: the plane as it stands
+  const ws_options *opt = nullptr;
+  size_t ph = 0, pw = 0, n = 0;        // the (padded) plane
+  const uint32_t *keys = nullptr, *seg = nullptr;      // the flood's arrival stamps and segmenting labels
+  LevelPlan plan;
+  uint32_t levels = 0;
+  unsigned grid = 0;                   // workgroups of the per-level kernels
+  unsigned emit_grid = 0;              // ... and of the live-list walk
+  uint64_t *records = nullptr;         // (colour, area) pairs on the device: the context's buffer, or the caller's
+  const uint8_t *himg = nullptr;       // the image the hook is shown
+  std::vector<uint64_t> bounds;        // bucket bounds of the arriving pixels and of the crossing edges
 };
-//   history_hook (transform_history): the unions also stamp the merge forest (hook parents here, death levels in uf_death); nothing else
-template <class F>
-int level_range(ws_ctx *c, uint32_t l0, uint32_t l1, bool merging, bool want_sizes, unsigned grid, F per_level, const FusedEmit &fe = FusedEmit(),
-                uint32_t *history_hook = nullptr) {
-  uint32_t *parent = (uint32_t *)c->uf_parent.p, *size = (uint32_t *)c->uf_size.p, *hooked = (uint32_t *)c->uf_hooked.p;
+
+// The hook of level l: the level's plane to the host (device state current on c->stream), then the caller's function
+int level_hook(ws_ctx *c, const LevelJob &job, const LevelRun &r, uint32_t l) {
+  uint32_t *parent = (uint32_t *)c->uf_parent.p;
+  uint64_t *d_out64 = (uint64_t *)c->out64.p;
+  const size_t n = r.n;
+  if (host_copy_in_chunks(c, n)) {      // the level's plane as u32 (in the u64 buffer, which that path leaves alone), widened by host threads
+    if (job.merging) HIP_TRY(c, relabel_u32(c->stream, r.keys, r.seg, parent, (uint32_t *)d_out64, n, l));
+    else HIP_TRY(c, snapshot_level_u32(c->stream, r.keys, r.seg, (uint32_t *)d_out64, n, l));
+    if (int rc_copy = labels_to_host_u64(c, (const uint32_t *)d_out64, c->host64.data(), n)) return rc_copy;
+  } else {
+    if (job.merging) HIP_TRY(c, relabel_u64(c->stream, r.keys, r.seg, parent, d_out64, n, l));
+    else HIP_TRY(c, snapshot_level(c->stream, r.keys, r.seg, d_out64, n, l));
+    HIP_TRY(c, hipMemcpyAsync(c->host64.data(), d_out64, n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  job.cb(job.user, (uint8_t)l, r.opt->max_water_level, r.himg, c->host64.data(), r.ph, r.pw);        // lib.rs:1510-1518
+  return WS_OK;
+}
+
+// Levels [l0, l1) of the per-level driver shared by the merging hook, both transform_to_list flavours and transform_history:
+// the plan's steps, level by level; launches only, unless a hook is called.
+int level_range(ws_ctx *c, const LevelJob &job, const LevelRun &r, uint32_t l0, uint32_t l1) {
+  uint32_t *parent = (uint32_t *)c->uf_parent.p, *size = (uint32_t *)c->uf_size.p, *death = (uint32_t *)c->uf_death.p;
+  uint32_t *hooked = r.plan.hooked_list ? (uint32_t *)c->uf_hooked.p : nullptr;
+  uint2 *sd = (uint2 *)c->uf_sd.p;
+  uint32_t *alive = (uint32_t *)c->alive.p;
   u64c *mf = (u64c *)c->mflags.p;
   uint32_t *hooked_count = (uint32_t *)(mf + MF_HOOKED);
   const uint32_t *px_items = (const uint32_t *)c->px_items.p;
   const uint2 *edge_items = (const uint2 *)c->edge_items.p;
-  for (uint32_t l = l0; l < l1; ++l) {
-    if (history_hook) {
-      HIP_TRY(c, union_stamped_ranged(c->stream, edge_items, mf + MF_OFF_ED + l, grid, parent, (uint32_t *)c->uf_death.p, history_hook, l));
-      int rc = per_level(l);
-      if (rc) return rc;
-      continue;
-    }
-    if (fe.on && !fe.live) {
-      HIP_TRY(c, union_emit(c->stream, edge_items, mf + MF_OFF_ED + l, grid, parent, hooked, hooked_count + l, (uint32_t *)c->uf_death.p, l,
-                            size, fe.n_colours, fe.lakes, fe.cap, mf + MF_LAKE_COUNT));
-      HIP_TRY(c, fold_and_add_ranged(c->stream, hooked, hooked_count + l, px_items, mf + MF_OFF_PX + l, grid, parent, size));
-      int rc = per_level(l);
-      if (rc) return rc;
-      continue;
-    }
-    if (fe.on) {
-      // lists without a hook, many colours: areas and death levels live side by side in uf_sd, level l - 1's records are found among level
-      // l - 2's live lakes, and the arrivals of a level are added up per wave and workgroup before they reach a lake's counter
-      static const bool split = tuning_env("WS_TOLIST_SPLIT") != nullptr;      // A/B knob for tools/: the two jobs as launches of their own
-      HIP_TRY(c, union_emit_alive(c->stream, edge_items, mf + MF_OFF_ED + l, grid, parent, hooked, hooked_count + l, (uint2 *)c->uf_sd.p, l,
-                                  fe.n_colours, (uint32_t *)c->alive.p, split ? 0u : fe.emit_grid, fe.lakes, fe.cap, mf + MF_LAKE_COUNT));
-      if (split && l > 0)
-        HIP_TRY(c, emit_alive(c->stream, (const uint2 *)c->uf_sd.p, fe.n_colours, (uint32_t *)c->alive.p, fe.emit_grid, fe.lakes, fe.cap, mf + MF_LAKE_COUNT, l - 1));
-      HIP_TRY(c, fold_and_add_sd(c->stream, hooked, hooked_count + l, px_items, mf + MF_OFF_PX + l, grid, parent, (uint2 *)c->uf_sd.p));
-      int rc = per_level(l);
-      if (rc) return rc;
-      continue;
-    }
-    if (merging) HIP_TRY(c, union_edges_ranged(c->stream, edge_items, mf + MF_OFF_ED + l, grid, parent, want_sizes ? hooked : nullptr, hooked_count + l));
-    // areas of the nodes hooked in this level move to their roots, arriving pixels are counted: one launch
-    if (want_sizes) HIP_TRY(c, fold_and_add_ranged(c->stream, merging ? hooked : nullptr, hooked_count + l, px_items, mf + MF_OFF_PX + l, grid, parent, size));
-    int rc = per_level(l);
-    if (rc) return rc;
-  }
+  const size_t n_colours = job.n_seeds + 1, cap = job.cap;
+  const unsigned grid = r.grid;
+  for (uint32_t l = l0; l < l1; ++l)
+    for (int i = 0; i < r.plan.n_steps; ++i)
+      switch (r.plan.steps[i]) {
+        case LevelStep::UNION_STAMPED:
+          HIP_TRY(c, union_stamped_ranged(c->stream, edge_items, mf + MF_OFF_ED + l, grid, parent, death, (uint32_t *)c->uf_hook.p, l));
+          break;
+        case LevelStep::UNION_EMIT:
+          HIP_TRY(c, union_emit(c->stream, edge_items, mf + MF_OFF_ED + l, grid, parent, hooked, hooked_count + l, death, l, size, n_colours, r.records, cap,
+                                mf + MF_LAKE_COUNT));
+          break;
+        case LevelStep::UNION_EMIT_ALIVE:
+          HIP_TRY(c, union_emit_alive(c->stream, edge_items, mf + MF_OFF_ED + l, grid, parent, hooked, hooked_count + l, sd, l, n_colours, alive,
+                                      r.plan.split_emit ? 0u : r.emit_grid, r.records, cap, mf + MF_LAKE_COUNT));
+          break;
+        case LevelStep::EMIT_ALIVE_PREV:
+          if (l > 0) HIP_TRY(c, emit_alive(c->stream, sd, n_colours, alive, r.emit_grid, r.records, cap, mf + MF_LAKE_COUNT, l - 1));
+          break;
+        case LevelStep::UNION_EDGES:
+          HIP_TRY(c, union_edges_ranged(c->stream, edge_items, mf + MF_OFF_ED + l, grid, parent, hooked, hooked_count + l));
+          break;
+        case LevelStep::FOLD_ADD:
+          HIP_TRY(c, fold_and_add_ranged(c->stream, hooked, hooked_count + l, px_items, mf + MF_OFF_PX + l, grid, parent, size));
+          break;
+        case LevelStep::FOLD_ADD_SD:
+          HIP_TRY(c, fold_and_add_sd(c->stream, hooked, hooked_count + l, px_items, mf + MF_OFF_PX + l, grid, parent, sd));
+          break;
+        case LevelStep::EMIT_LAKES:      // offsets are prefix sums of the record counts, taken on the host
+          HIP_TRY(c, emit_lakes(c->stream, parent, size, n_colours, r.records, cap, mf + MF_LAKE_COUNT, l));
+          break;
+        case LevelStep::HOOK:
+          if (int rc = level_hook(c, job, r, l)) return rc;
+          break;
+      }
   return WS_OK;
 }
-
-// dev (nullable): the device-resident form (ws_transform_to_list_device) -- image and u32 seed pairs are already in HBM and
-// the lake records stay there, in the caller's buffer; only the per-level offsets and uncoloured counts go to the host
-struct DeviceLists {
-  const uint8_t *d_img;
-  const uint32_t *d_seeds_rc;
-  ws_lake *d_lakes;
-  // the arrival form (ws_lists_from_arrival_device): the segmenting transform has been run elsewhere -- its stamps and labels
-  // are all the per-level paths read; no image, no seed list, h x w is the plane as it stands
-  const uint32_t *d_keys = nullptr, *d_seg = nullptr;
-  // ... of a stack of slices of slice_h rows whose labels restart at 1 in every slice: colour c of slice k is c + d_slice_base[k]
-  // (ws_transform_to_list_batch_device)
-  int slice_h = 0;
-  const uint32_t *d_slice_base = nullptr;
-};
 
 // Records [from, end) of the device array d_rec into the host's `lakes`, on stream `on` (returns with the copy complete when the
 // chunked road is taken; otherwise queued).  A piece of two million records and more (2048^2 planes on) crosses the bus as u32 --
@@ -156,107 +172,95 @@ int records_to_host(ws_ctx *c, const ws_lake *d_rec, ws_lake *lakes, size_t from
   }
   return WS_OK;
 }
-int merge_host(ws_ctx *c, bool merging, const uint8_t *img, size_t h, size_t w, size_t stride, const uint64_t *seeds_rc,
-               size_t n_seeds, const ws_options *opt, ws_level_cb cb, void *user, uint64_t *out_labels,
-               ws_lake *lakes, size_t cap, size_t *n_lakes, uint64_t *offsets, uint64_t *uncoloured, const DeviceLists *dev = nullptr,
-               bool history = false) {      // history: no lists, no hook; merging: unions that stamp the merge forest (the planes are rendered afterwards)
-  if (!c) return WS_ERR_BAD_ARG;
-  size_t ph, pw;
-  const bool from_arrival = dev && dev->d_keys;
-  ws_options plain;
-  if (from_arrival) { plain = *opt; plain.edge_correction = 0; opt = &plain; }      // the plane as it stands
-  int rc = check_plane(c, h, w, stride, opt, &ph, &pw);
+
+// ---- merge_host: the per-level driver, stage by stage (the job and its plan: ws_level_plan.hpp) --------------------------------------
+
+// Source: the plane checked, the inputs on the device, the flood.  Yields r.keys and r.seg.
+int level_source(ws_ctx *c, const LevelJob &job, LevelRun &r) {
+  const bool from_arrival = job.source == LevelSource::ARRIVAL;
+  r.opt = job.opt;
+  if (from_arrival) { r.plain = *job.opt; r.plain.edge_correction = 0; r.opt = &r.plain; }      // the plane as it stands
+  const ws_options *opt = r.opt;
+  int rc = check_plane(c, job.h, job.w, job.stride, opt, &r.ph, &r.pw);
   if (rc) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
-  const size_t n = ph * pw;
-  const bool want_list = n_lakes != nullptr;
+  const size_t ph = r.ph, pw = r.pw, n = ph * pw, n_seeds = job.n_seeds;
+  r.n = n;
   const uint8_t *d_img = nullptr;
   size_t d_stride = 0;
   const uint32_t *d_seeds = nullptr;
   if (!from_arrival && (rc = ensure(c, c->labels, (n ? n : 1) * sizeof(uint32_t)))) return rc;
-  if (!dev && (rc = ensure(c, c->out64, (n ? n : 1) * sizeof(uint64_t)))) return rc;
+  if (job.source == LevelSource::HOST && (rc = ensure(c, c->out64, (n ? n : 1) * sizeof(uint64_t)))) return rc;
   stats_begin(c);
-  if (from_arrival) {
-    if (n_seeds >= 0xFFFFFFFFull) return fail(c, WS_ERR_TOO_LARGE, "too many seeds");
-  } else if (dev) {
-    if (n_seeds >= 0xFFFFFFFFull) return fail(c, WS_ERR_TOO_LARGE, "too many seeds");
-    d_img = dev->d_img;
-    d_stride = stride;
-    if (opt->edge_correction && h * w == 0 && (rc = empty_image_block(c, &d_img, &d_stride, h, w))) return rc;
-    if ((rc = shifted_seeds(c, dev->d_seeds_rc, n_seeds, opt, &d_seeds))) return rc;
-  } else if ((rc = stage_inputs(c, img, h, w, stride, seeds_rc, n_seeds, opt, ph, pw, &d_img, &d_stride, &d_seeds))) return rc;
-  const uint32_t *seg = from_arrival ? dev->d_seg : (const uint32_t *)c->labels.p;
-  uint64_t *d_out64 = (uint64_t *)c->out64.p;
+  switch (job.source) {
+    case LevelSource::ARRIVAL:
+      if (n_seeds >= 0xFFFFFFFFull) return fail(c, WS_ERR_TOO_LARGE, "too many seeds");
+      break;
+    case LevelSource::DEVICE:
+      if (n_seeds >= 0xFFFFFFFFull) return fail(c, WS_ERR_TOO_LARGE, "too many seeds");
+      d_img = job.d_img;
+      d_stride = job.stride;
+      if (opt->edge_correction && job.h * job.w == 0 && (rc = empty_image_block(c, &d_img, &d_stride, job.h, job.w))) return rc;
+      if ((rc = shifted_seeds(c, job.d_seeds_rc, n_seeds, opt, &d_seeds))) return rc;
+      break;
+    case LevelSource::HOST:
+      if ((rc = stage_inputs(c, job.img, job.h, job.w, job.stride, job.seeds_rc, n_seeds, opt, ph, pw, &d_img, &d_stride, &d_seeds))) return rc;
+      break;
+  }
+  r.seg = from_arrival ? job.d_seg : (const uint32_t *)c->labels.p;
   // the flood itself is the segmenting one (same coloured set, same arrival stamps: lib.rs:1394-1438 == 1704-1748)
   if (!from_arrival && (rc = run_fused(c, d_img, d_stride, (int)ph, (int)pw, opt->max_water_level, d_seeds, n_seeds, (uint32_t *)c->labels.p, opt->edge_correction != 0))) return rc;
-  const uint32_t *keys = from_arrival ? dev->d_keys : (const uint32_t *)c->keys.p;
-  if (history && !merging) return stats_end(c);      // the segmenting history is the flood's stamps and labels: nothing per level
-  // every buffer first, so that nothing moves once launches (or captured graphs) hold its address
+  r.keys = from_arrival ? job.d_keys : (const uint32_t *)c->keys.p;
+  return WS_OK;
+}
+
+// Prepare: every buffer first, so that nothing moves once launches (or captured graphs) hold its address; then the buckets, the
+// union-find and the mode's start state.
+int level_prepare(ws_ctx *c, const LevelJob &job, LevelRun &r) {
+  int rc;
+  const size_t n = r.n, n_seeds = job.n_seeds;
   if ((rc = ensure_uf(c, n_seeds + 1))) return rc;
-  if (history && (rc = ensure(c, c->uf_hook, (n_seeds + 1) * sizeof(uint32_t)))) return rc;
-  // Planes with a million colours and more (4096^2 random fields on) write their lake records from the list of the lakes
-  // still alive, not from a look at every colour at every level (8192^2: 66.8 -> 20.5 ms); below that the per-level
-  // launches are latency-bound either way and the older, shorter kernels win (1024^2, the core_bench shape: 3.8 against 5.0 ms).
-  // (ws_ctx_set_live_list_min_colours: tests lower the threshold to cover the form on small planes)
-  const bool live_lists = merging && want_list && !cb && n_seeds >= c->live_list_min;
-  if (live_lists) {
+  if (r.plan.ensure_hook && (rc = ensure(c, c->uf_hook, (n_seeds + 1) * sizeof(uint32_t)))) return rc;
+  if (r.plan.ensure_live) {
     if ((rc = ensure(c, c->uf_sd, (n_seeds + 1) * sizeof(uint2)))) return rc;
     if ((rc = ensure(c, c->alive, 2 * alive_list_words(n_seeds + 1) * sizeof(uint32_t)))) return rc;
   }
-  if (want_list && !dev && (rc = ensure(c, c->lakes, (cap ? cap : 1) * 2 * sizeof(uint64_t)))) return rc;
-  uint64_t *d_records = dev ? (uint64_t *)dev->d_lakes : (uint64_t *)c->lakes.p;      // (colour, area) pairs
-  if ((rc = build_buckets(c, keys, seg, (int)ph, (int)pw, dev ? dev->slice_h : 0, dev ? dev->d_slice_base : nullptr))) return rc;
-  uint32_t *parent = (uint32_t *)c->uf_parent.p;
-  u64c *mf = (u64c *)c->mflags.p;
-  HIP_TRY(c, uf_init(c->stream, parent, (uint32_t *)c->uf_size.p, n_seeds + 1));
-  const uint8_t *himg = cb ? hook_image(c, img, h, w, stride, opt->edge_correction) : nullptr;
-  if (cb) c->host64.resize(n ? n : 1);
-  const uint32_t levels = (uint32_t)opt->max_water_level + 1;
-  const unsigned grid = level_grid(n);
-
-  // merging lists without a hook: level l's records are written by the launch that joins level l + 1's edges
-  FusedEmit fe;
-  fe.on = merging && want_list && !cb;
-  fe.n_colours = n_seeds + 1; fe.cap = cap; fe.lakes = d_records;
-  fe.live = live_lists;
-  if (fe.on && fe.live) {
-    fe.emit_grid = (unsigned)std::min<size_t>(std::max<size_t>((n_seeds + 4095) / 4096, 1), 1024);
-    HIP_TRY(c, sd_init(c->stream, (uint2 *)c->uf_sd.p, n_seeds + 1));      // no pixels yet, every colour a root
-  } else if (fe.on || history) {
-    HIP_TRY(c, hipMemsetAsync(c->uf_death.p, 0xFF, (n_seeds + 1) * sizeof(uint32_t), c->stream));      // every colour a root
+  if (job.lists() && !job.device_records() && (rc = ensure(c, c->lakes, (job.cap ? job.cap : 1) * 2 * sizeof(uint64_t)))) return rc;
+  r.records = job.device_records() ? (uint64_t *)job.d_lakes : (uint64_t *)c->lakes.p;
+  if ((rc = build_buckets(c, r.keys, r.seg, (int)r.ph, (int)r.pw, job.slice_h, job.d_slice_base))) return rc;
+  HIP_TRY(c, uf_init(c->stream, (uint32_t *)c->uf_parent.p, (uint32_t *)c->uf_size.p, n_seeds + 1));
+  r.himg = job.cb ? hook_image(c, job.img, job.h, job.w, job.stride, r.opt->edge_correction) : nullptr;
+  if (job.cb) c->host64.resize(n ? n : 1);
+  r.levels = (uint32_t)r.opt->max_water_level + 1;
+  r.grid = level_grid(n);
+  if (r.plan.sd_init) {
+    r.emit_grid = (unsigned)std::min<size_t>(std::max<size_t>((n_seeds + 4095) / 4096, 1), 1024);
+    HIP_TRY(c, sd_init(c->stream, (uint2 *)c->uf_sd.p, n_seeds + 1));
+  } else if (r.plan.death_all_ones) {
+    HIP_TRY(c, hipMemsetAsync(c->uf_death.p, 0xFF, (n_seeds + 1) * sizeof(uint32_t), c->stream));
   }
-  uint32_t *history_hook = history ? (uint32_t *)c->uf_hook.p : nullptr;
-  auto per_level = [&](uint32_t l) -> int {
-    if (want_list && !fe.on)      // the kernel leaves this level's record count in its counter; offsets are prefix sums, taken on the host
-      HIP_TRY(c, emit_lakes(c->stream, parent, (const uint32_t *)c->uf_size.p, n_seeds + 1, d_records, cap, mf + MF_LAKE_COUNT, l));
-    if (cb) {
-      if (host_copy_in_chunks(c, n)) {      // the level's plane as u32 (in the u64 buffer, which that path leaves alone), widened by host threads
-        if (merging) HIP_TRY(c, relabel_u32(c->stream, keys, seg, parent, (uint32_t *)d_out64, n, l));
-        else HIP_TRY(c, snapshot_level_u32(c->stream, keys, seg, (uint32_t *)d_out64, n, l));
-        if (int rc_copy = labels_to_host_u64(c, (const uint32_t *)d_out64, c->host64.data(), n)) return rc_copy;
-      } else {
-        if (merging) HIP_TRY(c, relabel_u64(c->stream, keys, seg, parent, d_out64, n, l));
-        else HIP_TRY(c, snapshot_level(c->stream, keys, seg, d_out64, n, l));
-        HIP_TRY(c, hipMemcpyAsync(c->host64.data(), d_out64, n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-      }
-      cb(user, (uint8_t)l, opt->max_water_level, himg, c->host64.data(), ph, pw);        // lib.rs:1510-1518
-    }
-    return WS_OK;
-  };
+  return WS_OK;
+}
 
-  // The level loop is ~3 launches of a few microseconds per level and has no host decision in it: a call that repeats
-  // the previous one's shape and buffers replays it as hipGraphs, one per group of LIST_GROUP levels (the groups' record
-  // copies still overlap the later groups).  The second such call captures, later ones replay.
+// Run: all levels queued, in groups of LIST_GROUP.
+// The level loop is ~3 launches of a few microseconds per level and has no host decision in it: a call that repeats
+// the previous one's shape and buffers replays it as hipGraphs, one per group of LIST_GROUP levels (the groups' record
+// copies still overlap the later groups).  The second such call captures, later ones replay.
+int level_run(ws_ctx *c, const LevelJob &job, const LevelRun &r) {
+  int rc;
+  const size_t n = r.n, n_seeds = job.n_seeds;
+  const uint32_t levels = r.levels;
+  const bool want_list = job.lists();
   ws_ctx::ListKey key;
-  // (the fused-record mode follows from merging, want_list and cb == null)
-  key.merging = merging; key.want_list = want_list; key.levels = levels; key.n_colours = n_seeds + 1; key.n = n; key.cap = cap;
-  key.records = d_records;
-  key.keys = keys; key.seg = seg;
-  key.slice_h = dev && dev->d_slice_base ? (size_t)dev->slice_h : 0;
-  key.history = history;      // (its unions are other kernels: never replay a history graph for lists or final labels, nor the reverse)
+  // (the mode follows from merging, want_list, history, cb == null -- which capture needs anyway -- and n_colours against the
+  // context's threshold, whose setter starts a new generation)
+  key.merging = job.merging; key.want_list = want_list; key.levels = levels; key.n_colours = n_seeds + 1; key.n = n; key.cap = job.cap;
+  key.records = r.records;
+  key.keys = r.keys; key.seg = r.seg;
+  key.slice_h = job.d_slice_base ? (size_t)job.slice_h : 0;
+  key.history = job.history;      // (its unions are other kernels: never replay a history graph for lists or final labels, nor the reverse)
   key.generation = c->buffer_generation;
-  const bool graph_able = !cb && c->stream != nullptr && !c->graph_unusable && !c->profiling && n != 0;
+  const bool graph_able = level_capturable(job, c->stream != nullptr, c->graph_unusable, c->profiling, n);
   bool use_graphs = graph_able && key == c->list_seen_key;
   c->list_seen_key = graph_able ? key : ws_ctx::ListKey();
   if (!(use_graphs && key == c->list_graph_key)) {      // another shape: yesterday's graphs are of no use
@@ -265,7 +269,8 @@ int merge_host(ws_ctx *c, bool merging, const uint8_t *img, size_t h, size_t w, 
   }
   if (tuning_env("WS_DEBUG_LIST"))
     std::fprintf(stderr, "[ws] merge_host: merging %d list %d cb %d levels %u colours %zu n %zu cap %zu gen %llu graph_able %d use_graphs %d fused %d\n",
-                 (int)merging, (int)want_list, cb != nullptr, levels, n_seeds + 1, n, cap, (unsigned long long)key.generation, (int)graph_able, (int)use_graphs, (int)fe.on);
+                 (int)job.merging, (int)want_list, job.cb != nullptr, levels, n_seeds + 1, n, job.cap, (unsigned long long)key.generation, (int)graph_able,
+                 (int)use_graphs, (int)(r.plan.tail != LevelTail::NONE));
   for (uint32_t g0 = 0; g0 < levels; g0 += LIST_GROUP) {
     const uint32_t g1 = std::min(g0 + LIST_GROUP, levels), gi = g0 / LIST_GROUP;
     bool done = false;
@@ -273,7 +278,7 @@ int merge_host(ws_ctx *c, bool merging, const uint8_t *img, size_t h, size_t w, 
       if (!c->list_graphs[gi]) {
         hipGraph_t graph = nullptr;
         if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-          const int lrc = level_range(c, g0, g1, merging, want_list, grid, per_level, fe, history_hook);
+          const int lrc = level_range(c, job, r, g0, g1);
           const hipError_t e2 = hipStreamEndCapture(c->stream, &graph);
           if (lrc == WS_OK && e2 == hipSuccess && hipGraphInstantiate(&c->list_graphs[gi], graph, nullptr, nullptr, 0) != hipSuccess) c->list_graphs[gi] = nullptr;
           if (graph) (void)hipGraphDestroy(graph);
@@ -290,65 +295,96 @@ int merge_host(ws_ctx *c, bool merging, const uint8_t *img, size_t h, size_t w, 
         done = true;
       }
     }
-    if (!done && (rc = level_range(c, g0, g1, merging, want_list, grid, per_level, fe, history_hook))) return rc;
+    if (!done && (rc = level_range(c, job, r, g0, g1))) return rc;
     // a marker per group, so that the records of finished levels can travel to the host while later levels are computed
     if (want_list) HIP_TRY(c, hipEventRecord(c->kern_ev[gi], c->stream));
   }
-  const uint32_t n_groups = (levels + LIST_GROUP - 1) / LIST_GROUP;
-  if (fe.on) {      // the last level's records; and a marker behind them: in this mode a group's last level is complete one launch later
-    if (fe.live)
-      HIP_TRY(c, emit_alive(c->stream, (const uint2 *)c->uf_sd.p, n_seeds + 1, (uint32_t *)c->alive.p, fe.emit_grid, d_records, cap, mf + MF_LAKE_COUNT,
-                            levels - 1));
-    else
-      HIP_TRY(c, emit_lakes(c->stream, parent, (const uint32_t *)c->uf_size.p, n_seeds + 1, d_records, cap, mf + MF_LAKE_COUNT, levels - 1,
-                            (const uint32_t *)c->uf_death.p));
-    HIP_TRY(c, hipEventRecord(c->kern_ev[n_groups], c->stream));
-  }
-
-  std::vector<uint64_t> bounds(2 * (NLEVELS + 1));
-  if (want_list) {
-    // All levels are queued.  Group by group: wait for the group's marker, read its offsets, copy its records
-    // (155 MB at 1024^2: as long over PCIe as the levels take to compute, so the two are overlapped).
-    offsets[0] = 0;
-    size_t copied = 0;
-    for (uint32_t g0 = 0; g0 < levels; g0 += LIST_GROUP) {
-      const uint32_t g1 = std::min(g0 + LIST_GROUP, levels);
-      // (fused records: group g's last level is written by group g + 1's first launch -- wait for that group's marker)
-      HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, c->kern_ev[g0 / LIST_GROUP + (fe.on ? 1 : 0)], 0));
-      HIP_TRY(c, hipMemcpyAsync(offsets + g0 + 1, mf + MF_LAKE_COUNT + g0, (g1 - g0) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->copy_stream));
-      if (g0 == 0)      // the bucket bounds were final before the first level: they ride along with the first group
-        HIP_TRY(c, hipMemcpyAsync(bounds.data(), mf + MF_OFF_PX, 2 * (NLEVELS + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->copy_stream));
-      HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
-      for (uint32_t l = g0; l < g1; ++l) offsets[l + 1] += offsets[l];      // counts -> offsets
-      const size_t end = std::min<size_t>(offsets[g1], cap);
-      if (!dev && end > copied) {      // (the records of this group travel while later levels are computed)
-        if ((rc = records_to_host(c, (const ws_lake *)c->lakes.p, lakes, copied, end, n, c->copy_stream))) return rc;
-        copied = end;
-      }
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
-    *n_lakes = offsets[levels];
-    for (uint32_t l = 0; l < levels; ++l) uncoloured[l] = n - bounds[l + 1];                   // index 0 of lib.rs:630's vector
-  } else {
-    HIP_TRY(c, hipMemcpyAsync(bounds.data(), mf + MF_OFF_PX, 2 * (NLEVELS + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  }
-  if (out_labels && n) {
-    if (merging && !host_copy_in_chunks(c, n)) {
-      HIP_TRY(c, relabel_u64(c->stream, keys, seg, parent, d_out64, n, opt->max_water_level));
-      HIP_TRY(c, hipMemcpyAsync(out_labels, d_out64, n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    } else {
-      // a large plane crosses the bus as u32 and is widened by host threads (ws_hostcopy.hip); the relabelled u32 plane of
-      // the merging transform borrows the u64 buffer, which that path does not use
-      if (merging) HIP_TRY(c, relabel_u32(c->stream, keys, seg, parent, (uint32_t *)d_out64, n, opt->max_water_level));
-      if ((rc = labels_to_host_u64(c, merging ? (const uint32_t *)d_out64 : seg, out_labels, n))) return rc;
-    }
-  }
-  rc = stats_end(c);
-  if (rc) return rc;
-  if (merging)
-    for (uint32_t l = 0; l < levels; ++l) c->stats.merge_levels += bounds[NLEVELS + 1 + l + 1] > bounds[NLEVELS + 1 + l] ? 1u : 0u;
-  if (want_list && *n_lakes > cap) return fail(c, WS_ERR_CAPACITY, "lake buffer too small");
+  if (r.plan.tail == LevelTail::NONE) return WS_OK;
+  // the fused modes' last level; and a marker behind it: there a group's last level is complete one launch later
+  u64c *mf = (u64c *)c->mflags.p;
+  if (r.plan.tail == LevelTail::EMIT_ALIVE)
+    HIP_TRY(c, emit_alive(c->stream, (const uint2 *)c->uf_sd.p, n_seeds + 1, (uint32_t *)c->alive.p, r.emit_grid, r.records, job.cap, mf + MF_LAKE_COUNT,
+                          levels - 1));
+  else
+    HIP_TRY(c, emit_lakes(c->stream, (uint32_t *)c->uf_parent.p, (const uint32_t *)c->uf_size.p, n_seeds + 1, r.records, job.cap, mf + MF_LAKE_COUNT, levels - 1,
+                          (const uint32_t *)c->uf_death.p));
+  HIP_TRY(c, hipEventRecord(c->kern_ev[(levels + LIST_GROUP - 1) / LIST_GROUP], c->stream));
   return WS_OK;
+}
+
+// Collect: the bucket bounds; and, for lists, group by group: wait for the group's marker, read its offsets, copy its records
+// (155 MB at 1024^2: as long over PCIe as the levels take to compute, so the two are overlapped).
+int level_collect(ws_ctx *c, const LevelJob &job, LevelRun &r) {
+  int rc;
+  u64c *mf = (u64c *)c->mflags.p;
+  const uint32_t levels = r.levels;
+  r.bounds.assign(2 * (NLEVELS + 1), 0);
+  if (!job.lists()) {
+    HIP_TRY(c, hipMemcpyAsync(r.bounds.data(), mf + MF_OFF_PX, 2 * (NLEVELS + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    return WS_OK;
+  }
+  uint64_t *offsets = job.offsets;
+  offsets[0] = 0;
+  size_t copied = 0;
+  for (uint32_t g0 = 0; g0 < levels; g0 += LIST_GROUP) {
+    const uint32_t g1 = std::min(g0 + LIST_GROUP, levels);
+    HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, c->kern_ev[g0 / LIST_GROUP + r.plan.marker_shift], 0));
+    HIP_TRY(c, hipMemcpyAsync(offsets + g0 + 1, mf + MF_LAKE_COUNT + g0, (g1 - g0) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->copy_stream));
+    if (g0 == 0)      // the bucket bounds were final before the first level: they ride along with the first group
+      HIP_TRY(c, hipMemcpyAsync(r.bounds.data(), mf + MF_OFF_PX, 2 * (NLEVELS + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->copy_stream));
+    HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
+    for (uint32_t l = g0; l < g1; ++l) offsets[l + 1] += offsets[l];      // counts -> offsets
+    const size_t end = std::min<size_t>(offsets[g1], job.cap);
+    if (!job.device_records() && end > copied) {      // (the records of this group travel while later levels are computed)
+      if ((rc = records_to_host(c, (const ws_lake *)c->lakes.p, job.lakes, copied, end, r.n, c->copy_stream))) return rc;
+      copied = end;
+    }
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
+  *job.n_lakes = offsets[levels];
+  for (uint32_t l = 0; l < levels; ++l) job.uncoloured[l] = r.n - r.bounds[l + 1];                   // index 0 of lib.rs:630's vector
+  return WS_OK;
+}
+
+// Final labels: the plane at max_water_level to the host
+int level_labels(ws_ctx *c, const LevelJob &job, const LevelRun &r) {
+  const size_t n = r.n;
+  if (!job.out_labels || !n) return WS_OK;
+  uint32_t *parent = (uint32_t *)c->uf_parent.p;
+  uint64_t *d_out64 = (uint64_t *)c->out64.p;
+  if (job.merging && !host_copy_in_chunks(c, n)) {
+    HIP_TRY(c, relabel_u64(c->stream, r.keys, r.seg, parent, d_out64, n, r.opt->max_water_level));
+    HIP_TRY(c, hipMemcpyAsync(job.out_labels, d_out64, n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    return WS_OK;
+  }
+  // a large plane crosses the bus as u32 and is widened by host threads (ws_hostcopy.hip); the relabelled u32 plane of
+  // the merging transform borrows the u64 buffer, which that path does not use
+  if (job.merging) HIP_TRY(c, relabel_u32(c->stream, r.keys, r.seg, parent, (uint32_t *)d_out64, n, r.opt->max_water_level));
+  return labels_to_host_u64(c, job.merging ? (const uint32_t *)d_out64 : r.seg, job.out_labels, n);
+}
+
+int level_epilogue(ws_ctx *c, const LevelJob &job, const LevelRun &r) {
+  if (int rc = stats_end(c)) return rc;
+  if (job.merging)
+    for (uint32_t l = 0; l < r.levels; ++l) c->stats.merge_levels += r.bounds[NLEVELS + 1 + l + 1] > r.bounds[NLEVELS + 1 + l] ? 1u : 0u;
+  if (job.lists() && *job.n_lakes > job.cap) return fail(c, WS_ERR_CAPACITY, "lake buffer too small");
+  return WS_OK;
+}
+
+int merge_host(ws_ctx *c, const LevelJob &job) {
+  if (!c) return WS_ERR_BAD_ARG;
+  int rc = check_job(c, job);
+  if (rc) return rc;
+  static const bool split_emit = tuning_env("WS_TOLIST_SPLIT") != nullptr;      // A/B knob for tools/
+  LevelRun r;
+  r.plan = level_plan(job, c->live_list_min, split_emit);
+  if ((rc = level_source(c, job, r))) return rc;
+  if (r.plan.mode == LevelMode::NONE) return stats_end(c);      // the segmenting history is the flood's stamps and labels
+  if ((rc = level_prepare(c, job, r))) return rc;
+  if ((rc = level_run(c, job, r))) return rc;
+  if ((rc = level_collect(c, job, r))) return rc;
+  if ((rc = level_labels(c, job, r))) return rc;
+  return level_epilogue(c, job, r);
 }
 
 void stats_add(ws_stats &a, const ws_stats &b) {
@@ -376,6 +412,60 @@ bool stackable(ws_ctx *c, size_t n_slices, size_t h, size_t w, size_t stride, si
   return true;
 }
 
+// A batch that stacks, as its drivers hand it to flood_group
+struct StackBatch {
+  const uint8_t *d_cube = nullptr;
+  size_t h = 0, stride = 0, ph = 0, pw = 0;
+  const uint32_t *d_seeds_rc = nullptr;
+  const size_t *seed_offsets = nullptr;
+  const ws_options *opt = nullptr;
+};
+
+// The flood of slices [k0, k0 + g) as one stack (flood_stack) into `labels`; first (g + 1): every slice's first seed within the
+// group.  true: flooded, and the statistics span is still OPEN -- the drivers differ in where they close it.  false: the flood
+// failed or mispredicted; the span is closed, the error cleared, and the slice-by-slice loop repeats the work and names the slice.
+bool flood_group(ws_ctx *c, const StackBatch &b, size_t k0, size_t g, uint32_t *labels, std::vector<uint32_t> &first) {
+  const size_t s0 = b.seed_offsets[k0];
+  first.resize(g + 1);
+  for (size_t k = 0; k <= g; ++k) first[k] = (uint32_t)(b.seed_offsets[k0 + k] - s0);
+  stats_begin(c);
+  bool mispredicted = false;
+  const int rc = flood_stack(c, b.d_cube + k0 * b.h * b.stride, b.stride, g, b.ph, b.pw, b.d_seeds_rc + 2 * s0, first.data(), b.opt, labels, &mispredicted);
+  c->have_keys = false;      // the stamps are those of a stack, not of an image
+  if (rc == WS_OK && !mispredicted) return true;
+  (void)stats_end(c);
+  c->err.clear();
+  return false;
+}
+
+// The arrival-form job of a flooded stack of slices of ph rows: the per-level driver over the stack's numbering of colours
+LevelJob stack_job(ws_ctx *c, bool merging, size_t g, size_t ph, size_t pw, size_t n_seeds, const ws_options *opt, const uint32_t *labels,
+                   const uint32_t *d_base) {
+  LevelJob job;
+  job.merging = merging; job.h = g * ph; job.w = pw; job.stride = pw; job.n_seeds = n_seeds; job.opt = opt;
+  job.source = LevelSource::ARRIVAL; job.d_keys = (const uint32_t *)c->keys.p; job.d_seg = labels;
+  job.slice_h = (int)ph; job.d_slice_base = d_base;
+  return job;
+}
+
+// The history job of a device-resident image: the flood and, merging, the stamped level loop; nothing leaves the context
+LevelJob history_job_device(bool merging, const uint8_t *d_img, size_t h, size_t w, size_t stride, const uint32_t *d_seeds_rc, size_t n_seeds,
+                            const ws_options *opt) {
+  LevelJob job;
+  job.merging = merging; job.h = h; job.w = w; job.stride = stride; job.n_seeds = n_seeds; job.opt = opt;
+  job.source = LevelSource::DEVICE; job.d_img = d_img; job.d_seeds_rc = d_seeds_rc; job.history = true;
+  return job;
+}
+
+// ... and of a host image
+LevelJob history_job_host(bool merging, const uint8_t *img, size_t h, size_t w, size_t stride, const uint64_t *seeds_rc, size_t n_seeds,
+                          const ws_options *opt) {
+  LevelJob job;
+  job.merging = merging; job.h = h; job.w = w; job.stride = stride; job.n_seeds = n_seeds; job.opt = opt;
+  job.img = img; job.seeds_rc = seeds_rc; job.history = true;
+  return job;
+}
+
 // ws_transform_to_list_batch_device on a stack: per group of slices, the flood of the stack (flood_stack), the per-level driver
 // over the stack's numbering of colours (merge_host, arrival form: the bucketing adds the slice's base to every colour and pairs
 // no pixels across a slice border), then the split of the group's records (level-major, stack colours) into the caller's
@@ -396,6 +486,8 @@ int lists_batch_stacked(ws_ctx *c, bool merging, const uint8_t *d_cube, size_t n
   std::vector<uint32_t> first;
   std::vector<uint64_t> goff(levels + 1), gunc(levels);
   std::vector<u64c> bins;
+  StackBatch batch;
+  batch.d_cube = d_cube; batch.h = h; batch.stride = stride; batch.ph = ph; batch.pw = pw; batch.d_seeds_rc = d_seeds_rc; batch.seed_offsets = seed_offsets; batch.opt = opt;
   for (size_t k0 = 0; k0 < n_slices; k0 += per_group) {
     const size_t g = std::min(per_group, n_slices - k0);
     const size_t s0 = seed_offsets[k0], ns = seed_offsets[k0 + g] - s0;
@@ -403,32 +495,18 @@ int lists_batch_stacked(ws_ctx *c, bool merging, const uint8_t *d_cube, size_t n
     if ((rc = ensure(c, c->stack_labels, g * plane * sizeof(uint32_t)))) return rc;
     if ((rc = ensure(c, c->stack_records, std::max<size_t>(gcap, 1) * sizeof(ws_lake)))) return rc;
     if ((rc = ensure(c, c->stack_bins, (levels + 1 + n_bins + g * NLEVELS) * sizeof(u64c)))) return rc;
-    first.resize(g + 1);
-    for (size_t k = 0; k <= g; ++k) first[k] = (uint32_t)(seed_offsets[k0 + k] - s0);
-    stats_begin(c);
-    bool mispredicted = false;
     uint32_t *labels = (uint32_t *)c->stack_labels.p;
-    rc = flood_stack(c, d_cube + k0 * h * stride, stride, g, ph, pw, d_seeds_rc + 2 * s0, first.data(), opt, labels, &mispredicted);
-    c->have_keys = false;      // the stamps are those of a stack, not of an image
-    if (rc != WS_OK || mispredicted) {      // the loop repeats the work and names the slice
-      (void)stats_end(c);
-      c->err.clear();
-      return WS_OK;
-    }
+    if (!flood_group(c, batch, k0, g, labels, first)) return WS_OK;      // the loop takes the batch
     if ((rc = stats_end(c))) return rc;
     stats_add(acc, c->stats);
     const uint32_t *d_base = stacked_first(c, ns);
     u64c *d_off = (u64c *)c->stack_bins.p, *d_bins = d_off + levels + 1, *d_hist = d_bins + n_bins;
     HIP_TRY(c, hipMemsetAsync(d_bins, 0, (n_bins + g * NLEVELS) * sizeof(u64c), c->stream));
     HIP_TRY(c, slice_arrivals(c->stream, (const uint32_t *)c->keys.p, plane, g, d_hist));
-    DeviceLists dev{nullptr, nullptr, (ws_lake *)c->stack_records.p};
-    dev.d_keys = (const uint32_t *)c->keys.p;
-    dev.d_seg = labels;
-    dev.slice_h = (int)ph;
-    dev.d_slice_base = d_base;
     size_t got = 0;
-    rc = merge_host(c, merging, nullptr, g * ph, pw, pw, nullptr, ns, opt, nullptr, nullptr, nullptr, nullptr, gcap, &got, goff.data(),
-                    gunc.data(), &dev);
+    LevelJob job = stack_job(c, merging, g, ph, pw, ns, opt, labels, d_base);
+    job.d_lakes = (ws_lake *)c->stack_records.p; job.cap = gcap; job.n_lakes = &got; job.offsets = goff.data(); job.uncoloured = gunc.data();
+    rc = merge_host(c, job);
     if (rc != WS_OK && rc != WS_ERR_CAPACITY) return rc;
     stats_add(acc, c->stats);
     need += got;
@@ -490,22 +568,14 @@ int merge_batch_stacked(ws_ctx *c, const uint8_t *d_cube, size_t n_slices, size_
   const size_t plane = ph * pw;
   ws_stats acc{};
   std::vector<uint32_t> first;
+  StackBatch batch;
+  batch.d_cube = d_cube; batch.h = h; batch.stride = stride; batch.ph = ph; batch.pw = pw; batch.d_seeds_rc = d_seeds_rc; batch.seed_offsets = seed_offsets; batch.opt = opt;
   for (size_t k0 = 0; k0 < n_slices; k0 += per_group) {
     const size_t g = std::min(per_group, n_slices - k0);
-    const size_t s0 = seed_offsets[k0], ns = seed_offsets[k0 + g] - s0;
+    const size_t ns = seed_offsets[k0 + g] - seed_offsets[k0];
     if ((rc = ensure_uf(c, ns + 1))) return rc;
-    first.resize(g + 1);
-    for (size_t k = 0; k <= g; ++k) first[k] = (uint32_t)(seed_offsets[k0 + k] - s0);
-    stats_begin(c);
-    bool mispredicted = false;
     uint32_t *labels = d_labels + k0 * plane;
-    rc = flood_stack(c, d_cube + k0 * h * stride, stride, g, ph, pw, d_seeds_rc + 2 * s0, first.data(), opt, labels, &mispredicted);
-    c->have_keys = false;
-    if (rc != WS_OK || mispredicted) {
-      (void)stats_end(c);
-      c->err.clear();
-      return WS_OK;
-    }
+    if (!flood_group(c, batch, k0, g, labels, first)) return WS_OK;      // the loop takes the batch
     HIP_TRY(c, uf_init(c->stream, (uint32_t *)c->uf_parent.p, (uint32_t *)c->uf_size.p, ns + 1));
     {
       Span sp(c, KC_OTHER);
@@ -535,6 +605,15 @@ int check_batch(ws_ctx *c, size_t n_slices, size_t h, size_t row_stride, size_t 
 // ---- transform_history (lib.rs:1233-1237, 1538-1549, 1824-1835) for a list of levels ------------------------------------------------
 
 constexpr size_t HISTORY_SCRATCH_BYTES = (size_t)256 << 20;      // the host form's u32 planes on the device, at most, per chunk of levels
+
+// n_planes planes of n u32 words, contiguous on the device, into the host's u64 planes: in ONE labels_to_host_u64 where the host
+// threads widen (host_copy_in_chunks), else plane by plane, widened on the device in the u64 buffer the context holds for one plane
+int planes_to_host(ws_ctx *c, const uint32_t *src, uint64_t *dst, size_t n_planes, size_t n) {
+  if (host_copy_in_chunks(c, n_planes * n)) return labels_to_host_u64(c, src, dst, n_planes * n);
+  for (size_t i = 0; i < n_planes; ++i)
+    if (int rc = labels_to_host_u64(c, src + i * n, dst + i * n, n)) return rc;
+  return WS_OK;
+}
 
 // what both forms check before anything runs; *n_px: pixels of the (padded) plane
 int check_history(ws_ctx *c, size_t h, size_t w, size_t stride, const ws_options *opt, const uint8_t *levels, size_t n_levels, size_t *n_px) {
@@ -636,6 +715,76 @@ int build_lake_stats(ws_ctx *c, const uint32_t *d_seeds, size_t n_seeds, const w
   return WS_OK;
 }
 
+// ---- the tree entry points' bodies: ws_merge_tree(_device), and with ls, ws_merge_tree_stats(_device) ---------------------------------
+
+// the statistics request of ws_merge_tree_stats(_device): the weights (null: the image itself) and where the records go --
+// device pointers in the device form, host pointers in the host form
+struct LakeStatsWanted {
+  const void *weight = nullptr;
+  int dtype = 0;
+  size_t stride = 0;
+  ws_lake_stats *stats = nullptr;
+};
+
+// All argument checks come before device work, and every buffer is ensured BEFORE the transform (ensure_tree).
+int merge_tree_device_body(ws_ctx *c, const uint8_t *d_img, size_t h, size_t w, size_t stride, const uint32_t *d_seeds_rc, size_t n_seeds,
+                           const ws_options *opt, ws_tree_node *d_tree, uint32_t *d_labels, const LakeStatsWanted *ls) {
+  size_t ph = 0, pw = 0;
+  if (int rc = check_tree(c, h, w, stride, opt, n_seeds, &ph, &pw)) return rc;
+  if (ls)
+    if (int rc = check_lake_weights(c, w, ph, pw, ls->weight, ls->dtype, ls->stride)) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (int rc = ensure_tree(c, n_seeds, false)) return rc;
+  if (ls)
+    if (int rc = ensure_lake(c, n_seeds, false)) return rc;
+  if (int rc = merge_host(c, history_job_device(true, d_img, h, w, stride, d_seeds_rc, n_seeds, opt))) return rc;
+  // the seed pairs as the flood took them: the caller's, or (shifted_seeds) moved into the padded plane in the context's buffer
+  const uint32_t *seeds = seed_shift_of(opt) && n_seeds ? (const uint32_t *)c->seeds.p : d_seeds_rc;
+  if (int rc = build_tree(c, seeds, n_seeds, opt, ph, pw, d_tree)) return rc;
+  if (ls) {
+    const uint32_t off = opt->edge_correction ? 1u : 0u;
+    const LakeWeights wt = ls->weight ? LakeWeights{ls->weight, ls->stride, (uint32_t)h, (uint32_t)w, off, ls->dtype == WS_U16}
+                                      : LakeWeights{d_img, stride, (uint32_t)h, (uint32_t)w, off, 0};
+    if (int rc = build_lake_stats(c, seeds, n_seeds, opt, ph, pw, d_tree, wt, ls->stats)) return rc;
+  }
+  if (d_labels && ph * pw) HIP_TRY(c, hipMemcpyAsync(d_labels, c->labels.p, ph * pw * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return WS_OK;
+}
+
+int merge_tree_host_body(ws_ctx *c, const uint8_t *img, size_t h, size_t w, size_t stride, const uint64_t *seeds_rc, size_t n_seeds,
+                         const ws_options *opt, ws_tree_node *tree, uint64_t *labels, const LakeStatsWanted *ls) {
+  size_t ph = 0, pw = 0;
+  if (int rc = check_tree(c, h, w, stride, opt, n_seeds, &ph, &pw)) return rc;
+  if (ls)
+    if (int rc = check_lake_weights(c, w, ph, pw, ls->weight, ls->dtype, ls->stride)) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (int rc = ensure_tree(c, n_seeds, true)) return rc;
+  if (ls)
+    if (int rc = ensure_lake(c, n_seeds, true)) return rc;
+  const size_t elem = ls && ls->weight && ls->dtype == WS_U16 ? 2 : 1;
+  const bool own_plane = ls && ls->weight && h * w;
+  if (own_plane) {      // contiguous on the context, before the transform: nothing moves under the level loop's graphs
+    if (int rc = ensure(c, c->lake_weight, h * w * elem)) return rc;
+    HIP_TRY(c, hipMemcpy2DAsync(c->lake_weight.p, w * elem, ls->weight, ls->stride * elem, w * elem, h, hipMemcpyHostToDevice, c->stream));
+  }
+  if (int rc = merge_host(c, history_job_host(true, img, h, w, stride, seeds_rc, n_seeds, opt))) return rc;
+  const uint32_t *seeds = (const uint32_t *)c->seeds.p;      // stage_inputs: narrowed, shifted where the options say so
+  ws_tree_node *d_tree = (ws_tree_node *)c->tree_out.p;
+  if (int rc = build_tree(c, seeds, n_seeds, opt, ph, pw, d_tree)) return rc;
+  if (ls) {
+    // (no weights: the image as stage_inputs left it on the device, w bytes a row)
+    const LakeWeights wt{own_plane ? c->lake_weight.p : c->img.p, w, (uint32_t)h, (uint32_t)w, opt->edge_correction ? 1u : 0u, elem == 2};
+    if (int rc = build_lake_stats(c, seeds, n_seeds, opt, ph, pw, d_tree, wt, (ws_lake_stats *)c->lake_out.p)) return rc;
+  }
+  HIP_TRY(c, hipMemcpyAsync(tree, d_tree, (n_seeds + 1) * sizeof(ws_tree_node), hipMemcpyDeviceToHost, c->stream));
+  if (ls) HIP_TRY(c, hipMemcpyAsync(ls->stats, c->lake_out.p, (n_seeds + 1) * sizeof(ws_lake_stats), hipMemcpyDeviceToHost, c->stream));
+  if (labels && ph * pw)
+    if (int rc = labels_to_host_u64(c, (const uint32_t *)c->labels.p, labels, ph * pw)) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return WS_OK;
+}
+
 // ---- transform_history of a cube of slices (ws_transform_history_batch(_device)) ---------------------------------------------------
 
 // The transform of slices [k_first, k_first + g) of a batch, left on the context for rendering: a stack (labels restart at 1 in every
@@ -672,20 +821,14 @@ int history_batch_run(ws_ctx *c, bool merging, const uint8_t *d_cube, size_t n_s
   if (n_slices > 1 && slice_stride == h * stride && d_cube && d_seeds_rc && stackable(c, n_slices, h, w, stride, ph, pw, seed_offsets, opt, &per_group)) {
     bool stacked = true;
     std::vector<uint32_t> first;
+    StackBatch batch;
+    batch.d_cube = d_cube; batch.h = h; batch.stride = stride; batch.ph = ph; batch.pw = pw; batch.d_seeds_rc = d_seeds_rc; batch.seed_offsets = seed_offsets; batch.opt = opt;
     for (size_t k0 = 0; k0 < n_slices && stacked; k0 += per_group) {
       const size_t g = std::min(per_group, n_slices - k0);
-      const size_t s0 = seed_offsets[k0], ns = seed_offsets[k0 + g] - s0;
+      const size_t ns = seed_offsets[k0 + g] - seed_offsets[k0];
       if ((rc = ensure(c, c->stack_labels, g * plane * sizeof(uint32_t)))) return rc;
-      first.resize(g + 1);
-      for (size_t k = 0; k <= g; ++k) first[k] = (uint32_t)(seed_offsets[k0 + k] - s0);
-      stats_begin(c);
-      bool mispredicted = false;
       uint32_t *labels = (uint32_t *)c->stack_labels.p;
-      rc = flood_stack(c, d_cube + k0 * h * stride, stride, g, ph, pw, d_seeds_rc + 2 * s0, first.data(), opt, labels, &mispredicted);
-      c->have_keys = false;      // the stamps are those of a stack, not of an image
-      if (rc != WS_OK || mispredicted) {      // the loop repeats the work and names the slice
-        (void)stats_end(c);
-        c->err.clear();
+      if (!flood_group(c, batch, k0, g, labels, first)) {
         stacked = false;
         break;
       }
@@ -693,14 +836,9 @@ int history_batch_run(ws_ctx *c, bool merging, const uint8_t *d_cube, size_t n_s
       stats_add(acc, c->stats);
       const uint32_t *d_base = stacked_first(c, ns);
       if (merging) {
-        DeviceLists dev{nullptr, nullptr, nullptr};
-        dev.d_keys = (const uint32_t *)c->keys.p;
-        dev.d_seg = labels;
-        dev.slice_h = (int)ph;
-        dev.d_slice_base = d_base;
-        if ((rc = merge_host(c, true, nullptr, g * ph, pw, pw, nullptr, ns, opt, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
-                             &dev, true)))
-          return rc;
+        LevelJob job = stack_job(c, true, g, ph, pw, ns, opt, labels, d_base);
+        job.history = true;
+        if ((rc = merge_host(c, job))) return rc;
         stats_add(acc, c->stats);
       }
       if ((rc = emit(HistoryGroup{k0, g, (const uint32_t *)c->keys.p, labels, d_base}))) return rc;
@@ -713,8 +851,7 @@ int history_batch_run(ws_ctx *c, bool merging, const uint8_t *d_cube, size_t n_s
   }
   for (size_t k = 0; k < n_slices; ++k) {
     const size_t ns = seed_offsets[k + 1] - seed_offsets[k];
-    const DeviceLists dev{d_cube + k * slice_stride, ns ? d_seeds_rc + 2 * seed_offsets[k] : nullptr, nullptr};
-    rc = merge_host(c, merging, nullptr, h, w, stride, nullptr, ns, opt, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, &dev, true);
+    rc = merge_host(c, history_job_device(merging, d_cube + k * slice_stride, h, w, stride, ns ? d_seeds_rc + 2 * seed_offsets[k] : nullptr, ns, opt));
     if (rc == WS_OK) {
       stats_add(acc, c->stats);
       rc = emit(HistoryGroup{k, 1, (const uint32_t *)c->keys.p, (const uint32_t *)c->labels.p, nullptr});
@@ -855,10 +992,7 @@ int ws_transform_history_device(ws_ctx *c, int merging, const uint8_t *d_img, si
   if (plane_stride < n) return fail(c, WS_ERR_BAD_ARG, "plane_stride is shorter than the plane");
   if (n_levels == 0) return WS_OK;
   if (!d_out && n) return fail(c, WS_ERR_BAD_ARG, "null pointer");
-  const DeviceLists dev{d_img, d_seeds_rc, nullptr};
-  if (int rc = merge_host(c, merging != 0, nullptr, h, w, stride, nullptr, n_seeds, opt, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
-                          nullptr, &dev, true))
-    return rc;
+  if (int rc = merge_host(c, history_job_device(merging != 0, d_img, h, w, stride, d_seeds_rc, n_seeds, opt))) return rc;
   return render_levels(c, merging != 0, history_table(levels, 0, n_levels), d_out, plane_stride, n);
 }
 
@@ -871,9 +1005,7 @@ int ws_transform_history(ws_ctx *c, int merging, const uint8_t *img, size_t h, s
   if (int rc = check_history(c, h, w, stride, opt, levels, n_levels, &n)) return rc;
   if (n_levels == 0) return WS_OK;
   if (!out && n) return fail(c, WS_ERR_BAD_ARG, "null pointer");
-  if (int rc = merge_host(c, merging != 0, img, h, w, stride, seeds_rc, n_seeds, opt, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
-                          nullptr, nullptr, true))
-    return rc;
+  if (int rc = merge_host(c, history_job_host(merging != 0, img, h, w, stride, seeds_rc, n_seeds, opt))) return rc;
   if (n == 0) return WS_OK;
   // chunks of levels rendered into bounded scratch; a chunk's planes are contiguous there and in `out`, so a chunk of 2^21 words
   // and more crosses the bus in ONE labels_to_host_u64 as u32, widened by the host threads while its next pieces are in flight.
@@ -885,12 +1017,7 @@ int ws_transform_history(ws_ctx *c, int merging, const uint8_t *img, size_t h, s
   for (size_t k0 = 0; k0 < n_levels; k0 += per) {
     const size_t k1 = std::min(k0 + per, n_levels);
     if (int rc = render_levels(c, merging != 0, history_table(levels, k0, k1), planes, n, n)) return rc;
-    if (host_copy_in_chunks(c, (k1 - k0) * n)) {
-      if (int rc = labels_to_host_u64(c, planes, out + k0 * n, (k1 - k0) * n)) return rc;
-    } else {
-      for (size_t k = k0; k < k1; ++k)
-        if (int rc = labels_to_host_u64(c, planes + (k - k0) * n, out + k * n, n)) return rc;
-    }
+    if (int rc = planes_to_host(c, planes, out + k0 * n, k1 - k0, n)) return rc;
   }
   return WS_OK;
 }
@@ -900,20 +1027,7 @@ int ws_merge_tree_device(ws_ctx *c, const uint8_t *d_img, size_t h, size_t w, si
   if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
   if (!c) return WS_ERR_BAD_ARG;
   if (!opt || !d_tree || (!d_img && h * w) || (!d_seeds_rc && n_seeds)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
-  size_t ph = 0, pw = 0;
-  if (int rc = check_tree(c, h, w, stride, opt, n_seeds, &ph, &pw)) return rc;
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (int rc = ensure_tree(c, n_seeds, false)) return rc;
-  const DeviceLists dev{d_img, d_seeds_rc, nullptr};
-  if (int rc = merge_host(c, true, nullptr, h, w, stride, nullptr, n_seeds, opt, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
-                          &dev, true))
-    return rc;
-  // the seed pairs as the flood took them: the caller's, or (shifted_seeds) moved into the padded plane in the context's buffer
-  const uint32_t *seeds = seed_shift_of(opt) && n_seeds ? (const uint32_t *)c->seeds.p : d_seeds_rc;
-  if (int rc = build_tree(c, seeds, n_seeds, opt, ph, pw, d_tree)) return rc;
-  if (d_labels && ph * pw) HIP_TRY(c, hipMemcpyAsync(d_labels, c->labels.p, ph * pw * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return WS_OK;
+  return merge_tree_device_body(c, d_img, h, w, stride, d_seeds_rc, n_seeds, opt, d_tree, d_labels, nullptr);
 }
 
 int ws_merge_tree(ws_ctx *c, const uint8_t *img, size_t h, size_t w, size_t stride, const uint64_t *seeds_rc, size_t n_seeds,
@@ -921,20 +1035,7 @@ int ws_merge_tree(ws_ctx *c, const uint8_t *img, size_t h, size_t w, size_t stri
   if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
   if (!c) return WS_ERR_BAD_ARG;
   if (!opt || !tree || (!img && h * w) || (!seeds_rc && n_seeds)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
-  size_t ph = 0, pw = 0;
-  if (int rc = check_tree(c, h, w, stride, opt, n_seeds, &ph, &pw)) return rc;
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (int rc = ensure_tree(c, n_seeds, true)) return rc;
-  if (int rc = merge_host(c, true, img, h, w, stride, seeds_rc, n_seeds, opt, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
-                          nullptr, true))
-    return rc;
-  const uint32_t *seeds = (const uint32_t *)c->seeds.p;      // stage_inputs: narrowed, shifted where the options say so
-  if (int rc = build_tree(c, seeds, n_seeds, opt, ph, pw, (ws_tree_node *)c->tree_out.p)) return rc;
-  HIP_TRY(c, hipMemcpyAsync(tree, c->tree_out.p, (n_seeds + 1) * sizeof(ws_tree_node), hipMemcpyDeviceToHost, c->stream));
-  if (labels && ph * pw)
-    if (int rc = labels_to_host_u64(c, (const uint32_t *)c->labels.p, labels, ph * pw)) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return WS_OK;
+  return merge_tree_host_body(c, img, h, w, stride, seeds_rc, n_seeds, opt, tree, labels, nullptr);
 }
 
 int ws_merge_tree_stats_device(ws_ctx *c, const uint8_t *d_img, size_t h, size_t w, size_t stride, const uint32_t *d_seeds_rc, size_t n_seeds,
@@ -943,25 +1044,9 @@ int ws_merge_tree_stats_device(ws_ctx *c, const uint8_t *d_img, size_t h, size_t
   if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
   if (!c) return WS_ERR_BAD_ARG;
   if (!opt || !d_tree || !d_stats || (!d_img && h * w) || (!d_seeds_rc && n_seeds)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
-  size_t ph = 0, pw = 0;
-  if (int rc = check_tree(c, h, w, stride, opt, n_seeds, &ph, &pw)) return rc;
-  if (int rc = check_lake_weights(c, w, ph, pw, d_weight, weight_dtype, weight_stride)) return rc;
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (int rc = ensure_tree(c, n_seeds, false)) return rc;
-  if (int rc = ensure_lake(c, n_seeds, false)) return rc;
-  const DeviceLists dev{d_img, d_seeds_rc, nullptr};
-  if (int rc = merge_host(c, true, nullptr, h, w, stride, nullptr, n_seeds, opt, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
-                          &dev, true))
-    return rc;
-  const uint32_t *seeds = seed_shift_of(opt) && n_seeds ? (const uint32_t *)c->seeds.p : d_seeds_rc;
-  if (int rc = build_tree(c, seeds, n_seeds, opt, ph, pw, d_tree)) return rc;
-  const uint32_t off = opt->edge_correction ? 1u : 0u;
-  const LakeWeights wt = d_weight ? LakeWeights{d_weight, weight_stride, (uint32_t)h, (uint32_t)w, off, weight_dtype == WS_U16}
-                                  : LakeWeights{d_img, stride, (uint32_t)h, (uint32_t)w, off, 0};
-  if (int rc = build_lake_stats(c, seeds, n_seeds, opt, ph, pw, d_tree, wt, d_stats)) return rc;
-  if (d_labels && ph * pw) HIP_TRY(c, hipMemcpyAsync(d_labels, c->labels.p, ph * pw * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return WS_OK;
+  LakeStatsWanted ls;
+  ls.weight = d_weight; ls.dtype = weight_dtype; ls.stride = weight_stride; ls.stats = d_stats;
+  return merge_tree_device_body(c, d_img, h, w, stride, d_seeds_rc, n_seeds, opt, d_tree, d_labels, &ls);
 }
 
 int ws_merge_tree_stats(ws_ctx *c, const uint8_t *img, size_t h, size_t w, size_t stride, const uint64_t *seeds_rc, size_t n_seeds,
@@ -970,33 +1055,9 @@ int ws_merge_tree_stats(ws_ctx *c, const uint8_t *img, size_t h, size_t w, size_
   if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
   if (!c) return WS_ERR_BAD_ARG;
   if (!opt || !tree || !stats || (!img && h * w) || (!seeds_rc && n_seeds)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
-  size_t ph = 0, pw = 0;
-  if (int rc = check_tree(c, h, w, stride, opt, n_seeds, &ph, &pw)) return rc;
-  if (int rc = check_lake_weights(c, w, ph, pw, weight, weight_dtype, weight_stride)) return rc;
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (int rc = ensure_tree(c, n_seeds, true)) return rc;
-  if (int rc = ensure_lake(c, n_seeds, true)) return rc;
-  const size_t elem = weight && weight_dtype == WS_U16 ? 2 : 1;
-  const bool own_plane = weight && h * w;
-  if (own_plane) {      // contiguous on the context, before the transform: nothing moves under the level loop's graphs
-    if (int rc = ensure(c, c->lake_weight, h * w * elem)) return rc;
-    HIP_TRY(c, hipMemcpy2DAsync(c->lake_weight.p, w * elem, weight, weight_stride * elem, w * elem, h, hipMemcpyHostToDevice, c->stream));
-  }
-  if (int rc = merge_host(c, true, img, h, w, stride, seeds_rc, n_seeds, opt, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
-                          nullptr, true))
-    return rc;
-  const uint32_t *seeds = (const uint32_t *)c->seeds.p;      // stage_inputs: narrowed, shifted where the options say so
-  ws_tree_node *d_tree = (ws_tree_node *)c->tree_out.p;
-  if (int rc = build_tree(c, seeds, n_seeds, opt, ph, pw, d_tree)) return rc;
-  // (no weights: the image as stage_inputs left it on the device, w bytes a row)
-  const LakeWeights wt{own_plane ? c->lake_weight.p : c->img.p, w, (uint32_t)h, (uint32_t)w, opt->edge_correction ? 1u : 0u, elem == 2};
-  if (int rc = build_lake_stats(c, seeds, n_seeds, opt, ph, pw, d_tree, wt, (ws_lake_stats *)c->lake_out.p)) return rc;
-  HIP_TRY(c, hipMemcpyAsync(tree, d_tree, (n_seeds + 1) * sizeof(ws_tree_node), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(stats, c->lake_out.p, (n_seeds + 1) * sizeof(ws_lake_stats), hipMemcpyDeviceToHost, c->stream));
-  if (labels && ph * pw)
-    if (int rc = labels_to_host_u64(c, (const uint32_t *)c->labels.p, labels, ph * pw)) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return WS_OK;
+  LakeStatsWanted ls;
+  ls.weight = weight; ls.dtype = weight_dtype; ls.stride = weight_stride; ls.stats = stats;
+  return merge_tree_host_body(c, img, h, w, stride, seeds_rc, n_seeds, opt, tree, labels, &ls);
 }
 
 // half: 0 the whole call; 1 ws_merge_device_begin (returns WS_INTERNAL_PENDING when the graph and the speculative unions
@@ -1094,7 +1155,11 @@ int ws_merge_device_end(ws_ctx *c) {
 int ws_merge_with_hook(ws_ctx *c, const uint8_t *img, size_t h, size_t w, size_t stride, const uint64_t *seeds_rc,
                        size_t n_seeds, const ws_options *opt, ws_level_cb cb, void *user, uint64_t *out_labels) {
   if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
-  return merge_host(c, true, img, h, w, stride, seeds_rc, n_seeds, opt, cb, user, out_labels, nullptr, 0, nullptr, nullptr, nullptr);
+  LevelJob job;
+  job.merging = true; job.h = h; job.w = w; job.stride = stride; job.n_seeds = n_seeds; job.opt = opt;
+  job.img = img; job.seeds_rc = seeds_rc;
+  job.cb = cb; job.user = user; job.out_labels = out_labels;
+  return merge_host(c, job);
 }
 
 int ws_transform_to_list_device(ws_ctx *c, int merging, const uint8_t *d_img, size_t h, size_t w, size_t stride,
@@ -1103,9 +1168,11 @@ int ws_transform_to_list_device(ws_ctx *c, int merging, const uint8_t *d_img, si
   if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
   if (!n_lakes || !offsets || !uncoloured || (!d_lakes && cap) || (!d_img && h * w) || (!d_seeds_rc && n_seeds))
     return fail(c, WS_ERR_BAD_ARG, "null pointer");
-  const DeviceLists dev{d_img, d_seeds_rc, d_lakes};
-  return merge_host(c, merging != 0, nullptr, h, w, stride, nullptr, n_seeds, opt, nullptr, nullptr, nullptr, nullptr, cap, n_lakes, offsets,
-                    uncoloured, &dev);
+  LevelJob job;
+  job.merging = merging != 0; job.h = h; job.w = w; job.stride = stride; job.n_seeds = n_seeds; job.opt = opt;
+  job.source = LevelSource::DEVICE; job.d_img = d_img; job.d_seeds_rc = d_seeds_rc;
+  job.d_lakes = d_lakes; job.cap = cap; job.n_lakes = n_lakes; job.offsets = offsets; job.uncoloured = uncoloured;
+  return merge_host(c, job);
 }
 
 int ws_lists_from_arrival_device(ws_ctx *c, int merging, const uint32_t *d_keys, const uint32_t *d_seg_labels, size_t h, size_t w,
@@ -1123,10 +1190,11 @@ int ws_lists_from_arrival_device(ws_ctx *c, int merging, const uint32_t *d_keys,
     offsets[(size_t)opt->max_water_level + 1] = 0;
     return WS_OK;
   }
-  DeviceLists dev{nullptr, nullptr, d_lakes};
-  dev.d_keys = d_keys; dev.d_seg = d_seg_labels;
-  return merge_host(c, merging != 0, nullptr, h, w, w, nullptr, n_seeds, opt, nullptr, nullptr, nullptr, nullptr, cap, n_lakes, offsets,
-                    uncoloured, &dev);
+  LevelJob job;
+  job.merging = merging != 0; job.h = h; job.w = w; job.stride = w; job.n_seeds = n_seeds; job.opt = opt;
+  job.source = LevelSource::ARRIVAL; job.d_keys = d_keys; job.d_seg = d_seg_labels;
+  job.d_lakes = d_lakes; job.cap = cap; job.n_lakes = n_lakes; job.offsets = offsets; job.uncoloured = uncoloured;
+  return merge_host(c, job);
 }
 
 int ws_transform_to_list(ws_ctx *c, int merging, const uint8_t *img, size_t h, size_t w, size_t stride,
@@ -1134,8 +1202,11 @@ int ws_transform_to_list(ws_ctx *c, int merging, const uint8_t *img, size_t h, s
                          size_t *n_lakes, uint64_t *offsets, uint64_t *uncoloured) {
   if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
   if (!n_lakes || !offsets || !uncoloured || (!lakes && cap)) return fail(c, WS_ERR_BAD_ARG, "null output pointer");
-  return merge_host(c, merging != 0, img, h, w, stride, seeds_rc, n_seeds, opt, nullptr, nullptr, nullptr, lakes, cap, n_lakes,
-                    offsets, uncoloured);
+  LevelJob job;
+  job.merging = merging != 0; job.h = h; job.w = w; job.stride = stride; job.n_seeds = n_seeds; job.opt = opt;
+  job.img = img; job.seeds_rc = seeds_rc;
+  job.lakes = lakes; job.cap = cap; job.n_lakes = n_lakes; job.offsets = offsets; job.uncoloured = uncoloured;
+  return merge_host(c, job);
 }
 
 int ws_transform_to_list_batch_device(ws_ctx *c, int merging, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w,
@@ -1279,12 +1350,6 @@ int ws_transform_history_batch(ws_ctx *c, int merging, const uint8_t *cube, size
   if ((rc = ensure(c, c->history_planes, (slices_per ? slices_per * slice_words : levels_per * n) * sizeof(uint32_t)))) return rc;
   if ((rc = ensure(c, c->out64, n * sizeof(uint64_t)))) return rc;      // (the plane-by-plane copy widens there)
   uint32_t *planes = (uint32_t *)c->history_planes.p;
-  auto to_host = [&](uint64_t *dst, size_t n_planes) -> int {
-    if (host_copy_in_chunks(c, n_planes * n)) return labels_to_host_u64(c, planes, dst, n_planes * n);
-    for (size_t i = 0; i < n_planes; ++i)
-      if (int rc_copy = labels_to_host_u64(c, planes + i * n, dst + i * n, n)) return rc_copy;
-    return (int)WS_OK;
-  };
   const HistoryTable all = history_table(levels, 0, n_levels);
   return history_batch_run(c, merging != 0, (const uint8_t *)c->batch_cube.p, n_slices, h, w, w, h * w, (const uint32_t *)c->batch_seeds.p,
                            offs.data(), opt, failed_slice, [&](const HistoryGroup &grp) -> int {
@@ -1292,7 +1357,7 @@ int ws_transform_history_batch(ws_ctx *c, int merging, const uint8_t *cube, size
                                for (size_t ka = 0; ka < grp.g; ka += slices_per) {
                                  const size_t kb = std::min(ka + slices_per, grp.g);
                                  if (int rc_r = render_group(c, merging != 0, grp, n, ka, kb, all, planes, n_levels, n)) return rc_r;
-                                 if (int rc_c = to_host(out + (grp.k_first + ka) * slice_words, (kb - ka) * n_levels)) return rc_c;
+                                 if (int rc_c = planes_to_host(c, planes, out + (grp.k_first + ka) * slice_words, (kb - ka) * n_levels, n)) return rc_c;
                                }
                                return (int)WS_OK;
                              }
@@ -1300,7 +1365,7 @@ int ws_transform_history_batch(ws_ctx *c, int merging, const uint8_t *cube, size
                                for (size_t j0 = 0; j0 < n_levels; j0 += levels_per) {
                                  const size_t j1 = std::min(j0 + levels_per, n_levels);
                                  if (int rc_r = render_group(c, merging != 0, grp, n, k, k + 1, history_table(levels, j0, j1), planes, 0, n)) return rc_r;
-                                 if (int rc_c = to_host(out + (grp.k_first + k) * slice_words + j0 * n, j1 - j0)) return rc_c;
+                                 if (int rc_c = planes_to_host(c, planes, out + (grp.k_first + k) * slice_words + j0 * n, j1 - j0, n)) return rc_c;
                                }
                              return (int)WS_OK;
                            });
@@ -1358,11 +1423,7 @@ int ws_merge_tree_batch(ws_ctx *c, const uint8_t *cube, size_t n_slices, size_t 
   rc = tree_batch_run(c, (const uint8_t *)c->batch_cube.p, n_slices, h, w, w, h * w, (const uint32_t *)c->batch_seeds.p, offs.data(), opt, ph, pw,
                       (ws_tree_node *)c->tree_out.p, failed_slice, [&](const HistoryGroup &grp) -> int {
                         if (!labels || !plane) return (int)WS_OK;
-                        uint64_t *dst = labels + grp.k_first * plane;
-                        if (host_copy_in_chunks(c, grp.g * plane)) return labels_to_host_u64(c, grp.labels, dst, grp.g * plane);
-                        for (size_t k = 0; k < grp.g; ++k)
-                          if (int rc_copy = labels_to_host_u64(c, grp.labels + k * plane, dst + k * plane, plane)) return rc_copy;
-                        return (int)WS_OK;
+                        return planes_to_host(c, grp.labels, labels + grp.k_first * plane, grp.g, plane);
                       });
   if (rc) return rc;
   HIP_TRY(c, hipMemcpyAsync(tree, c->tree_out.p, total * sizeof(ws_tree_node), hipMemcpyDeviceToHost, c->stream));
