@@ -733,10 +733,14 @@ const uint8_t *__restrict__ img, size_t img_stride, uint32_t *keys,
       dn[0] = dn4.x; dn[1] = dn4.y; dn[2] = dn4.z; dn[3] = dn4.w;
     }
     if (!SCAN) {
-      refresh_columns();
-      sweep_rows<false, true>(T, B, up, dn, Lh, Rh, untracked);       // down
-      refresh_columns();
-      sweep_cols<false, true>(T, B, up, dn, Lh, Rh, untracked);       // right
+      // (SEAM 1, the bands: from the second round on the free part of a round is the sweep up alone -- k_relax0_tall has the
+      // recipe, the replay and why the fixpoint is the same)
+      if (!(SEAM == 1 && round > 1)) {
+        refresh_columns();
+        sweep_rows<false, true>(T, B, up, dn, Lh, Rh, untracked);       // down
+        refresh_columns();
+        sweep_cols<false, true>(T, B, up, dn, Lh, Rh, untracked);       // right
+      }
       refresh_columns();
       sweep_rows<false, false>(T, B, up, dn, Lh, Rh, untracked);      // up
     } else {
@@ -1225,8 +1229,15 @@ __global__ __launch_bounds__(64 * RX_NW, 4) void k_relax0_tall(const uint8_t *__
   publish_rows();
   __syncthreads();
 
-  // ---- relaxation: k_relax's rounds (three free sweeps, the band rows published, one checked sweep), its round cap, and
-  // from the third round on the checked sweep alone
+  // ---- relaxation: round 1 is k_relax's round (three free sweeps down, right, up; the band rows published; one checked sweep
+  // left); every later round is ONE free sweep, up, the band rows published, and the checked sweep left -- "DRU|L, then U|L".
+  // What a tile has left to settle after its first round has to travel in every direction, and a checked left sweep alone
+  // as a later round (the rule tuned on 256 x 32 tiles) left tiles moving at the round cap; a free sweep in another direction
+  // in front of the checked one lets them end.  The replay (tools/sim_tile_schedule.c, SIM_P0_RECIPE2 / SIM_P0_RECIPE_LATER)
+  // and the counts and times measured on the GPU: DESIGN section 10.
+  // Exactness needs no new argument: every sweep is a sequence of relaxation steps on stamps that start from an upper bound,
+  // any order of such steps reaches the same fixpoint, and a run still ends only when a CHECKED sweep over all its pixels, on
+  // published rows, has changed nothing -- or at the round cap, where it marks its tiles as before.
   uint32_t iters = 0;
   bool unfinished = max_iters == 0;
   uint32_t up[RX_P], dn[RX_P];
@@ -1238,13 +1249,15 @@ __global__ __launch_bounds__(64 * RX_NW, 4) void k_relax0_tall(const uint8_t *__
   };
   for (; max_iters != 0;) {
     ++iters;
-    if (iters <= 2) {
+    {
       bool untracked = false;
       fetch_rows();
-      refresh_columns();
-      sweep_rows<false, true>(T, B, up, dn, Lh, Rh, untracked);       // down
-      refresh_columns();
-      sweep_cols<false, true>(T, B, up, dn, Lh, Rh, untracked);       // right
+      if (iters == 1) {
+        refresh_columns();
+        sweep_rows<false, true>(T, B, up, dn, Lh, Rh, untracked);       // down
+        refresh_columns();
+        sweep_cols<false, true>(T, B, up, dn, Lh, Rh, untracked);       // right
+      }
       refresh_columns();
       sweep_rows<false, false>(T, B, up, dn, Lh, Rh, untracked);      // up
       publish_rows();
@@ -1265,6 +1278,8 @@ __global__ __launch_bounds__(64 * RX_NW, 4) void k_relax0_tall(const uint8_t *__
     if (!again) break;
     if (iters >= max_iters) { unfinished = true; break; }
   }
+  WS_STAMP(0);
+  WS_STAMP_VALUE(4, iters);      // (tools/diag_seam_rounds.hip: the rounds of this tile run)
 
   // ---- write every patch back (16 B per lane and row), ring-carry check, flags
   uint32_t ovf = 0;
@@ -1466,7 +1481,9 @@ __global__ __launch_bounds__(64 * RX_NW, 4) void k_relax_strips_tall(const uint8
   __syncthreads();
 
   // ---- relaxation: the strips' rounds -- three free sweeps, the band rows published, one checked sweep -- to the slice's
-  // fixpoint or the round cap
+  // fixpoint or the round cap.  (Full rounds in EVERY round, unlike k_relax0_tall and the bands: with the sweep up alone from
+  // the second round on a slice needs fewer sweeps but more rounds, and this launch is a chain of loads, barriers and stores,
+  // not of sweeps: measured slower)
   uint32_t iters = 0;
   bool unfinished = max_iters == 0;
   uint32_t up[RX_P], dn[RX_P];
@@ -1505,6 +1522,8 @@ __global__ __launch_bounds__(64 * RX_NW, 4) void k_relax_strips_tall(const uint8
     if (!again) break;
     if (iters >= max_iters) { unfinished = true; break; }
   }
+  WS_STAMP(0);
+  WS_STAMP_VALUE(4, iters);      // (tools/diag_seam_rounds.hip)
 
   // ---- write back the patches that changed (16 B per lane and row), ring-carry check, flags
   uint64_t sum_after = 0;

@@ -35,7 +35,7 @@ constexpr uint32_t RLQ_ROUND_CAP = 6;
 constexpr uint32_t RX_SAME_GRID_FROM = 7;
 constexpr uint32_t RX_LIST_FROM_PASS = 6;      // the bench field has converged by then (its passes 4 and 5 find nothing to do)
 constexpr unsigned RX_LIST_GRID = 512;       // two workgroups of the scan variant per CU: all resident, the tickets share the list out
-constexpr uint32_t SEAM_P0_ROUNDS = 6;      // two rounds of four sweeps, then up to four of one (k_relax, chunk == 3)
+constexpr uint32_t SEAM_P0_ROUNDS = 6;      // k_relax, chunk == 3: two rounds of four sweeps, then up to four of one; k_relax0_tall: one of four, then up to five of two
 // Round caps of the seam-repair flow: three rounds bring a tile of the bench field to its own fixpoint (the third finds
 // nothing to do); a tile, band or strip slice of a smooth map that is still moving then asks for a re-run in pass 2 instead
 // of carrying a flood across its 256 columns sweep by sweep.

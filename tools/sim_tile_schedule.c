@@ -33,6 +33,11 @@ static int g_matters;
 static int g_skip_l, g_skip_r;      /* columns at the left / right end of a tile whose changes do not count as a changed first / last row */
 static int g_fh;              /* SIM_REPAIR: rows of a flagged tile; a run reports its changed side columns per block of g_fh rows */
 static unsigned g_lcol, g_rcol;      /* bit k: the left / right column changed (and matters) in rows k * g_fh ... of the run */
+/* Per-round recipes (SIM_REPAIR): round 2 and the rounds after it may have a recipe of their own (NULL: the run's recipe);
+ * g_phase: who is running (0 the fixpoint loop, 1 pass 0, 2 bands, 3 strips), for the rounds-per-run histograms */
+static const char *g_recipe2, *g_recipe_later;
+static int g_phase;
+static long g_round_hist[4][17], g_phase_sweeps[4], g_phase_runs[4];
 static uint32_t g_side_min[5]; /* smallest new key among the changed pixels of the top / bottom / left / right border, and of the tile */
 
 static inline uint32_t med3(uint32_t lo, uint32_t x, uint32_t hi) { return x < lo ? lo : (x > hi ? hi : x); }
@@ -70,15 +75,19 @@ static int run_tile(int x0, int y0, int tw, int th, int cap, const char *recipe)
     }
   memcpy(bar, cur, cells * 4);
   int res = 0, round = 0;
-  const int nops = (int)strlen(recipe);
+  const char *const recipe1 = recipe;
+  ++g_phase_runs[g_phase];
   for (;;) {
     int changed_last = 0;
+    recipe = round == 0 ? recipe1 : (round == 1 ? (g_recipe2 ? g_recipe2 : recipe1) : (g_recipe_later ? g_recipe_later : recipe1));
+    const int nops = (int)strlen(recipe);
     for (int k = 0; k < nops; ++k) {
       const char op = recipe[k];
       int changed = 0;
       if (op == '|') { memcpy(bar, cur, cells * 4); continue; }
       ++g_ops[(int)op];
       if (op == 'D' || op == 'R' || op == 'U' || op == 'L') {
+        ++g_phase_sweeps[g_phase];
         memcpy(beg, cur, cells * 4);
         for (int py = 0; py < th; py += PS)
           for (int px = 0; px < tw; px += PS)
@@ -155,6 +164,7 @@ static int run_tile(int x0, int y0, int tw, int th, int cap, const char *recipe)
     if (!changed_last) break;
     if (cap && round >= cap) { res |= 32; break; }
   }
+  ++g_round_hist[g_phase][round < 16 ? round : 16];
   for (int k = 0; k < 5; ++k) g_side_min[k] = 0xFFFFFFFFu;
   g_lcol = g_rcol = 0;
   {
@@ -342,7 +352,11 @@ int main(int argc, char **argv) {
      * strip slices sh rows high (a multiple of th); both th when not given.  The flags stay those of the tw x th tiles: a
      * strip's side column flags the tile that holds the changed row, its first / last row the tile above / below the slice.
      * SIM_REPAIR_CAPS="p0,rep": round caps of pass 0 and of the bands and strips (0: none); who stops at its cap flags every
-     * tile it covers (pass 0) or touches (a band: above and below; a slice: both sides, every row block). */
+     * tile it covers (pass 0) or touches (a band: above and below; a slice: both sides, every row block).
+     * Per-round recipes: SIM_P0_RECIPE2 is pass 0's round 2 and SIM_P0_RECIPE_LATER its rounds from the third on;
+     * SIM_REP_RECIPE_LATER the bands' and strips' rounds from the second on (SIM_BAND_RECIPE_LATER / SIM_STRIP_RECIPE_LATER: one
+     * of the two only).  Unset: the run's recipe in every round.  The engine's pass 0 until the round recipes were revisited:
+     * SIM_P0_RECIPE_LATER='|L'.  Each phase prints how many of its runs ended in round 1, 2, ... and its sweeps per run. */
     int kb = 4, ks = 4, order = 0, p0h = th, sh = th, p0cap = 0, repcap = 0;
     sscanf(getenv("SIM_REPAIR"), "%d,%d,%d", &kb, &ks, &order);
     if (getenv("SIM_REPAIR_GEOM")) sscanf(getenv("SIM_REPAIR_GEOM"), "%d,%d", &p0h, &sh);
@@ -362,6 +376,10 @@ int main(int argc, char **argv) {
     long why[5] = {0, 0, 0, 0, 0};      /* band rows, strip columns, strip slice rows, band columns (only when no strips follow), pass-0 cap */
 #define FLAG(i_, j_, w_) do { if ((i_) >= 0 && (i_) < tx && (j_) >= 0 && (j_) < ty) { if (!flag[(size_t)(j_) * tx + (i_)]) ++why[w_]; flag[(size_t)(j_) * tx + (i_)] = 1; } } while (0)
     const int per0 = p0h / th, pers = sh / th;      /* flagged tile rows per pass-0 tile / per slice */
+    const char *rep_later = getenv("SIM_REP_RECIPE_LATER");
+    const char *band_later = getenv("SIM_BAND_RECIPE_LATER") ? getenv("SIM_BAND_RECIPE_LATER") : rep_later;
+    const char *strip_later = getenv("SIM_STRIP_RECIPE_LATER") ? getenv("SIM_STRIP_RECIPE_LATER") : rep_later;
+    g_phase = 1; g_recipe2 = getenv("SIM_P0_RECIPE2"); g_recipe_later = getenv("SIM_P0_RECIPE_LATER");
     for (int j = 0; j * p0h < N; ++j)
       for (int i = 0; i < tx; ++i) {
         const int r = run_tile(i * tw, j * p0h, tw, p0h, p0cap, recipe);
@@ -376,6 +394,7 @@ int main(int argc, char **argv) {
       if (what < 0) continue;
       const int last_bands = (order == 1);      /* no strips after the bands: their columns flag too */
       memcpy(snap, key, n * 4);
+      if (what == 0 || what == 3) { g_phase = 2; g_recipe2 = g_recipe_later = band_later; } else { g_phase = 3; g_recipe2 = g_recipe_later = strip_later; }
       if (what == 0 || what == 3) {
         const int xoff = what == 3 ? tw / 2 : 0;
         for (int j = 1; j * p0h < N; ++j)
@@ -416,6 +435,17 @@ int main(int argc, char **argv) {
             if (!rows_covered && (r & 2)) { FLAG(i - 1, (y0 + sh) / th, 2); FLAG(i, (y0 + sh) / th, 2); }
           }
       }
+    }
+    g_phase = 0; g_recipe2 = g_recipe_later = NULL;
+    {
+      static const char *const who[4] = {"", "pass 0", "bands", "strips"};
+      for (int ph = 1; ph < 4; ++ph) {
+        printf("%-6s: %ld runs ending in round", who[ph], g_phase_runs[ph]);
+        for (int k = 1; k <= 16; ++k) if (g_round_hist[ph][k]) printf(" %d:%ld", k, g_round_hist[ph][k]);
+        printf("  sweeps per run %.2f\n", g_phase_runs[ph] ? (double)g_phase_sweeps[ph] / g_phase_runs[ph] : 0.0);
+      }
+      printf("recipes: %s; pass 0 round 2 %s, later %s; bands later %s; strips later %s\n", recipe, getenv("SIM_P0_RECIPE2") ? getenv("SIM_P0_RECIPE2") : "=",
+             getenv("SIM_P0_RECIPE_LATER") ? getenv("SIM_P0_RECIPE_LATER") : "=", band_later ? band_later : "=", strip_later ? strip_later : "=");
     }
     long flagged = 0, wrong = 0, wrong_unflagged = 0;
     for (size_t t = 0; t < (size_t)tx * ty; ++t) flagged += flag[t];
