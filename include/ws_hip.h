@@ -522,6 +522,34 @@ int ws_merge_tree_batch_device(ws_ctx *ctx, const uint8_t *d_cube, size_t n_slic
 int ws_merge_tree_batch(ws_ctx *ctx, const uint8_t *cube, size_t n_slices, size_t h, size_t w, size_t row_stride, size_t slice_stride,
                         const uint64_t *seeds_rc, const size_t *seed_offsets, const ws_options *opt, ws_tree_node *tree, size_t cap,
                         size_t *n_records, uint64_t *labels, size_t *n_seeds, size_t *failed_slice);
+/* ws_merge_tree_stats_device of every slice of a cube in one call, everything in HBM.  The cube, the seeds, seed_offsets, the
+ * options, d_labels and *failed_slice as ws_merge_tree_batch_device; d_tree is exactly what that call writes.  d_stats has the
+ * same slice-major layout: slice k's n_k + 1 records start at (seed_offsets[k] - seed_offsets[0]) + k, seed count + n_slices
+ * records in all, and no other word of either array is written.  Every d_stats record is bit-identical to what
+ * ws_merge_tree_stats_device writes for that slice alone with that slice's weight plane: rows, columns and peak_pixel are those of
+ * the slice's own padded plane, record 0 of a slice measures the pixels of THAT slice the last level leaves uncoloured, and a
+ * slice without seeds owns that one record.  d_weight (nullable: the cube itself weighs, as u8): n_slices planes of h x w elements
+ * of weight_dtype (WS_U8 or WS_U16), weight_row_stride elements a row and weight_slice_stride elements from one slice's plane to
+ * the next -- both independent of the cube's strides.  Refused before anything runs, every output untouched: what
+ * ws_merge_tree_batch_device refuses, a null d_stats, another dtype (WS_ERR_UNSUPPORTED), weight_row_stride < w,
+ * weight_slice_stride < h * weight_row_stride with more than one slice, and a slice whose weighted moments could pass 64 bits
+ * (WS_ERR_TOO_LARGE: the bound of ws_merge_tree_stats_device, per slice).  n_slices == 0 writes nothing.  A group of slices that
+ * stacks runs the tree kernels and the statistics kernels once over the group -- one fold launch per level for all of its
+ * slices, the uncoloured pixels of every slice kept apart in an accumulator entry of their own; anything else, and a stack that
+ * fails or mispredicts, runs as a loop of ws_merge_tree_stats_device, which names the failing slice.  Scratch, kept by the
+ * context: as ws_merge_tree_batch_device and 68 B for every colour of the largest group, one more, and one per slice of a group. */
+int ws_merge_tree_stats_batch_device(ws_ctx *ctx, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w, size_t row_stride,
+                                     size_t slice_stride, const uint32_t *d_seeds_rc, const size_t *seed_offsets, const ws_options *opt,
+                                     const void *d_weight, int weight_dtype, size_t weight_row_stride, size_t weight_slice_stride,
+                                     ws_tree_node *d_tree, ws_lake_stats *d_stats, uint32_t *d_labels, size_t *failed_slice);
+/* The same from and into HOST memory: the cube, the seeds (seeds_rc == NULL: every slice's own find_local_minima), cap,
+ * *n_records, labels and n_seeds[] as ws_merge_tree_batch; `tree` and `stats` hold `cap` records each.  cap too small:
+ * WS_ERR_CAPACITY once the minima are found or counted and before any flood, `tree`, `stats` and `labels` untouched.  The weight
+ * cube (nullable) is copied contiguous onto the context before the first transform; both record arrays cross the bus once. */
+int ws_merge_tree_stats_batch(ws_ctx *ctx, const uint8_t *cube, size_t n_slices, size_t h, size_t w, size_t row_stride, size_t slice_stride,
+                              const uint64_t *seeds_rc, const size_t *seed_offsets, const ws_options *opt, const void *weight,
+                              int weight_dtype, size_t weight_row_stride, size_t weight_slice_stride, ws_tree_node *tree,
+                              ws_lake_stats *stats, size_t cap, size_t *n_records, uint64_t *labels, size_t *n_seeds, size_t *failed_slice);
 
 /* ---- input preparation (first "next" row) ---------------------------------------
  *

@@ -470,8 +470,79 @@ class MergingWatershed : public Watershed<T> {        // lib.rs:1297-1562
     if (n_seeds) *n_seeds = counts;
     return out;
   }
+  // not in the reference: merge_tree_stats of every slice of a contiguous cube as ONE call of the library
+  // (ws_merge_tree_stats_batch: slices that stack share one flood, one set of per-level unions and one fold launch per level of
+  // the tree and of the statistics).  Every catalogue is what merge_tree_stats returns for the slice alone: the slice's own
+  // colours, rows, columns and peak pixels.  weights: a contiguous u8 or u16 cube of the cube's shape; without one the cube itself
+  // weighs.  seeds and n_seeds as merge_tree_cube.
+  std::vector<LakeCatalogue> merge_tree_stats_cube(const std::uint8_t *cube, std::size_t n_slices, std::size_t rows, std::size_t cols,
+                                                   const std::vector<std::vector<Seed>> *seeds = nullptr, bool want_labels = false,
+                                                   std::vector<std::size_t> *n_seeds = nullptr) const {
+    return lake_catalogue_cube(cube, n_slices, rows, cols, nullptr, 0, seeds, want_labels, n_seeds);
+  }
+  // (a literal nullptr in the fifth place means "own minima, no weights", as it does for merge_tree_cube)
+  std::vector<LakeCatalogue> merge_tree_stats_cube(const std::uint8_t *cube, std::size_t n_slices, std::size_t rows, std::size_t cols,
+                                                   std::nullptr_t, bool want_labels = false, std::vector<std::size_t> *n_seeds = nullptr) const {
+    return lake_catalogue_cube(cube, n_slices, rows, cols, nullptr, 0, nullptr, want_labels, n_seeds);
+  }
+  std::vector<LakeCatalogue> merge_tree_stats_cube(const std::uint8_t *cube, std::size_t n_slices, std::size_t rows, std::size_t cols,
+                                                   const std::uint8_t *weights, const std::vector<std::vector<Seed>> *seeds = nullptr,
+                                                   bool want_labels = false, std::vector<std::size_t> *n_seeds = nullptr) const {
+    return lake_catalogue_cube(cube, n_slices, rows, cols, weights, WS_U8, seeds, want_labels, n_seeds);
+  }
+  std::vector<LakeCatalogue> merge_tree_stats_cube(const std::uint8_t *cube, std::size_t n_slices, std::size_t rows, std::size_t cols,
+                                                   const std::uint16_t *weights, const std::vector<std::vector<Seed>> *seeds = nullptr,
+                                                   bool want_labels = false, std::vector<std::size_t> *n_seeds = nullptr) const {
+    return lake_catalogue_cube(cube, n_slices, rows, cols, weights, WS_U16, seeds, want_labels, n_seeds);
+  }
 
  private:
+  std::vector<LakeCatalogue> lake_catalogue_cube(const std::uint8_t *cube, std::size_t n_slices, std::size_t rows, std::size_t cols,
+                                                 const void *weights, int dtype, const std::vector<std::vector<Seed>> *seeds,
+                                                 bool want_labels, std::vector<std::size_t> *n_seeds) const {
+    if (seeds && seeds->size() != n_slices) throw std::invalid_argument("one seed list per slice");
+    const std::size_t e = this->opt_.edge_correction ? 2 : 0, prow = rows + e, pcol = cols + e, npx = prow * pcol;
+    std::vector<std::uint64_t> packed;
+    std::vector<std::size_t> offs(n_slices + 1, 0), counts(n_slices, 0);
+    if (seeds)
+      for (std::size_t k = 0; k < n_slices; ++k) {
+        const auto one = detail::pack((*seeds)[k]);
+        packed.insert(packed.end(), one.begin(), one.end());
+        offs[k + 1] = offs[k] + (*seeds)[k].size();
+        counts[k] = (*seeds)[k].size();
+      }
+    // (as merge_tree_cube: a too small guess is answered before any flood with the count)
+    std::size_t cap = seeds ? offs[n_slices] + n_slices : n_slices * (rows * cols / 8 + 1), total = 0, failed = 0;
+    std::vector<ws_tree_node> flat(cap);
+    std::vector<ws_lake_stats> records(cap);
+    std::vector<usize> labels(want_labels ? n_slices * npx : 0);
+    for (int attempt = 0; attempt < 2; ++attempt) {
+      const int rc = ws_merge_tree_stats_batch(this->ctx_->get(), cube, n_slices, rows, cols, cols, rows * cols, seeds ? packed.data() : nullptr,
+                                               seeds ? offs.data() : nullptr, &this->opt_, weights, dtype, cols, rows * cols, flat.data(),
+                                               records.data(), cap, &total, want_labels ? labels.data() : nullptr, counts.data(), &failed);
+      if (rc == WS_ERR_CAPACITY && total > cap && attempt == 0) {
+        cap = total;
+        flat.resize(cap);
+        records.resize(cap);
+        continue;
+      }
+      this->ctx_->check(rc);
+      break;
+    }
+    std::vector<LakeCatalogue> out;
+    std::size_t at = 0;
+    for (std::size_t k = 0; k < n_slices; ++k) {
+      const std::size_t n = counts[k] + 1;
+      LakeCatalogue cat{MergeTree{std::vector<ws_tree_node>(flat.begin() + at, flat.begin() + at + n),
+                                  Array2<usize>(want_labels ? prow : 0, want_labels ? pcol : 0)},
+                        std::vector<ws_lake_stats>(records.begin() + at, records.begin() + at + n)};
+      if (want_labels) std::copy(labels.begin() + k * npx, labels.begin() + (k + 1) * npx, cat.tree.labels.data.begin());
+      out.push_back(std::move(cat));
+      at += n;
+    }
+    if (n_seeds) *n_seeds = counts;
+    return out;
+  }
   LakeCatalogue lake_catalogue(ArrayView2<std::uint8_t> input, const std::vector<Seed> &seeds, const void *weights, int dtype,
                                std::size_t weight_stride, bool want_labels) const {
     const std::size_t e = this->opt_.edge_correction ? 2 : 0;

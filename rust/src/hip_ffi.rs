@@ -276,6 +276,14 @@ extern "C" {
     pub fn ws_merge_tree_batch(ctx: *mut ws_ctx, cube: *const u8, n_slices: usize, h: usize, w: usize, row_stride: usize,
         slice_stride: usize, seeds_rc: *const u64, seed_offsets: *const usize, opt: *const ws_options, tree: *mut ws_tree_node,
         cap: usize, n_records: *mut usize, labels: *mut u64, n_seeds: *mut usize, failed_slice: *mut usize) -> c_int;
+    pub fn ws_merge_tree_stats_batch_device(ctx: *mut ws_ctx, d_cube: *const u8, n_slices: usize, h: usize, w: usize, row_stride: usize,
+        slice_stride: usize, d_seeds_rc: *const u32, seed_offsets: *const usize, opt: *const ws_options, d_weight: *const c_void,
+        weight_dtype: c_int, weight_row_stride: usize, weight_slice_stride: usize, d_tree: *mut ws_tree_node,
+        d_stats: *mut ws_lake_stats, d_labels: *mut u32, failed_slice: *mut usize) -> c_int;
+    pub fn ws_merge_tree_stats_batch(ctx: *mut ws_ctx, cube: *const u8, n_slices: usize, h: usize, w: usize, row_stride: usize,
+        slice_stride: usize, seeds_rc: *const u64, seed_offsets: *const usize, opt: *const ws_options, weight: *const c_void,
+        weight_dtype: c_int, weight_row_stride: usize, weight_slice_stride: usize, tree: *mut ws_tree_node, stats: *mut ws_lake_stats,
+        cap: usize, n_records: *mut usize, labels: *mut u64, n_seeds: *mut usize, failed_slice: *mut usize) -> c_int;
     pub fn ws_pre_processor_device(ctx: *mut ws_ctx, d_data: *const c_void, dtype: c_int, n_elems: usize,
         max_value: u8, d_out: *mut u8) -> c_int;
     pub fn ws_random_field_device(ctx: *mut ws_ctx, d_img: *mut u8, h: usize, w: usize, row_stride: usize,

@@ -164,6 +164,10 @@ SIGNATURES = {
     "ws_merge_tree_stats": (ctypes.c_int, [vp, vp, sz, sz, sz, vp, sz, ctypes.POINTER(Options), vp, ctypes.c_int, sz, vp, vp, vp]),
     "ws_merge_tree_batch_device": (ctypes.c_int, [vp, vp, sz, sz, sz, sz, sz, vp, szp, ctypes.POINTER(Options), vp, vp, szp]),
     "ws_merge_tree_batch": (ctypes.c_int, [vp, vp, sz, sz, sz, sz, sz, vp, szp, ctypes.POINTER(Options), vp, sz, szp, vp, szp, szp]),
+    "ws_merge_tree_stats_batch_device": (ctypes.c_int, [vp, vp, sz, sz, sz, sz, sz, vp, szp, ctypes.POINTER(Options), vp, ctypes.c_int, sz, sz,
+                                                        vp, vp, vp, szp]),
+    "ws_merge_tree_stats_batch": (ctypes.c_int, [vp, vp, sz, sz, sz, sz, sz, vp, szp, ctypes.POINTER(Options), vp, ctypes.c_int, sz, sz,
+                                                 vp, vp, sz, szp, vp, szp, szp]),
     "ws_pre_processor": (ctypes.c_int, [vp, vp, ctypes.c_int, sz, ctypes.c_uint8, vp]),
     "ws_pre_processor_device": (ctypes.c_int, [vp, vp, ctypes.c_int, sz, ctypes.c_uint8, vp]),
     "ws_block_init": (ctypes.c_int, [vp, sz, sz, vp, vp, sz, vp, vp]),

@@ -729,3 +729,74 @@ class MergingWatershed(_Transform):
             t = tree[first[k]:first[k + 1]]
             out.append(MergeTree(t[:, 0].copy(), t[:, 1].copy(), t[:, 2].copy(), t[:, 3].copy(), labels[k] if want_labels else None))
         return out if seeds is not None else (out, counts[:n].astype(np.int64))
+
+    def merge_tree_stats_cube(self, cube, seeds=None, weights=None, want_labels=False):
+        """merge_tree_stats of every slice cube[k] of a 3-D u8 array with seeds[k] -- or, with seeds None, the slice's own
+        find_local_minima -- and the weight plane weights[k] (a u8 or u16 cube of the cube's shape; None: the cube itself) in ONE
+        call of the library (ws_merge_tree_stats_batch: slices that stack run one flood, one set of per-level unions and one
+        fold launch per level, of the tree and of the statistics, for the whole cube).  Returns a list of (MergeTree, stats), one
+        per slice, as merge_tree_stats returns them for the slice alone: the slice's own colours, rows, columns and peak pixels
+        (and, with seeds None, the number of minima of every slice); want_labels as merge_tree_cube.  Not a method of the
+        reference."""
+        c = np.asarray(cube)
+        if c.ndim != 3:
+            raise ValueError("cube must be 3-D: (slices, rows, columns)")
+        if c.dtype != np.uint8:
+            raise ValueError("cube must be uint8")
+        n = c.shape[0]
+        if seeds is not None and len(seeds) != n:
+            raise ValueError("one seed list per slice")
+        wt, dtype = None, 0
+        if weights is not None:
+            wt = np.asarray(weights)
+            if wt.dtype not in (np.uint8, np.uint16) or wt.ndim != 3:
+                raise TypeError("weights must be a 3-D uint8 or uint16 array (quantise float data first: pre_processor_with_max)")
+            if wt.shape != c.shape:
+                raise ValueError(f"weights must have the cube's shape {c.shape}, not {wt.shape}")
+            wt = np.ascontiguousarray(wt)
+            dtype = _ffi.WS_DTYPES[wt.dtype.name]
+        c = np.ascontiguousarray(c)
+        _, h, w = c.shape
+        e = 2 if self.edge_correction else 0
+        if seeds is None:
+            flat, offs = None, None
+            cap = n * (h * w // 8 + 1)      # (as merge_tree_cube: a too small guess costs a second call, before any flood)
+        else:
+            lists = [np.asarray(s, dtype=np.uint64).reshape(-1, 2) for s in seeds]
+            offs = np.zeros(n + 1, dtype=np.uintp)
+            offs[1:] = np.cumsum([len(l) for l in lists])
+            flat = np.ascontiguousarray(np.concatenate(lists, axis=0) if lists else np.zeros((0, 2), dtype=np.uint64))
+            if flat.shape[0] == 0:
+                flat = np.zeros((1, 2), dtype=np.uint64)
+            cap = int(offs[n]) + n
+        labels = np.empty((n, h + e, w + e), dtype=np.uint64) if want_labels else None
+        counts = np.zeros(max(n, 1), dtype=np.uintp)
+        tree = np.empty((max(cap, 1), 4), dtype=np.uint32)
+        stats = np.empty(max(cap, 1), dtype=LAKE_STATS_DTYPE)
+        if n:
+            ctx = self._ctx()
+            total = ctypes.c_size_t(0)
+            failed = ctypes.c_size_t(0)
+            for attempt in range(2):
+                rc = _ffi.lib().ws_merge_tree_stats_batch(ctx.handle, c.ctypes.data, n, h, w, w, h * w,
+                                                          flat.ctypes.data if flat is not None else None,
+                                                          offs.ctypes.data_as(_ffi.szp) if offs is not None else None,
+                                                          ctypes.byref(self._opt), wt.ctypes.data if wt is not None else None, dtype, w, h * w,
+                                                          tree.ctypes.data, stats.ctypes.data, cap, ctypes.byref(total),
+                                                          labels.ctypes.data if want_labels else None, counts.ctypes.data_as(_ffi.szp),
+                                                          ctypes.byref(failed))
+                if rc == _ffi.WS_ERR_CAPACITY and total.value > cap and attempt == 0:
+                    cap = total.value
+                    tree = np.empty((cap, 4), dtype=np.uint32)
+                    stats = np.empty(cap, dtype=LAKE_STATS_DTYPE)
+                    continue
+                ctx.check(rc)
+                break
+        first = np.zeros(n + 1, dtype=np.int64)
+        first[1:] = np.cumsum((counts[:n] if seeds is None else np.diff(offs)).astype(np.int64) + 1)
+        out = []
+        for k in range(n):
+            t = tree[first[k]:first[k + 1]]
+            out.append((MergeTree(t[:, 0].copy(), t[:, 1].copy(), t[:, 2].copy(), t[:, 3].copy(), labels[k] if want_labels else None),
+                        stats[first[k]:first[k + 1]]))      # (views of one array, as the labels: 72 B a record add up)
+        return out if seeds is not None else (out, counts[:n].astype(np.int64))

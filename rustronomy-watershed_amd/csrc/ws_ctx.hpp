@@ -58,7 +58,9 @@ struct ws_ctx {
   wsapi::DevBuf tree_order, tree_ws, tree_out;
   // ws_merge_tree_batch(_device): a stack's records in the forest's numbering before they move to the caller's layout
   wsapi::DevBuf tree_forest;
-  // ws_merge_tree_stats(_device): the accumulator planes (68 B a colour); the host form's records and its weight plane on the device
+  // ws_merge_tree_stats(_device): the accumulator planes (68 B a colour); the host form's records and its weight plane on the device.
+  // ws_merge_tree_stats_batch(_device): the planes of the largest group (its colours, one entry more and one per slice of a group),
+  // the host form's records of the whole cube and its weight cube, contiguous
   wsapi::DevBuf lake_acc, lake_out, lake_weight;
   uint32_t *pinned = nullptr;      // FLAG_WORDS words of pinned host memory: the host's mirror of the flag block
   uint32_t *pinned_dev = nullptr;  // the same words as the device sees them (nullptr: not mapped, copies only)

@@ -937,13 +937,57 @@ int build_tree_stack(ws_ctx *c, const HistoryGroup &grp, size_t ns, const ws_opt
   return WS_OK;
 }
 
+// ---- merge_tree_stats of a cube of slices (ws_merge_tree_stats_batch(_device)) ------------------------------
+
+// the statistics request of a batch: the weight cube on the device (null: the image cube itself, u8) with its strides in
+// elements, and where the records go (device; the layout of d_tree)
+struct LakeBatchWanted {
+  const void *weight = nullptr;
+  int dtype = 0;
+  size_t stride = 0, slice_stride = 0;
+  ws_lake_stats *d_stats = nullptr;
+};
+
+// what both forms check after check_batch and check_plane, before anything runs: the weights as check_lake_weights for one slice's
+// plane (the 64-bit bound is a slice's: rows and columns restart in every slice), their slice stride as check_batch treats the cube's
+int check_lake_batch(ws_ctx *c, size_t n_slices, size_t h, size_t w, size_t ph, size_t pw, const void *weight, int dtype, size_t weight_stride,
+                     size_t weight_slice_stride) {
+  if (int rc = check_lake_weights(c, w, ph, pw, weight, dtype, weight_stride)) return rc;
+  if (weight && n_slices > 1 && weight_slice_stride < h * weight_stride) return fail(c, WS_ERR_BAD_ARG, "weight_slice_stride < h * weight_row_stride");
+  return WS_OK;
+}
+
+// the weights of slices k .. of the batch: the request's cube, or the image cube read as u8 with its own strides
+LakeWeights lake_weights_from(const LakeBatchWanted &ls, const uint8_t *d_cube, size_t stride, size_t slice_stride, size_t k, size_t h, size_t w,
+                              const ws_options *opt) {
+  const uint32_t off = opt->edge_correction ? 1u : 0u;
+  if (!ls.weight) return LakeWeights{d_cube + k * slice_stride, stride, (uint32_t)h, (uint32_t)w, off, 0, slice_stride};
+  const size_t elem = ls.dtype == WS_U16 ? 2 : 1;
+  return LakeWeights{(const uint8_t *)ls.weight + k * ls.slice_stride * elem, ls.stride, (uint32_t)h, (uint32_t)w, off, ls.dtype == WS_U16, ls.slice_stride};
+}
+
+// the statistics of the forest build_tree_stack has just folded in c->tree_forest (tree_fold's buckets are still in c->tree_ws and
+// c->tree_order), into the caller's layout at d_stats
+int build_lake_stats_stack(ws_ctx *c, const HistoryGroup &grp, size_t ns, const ws_options *opt, size_t ph, size_t pw, const LakeWeights &wt,
+                           ws_lake_stats *d_stats) {
+  const TreeStack st{grp.base, (uint32_t)grp.g, (uint32_t)(ph * pw)};
+  Span sp(c, KC_OTHER);
+  HIP_TRY(c, lake_stats_stack(c->stream, grp.keys, grp.labels, (const uint32_t *)c->uf_death.p, (const uint32_t *)c->uf_hook.p,
+                              (const TreeRec *)c->tree_forest.p, (const uint32_t *)c->seed_stack.p, ns + 1, (uint32_t)opt->max_water_level + 1,
+                              (const u64c *)c->tree_ws.p, (const uint32_t *)c->tree_order.p, wt, st, (int)pw, c->lake_acc.p,
+                              reinterpret_cast<LakeRec *>(d_stats)));
+  return WS_OK;
+}
+
 // The trees of a batch into d_tree (device; slice k's n_k + 1 records from (seed_offsets[k] - seed_offsets[0]) + k on), every group's
-// segmenting labels handed to labels(HistoryGroup) while they are on the context.  Every buffer the tree kernels need is sized for
-// the largest group BEFORE the first transform (as ensure_tree: nothing moves under the level loop's captured graphs).
+// segmenting labels handed to labels(HistoryGroup) while they are on the context; with ls, every group's statistics into
+// ls->d_stats in the same layout -- a stacked group's from the forest (lake_stats_stack: one fold launch per level for the group),
+// a looped slice's as ws_merge_tree_stats_device's with that slice's weight plane.  Every buffer the tree and statistics kernels
+// need is sized for the largest group BEFORE the first transform (as ensure_tree: nothing moves under the level loop's captured graphs).
 template <class F>
 int tree_batch_run(ws_ctx *c, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w, size_t stride, size_t slice_stride,
                    const uint32_t *d_seeds_rc, const size_t *seed_offsets, const ws_options *opt, size_t ph, size_t pw, ws_tree_node *d_tree,
-                   size_t *failed_slice, F labels) {
+                   size_t *failed_slice, F labels, const LakeBatchWanted *ls = nullptr) {
   HIP_TRY(c, hipSetDevice(c->device));
   size_t per_group = 0, most = 0, most_group = 0;
   for (size_t k = 0; k < n_slices; ++k) most = std::max(most, seed_offsets[k + 1] - seed_offsets[k]);
@@ -961,17 +1005,26 @@ int tree_batch_run(ws_ctx *c, const uint8_t *d_cube, size_t n_slices, size_t h, 
     if ((rc = ensure(c, c->tree_forest, (most_group + 1) * sizeof(TreeRec)))) return rc;
     if ((rc = ensure(c, c->seed_stack, (most_group * 2 + per_group + 1) * sizeof(uint32_t)))) return rc;      // (flood_stack's, for its largest group)
   }
+  // (the accumulator planes: a group's colours, the forest's entry 0 and one record 0 per slice of the group)
+  if (ls && (rc = ensure(c, c->lake_acc, (std::max(most, most_group) + 1 + per_group) * LAKE_ACC_BYTES))) return rc;
   const size_t s0 = seed_offsets[0];
   return history_batch_run(c, true, d_cube, n_slices, h, w, stride, slice_stride, d_seeds_rc, seed_offsets, opt, failed_slice,
                            [&](const HistoryGroup &grp) -> int {
                              const size_t k = grp.k_first, ns = seed_offsets[k + grp.g] - seed_offsets[k];
                              ws_tree_node *out = d_tree + (seed_offsets[k] - s0) + k;
+                             ws_lake_stats *out_stats = ls ? ls->d_stats + (seed_offsets[k] - s0) + k : nullptr;
                              if (grp.base) {
                                if (int rc_t = build_tree_stack(c, grp, ns, opt, ph, pw, out)) return rc_t;
+                               if (ls)
+                                 if (int rc_t = build_lake_stats_stack(c, grp, ns, opt, ph, pw, lake_weights_from(*ls, d_cube, stride, slice_stride, k, h, w, opt), out_stats))
+                                   return rc_t;
                              } else {
                                // the seed pairs as the flood took them: the caller's, or (shifted_seeds) moved into the padded plane
                                const uint32_t *seeds = seed_shift_of(opt) && ns ? (const uint32_t *)c->seeds.p : d_seeds_rc + 2 * seed_offsets[k];
                                if (int rc_t = build_tree(c, seeds, ns, opt, ph, pw, out)) return rc_t;
+                               if (ls)
+                                 if (int rc_t = build_lake_stats(c, seeds, ns, opt, ph, pw, out, lake_weights_from(*ls, d_cube, stride, slice_stride, k, h, w, opt), out_stats))
+                                   return rc_t;
                              }
                              return labels(grp);
                            });
@@ -1427,6 +1480,84 @@ int ws_merge_tree_batch(ws_ctx *c, const uint8_t *cube, size_t n_slices, size_t 
                       });
   if (rc) return rc;
   HIP_TRY(c, hipMemcpyAsync(tree, c->tree_out.p, total * sizeof(ws_tree_node), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return WS_OK;
+}
+
+int ws_merge_tree_stats_batch_device(ws_ctx *c, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w, size_t row_stride,
+                                     size_t slice_stride, const uint32_t *d_seeds_rc, const size_t *seed_offsets, const ws_options *opt,
+                                     const void *d_weight, int weight_dtype, size_t weight_row_stride, size_t weight_slice_stride,
+                                     ws_tree_node *d_tree, ws_lake_stats *d_stats, uint32_t *d_labels, size_t *failed_slice) {
+  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
+  if (!c) return WS_ERR_BAD_ARG;
+  if (failed_slice) *failed_slice = 0;
+  if (int rc = check_batch(c, n_slices, h, row_stride, slice_stride, seed_offsets, opt)) return rc;
+  size_t ph = 0, pw = 0;
+  if (int rc = check_plane(c, h, w, row_stride, opt, &ph, &pw)) return rc;
+  if (int rc = check_lake_batch(c, n_slices, h, w, ph, pw, d_weight, weight_dtype, weight_row_stride, weight_slice_stride)) return rc;
+  if (n_slices == 0) return WS_OK;
+  const size_t total = seed_offsets[n_slices] - seed_offsets[0], plane = ph * pw;
+  if (total >= 0xFFFFFFFFull) return fail(c, WS_ERR_TOO_LARGE, "too many seeds");
+  if (!d_tree || !d_stats || (!d_cube && h * w) || (!d_seeds_rc && total)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  LakeBatchWanted ls;
+  ls.weight = h * w ? d_weight : nullptr; ls.dtype = weight_dtype; ls.stride = weight_row_stride; ls.slice_stride = weight_slice_stride; ls.d_stats = d_stats;
+  if (int rc = tree_batch_run(c, d_cube, n_slices, h, w, row_stride, slice_stride, d_seeds_rc, seed_offsets, opt, ph, pw, d_tree, failed_slice,
+                              [&](const HistoryGroup &grp) -> int {
+                                if (d_labels && plane)
+                                  HIP_TRY(c, hipMemcpyAsync(d_labels + grp.k_first * plane, grp.labels, grp.g * plane * sizeof(uint32_t),
+                                                            hipMemcpyDeviceToDevice, c->stream));
+                                return (int)WS_OK;
+                              }, &ls))
+    return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return WS_OK;
+}
+
+int ws_merge_tree_stats_batch(ws_ctx *c, const uint8_t *cube, size_t n_slices, size_t h, size_t w, size_t row_stride, size_t slice_stride,
+                              const uint64_t *seeds_rc, const size_t *seed_offsets, const ws_options *opt, const void *weight, int weight_dtype,
+                              size_t weight_row_stride, size_t weight_slice_stride, ws_tree_node *tree, ws_lake_stats *stats, size_t cap,
+                              size_t *n_records, uint64_t *labels, size_t *n_seeds, size_t *failed_slice) {
+  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
+  if (!c) return WS_ERR_BAD_ARG;
+  if (failed_slice) *failed_slice = 0;
+  if (int rc = check_batch(c, seeds_rc ? n_slices : 0, h, row_stride, slice_stride, seed_offsets, opt)) return rc;
+  size_t ph = 0, pw = 0;
+  int rc = check_plane(c, h, w, row_stride, opt, &ph, &pw);
+  if (rc) return rc;
+  if ((rc = check_lake_batch(c, n_slices, h, w, ph, pw, weight, weight_dtype, weight_row_stride, weight_slice_stride))) return rc;
+  if (n_slices == 0) {
+    if (n_records) *n_records = 0;
+    return WS_OK;
+  }
+  if ((!cube && h * w) || ((!tree || !stats) && cap)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  if (seeds_rc && seed_offsets[n_slices] - seed_offsets[0] >= 0xFFFFFFFFull) return fail(c, WS_ERR_TOO_LARGE, "too many seeds");
+  std::vector<size_t> offs;
+  if ((rc = upload_batch(c, cube, n_slices, h, w, row_stride, slice_stride, seeds_rc, seed_offsets, offs, n_seeds, failed_slice))) return rc;
+  const size_t total = offs[n_slices] + n_slices, plane = ph * pw;
+  if (n_records) *n_records = total;
+  if (offs[n_slices] >= 0xFFFFFFFFull) return fail(c, WS_ERR_TOO_LARGE, "too many seeds");
+  if (cap < total) return fail(c, WS_ERR_CAPACITY, "record buffers too small");      // counted, nothing flooded
+  if ((rc = ensure(c, c->tree_out, total * sizeof(ws_tree_node)))) return rc;
+  if ((rc = ensure(c, c->lake_out, total * sizeof(ws_lake_stats)))) return rc;
+  if (labels && (rc = ensure(c, c->out64, std::max<size_t>(plane, 1) * sizeof(uint64_t)))) return rc;      // (the plane-by-plane copy widens there)
+  LakeBatchWanted ls;
+  ls.d_stats = (ws_lake_stats *)c->lake_out.p;
+  if (weight && h * w) {      // the weight cube contiguous on the context, before the first transform: nothing moves under the level loop's graphs
+    const size_t elem = weight_dtype == WS_U16 ? 2 : 1;
+    if ((rc = ensure(c, c->lake_weight, n_slices * h * w * elem))) return rc;
+    for (size_t k = 0; k < n_slices; ++k)
+      HIP_TRY(c, hipMemcpy2DAsync((uint8_t *)c->lake_weight.p + k * h * w * elem, w * elem, (const uint8_t *)weight + k * weight_slice_stride * elem,
+                                  weight_row_stride * elem, w * elem, h, hipMemcpyHostToDevice, c->stream));
+    ls.weight = c->lake_weight.p; ls.dtype = weight_dtype; ls.stride = w; ls.slice_stride = h * w;
+  }
+  rc = tree_batch_run(c, (const uint8_t *)c->batch_cube.p, n_slices, h, w, w, h * w, (const uint32_t *)c->batch_seeds.p, offs.data(), opt, ph, pw,
+                      (ws_tree_node *)c->tree_out.p, failed_slice, [&](const HistoryGroup &grp) -> int {
+                        if (!labels || !plane) return (int)WS_OK;
+                        return planes_to_host(c, grp.labels, labels + grp.k_first * plane, grp.g, plane);
+                      }, &ls);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemcpyAsync(tree, c->tree_out.p, total * sizeof(ws_tree_node), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(stats, c->lake_out.p, total * sizeof(ws_lake_stats), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return WS_OK;
 }

@@ -1705,6 +1705,13 @@ __device__ __forceinline__ uint32_t lake_weight(const LakeWeights &wt, uint32_t 
   return yy < wt.h && xx < wt.w ? (uint32_t)reinterpret_cast<const T *>(wt.p)[(size_t)yy * wt.stride + xx] : 0u;
 }
 
+// ... of slice k of a stack: the same plane, k slice strides on
+template <typename T>
+__device__ __forceinline__ uint32_t lake_weight_of_slice(const LakeWeights &wt, uint32_t k, uint32_t y, uint32_t x) {
+  const uint32_t yy = y - wt.off, xx = x - wt.off;
+  return yy < wt.h && xx < wt.w ? (uint32_t)reinterpret_cast<const T *>(wt.p)[(size_t)k * wt.slice_stride + (size_t)yy * wt.stride + xx] : 0u;
+}
+
 __global__ __launch_bounds__(256) void k_lake_init(u64c *sum, uint32_t *box, size_t n) {
   const size_t c = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (c < n) lake_store(sum, box, n, c, lake_none());
@@ -1739,10 +1746,16 @@ __device__ __forceinline__ void lake_flush(uint32_t *s_key, u64c *s_sum, uint32_
 // table takes the rest, and memory is touched once per root and workgroup.  The table lives across the workgroup's steps (the big
 // lake keeps its slot) until a step leaves it more than half full: below the percolation level a long run meets thousands of small
 // roots, and a table they have filled sends every newcomer to memory field by field; it is written out and starts again empty.
-template <typename T>
+// STACKED (lake_stats_stack): labels hold every slice's own colours and the accumulator planes have n_colours = the forest's colours
+// + stack.g entries.  A quad's slice is k = i0 / stack.plane (stack.plane % 4 == 0: a quad never straddles two slices, a workgroup's
+// step may); its colours move to the forest's numbering before the walk, its uncoloured pixels go to entry n_colours - stack.g + k
+// -- the slice's own record 0, which stands in for the root in the lane's join, the wave's and the table -- and rows, columns, the
+// pixel index of the peak and the weight plane are those of the slice.
+template <typename T, bool STACKED>
 __global__ __launch_bounds__(256) void k_lake_own(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ labels,
                                                   const uint32_t *__restrict__ death, const uint32_t *__restrict__ hook, LakeWeights wt,
-                                                  uint32_t W, u64c *sum, uint32_t *box, size_t n_colours, size_t n, size_t steps) {
+                                                  uint32_t W, u64c *sum, uint32_t *box, size_t n_colours, size_t n, size_t steps,
+                                                  TreeStack stack) {
   __shared__ u64c s_sum[6 * LAKE_SLOTS];
   __shared__ uint32_t s_box[5 * LAKE_SLOTS], s_key[LAKE_SLOTS], s_used;
   for (int j = threadIdx.x; j < LAKE_SLOTS; j += 256) {
@@ -1769,11 +1782,19 @@ __global__ __launch_bounds__(256) void k_lake_own(const uint32_t *__restrict__ k
         col[p] = in ? labels[i0 + p] : 0u;
       }
     }
+    uint32_t slice = 0, none = 0;      // the quad's slice and where its uncoloured pixels go
+    if constexpr (STACKED) {
+      slice = i0 < n ? (uint32_t)i0 / stack.plane : 0u;      // (n < 2^32: lake_stats_stack)
+      none = (uint32_t)n_colours - stack.g + slice;
+      const uint32_t b = stack.base[slice];
+#pragma unroll
+      for (int p = 0; p < 4; ++p) col[p] += col[p] != 0u ? b : 0u;
+    }
     uint32_t r[4], d[4];
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       const bool coloured = col[p] != 0u && arr[p] != 0xFFu;      // (as k_tree_own)
-      r[p] = coloured ? col[p] : 0u;
+      r[p] = coloured ? col[p] : none;
       d[p] = coloured ? death[col[p]] : TREE_ALIVE;
     }
     for (;;) {      // the root at the pixel's arrival level, four walks side by side
@@ -1786,13 +1807,17 @@ __global__ __launch_bounds__(256) void k_lake_own(const uint32_t *__restrict__ k
 #pragma unroll
       for (int p = 0; p < 4; ++p) if (go[p]) d[p] = death[r[p]];
     }
-    uint32_t y = i0 < n ? (uint32_t)i0 / W : 0u, x = i0 < n ? (uint32_t)i0 % W : 0u;      // (n < 2^32)
+    const uint32_t in0 = STACKED ? (uint32_t)i0 - slice * stack.plane : (uint32_t)i0;      // the quad's first pixel within its plane
+    uint32_t y = i0 < n ? in0 / W : 0u, x = i0 < n ? in0 % W : 0u;      // (n < 2^32)
     LakePart part[4];
     bool live[4];
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       live[p] = i0 + p < n;
-      part[p] = lake_pixel(live[p] ? lake_weight<T>(wt, y, x) : 0u, y, x, (uint32_t)(i0 + p));
+      uint32_t v = 0u;
+      if constexpr (STACKED) v = live[p] ? lake_weight_of_slice<T>(wt, slice, y, x) : 0u;
+      else v = live[p] ? lake_weight<T>(wt, y, x) : 0u;
+      part[p] = lake_pixel(v, y, x, in0 + (uint32_t)p);
       if (++x == W) { x = 0; ++y; }
     }
 #pragma unroll
@@ -1861,21 +1886,41 @@ __global__ __launch_bounds__(256) void k_lake_fold(const TreeRec *__restrict__ t
 }
 
 // The records.  A colour that dies at level 0 handed on nothing and was never the root of a pixel: it takes its seed pixel alone.
-template <typename T>
+// STACKED: entry c of the n_colours accumulator entries is forest colour c (1 .. n_colours - stack.g - 1: the record at
+// out[c + its slice], its seed pair in stacked rows) or slice k's uncoloured pixels (n_colours - stack.g + k: the record at
+// out[base[k] + k]); entry 0 of the forest is nobody's.
+template <typename T, bool STACKED>
 __global__ __launch_bounds__(256) void k_lake_write(const TreeRec *__restrict__ tree, const uint32_t *__restrict__ seeds_rc, LakeWeights wt, uint32_t W,
-                                                    const u64c *__restrict__ sum, const uint32_t *__restrict__ box, size_t n_colours, LakeRec *out) {
+                                                    const u64c *__restrict__ sum, const uint32_t *__restrict__ box, size_t n_colours, LakeRec *out,
+                                                    TreeStack stack) {
   const size_t c = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (c >= n_colours) return;
   LakePart a = lake_load(sum, box, n_colours, c);
-  if (c != 0) {
+  size_t at = c;
+  if constexpr (STACKED) {
+    const size_t forest = n_colours - stack.g;
+    if (c == 0) return;
+    if (c >= forest) {
+      const uint32_t k = (uint32_t)(c - forest);
+      at = (size_t)stack.base[k] + k;
+    } else {
+      const uint32_t k = slice_of_colour(stack.base, stack.g, (uint32_t)c);
+      at = c + k;
+      const TreeRec t = tree[c];
+      if (t.death_level == 0u && t.n_leaves != 0u) {
+        const uint32_t y = seeds_rc[2 * (c - 1)] - k * (stack.plane / W), x = seeds_rc[2 * (c - 1) + 1];
+        a = lake_pixel(lake_weight_of_slice<T>(wt, k, y, x), y, x, y * W + x);
+      }
+    }
+  } else if (c != 0) {
     const TreeRec t = tree[c];
     if (t.death_level == 0u && t.n_leaves != 0u) {
       const uint32_t y = seeds_rc[2 * (c - 1)], x = seeds_rc[2 * (c - 1) + 1];
       a = lake_pixel(lake_weight<T>(wt, y, x), y, x, y * W + x);
     }
   }
-  out[c] = LakeRec{a.w, a.wr, a.wc, a.r, a.c, a.r_min, a.r_max, a.c_min, a.c_max, a.w_min, (uint32_t)(a.peak >> 32),
-                   0xFFFFFFFFu - (uint32_t)a.peak, 0u};
+  out[at] = LakeRec{a.w, a.wr, a.wc, a.r, a.c, a.r_min, a.r_max, a.c_min, a.c_max, a.w_min, (uint32_t)(a.peak >> 32),
+                    0xFFFFFFFFu - (uint32_t)a.peak, 0u};
 }
 
 hipError_t lake_stats(hipStream_t s, const uint32_t *keys, const uint32_t *labels, const uint32_t *death, const uint32_t *hook, const TreeRec *tree,
@@ -1894,8 +1939,8 @@ hipError_t lake_stats(hipStream_t s, const uint32_t *keys, const uint32_t *label
     const size_t quads = (n + 1023) / 1024;
     const size_t steps = std::max<size_t>((quads + 2047) / 2048, 1);
     const unsigned grid = (unsigned)((quads + steps - 1) / steps);
-    if (wt.u16) k_lake_own<uint16_t><<<grid, 256, 0, s>>>(keys, labels, death, hook, wt, (uint32_t)w, sum, box, n_colours, n, steps);
-    else k_lake_own<uint8_t><<<grid, 256, 0, s>>>(keys, labels, death, hook, wt, (uint32_t)w, sum, box, n_colours, n, steps);
+    if (wt.u16) k_lake_own<uint16_t, false><<<grid, 256, 0, s>>>(keys, labels, death, hook, wt, (uint32_t)w, sum, box, n_colours, n, steps, TreeStack{});
+    else k_lake_own<uint8_t, false><<<grid, 256, 0, s>>>(keys, labels, death, hook, wt, (uint32_t)w, sum, box, n_colours, n, steps, TreeStack{});
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   if (n_colours > 1) {      // (tree_fold built order[] and its bounds under the same condition)
@@ -1906,8 +1951,44 @@ hipError_t lake_stats(hipStream_t s, const uint32_t *keys, const uint32_t *label
       if ((e = hipGetLastError()) != hipSuccess) return e;
     }
   }
-  if (wt.u16) k_lake_write<uint16_t><<<per_colour, 256, 0, s>>>(tree, seeds_rc, wt, (uint32_t)w, sum, box, n_colours, out);
-  else k_lake_write<uint8_t><<<per_colour, 256, 0, s>>>(tree, seeds_rc, wt, (uint32_t)w, sum, box, n_colours, out);
+  if (wt.u16) k_lake_write<uint16_t, false><<<per_colour, 256, 0, s>>>(tree, seeds_rc, wt, (uint32_t)w, sum, box, n_colours, out, TreeStack{});
+  else k_lake_write<uint8_t, false><<<per_colour, 256, 0, s>>>(tree, seeds_rc, wt, (uint32_t)w, sum, box, n_colours, out, TreeStack{});
+  return hipGetLastError();
+}
+
+hipError_t lake_stats_stack(hipStream_t s, const uint32_t *keys, const uint32_t *labels, const uint32_t *death, const uint32_t *hook,
+                            const TreeRec *forest, const uint32_t *stacked_rc, size_t n_colours, uint32_t levels, const u64c *ws,
+                            const uint32_t *order, const LakeWeights &wt, const TreeStack &st, int w, void *acc, LakeRec *out) {
+  if (n_colours == 0 || st.g == 0) return hipSuccess;
+  const size_t n = (size_t)st.g * st.plane, n_acc = n_colours + st.g;      // every slice's record 0 behind the forest's colours
+  // (slices, rows and columns are u32 divisions; a quad must not straddle two slices, a row must not either)
+  if (n > 0xFFFFFFFFull || n_acc > 0xFFFFFFFFull || st.plane == 0 || (st.plane & 3u) != 0 || w <= 0 || st.plane % (uint32_t)w != 0 ||
+      (reinterpret_cast<uintptr_t>(acc) & 7u) != 0)
+    return hipErrorInvalidValue;
+  u64c *sum = (u64c *)acc;
+  uint32_t *box = (uint32_t *)(sum + 6 * n_acc);
+  const unsigned per_entry = (unsigned)((n_acc + 255) / 256);
+  k_lake_init<<<per_entry, 256, 0, s>>>(sum, box, n_acc);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  {      // the grid of tree_own_counts_stack
+    const size_t quads = (n + 1023) / 1024;
+    const size_t steps = std::max<size_t>((quads + 2047) / 2048, 1);
+    const unsigned grid = (unsigned)((quads + steps - 1) / steps);
+    if (wt.u16) k_lake_own<uint16_t, true><<<grid, 256, 0, s>>>(keys, labels, death, hook, wt, (uint32_t)w, sum, box, n_acc, n, steps, st);
+    else k_lake_own<uint8_t, true><<<grid, 256, 0, s>>>(keys, labels, death, hook, wt, (uint32_t)w, sum, box, n_acc, n, steps, st);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  if (n_colours > 1) {      // ONE launch per level for the whole stack: parents are the forest's, the planes are n_acc long
+    const u64c *off = ws + NLEVELS + 1;
+    const unsigned grid = (unsigned)std::min<size_t>(std::max<size_t>(n_colours / (256 * 64), 1), 128);
+    for (uint32_t l = 1; l < levels; ++l) {
+      k_lake_fold<<<grid, 256, 0, s>>>(forest, sum, box, n_acc, order, off + l);
+      if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+  }
+  if (wt.u16) k_lake_write<uint16_t, true><<<per_entry, 256, 0, s>>>(forest, stacked_rc, wt, (uint32_t)w, sum, box, n_acc, out, st);
+  else k_lake_write<uint8_t, true><<<per_entry, 256, 0, s>>>(forest, stacked_rc, wt, (uint32_t)w, sum, box, n_acc, out, st);
   return hipGetLastError();
 }
 

@@ -173,12 +173,14 @@ struct LakeRec {      // == ws_lake_stats
   uint32_t r_min, r_max, c_min, c_max, w_min, w_max, peak_pixel, reserved;
 };
 // the weight plane: h x w elements of u8 or u16 (u16 != 0), `stride` elements a row; pixel (r, x) of it sits at (r + off, x + off)
-// of the padded plane and every other pixel of that plane weighs 0
+// of the padded plane and every other pixel of that plane weighs 0.  A stack of slices (lake_stats_stack) reads slice k's plane
+// slice_stride elements behind slice k - 1's (last, so that the single field's aggregate initialisers leave it 0).
 struct LakeWeights {
   const void *p;
   size_t stride;
   uint32_t h, w, off;
   int u16;
+  size_t slice_stride;
 };
 constexpr size_t LAKE_ACC_BYTES = 6 * sizeof(u64c) + 5 * sizeof(uint32_t);      // per colour: five sums and the packed peak, then the box and w_min
 // After tree_init / tree_own_counts / tree_fold of the same transform (tree: finished records; ws, order: tree_fold's buckets, left
@@ -187,5 +189,14 @@ constexpr size_t LAKE_ACC_BYTES = 6 * sizeof(u64c) + 5 * sizeof(uint32_t);      
 hipError_t lake_stats(hipStream_t s, const uint32_t *keys, const uint32_t *labels, const uint32_t *death, const uint32_t *hook, const TreeRec *tree,
                       const uint32_t *seeds_rc, size_t n_colours, uint32_t levels, const u64c *ws, const uint32_t *order, const LakeWeights &wt, int h,
                       int w, void *acc, LakeRec *out);
+// The same over the forest of a stack (ws_merge_tree_stats_batch_device), after tree_init_stack / tree_own_counts_stack / tree_fold:
+// `forest` in the forest's numbering (n_colours = the stack's seeds + 1), stacked_rc the stacked seed pairs (flood_stack: row =
+// slice * slice rows + the row in the padded plane), w the plane's width.  Rows, columns and peak_pixel are those of a pixel within
+// its own slice, its weight comes from its slice's plane, and an uncoloured pixel of slice k goes to accumulator entry n_colours + k:
+// acc holds (n_colours + st.g) * LAKE_ACC_BYTES.  Writes the caller's slice-major layout: forest colour c at out[c + its slice],
+// slice k's record 0 at out[base[k] + k] -- n_colours - 1 + st.g records.
+hipError_t lake_stats_stack(hipStream_t s, const uint32_t *keys, const uint32_t *labels, const uint32_t *death, const uint32_t *hook,
+                            const TreeRec *forest, const uint32_t *stacked_rc, size_t n_colours, uint32_t levels, const u64c *ws,
+                            const uint32_t *order, const LakeWeights &wt, const TreeStack &st, int w, void *acc, LakeRec *out);
 
 }  // namespace wsk

@@ -374,5 +374,47 @@ class DeviceEngine:
                                                                  ctypes.byref(failed)))
         return (out, labels) if want_labels else out
 
+    def merge_tree_stats_batch(self, cube, seeds, seed_offsets, weights=None, max_level=254, edge=False, seed_shift=False,
+                               want_labels=False, out=None, out_stats=None):
+        """merge_tree_stats of every slice of a cube with everything in HBM (ws_merge_tree_stats_batch_device); cube, seeds and
+        seed_offsets as merge_tree_batch.  Returns (tree, stats): the (n_seeds_total + S, 4) int32 tensor of merge_tree_batch and
+        an (n_seeds_total + S, 9) int64 tensor of raw ws_lake_stats records as merge_tree_stats's, in the same slice-major layout
+        -- every slice's records are those of merge_tree_stats on the slice alone.  weights: a 3-D uint8 or int16 / uint16 (taken
+        as u16 bits) device tensor of the cube's shape whose rows are contiguous (row and slice strides in elements are
+        honoured), None: the cube itself.  With want_labels returns (tree, stats, labels).  `out`, `out_stats`: reusable
+        contiguous tensors of those shapes."""
+        offs = self._batch_args(cube, seeds, seed_offsets)
+        s, h, w = cube.shape
+        e = 2 if edge else 0
+        dtype, wrow, wslice = 0, 0, 0
+        if weights is not None:
+            u16 = {torch.int16, getattr(torch, "uint16", torch.int16)}
+            if weights.dtype != torch.uint8 and weights.dtype not in u16:
+                raise TypeError("weights must be a uint8, uint16 or int16 (u16 bits) tensor")
+            if not weights.is_cuda or weights.dim() != 3 or tuple(weights.shape) != (s, h, w) or (w > 1 and weights.stride(2) != 1):
+                raise ValueError(f"weights must be a device tensor of shape {(s, h, w)} with contiguous rows")
+            dtype = _ffi.WS_DTYPES["uint8" if weights.dtype == torch.uint8 else "uint16"]
+            wrow = weights.stride(1) if h > 1 else w
+            wslice = weights.stride(0) if s > 1 else h * wrow
+        total = int(seed_offsets[-1]) - int(seed_offsets[0]) + s
+        if out is None:
+            out = torch.empty((total, 4), dtype=torch.int32, device=self.device)
+        elif out.dtype != torch.int32 or not out.is_contiguous() or tuple(out.shape) != (total, 4):
+            raise ValueError(f"out must be a contiguous int32 tensor of shape {(total, 4)}")
+        if out_stats is None:
+            out_stats = torch.empty((total, 9), dtype=torch.int64, device=self.device)
+        elif out_stats.dtype != torch.int64 or not out_stats.is_contiguous() or tuple(out_stats.shape) != (total, 9):
+            raise ValueError(f"out_stats must be a contiguous int64 tensor of shape {(total, 9)}")
+        labels = torch.empty((s, h + e, w + e), dtype=torch.int32, device=self.device) if want_labels else None
+        if s:
+            opt = self.options(max_level, edge, None, seed_shift)
+            failed = ctypes.c_size_t(0)
+            self.ctx.check(_ffi.lib().ws_merge_tree_stats_batch_device(self.ctx.handle, cube.data_ptr(), s, h, w, w, h * w,
+                                                                       seeds.data_ptr() if seeds.numel() else None, offs, ctypes.byref(opt),
+                                                                       weights.data_ptr() if weights is not None else None, dtype, wrow, wslice,
+                                                                       out.data_ptr(), out_stats.data_ptr(),
+                                                                       labels.data_ptr() if want_labels else None, ctypes.byref(failed)))
+        return (out, out_stats, labels) if want_labels else (out, out_stats)
+
     def stats(self):
         return self.ctx.stats()

@@ -121,6 +121,8 @@ def drive():
                 ("ws_transform_history_batch", lambda: mer.transform_history_cube(hcube, hlists, levels=[0, 100, 254])),
                 ("ws_merge_tree_batch_device", lambda: eng.merge_tree_batch(cube, bseeds, offs, edge=edge, want_labels=True)),
                 ("ws_merge_tree_batch", lambda: mer.merge_tree_cube(hcube, hlists, want_labels=True)),
+                ("ws_merge_tree_stats_batch_device", lambda: eng.merge_tree_stats_batch(cube, bseeds, offs, edge=edge, want_labels=True)),
+                ("ws_merge_tree_stats_batch", lambda: mer.merge_tree_stats_cube(hcube, hlists, want_labels=True)),
             ]
             # the live-list form of the merging lists, with the threshold lowered (1: the lowest that can be set)
             live = [c for c in calls if c[0] in ("ws_transform_to_list_device mer", "ws_lists_from_arrival_device mer", "ws_transform_to_list mer",
