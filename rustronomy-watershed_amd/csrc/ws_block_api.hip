@@ -106,8 +106,12 @@ int ws_block_resolve_ring(ws_ctx *c, const uint32_t *d_keys, uint32_t *d_labels,
   uint32_t *flags = (uint32_t *)c->flags.p;
   HIP_TRY(c, hipMemsetAsync(flags + FLAG_OVERFLOW, 0, sizeof(uint32_t), c->stream));
   c->misc_clean = false;
-  HIP_TRY(c, resolve_two_launch(c->stream, d_keys, d_labels, (int)h, (int)w, (uint32_t *)c->refs.p, c->debug_max_iters, nullptr, nullptr,
-                                nullptr, nullptr, 0, flags + FLAG_OVERFLOW, nullptr, 4));
+  ResolveJob job;
+  job.keys = d_keys; job.labels = d_labels; job.h = (int)h; job.w = (int)w;
+  job.ref_scratch = (uint32_t *)c->refs.p; job.max_rounds = c->debug_max_iters;
+  job.carry_flag = flags + FLAG_OVERFLOW;
+  job.halo_flags = 4;      // the border ring
+  HIP_TRY(c, resolve_two_launch(c->stream, job));
   HIP_TRY(c, hipMemcpyAsync(&c->pinned[FLAG_OVERFLOW], flags + FLAG_OVERFLOW, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (c->pinned[FLAG_OVERFLOW]) return fail(c, WS_ERR_RING_OVERFLOW, "more than 2^24-1 flood rings inside one level");
@@ -223,8 +227,13 @@ int ws_block_resolve_local(ws_ctx *c, const uint32_t *d_keys, uint32_t *d_labels
   uint32_t *seed_mask = (uint32_t *)c->seed_tab.p, *word_base = seed_mask + nwords;
   const int halo = (halo_top ? 1 : 0) | (halo_bottom ? 2 : 0);
   c->misc_clean = false;
-  HIP_TRY(c, resolve_two_launch(c->stream, d_keys, d_labels, (int)h, (int)w, (uint32_t *)c->refs.p, c->debug_max_iters, seed_mask, word_base,
-                                nullptr, nullptr, 0, flags + FLAG_OVERFLOW, flags + FLAG_SEED_ERR, halo));
+  ResolveJob job;
+  job.keys = d_keys; job.labels = d_labels; job.h = (int)h; job.w = (int)w;
+  job.ref_scratch = (uint32_t *)c->refs.p; job.max_rounds = c->debug_max_iters;
+  job.seed_mask = seed_mask; job.word_base = word_base; job.seed_err = flags + FLAG_SEED_ERR;
+  job.carry_flag = flags + FLAG_OVERFLOW;
+  job.halo_flags = halo;
+  HIP_TRY(c, resolve_two_launch(c->stream, job));
   HIP_TRY(c, hipMemcpyAsync(&c->pinned[FLAG_OVERFLOW], flags + FLAG_OVERFLOW, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (c->pinned[FLAG_OVERFLOW]) return fail(c, WS_ERR_RING_OVERFLOW, "more than 2^24-1 flood rings inside one level");

@@ -128,7 +128,7 @@ struct RelaxPlane {
   const uint32_t *seed_labels = nullptr;    // non-null: pass 0 derives the stamps from this label plane
   bool seed_bits = false;                   // ... which is one bit per pixel (seed_tables) instead
   int slice_h = 0;                          // > 0: the plane is a stack of independent slices of this many rows
-  bool carry_checked_later = false;         // the caller's resolve_two_launch(.., carry_flag) looks for ring carries
+  bool carry_checked_later = false;         // the caller's resolve_two_launch (ResolveJob::carry_flag) looks for ring carries
   bool padded = false;                      // edge correction: img is the caller's (h-2) x (w-2) image, the ring of zeros is virtual
   uint32_t *tile_list = nullptr;            // relax_list_words(h, w) words: late passes run from a compacted list of tiles
   size_t seam_min_px = (size_t)1 << 24;     // planes from this many pixels on repair pass 0's seams with bands and strips (ws_relax_plan.hpp)
@@ -139,22 +139,28 @@ struct RelaxPlan;
 RelaxPlan relax_plan_for(const RelaxPlane &plane, uint32_t pass);      // what relax_pass launches for that pass (ws_relax_plan.hpp)
 size_t relax_list_words(int h, int w);
 
-// label resolve, iterative form (row blocks of a tiled field, planes >= 2^31 pixels): 64x64 tiles
+// label resolve (ws_resolve.hip, ws_resolve_tile.hpp), iterative form (row blocks of a tiled field, planes >= 2^31 pixels): 64x64 tiles
 size_t resolve_tiles(int h, int w);
 hipError_t resolve_pass(hipStream_t s, const uint32_t *keys, uint32_t *labels, int h, int w,
                         uint32_t pass, uint32_t *stamps, PassFlags pf);
 // label resolve without a launch loop (pointer jumping in LDS + reference chase); needs h*w < 2^31
-// ref_scratch: resolve_ref_capacity(h, w) words (per-wave work lists of the pixels whose chain leaves their tile)
 size_t resolve_ref_capacity(int h, int w);
-hipError_t resolve_two_launch(hipStream_t s, const uint32_t *keys, uint32_t *labels, int h, int w, uint32_t *ref_scratch,
-                              uint32_t max_rounds = 0xFFFFFFFFu,
-                              const uint32_t *seed_mask = nullptr, const uint32_t *word_base = nullptr,    // seed_tables() form
-                              uint32_t *tile_min = nullptr,       // merging: per 64x64 tile, one lake? + a colour of it (ws_merge.hpp)
-                              const uint32_t *gate = nullptr,     // speculative launch: a pass's convergence slot; both kernels leave if it is set
-                              int slice_h = 0,                    // > 0: stack of independent slices (see relax_pass)
-                              uint32_t *carry_flag = nullptr,     // set when a stamp carried out of its ring field (relax_pass with fresh_keys leaves the test to this kernel)
-                              const uint32_t *seed_err = nullptr,    // seed_tables()' three error words: both kernels leave when the tables are invalid
-                              int halo_flags = 0);                   // row block: bit 0 / 1 = the first / last row is a neighbour's (chains stop there)
+// One two-launch resolve: a caller fills what it uses.
+struct ResolveJob {
+  const uint32_t *keys = nullptr;           // the finished stamp plane
+  uint32_t *labels = nullptr;               // label plane: painted seeds in (or nothing, with seed tables), every pixel's colour out
+  int h = 0, w = 0;
+  uint32_t *ref_scratch = nullptr;          // resolve_ref_capacity(h, w) words (per-wave work lists of the pixels whose chain leaves their tile)
+  uint32_t max_rounds = 0xFFFFFFFFu;        // cap on the in-tile jumping rounds: timing experiments only (WS_DEBUG_MAXIT)
+  const uint32_t *seed_mask = nullptr;      // seed_tables() form: one bit per pixel, the seeds were never painted ...
+  const uint32_t *word_base = nullptr;      // ... and per 32-pixel word the list index of its first seed
+  uint32_t *tile_min = nullptr;             // merging: per 64x64 tile, one lake? + a colour of it (ws_merge.hpp); ignored when halo_flags is set
+  const uint32_t *gate = nullptr;           // speculative launch: a pass's convergence slot; both kernels leave if it is set
+  uint32_t *carry_flag = nullptr;           // set when a stamp carried out of its ring field (relax_pass with carry_checked_later leaves the test to this kernel)
+  const uint32_t *seed_err = nullptr;       // seed_tables()' three error words: both kernels leave when the tables are invalid
+  int halo_flags = 0;                       // row block: 1 / 2 = the first / last row is a neighbour's (chains stop there); 4, without seed tables: a tile of a field cut both ways, the plane's border RING holds other ranks' pixels (roots like seeds, not flooded here)
+};
+hipError_t resolve_two_launch(hipStream_t s, const ResolveJob &job);
 hipError_t resolve_chase_again(hipStream_t s, uint32_t *labels, int h, int w, uint32_t *ref_scratch);
 
 // row blocks of one field tiled over ranks (ws_block.hip)

@@ -81,6 +81,17 @@ int run_fused_form(ws_ctx *c, const uint8_t *d_img, size_t stride, int ph, int p
   key.from_minima = minima != nullptr;
   key.persist_mode = persist_mode;
   if (minima) { key.seeds = minima->d_list; key.n_seeds = minima->cap; }
+  // the label resolve of this transform (a stack of slices resolves like one plane: a slice's border rows never flood)
+  auto resolve_job = [&](const uint32_t *gate) {
+    ResolveJob job;
+    job.keys = keys; job.labels = d_labels; job.h = ph; job.w = pw;
+    job.ref_scratch = (uint32_t *)c->refs.p; job.max_rounds = c->debug_max_iters;
+    job.seed_mask = seed_mask; job.word_base = word_base; job.seed_err = flags + FLAG_SEED_ERR;
+    job.tile_min = c->tile_min_out;
+    job.gate = gate;
+    job.carry_flag = flags + FLAG_OVERFLOW;
+    return job;
+  };
   // the tables: from the list, or from the image
   auto make_tables = [&]() -> hipError_t {
     if (!minima)
@@ -121,8 +132,7 @@ int run_fused_form(ws_ctx *c, const uint8_t *d_img, size_t stride, int ph, int p
     for (uint32_t pass = 0; pass < GRAPH_PASSES && e == hipSuccess; ++pass) e = relax_pass(c->stream, captured, pass);
     const uint32_t last = GRAPH_PASSES - 1;
     if (e == hipSuccess)
-      e = resolve_two_launch(c->stream, keys, d_labels, ph, pw, (uint32_t *)c->refs.p, c->debug_max_iters, seed_mask, word_base,
-                             c->tile_min_out, edge_slot(flags, last), slice_h, flags + FLAG_OVERFLOW, flags + FLAG_SEED_ERR);
+      e = resolve_two_launch(c->stream, resolve_job(edge_slot(flags, last)));
     // the read-backs: the lookahead pass's convergence slot and the error words
     if (e == hipSuccess && c->pinned_dev)
       e = words_to_host(c->stream, edge_slot(flags, last), FLAG_SLOT, c->pinned_dev + FLAG_EDGE + (last % COUNTER_RING) * FLAG_SLOT,
@@ -184,8 +194,7 @@ int run_fused_form(ws_ctx *c, const uint8_t *d_img, size_t stride, int ph, int p
   if (two_launch && (rc = ensure(c, c->refs, resolve_ref_capacity(ph, pw) * sizeof(uint32_t)))) return rc;
   auto resolve = [&](const uint32_t *gate) -> int {
     Span sp(c, KC_RESOLVE);
-    HIP_TRY(c, resolve_two_launch(c->stream, keys, d_labels, ph, pw, (uint32_t *)c->refs.p, c->debug_max_iters, seed_mask, word_base,
-                                  c->tile_min_out, gate, slice_h, flags + FLAG_OVERFLOW, flags + FLAG_SEED_ERR));
+    HIP_TRY(c, resolve_two_launch(c->stream, resolve_job(gate)));
     return WS_OK;
   };
   uint32_t speculated_after = 0xFFFFFFFFu, converged_at = 0xFFFFFFFFu;

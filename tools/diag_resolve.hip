@@ -2,6 +2,7 @@
 // hipcc --offload-arch=gfx950 -O3 -std=c++17 -DWS_DIAG_STAMPS -Irustronomy-watershed_amd/csrc -o tools/_build/diag_resolve tools/diag_resolve.hip
 #include "../rustronomy-watershed_amd/csrc/ws_relax.hip"
 #include "../rustronomy-watershed_amd/csrc/ws_kernels.hip"
+#include "../rustronomy-watershed_amd/csrc/ws_resolve.hip"      // after ws_relax.hip, whose WS_STAMP hooks ws_resolve_tile.hpp then keeps
 #include <algorithm>
 #include <cstdio>
 #include <vector>
@@ -38,7 +39,8 @@ int main() {
     CHECK(hipMemset(diag, 0, (size_t)rtiles * 64));
     CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_diag), &diag, sizeof(diag)));
     hipEvent_t a, b; CHECK(hipEventCreate(&a)); CHECK(hipEventCreate(&b)); CHECK(hipEventRecord(a));
-    CHECK(resolve_two_launch(0, keys, labels, H, W, refs));
+    ResolveJob job; job.keys = keys; job.labels = labels; job.h = H; job.w = W; job.ref_scratch = refs;
+    CHECK(resolve_two_launch(0, job));
     CHECK(hipEventRecord(b)); CHECK(hipEventSynchronize(b)); float ms; CHECK(hipEventElapsedTime(&ms, a, b));
     std::vector<unsigned long long> h((size_t)rtiles * 8); CHECK(hipMemcpy(h.data(), diag, h.size() * 8, hipMemcpyDeviceToHost));
     std::vector<double> ph[5], life; double rounds = 0; unsigned long long t_first = ~0ull, t_last = 0;
