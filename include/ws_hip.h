@@ -471,6 +471,23 @@ int ws_merge_tree_stats_device(ws_ctx *ctx, const uint8_t *d_img, size_t h, size
 int ws_merge_tree_stats(ws_ctx *ctx, const uint8_t *img, size_t h, size_t w, size_t row_stride, const uint64_t *seeds_rc,
                         size_t n_seeds, const ws_options *opt, const void *weight, int weight_dtype, size_t weight_row_stride,
                         ws_tree_node *tree, ws_lake_stats *stats, uint64_t *labels);
+/* The same tree, and with d_stats != NULL the same catalogue, from a segmenting transform that has already run -- here or on other
+ * devices -- without a second flood: d_keys and d_seg_labels as ws_lists_from_arrival_device (h x w u32 planes as they stand, a
+ * padded plane passed padded; opt->edge_correction is ignored, only max_water_level is read), n_seeds = the number of colours.
+ * No seed list comes in: seeds are coloured before level 0 and nothing else is (lib.rs:1675-1677), so stamp 0 marks the seed
+ * pixels and the label there is the colour that survived seeding (lib.rs:1670-1677); a colour without a stamp-0 pixel does not
+ * exist.  d_tree: n_seeds + 1 records, bit-identical to ws_merge_tree_device's for the transform that produced the planes.
+ * d_stats == NULL: the tree alone, the weight arguments are ignored.  d_stats != NULL: n_seeds + 1 records, bit-identical to
+ * ws_merge_tree_stats_device's; d_weight is an h x w plane of the shape passed, no offset, WS_U8 or WS_U16 (anything else:
+ * WS_ERR_UNSUPPORTED), weight_row_stride elements a row -- this form has no image, so d_weight == NULL is WS_ERR_BAD_ARG; a
+ * plane too large for 64-bit moments is WS_ERR_TOO_LARGE as there.  n_seeds == 0 or h * w == 0 writes record 0 only.  Null
+ * planes with a non-zero size, bad options and a context that holds a begun transform are refused before anything runs and
+ * leave the outputs untouched.  The planes stay the caller's (they may be views off 16-byte alignment: scalar loads then), and
+ * ws_last_arrival_device keeps reporting what it reported before.  Workspace as ws_merge_tree(_stats)_device's without the
+ * flood's, plus 8 B a colour for the recovered seed pixels. */
+int ws_merge_tree_from_arrival_device(ws_ctx *ctx, const uint32_t *d_keys, const uint32_t *d_seg_labels, size_t h, size_t w,
+                                      size_t n_seeds, const ws_options *opt, const void *d_weight, int weight_dtype,
+                                      size_t weight_row_stride, ws_tree_node *d_tree, ws_lake_stats *d_stats);
 /* transform_history of every slice of a cube for a list of water levels (tests/integration.rs:267,356 take a cube apart slice by
  * slice), everything in HBM.  Slices, seeds, seed_offsets (n_slices + 1 entries, on the HOST), edge correction, duplicate seeds
  * and *failed_slice as ws_transform_to_list_batch_device; levels, n_levels (0: nothing runs, nothing is written), merging and the
@@ -738,6 +755,32 @@ int ws_transform_to_list_tiled2d_device(ws_group *g, size_t field_h, size_t fiel
 int ws_segment_tiled2d(ws_group *g, const uint8_t *img, size_t h, size_t w, size_t row_stride, const uint64_t *seeds_rc,
                        size_t n_seeds, const ws_options *opt, int py, int px, int merging, uint64_t *out_labels,
                        uint32_t *exchange_rounds);
+
+/* The merging transform's lake hierarchy (ws_merge_tree_device) and, with d_stats != NULL, the catalogue of its lakes
+ * (ws_merge_tree_stats_device) of a field in row blocks: blocks and flood as ws_transform_to_list_tiled_device -- the segmenting
+ * flood runs on all ranks and leaves every block's labels in d_labels -- then the owned rows of stamps and labels are gathered on
+ * rank 0 (8 B per pixel), whose context calls ws_merge_tree_from_arrival_device on the whole plane.  d_tree, d_stats (n_seeds_total
+ * + 1 records each) and d_weight (the whole field_h x w plane, weight_row_stride elements a row) live on rank 0's device, in the
+ * process that holds rank 0; elsewhere they are ignored.  No rank holds the whole image: d_stats != NULL with d_weight == NULL is
+ * WS_ERR_BAD_ARG before anything runs.  Edge correction is WS_ERR_UNSUPPORTED (pad the field first), colours stay below 2^31 and
+ * every rank owns a row, as for the lists.  The records equal the single-context call's on the whole field bit for bit.  Rank 0
+ * holds, per pixel, the 8 B gathered and the unions' buckets (at most 20 B); per colour 16 B of union-find and forest, 8 B of
+ * recovered seed pixels, 4 B of ordering, and 68 B more with the catalogue -- all reserved before the first gather. */
+int ws_merge_tree_tiled_device(ws_group *g, size_t field_h, size_t w, size_t n_seeds_total, const ws_tile_block *blocks,
+                               const ws_options *opt, const void *d_weight, int weight_dtype, size_t weight_row_stride,
+                               ws_tree_node *d_tree, ws_lake_stats *d_stats, uint32_t *exchange_rounds);
+/* ... of a field in py x px tiles: blocks and flood as ws_transform_to_list_tiled2d_device, the owned rectangles gathered on rank 0. */
+int ws_merge_tree_tiled2d_device(ws_group *g, size_t field_h, size_t field_w, int py, int px, size_t n_seeds_total,
+                                 const ws_tile_block2d *blocks, const ws_options *opt, const void *d_weight, int weight_dtype,
+                                 size_t weight_row_stride, ws_tree_node *d_tree, ws_lake_stats *d_stats, uint32_t *exchange_rounds);
+/* ... and with host buffers, as ws_transform_to_list_tiled takes them: every rank of the group calls it with the SAME arguments
+ * and uploads its rows; `tree` and `stats` (nullable; n_seeds + 1 records each) are filled in the process that holds rank 0.
+ * Edge correction pads the field first (lib.rs:1640-1666): the tree is that of the padded plane, seed_shift is honoured and the
+ * weight plane gets a ring of weight 0, as ws_merge_tree_stats does it.  weight == NULL: the image itself as u8, which rank 0
+ * uploads whole.  For every option combination ws_merge_tree_stats accepts the records equal its records on the same arguments. */
+int ws_merge_tree_tiled(ws_group *g, const uint8_t *img, size_t h, size_t w, size_t row_stride, const uint64_t *seeds_rc,
+                        size_t n_seeds, const ws_options *opt, const void *weight, int weight_dtype, size_t weight_row_stride,
+                        ws_tree_node *tree, ws_lake_stats *stats, uint32_t *exchange_rounds);
 
 /* BASELINE config C4 over a group: a batch of independent slices, slice i on rank i % world, a rank's slices as ONE stacked
  * transform (ws_segment_batch_device) -- no exchange step at all.  One descriptor per LOCAL rank: the rank's own slices,

@@ -270,6 +270,9 @@ extern "C" {
     pub fn ws_merge_tree_stats(ctx: *mut ws_ctx, img: *const u8, h: usize, w: usize, row_stride: usize, seeds_rc: *const u64,
         n_seeds: usize, opt: *const ws_options, weight: *const c_void, weight_dtype: c_int, weight_row_stride: usize,
         tree: *mut ws_tree_node, stats: *mut ws_lake_stats, labels: *mut u64) -> c_int;
+    pub fn ws_merge_tree_from_arrival_device(ctx: *mut ws_ctx, d_keys: *const u32, d_seg_labels: *const u32, h: usize, w: usize, n_seeds: usize,
+        opt: *const ws_options, d_weight: *const c_void, weight_dtype: c_int, weight_row_stride: usize, d_tree: *mut ws_tree_node,
+        d_stats: *mut ws_lake_stats) -> c_int;
     pub fn ws_merge_tree_batch_device(ctx: *mut ws_ctx, d_cube: *const u8, n_slices: usize, h: usize, w: usize, row_stride: usize,
         slice_stride: usize, d_seeds_rc: *const u32, seed_offsets: *const usize, opt: *const ws_options, d_tree: *mut ws_tree_node,
         d_labels: *mut u32, failed_slice: *mut usize) -> c_int;
@@ -344,6 +347,15 @@ extern "C" {
                                                uncoloured: *mut u64, exchange_rounds: *mut u32) -> c_int;
     pub fn ws_segment_tiled2d(g: *mut ws_group, img: *const u8, h: usize, w: usize, row_stride: usize, seeds_rc: *const u64,
         n_seeds: usize, opt: *const ws_options, py: c_int, px: c_int, merging: c_int, out_labels: *mut u64, exchange_rounds: *mut u32) -> c_int;
+    pub fn ws_merge_tree_tiled_device(g: *mut ws_group, field_h: usize, w: usize, n_seeds_total: usize, blocks: *const ws_tile_block, opt: *const ws_options,
+        d_weight: *const c_void, weight_dtype: c_int, weight_row_stride: usize, d_tree: *mut ws_tree_node, d_stats: *mut ws_lake_stats,
+        exchange_rounds: *mut u32) -> c_int;
+    pub fn ws_merge_tree_tiled2d_device(g: *mut ws_group, field_h: usize, field_w: usize, py: c_int, px: c_int, n_seeds_total: usize,
+        blocks: *const ws_tile_block2d, opt: *const ws_options, d_weight: *const c_void, weight_dtype: c_int, weight_row_stride: usize,
+        d_tree: *mut ws_tree_node, d_stats: *mut ws_lake_stats, exchange_rounds: *mut u32) -> c_int;
+    pub fn ws_merge_tree_tiled(g: *mut ws_group, img: *const u8, h: usize, w: usize, row_stride: usize, seeds_rc: *const u64, n_seeds: usize,
+        opt: *const ws_options, weight: *const c_void, weight_dtype: c_int, weight_row_stride: usize, tree: *mut ws_tree_node,
+        stats: *mut ws_lake_stats, exchange_rounds: *mut u32) -> c_int;
     pub fn ws_segment_batch_group(g: *mut ws_group, h: usize, w: usize, parts: *const ws_batch_part, opt: *const ws_options,
         failed_rank: *mut usize, failed_slice: *mut usize) -> c_int;
 }

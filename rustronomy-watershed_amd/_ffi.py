@@ -162,6 +162,7 @@ SIGNATURES = {
     "ws_merge_tree": (ctypes.c_int, [vp, vp, sz, sz, sz, vp, sz, ctypes.POINTER(Options), vp, vp]),
     "ws_merge_tree_stats_device": (ctypes.c_int, [vp, vp, sz, sz, sz, vp, sz, ctypes.POINTER(Options), vp, ctypes.c_int, sz, vp, vp, vp]),
     "ws_merge_tree_stats": (ctypes.c_int, [vp, vp, sz, sz, sz, vp, sz, ctypes.POINTER(Options), vp, ctypes.c_int, sz, vp, vp, vp]),
+    "ws_merge_tree_from_arrival_device": (ctypes.c_int, [vp, vp, vp, sz, sz, sz, ctypes.POINTER(Options), vp, ctypes.c_int, sz, vp, vp]),
     "ws_merge_tree_batch_device": (ctypes.c_int, [vp, vp, sz, sz, sz, sz, sz, vp, szp, ctypes.POINTER(Options), vp, vp, szp]),
     "ws_merge_tree_batch": (ctypes.c_int, [vp, vp, sz, sz, sz, sz, sz, vp, szp, ctypes.POINTER(Options), vp, sz, szp, vp, szp, szp]),
     "ws_merge_tree_stats_batch_device": (ctypes.c_int, [vp, vp, sz, sz, sz, sz, sz, vp, szp, ctypes.POINTER(Options), vp, ctypes.c_int, sz, sz,
@@ -200,6 +201,9 @@ SIGNATURES = {
     "ws_segment_tiled2d_device": (ctypes.c_int, [vp, sz, sz, ctypes.c_int, ctypes.c_int, sz, ctypes.POINTER(TileBlock2D), ctypes.POINTER(Options), ctypes.c_int, u32p]),
     "ws_transform_to_list_tiled2d_device": (ctypes.c_int, [vp, sz, sz, ctypes.c_int, ctypes.c_int, sz, vp, ctypes.POINTER(Options), ctypes.c_int, vp, sz, szp, vp, vp, u32p]),
     "ws_segment_tiled2d": (ctypes.c_int, [vp, vp, sz, sz, sz, vp, sz, ctypes.POINTER(Options), ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, u32p]),
+    "ws_merge_tree_tiled_device": (ctypes.c_int, [vp, sz, sz, sz, vp, ctypes.POINTER(Options), vp, ctypes.c_int, sz, vp, vp, u32p]),
+    "ws_merge_tree_tiled2d_device": (ctypes.c_int, [vp, sz, sz, ctypes.c_int, ctypes.c_int, sz, vp, ctypes.POINTER(Options), vp, ctypes.c_int, sz, vp, vp, u32p]),
+    "ws_merge_tree_tiled": (ctypes.c_int, [vp, vp, sz, sz, sz, vp, sz, ctypes.POINTER(Options), vp, ctypes.c_int, sz, vp, vp, u32p]),
     "ws_segment_batch_group": (ctypes.c_int, [vp, sz, sz, ctypes.POINTER(BatchPart), ctypes.POINTER(Options), szp, szp]),
 }
 

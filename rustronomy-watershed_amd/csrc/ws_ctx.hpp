@@ -62,6 +62,8 @@ struct ws_ctx {
   // ws_merge_tree_stats_batch(_device): the planes of the largest group (its colours, one entry more and one per slice of a group),
   // the host form's records of the whole cube and its weight cube, contiguous
   wsapi::DevBuf lake_acc, lake_out, lake_weight;
+  // ws_merge_tree_from_arrival_device: the seed pairs recovered from the planes (8 B a colour: seed_pixels_from_planes)
+  wsapi::DevBuf tree_seed_px;
   uint32_t *pinned = nullptr;      // FLAG_WORDS words of pinned host memory: the host's mirror of the flag block
   uint32_t *pinned_dev = nullptr;  // the same words as the device sees them (nullptr: not mapped, copies only)
   hipEvent_t ring_ev[wsk::COUNTER_RING]{};   // flag slot copied to the host
@@ -305,6 +307,10 @@ inline int pick_engine(const ws_options *opt) {
 // lib.rs:1675-1677 indexes the padded plane with the caller's coordinates (seed_shift 0); seed_shift 1 moves every seed
 // by (+1, +1), onto the pixel it was found at.  Only meaningful with edge correction.
 inline uint32_t seed_shift_of(const ws_options *opt) { return opt->edge_correction && opt->seed_shift ? 1u : 0u; }
+
+// ws_lists.hip: what ws_merge_tree_from_arrival_device will ensure for n_seeds colours (with the catalogue: stats), ahead of time --
+// a rank that is about to gather planes from its peers must not fail an allocation between two collectives
+int merge_tree_arrival_reserve(ws_ctx *c, size_t n_seeds, bool stats);
 
 // ws_ctx.hip: staging
 int empty_image_block(ws_ctx *c, const uint8_t **d_img, size_t *d_stride, size_t h = 0, size_t w = 0);

@@ -466,6 +466,14 @@ LevelJob history_job_host(bool merging, const uint8_t *img, size_t h, size_t w, 
   return job;
 }
 
+// ... and of a finished transform's planes (ws_merge_tree_from_arrival_device): no flood, the stamped level loop alone
+LevelJob history_job_arrival(const uint32_t *d_keys, const uint32_t *d_seg, size_t h, size_t w, size_t n_seeds, const ws_options *opt) {
+  LevelJob job;
+  job.merging = true; job.h = h; job.w = w; job.stride = w; job.n_seeds = n_seeds; job.opt = opt;
+  job.source = LevelSource::ARRIVAL; job.d_keys = d_keys; job.d_seg = d_seg; job.history = true;
+  return job;
+}
+
 // ws_transform_to_list_batch_device on a stack: per group of slices, the flood of the stack (flood_stack), the per-level driver
 // over the stack's numbering of colours (merge_host, arrival form: the bucketing adds the slice's base to every colour and pairs
 // no pixels across a slice border), then the split of the group's records (level-major, stack colours) into the caller's
@@ -664,11 +672,12 @@ int ensure_tree(ws_ctx *c, size_t n_seeds, bool host_records) {
   return WS_OK;
 }
 
-// the records from the transform merge_host(merging, history) has just run on this context
-int build_tree(ws_ctx *c, const uint32_t *d_seeds, size_t n_seeds, const ws_options *opt, size_t ph, size_t pw, ws_tree_node *d_tree) {
+// the records from the transform merge_host(merging, history) has just run on this context over the planes keys and seg (the
+// context's own, or the arrival form's); d_seeds: the seed pairs in those planes' coordinates
+int build_tree(ws_ctx *c, const uint32_t *keys, const uint32_t *seg, const uint32_t *d_seeds, size_t n_seeds, const ws_options *opt, size_t ph, size_t pw,
+               ws_tree_node *d_tree) {
   const uint32_t levels = (uint32_t)opt->max_water_level + 1;
   const uint32_t *death = (const uint32_t *)c->uf_death.p, *hook = (const uint32_t *)c->uf_hook.p;
-  const uint32_t *keys = (const uint32_t *)c->keys.p, *seg = (const uint32_t *)c->labels.p;
   u64c *ws = (u64c *)c->tree_ws.p;
   TreeRec *tree = reinterpret_cast<TreeRec *>(d_tree);
   Span sp(c, KC_OTHER);
@@ -704,11 +713,11 @@ int ensure_lake(ws_ctx *c, size_t n_seeds, bool host_records) {
   return WS_OK;
 }
 
-// the statistics of the tree build_tree has just finished at d_tree, from the same transform
-int build_lake_stats(ws_ctx *c, const uint32_t *d_seeds, size_t n_seeds, const ws_options *opt, size_t ph, size_t pw, const ws_tree_node *d_tree,
-                     const LakeWeights &wt, ws_lake_stats *d_stats) {
+// the statistics of the tree build_tree has just finished at d_tree, from the same transform and planes
+int build_lake_stats(ws_ctx *c, const uint32_t *keys, const uint32_t *seg, const uint32_t *d_seeds, size_t n_seeds, const ws_options *opt, size_t ph,
+                     size_t pw, const ws_tree_node *d_tree, const LakeWeights &wt, ws_lake_stats *d_stats) {
   Span sp(c, KC_OTHER);
-  HIP_TRY(c, lake_stats(c->stream, (const uint32_t *)c->keys.p, (const uint32_t *)c->labels.p, (const uint32_t *)c->uf_death.p,
+  HIP_TRY(c, lake_stats(c->stream, keys, seg, (const uint32_t *)c->uf_death.p,
                         (const uint32_t *)c->uf_hook.p, reinterpret_cast<const TreeRec *>(d_tree), d_seeds, n_seeds + 1,
                         (uint32_t)opt->max_water_level + 1, (const u64c *)c->tree_ws.p, (const uint32_t *)c->tree_order.p, wt, (int)ph, (int)pw,
                         c->lake_acc.p, reinterpret_cast<LakeRec *>(d_stats)));
@@ -740,12 +749,12 @@ int merge_tree_device_body(ws_ctx *c, const uint8_t *d_img, size_t h, size_t w, 
   if (int rc = merge_host(c, history_job_device(true, d_img, h, w, stride, d_seeds_rc, n_seeds, opt))) return rc;
   // the seed pairs as the flood took them: the caller's, or (shifted_seeds) moved into the padded plane in the context's buffer
   const uint32_t *seeds = seed_shift_of(opt) && n_seeds ? (const uint32_t *)c->seeds.p : d_seeds_rc;
-  if (int rc = build_tree(c, seeds, n_seeds, opt, ph, pw, d_tree)) return rc;
+  if (int rc = build_tree(c, (const uint32_t *)c->keys.p, (const uint32_t *)c->labels.p, seeds, n_seeds, opt, ph, pw, d_tree)) return rc;
   if (ls) {
     const uint32_t off = opt->edge_correction ? 1u : 0u;
     const LakeWeights wt = ls->weight ? LakeWeights{ls->weight, ls->stride, (uint32_t)h, (uint32_t)w, off, ls->dtype == WS_U16}
                                       : LakeWeights{d_img, stride, (uint32_t)h, (uint32_t)w, off, 0};
-    if (int rc = build_lake_stats(c, seeds, n_seeds, opt, ph, pw, d_tree, wt, ls->stats)) return rc;
+    if (int rc = build_lake_stats(c, (const uint32_t *)c->keys.p, (const uint32_t *)c->labels.p, seeds, n_seeds, opt, ph, pw, d_tree, wt, ls->stats)) return rc;
   }
   if (d_labels && ph * pw) HIP_TRY(c, hipMemcpyAsync(d_labels, c->labels.p, ph * pw * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -771,16 +780,68 @@ int merge_tree_host_body(ws_ctx *c, const uint8_t *img, size_t h, size_t w, size
   if (int rc = merge_host(c, history_job_host(true, img, h, w, stride, seeds_rc, n_seeds, opt))) return rc;
   const uint32_t *seeds = (const uint32_t *)c->seeds.p;      // stage_inputs: narrowed, shifted where the options say so
   ws_tree_node *d_tree = (ws_tree_node *)c->tree_out.p;
-  if (int rc = build_tree(c, seeds, n_seeds, opt, ph, pw, d_tree)) return rc;
+  if (int rc = build_tree(c, (const uint32_t *)c->keys.p, (const uint32_t *)c->labels.p, seeds, n_seeds, opt, ph, pw, d_tree)) return rc;
   if (ls) {
     // (no weights: the image as stage_inputs left it on the device, w bytes a row)
     const LakeWeights wt{own_plane ? c->lake_weight.p : c->img.p, w, (uint32_t)h, (uint32_t)w, opt->edge_correction ? 1u : 0u, elem == 2};
-    if (int rc = build_lake_stats(c, seeds, n_seeds, opt, ph, pw, d_tree, wt, (ws_lake_stats *)c->lake_out.p)) return rc;
+    if (int rc = build_lake_stats(c, (const uint32_t *)c->keys.p, (const uint32_t *)c->labels.p, seeds, n_seeds, opt, ph, pw, d_tree, wt, (ws_lake_stats *)c->lake_out.p))
+      return rc;
   }
   HIP_TRY(c, hipMemcpyAsync(tree, d_tree, (n_seeds + 1) * sizeof(ws_tree_node), hipMemcpyDeviceToHost, c->stream));
   if (ls) HIP_TRY(c, hipMemcpyAsync(ls->stats, c->lake_out.p, (n_seeds + 1) * sizeof(ws_lake_stats), hipMemcpyDeviceToHost, c->stream));
   if (labels && ph * pw)
     if (int rc = labels_to_host_u64(c, (const uint32_t *)c->labels.p, labels, ph * pw)) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return WS_OK;
+}
+
+// every buffer the arrival form needs that is sized by the colours alone: the tree's and the catalogue's workspace, the recovered
+// seed pairs and the union-find of the stamped level loop (the tiled forms call this on rank 0 before their gathers)
+int reserve_tree_arrival(ws_ctx *c, size_t n_seeds, bool stats) {
+  int rc;
+  if ((rc = ensure_tree(c, n_seeds, false))) return rc;
+  if (stats && (rc = ensure_lake(c, n_seeds, false))) return rc;
+  if ((rc = ensure(c, c->tree_seed_px, std::max<size_t>(n_seeds, 1) * 2 * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure_uf(c, n_seeds + 1))) return rc;
+  return ensure(c, c->uf_hook, (n_seeds + 1) * sizeof(uint32_t));
+}
+
+// ws_merge_tree_from_arrival_device: the planes of a finished segmenting transform instead of an image and a seed list.  The stamped
+// level loop reads nothing else (merge_host, arrival form), and the seed pixels tree_init and lake_stats want are in the planes:
+// stamp 0 marks them (seed_pixels_from_planes).  The plane is taken as it stands -- a padded plane comes in padded -- so the
+// weights have no offset.  No pixel (or no seed): the plane's record 0 alone.
+int merge_tree_arrival_body(ws_ctx *c, const uint32_t *d_keys, const uint32_t *d_seg, size_t h, size_t w, size_t n_seeds, const ws_options *opt,
+                            ws_tree_node *d_tree, const LakeStatsWanted *ls) {
+  ws_options plain = *opt;
+  plain.edge_correction = 0;
+  size_t ph = 0, pw = 0;
+  if (int rc = check_tree(c, h, w, w, &plain, n_seeds, &ph, &pw)) return rc;
+  if (pick_engine(opt) == WS_ENGINE_SWEEP) return fail(c, WS_ERR_UNSUPPORTED, "the sweep engine keeps no arrival stamps");
+  if (ls) {
+    if (!ls->weight) return fail(c, WS_ERR_BAD_ARG, "this form has no image: d_weight is null");
+    if (int rc = check_lake_weights(c, w, ph, pw, ls->weight, ls->dtype, ls->stride)) return rc;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (ph * pw == 0) {      // no pixel: nothing is uncoloured, no colour exists -- record 0 is the fold's identity
+    const ws_tree_node none{0u, WS_TREE_ALIVE, 0u, 0u};
+    const ws_lake_stats nothing{0, 0, 0, 0, 0, 0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u};
+    HIP_TRY(c, hipMemcpyAsync(d_tree, &none, sizeof none, hipMemcpyHostToDevice, c->stream));
+    if (ls) HIP_TRY(c, hipMemcpyAsync(ls->stats, &nothing, sizeof nothing, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return WS_OK;
+  }
+  if (int rc = reserve_tree_arrival(c, n_seeds, ls != nullptr)) return rc;
+  if (int rc = merge_host(c, history_job_arrival(d_keys, d_seg, h, w, n_seeds, &plain))) return rc;
+  const uint32_t *seeds = (const uint32_t *)c->tree_seed_px.p;
+  {
+    Span sp(c, KC_OTHER);
+    HIP_TRY(c, seed_pixels_from_planes(c->stream, d_keys, d_seg, (int)ph, (int)pw, n_seeds + 1, (uint32_t *)c->tree_seed_px.p));
+  }
+  if (int rc = build_tree(c, d_keys, d_seg, seeds, n_seeds, &plain, ph, pw, d_tree)) return rc;
+  if (ls) {
+    const LakeWeights wt{ls->weight, ls->stride, (uint32_t)h, (uint32_t)w, 0u, ls->dtype == WS_U16};
+    if (int rc = build_lake_stats(c, d_keys, d_seg, seeds, n_seeds, &plain, ph, pw, d_tree, wt, ls->stats)) return rc;
+  }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return WS_OK;
 }
@@ -1021,9 +1082,9 @@ int tree_batch_run(ws_ctx *c, const uint8_t *d_cube, size_t n_slices, size_t h, 
                              } else {
                                // the seed pairs as the flood took them: the caller's, or (shifted_seeds) moved into the padded plane
                                const uint32_t *seeds = seed_shift_of(opt) && ns ? (const uint32_t *)c->seeds.p : d_seeds_rc + 2 * seed_offsets[k];
-                               if (int rc_t = build_tree(c, seeds, ns, opt, ph, pw, out)) return rc_t;
+                               if (int rc_t = build_tree(c, grp.keys, grp.labels, seeds, ns, opt, ph, pw, out)) return rc_t;
                                if (ls)
-                                 if (int rc_t = build_lake_stats(c, seeds, ns, opt, ph, pw, out, lake_weights_from(*ls, d_cube, stride, slice_stride, k, h, w, opt), out_stats))
+                                 if (int rc_t = build_lake_stats(c, grp.keys, grp.labels, seeds, ns, opt, ph, pw, out, lake_weights_from(*ls, d_cube, stride, slice_stride, k, h, w, opt), out_stats))
                                    return rc_t;
                              }
                              return labels(grp);
@@ -1031,6 +1092,13 @@ int tree_batch_run(ws_ctx *c, const uint8_t *d_cube, size_t n_slices, size_t h, 
 }
 
 }  // namespace
+
+namespace wsapi {
+int merge_tree_arrival_reserve(ws_ctx *c, size_t n_seeds, bool stats) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  return reserve_tree_arrival(c, n_seeds, stats);
+}
+}  // namespace wsapi
 
 extern "C" {
 
@@ -1111,6 +1179,18 @@ int ws_merge_tree_stats(ws_ctx *c, const uint8_t *img, size_t h, size_t w, size_
   LakeStatsWanted ls;
   ls.weight = weight; ls.dtype = weight_dtype; ls.stride = weight_stride; ls.stats = stats;
   return merge_tree_host_body(c, img, h, w, stride, seeds_rc, n_seeds, opt, tree, labels, &ls);
+}
+
+int ws_merge_tree_from_arrival_device(ws_ctx *c, const uint32_t *d_keys, const uint32_t *d_seg_labels, size_t h, size_t w, size_t n_seeds,
+                                      const ws_options *opt, const void *d_weight, int weight_dtype, size_t weight_row_stride,
+                                      ws_tree_node *d_tree, ws_lake_stats *d_stats) {
+  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
+  if (!c) return WS_ERR_BAD_ARG;
+  if (!opt || !d_tree || ((!d_keys || !d_seg_labels) && h * w)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  if (!d_stats) return merge_tree_arrival_body(c, d_keys, d_seg_labels, h, w, n_seeds, opt, d_tree, nullptr);
+  LakeStatsWanted ls;
+  ls.weight = d_weight; ls.dtype = weight_dtype; ls.stride = weight_row_stride; ls.stats = d_stats;
+  return merge_tree_arrival_body(c, d_keys, d_seg_labels, h, w, n_seeds, opt, d_tree, &ls);
 }
 
 // half: 0 the whole call; 1 ws_merge_device_begin (returns WS_INTERNAL_PENDING when the graph and the speculative unions

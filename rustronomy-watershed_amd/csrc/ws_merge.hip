@@ -83,8 +83,8 @@ __device__ __forceinline__ bool interior(int y, int x, int H, int W) {
 }
 
 // Loads first, unconditional and on clamped addresses (a load under a data-dependent branch is waited for before the next is
-// issued: 24 dependent round trips per thread in the first form of this function), predicates afterwards.  With W % 4 == 0 the
-// four pixels and the four below them are 16-byte loads.
+// issued: 24 dependent round trips per thread in the first form of this function), predicates afterwards.  With W % 4 == 0 and
+// planes on 16-byte alignment the four pixels and the four below them are 16-byte loads.
 typedef uint32_t u32x4_m __attribute__((ext_vector_type(4)));
 
 // STACK: H rows of slices of slice_h rows each (ws_transform_to_list_batch_device): "interior" and the pixel below are taken
@@ -97,7 +97,9 @@ __device__ __forceinline__ void gather_items(const uint32_t *__restrict__ keys, 
   const int yd = min(y + 1, H - 1);
   const int ys = STACK ? y % slice_h : y, hs = STACK ? slice_h : H;      // row and height within the slice
   const uint32_t add = STACK ? base[y / slice_h] : 0u;
-  if ((W & 3) == 0 && x0 + 3 < W) {
+  // (a caller's planes -- the arrival forms -- may be views off 16-byte alignment: those take the scalar loads)
+  const bool aligned = ((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(labels)) & 15u) == 0;
+  if ((W & 3) == 0 && aligned && x0 + 3 < W) {
     const size_t p = (size_t)y * W + x0, q = (size_t)yd * W + x0;
     const u32x4_m a = *reinterpret_cast<const u32x4_m *>(keys + p), b = *reinterpret_cast<const u32x4_m *>(labels + p);
     const u32x4_m c = *reinterpret_cast<const u32x4_m *>(keys + q), d = *reinterpret_cast<const u32x4_m *>(labels + q);
@@ -1426,6 +1428,43 @@ hipError_t tree_init_stack(hipStream_t s, const uint32_t *death, const uint32_t 
   if (n_colours == 0) return hipSuccess;
   if (st.g == 0 || st.plane == 0 || (size_t)h * (size_t)w != (size_t)st.g * st.plane) return hipErrorInvalidValue;
   k_tree_init<true><<<(unsigned)((n_colours + TREE_CHUNK - 1) / TREE_CHUNK), 256, 0, s>>>(death, hook, stacked_rc, seg_labels, h, w, nullptr, tree, n_colours, ws, st);
+  return hipGetLastError();
+}
+
+// The seed pixels of a finished transform, from its planes alone (ws_merge_tree_from_arrival_device).  A seed is coloured before
+// level 0 (lib.rs:1675-1677) and nothing else is: stamp 0 marks exactly the painted pixels, and the label there is the colour that
+// survived the painting.  So every colour that exists has ONE stamp-0 pixel, which writes its (row, col) pair -- no atomics -- and
+// a colour that never was keeps the pair the fill left, which k_tree_init reads as "outside the plane".  A plain stream over the
+// stamps, 16 bytes a lane; the labels are read only where a stamp is 0.  A label outside 1 .. n_seeds is never an index.
+__device__ __forceinline__ void seed_pixel_at(const uint32_t *__restrict__ seg, size_t i, uint32_t W, uint32_t n_seeds, uint2 *out_rc) {
+  const uint32_t c = seg[i];
+  if (c - 1u < n_seeds) out_rc[c - 1u] = make_uint2((uint32_t)(i / W), (uint32_t)(i % W));
+}
+
+__global__ __launch_bounds__(256) void k_seed_pixels(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ seg, size_t n, uint32_t W,
+                                                     uint32_t n_seeds, uint2 *out_rc) {
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, step = (size_t)gridDim.x * blockDim.x;
+  const size_t nq = (reinterpret_cast<uintptr_t>(keys) & 15u) == 0 ? n / 4 : 0;
+  for (size_t q = tid; q < nq; q += step) {
+    const u32x4_m k = reinterpret_cast<const u32x4_m *>(keys)[q];
+    if (k.x != 0u && k.y != 0u && k.z != 0u && k.w != 0u) continue;
+    if (k.x == 0u) seed_pixel_at(seg, 4 * q, W, n_seeds, out_rc);
+    if (k.y == 0u) seed_pixel_at(seg, 4 * q + 1, W, n_seeds, out_rc);
+    if (k.z == 0u) seed_pixel_at(seg, 4 * q + 2, W, n_seeds, out_rc);
+    if (k.w == 0u) seed_pixel_at(seg, 4 * q + 3, W, n_seeds, out_rc);
+  }
+  for (size_t i = nq * 4 + tid; i < n; i += step)      // the tail (all of the plane when the stamps are a view off 16-byte alignment)
+    if (keys[i] == 0u) seed_pixel_at(seg, i, W, n_seeds, out_rc);
+}
+
+hipError_t seed_pixels_from_planes(hipStream_t s, const uint32_t *keys, const uint32_t *seg, int h, int w, size_t n_colours, uint32_t *out_rc) {
+  if (n_colours <= 1) return hipSuccess;
+  if (n_colours > 0xFFFFFFFFull || (reinterpret_cast<uintptr_t>(out_rc) & 7u) != 0) return hipErrorInvalidValue;
+  const size_t n = (size_t)h * (size_t)w, n_seeds = n_colours - 1;
+  hipError_t e = hipMemsetAsync(out_rc, 0xFF, 2 * n_seeds * sizeof(uint32_t), s);
+  if (e != hipSuccess || n == 0) return e;
+  const unsigned blocks = (unsigned)std::min<size_t>((n / 4 + 255) / 256 + 1, 16384);
+  k_seed_pixels<<<blocks, 256, 0, s>>>(keys, seg, n, (uint32_t)w, (uint32_t)n_seeds, reinterpret_cast<uint2 *>(out_rc));
   return hipGetLastError();
 }
 

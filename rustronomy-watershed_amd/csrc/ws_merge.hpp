@@ -145,6 +145,10 @@ constexpr int TREE_WS_WORDS = 3 * (NLEVELS + 1);      // u64 words of scratch: d
 // ws: TREE_WS_WORDS zeroed words; ws[l] += colours that die at level l
 hipError_t tree_init(hipStream_t s, const uint32_t *death, const uint32_t *hook, const uint32_t *seeds_rc, const uint32_t *seg_labels, int h, int w,
                      const u64c *arrived, TreeRec *tree, size_t n_colours, u64c *ws);
+// the seed pairs tree_init and lake_stats read, recovered from a finished transform's planes (ws_merge_tree_from_arrival_device):
+// out_rc (2 * (n_colours - 1) words, 8-byte aligned) is filled with 0xFFFFFFFF -- "never was" -- and every stamp-0 pixel whose
+// label c lies in 1 .. n_colours - 1 writes its (row, col) to pair c - 1.  keys and seg need only be 4-byte aligned.
+hipError_t seed_pixels_from_planes(hipStream_t s, const uint32_t *keys, const uint32_t *seg, int h, int w, size_t n_colours, uint32_t *out_rc);
 // tree[r].area += 1 for every coloured pixel, r = the root of its colour at its arrival level
 hipError_t tree_own_counts(hipStream_t s, const uint32_t *keys, const uint32_t *labels, const uint32_t *death, const uint32_t *hook, TreeRec *tree, size_t n);
 // order[]: the colours that die, bucketed by death level (bounds: ws[NLEVELS + 1 + l]); then level by level, ascending, every dying

@@ -99,7 +99,7 @@ struct Grow {      // a device buffer that only ever grows
 struct Rank {
   int rank = 0, device = 0;
   ws_ctx *ctx = nullptr;
-  Grow keys, labels, recv, rows, table, parent, img, seeds, colours, out64, cols, full_keys, full_labels;
+  Grow keys, labels, recv, rows, table, parent, img, seeds, colours, out64, cols, full_keys, full_labels, weight;
   uint32_t *flag = nullptr;           // device: 4 words (the exchange loop's stop word; reduce scratch)
   uint32_t *flag_host = nullptr;      // pinned mirror
   // what the LOCAL exchange steps read from their neighbours (published before the barrier)
@@ -704,7 +704,7 @@ void ws_group_destroy(ws_group *g) {
   for (Rank &r : g->ranks) {
     (void)hipSetDevice(r.device);
     if (r.ctx) { (void)ws_ctx_synchronize(r.ctx); }
-    for (Grow *b : {&r.keys, &r.labels, &r.recv, &r.rows, &r.table, &r.parent, &r.img, &r.seeds, &r.colours, &r.out64})
+    for (Grow *b : {&r.keys, &r.labels, &r.recv, &r.rows, &r.table, &r.parent, &r.img, &r.seeds, &r.colours, &r.out64, &r.cols, &r.full_keys, &r.full_labels, &r.weight})
       if (b->p) (void)hipFree(b->p);
     if (r.flag) (void)hipFree(r.flag);
     if (r.flag_host) (void)hipHostFree(r.flag_host);
@@ -978,6 +978,133 @@ int ws_transform_to_list_tiled2d_device(ws_group *g, size_t field_h, size_t fiel
   return rc;
 }
 
+// ---- merge_tree and the lake catalogue of a tiled field -------------------------------------------------------
+// The route the lists take: the flood on all ranks, the two planes gathered on rank 0, the arrival form there.  The tree is a global
+// object as the lists are, and the stamped level loop reads nothing but the two planes; the seed pixels are in them too (stamp 0).
+
+// the catalogue request of the tiled tree forms: the whole field's weight plane and the records, on rank 0's device
+struct TreeWeights {
+  const void *weight;
+  int dtype;
+  size_t stride;
+};
+
+// the weight arguments, checked on every rank before anything runs, as ws_merge_tree_from_arrival_device checks them on rank 0
+// afterwards (check_lake_weights): a call that rank 0 would refuse after the flood has left its peers' work for nothing
+static int check_tree_weights(ws_group *g, bool stats, const TreeWeights &wt, bool image_stands_in, size_t w, size_t ph, size_t pw) {
+  if (!stats) return WS_OK;
+  uint64_t wmax = 0xFFull;
+  if (wt.weight) {
+    if (wt.dtype != WS_U8 && wt.dtype != WS_U16) return gfail(g, WS_ERR_UNSUPPORTED, "weights are u8 or u16");
+    if (wt.stride < w) return gfail(g, WS_ERR_BAD_ARG, "weight_row_stride < w");
+    if (wt.dtype == WS_U16) wmax = 0xFFFFull;
+  } else if (!image_stands_in) {
+    return gfail(g, WS_ERR_BAD_ARG, "no rank holds the whole image: the catalogue needs d_weight");
+  }
+  const uint64_t pixels = (uint64_t)ph * pw, longest = std::max(ph, pw);
+  if (longest && pixels > UINT64_MAX / wmax / longest) return gfail(g, WS_ERR_TOO_LARGE, "the weighted moments do not fit in 64 bits");
+  return WS_OK;
+}
+
+// rank 0, before the first gather: the two whole planes and everything the arrival form will ensure for the colours -- no
+// allocation may fail between two collectives, where the peers would wait for a rank that has left
+static int reserve_tree_root(ws_group *g, Rank &me, size_t n, size_t n_seeds, bool stats) {
+  int rc;
+  if ((rc = grow(g, me.full_keys, (n ? n : 1) * sizeof(uint32_t)))) return rc;
+  if ((rc = grow(g, me.full_labels, (n ? n : 1) * sizeof(uint32_t)))) return rc;
+  G_WS(g, me, merge_tree_arrival_reserve(me.ctx, n_seeds, stats));
+  return WS_OK;
+}
+
+int ws_merge_tree_tiled_device(ws_group *g, size_t field_h, size_t w, size_t n_seeds_total, const ws_tile_block *blocks, const ws_options *opt,
+                               const void *d_weight, int weight_dtype, size_t weight_row_stride, ws_tree_node *d_tree, ws_lake_stats *d_stats,
+                               uint32_t *exchange_rounds) {
+  int rc = check_group_call(g, opt);
+  if (rc) return rc;
+  if (!blocks) return gfail(g, WS_ERR_BAD_ARG, "null pointer");
+  if (opt->edge_correction) return gfail(g, WS_ERR_UNSUPPORTED, "the tiled transforms take the field as it is: pad it first");
+  if (n_seeds_total >= 0x7FFFFFFFull) return gfail(g, WS_ERR_TOO_LARGE, "colours must stay below 2^31");
+  if (field_h < (size_t)g->world) return gfail(g, WS_ERR_BAD_ARG, "a field needs at least one row per rank");
+  if (g->first_local == 0 && !d_tree) return gfail(g, WS_ERR_BAD_ARG, "d_tree is null");
+  const TreeWeights wt{d_weight, weight_dtype, weight_row_stride};
+  if ((rc = check_tree_weights(g, d_stats != nullptr, wt, false, w, field_h, w))) return rc;
+  for (size_t i = 0; i < g->ranks.size(); ++i) {
+    const ws_tile_block &b = blocks[i];
+    if (b.reserved != 0 || (field_h * w && (!b.d_img || !b.d_labels)) || (b.n_seeds && !b.d_seeds_rc))
+      return gfail(g, WS_ERR_BAD_ARG, "bad block descriptor");
+  }
+  if (exchange_rounds) *exchange_rounds = 0;
+  std::vector<uint32_t> rounds(g->ranks.size(), 0);
+  rc = for_local_ranks(g, [&](Rank &me) -> int {
+    const size_t i = (size_t)(me.rank - g->first_local);
+    const ws_tile_block &b = blocks[i];
+    int rc2;
+    size_t r0, r1, lo, hi;
+    if ((rc2 = ws_tile_rows(field_h, me.rank, g->world, &r0, &r1, &lo, &hi))) return gfail(g, rc2, "a field needs at least one row per rank");
+    if (g->world == 1) {
+      if ((rc2 = single_rank(g, me, field_h, w, b, opt, 0))) return rc2;
+      const uint32_t *k = nullptr; size_t kh = 0, kw = 0;
+      G_WS(g, me, ws_last_arrival_device(me.ctx, &k, &kh, &kw));
+      return gfail_if(g, me, ws_merge_tree_from_arrival_device(me.ctx, k, b.d_labels, field_h, w, n_seeds_total, opt, d_weight, weight_dtype,
+                                                               weight_row_stride, d_tree, d_stats));
+    }
+    if ((rc2 = tiled_rank(g, me, field_h, w, n_seeds_total, b, opt, 0, &rounds[i]))) return rc2;
+    const uint32_t *keys = (const uint32_t *)me.keys.p, *labels = b.d_labels;      // the rank's block: rows [lo, hi) of the field
+    Exchange x{g, me};
+    if (me.rank == 0 && (rc2 = reserve_tree_root(g, me, field_h * w, n_seeds_total, d_stats != nullptr))) return rc2;
+    G_HIP(g, hipStreamSynchronize(me.ctx->stream));
+    if ((rc2 = x.gather_rows(keys + (r0 - lo) * w, field_h, w, (uint32_t *)me.full_keys.p))) return rc2;
+    if ((rc2 = x.gather_rows(labels + (r0 - lo) * w, field_h, w, (uint32_t *)me.full_labels.p))) return rc2;
+    if (me.rank != 0) return WS_OK;
+    return gfail_if(g, me, ws_merge_tree_from_arrival_device(me.ctx, (const uint32_t *)me.full_keys.p, (const uint32_t *)me.full_labels.p, field_h, w,
+                                                             n_seeds_total, opt, d_weight, weight_dtype, weight_row_stride, d_tree, d_stats));
+  });
+  if (exchange_rounds) *exchange_rounds = rounds[0];
+  return rc;
+}
+
+int ws_merge_tree_tiled2d_device(ws_group *g, size_t field_h, size_t field_w, int py, int px, size_t n_seeds_total, const ws_tile_block2d *blocks,
+                                 const ws_options *opt, const void *d_weight, int weight_dtype, size_t weight_row_stride, ws_tree_node *d_tree,
+                                 ws_lake_stats *d_stats, uint32_t *exchange_rounds) {
+  int rc = check_group_call(g, opt);
+  if (rc) return rc;
+  if (!blocks) return gfail(g, WS_ERR_BAD_ARG, "null pointer");
+  if (py < 1 || px < 1 || py * px != g->world) return gfail(g, WS_ERR_BAD_ARG, "py * px must be the group's number of ranks");
+  if (opt->edge_correction) return gfail(g, WS_ERR_UNSUPPORTED, "the tiled transforms take the field as it is: pad it first");
+  if (field_h < (size_t)py || field_w < (size_t)px) return gfail(g, WS_ERR_BAD_ARG, "a field needs at least one row and one column per tile");
+  if (n_seeds_total >= 0x7FFFFFFFull) return gfail(g, WS_ERR_TOO_LARGE, "colours must stay below 2^31");
+  if (g->first_local == 0 && !d_tree) return gfail(g, WS_ERR_BAD_ARG, "d_tree is null");
+  const TreeWeights wt{d_weight, weight_dtype, weight_row_stride};
+  if ((rc = check_tree_weights(g, d_stats != nullptr, wt, false, field_w, field_h, field_w))) return rc;
+  for (size_t i = 0; i < g->ranks.size(); ++i) {
+    const ws_tile_block2d &b = blocks[i];
+    size_t rws[4], cls[4];
+    if (ws_tile_grid(field_h, field_w, g->first_local + (int)i, py, px, rws, cls)) return gfail(g, WS_ERR_BAD_ARG, "bad tile grid");
+    if (!b.d_img || !b.d_labels || b.img_stride < cls[3] - cls[2] || (b.n_seeds && (!b.d_seeds_rc || !b.d_colours)))
+      return gfail(g, WS_ERR_BAD_ARG, "bad block descriptor");
+  }
+  if (exchange_rounds) *exchange_rounds = 0;
+  std::vector<uint32_t> rounds(g->ranks.size(), 0);
+  rc = for_local_ranks(g, [&](Rank &me) -> int {
+    const size_t i = (size_t)(me.rank - g->first_local);
+    int rc2;
+    if ((rc2 = tiled2d_rank(g, me, field_h, field_w, py, px, n_seeds_total, blocks[i], opt, 0, &rounds[i]))) return rc2;
+    size_t rows[4], cols[4];
+    (void)ws_tile_grid(field_h, field_w, me.rank, py, px, rows, cols);
+    const size_t bw = cols[3] - cols[2];
+    if (me.rank == 0 && (rc2 = reserve_tree_root(g, me, field_h * field_w, n_seeds_total, d_stats != nullptr))) return rc2;
+    Exchange x{g, me};
+    G_HIP(g, hipStreamSynchronize(me.ctx->stream));
+    if ((rc2 = x.gather_rect((const uint32_t *)me.keys.p, bw, field_h, field_w, py, px, (uint32_t *)me.full_keys.p))) return rc2;
+    if ((rc2 = x.gather_rect(blocks[i].d_labels, bw, field_h, field_w, py, px, (uint32_t *)me.full_labels.p))) return rc2;
+    if (me.rank != 0) return WS_OK;
+    return gfail_if(g, me, ws_merge_tree_from_arrival_device(me.ctx, (const uint32_t *)me.full_keys.p, (const uint32_t *)me.full_labels.p, field_h, field_w,
+                                                             n_seeds_total, opt, d_weight, weight_dtype, weight_row_stride, d_tree, d_stats));
+  });
+  if (exchange_rounds) *exchange_rounds = rounds[0];
+  return rc;
+}
+
 // Host buffers in and out.  Seeds: a list whose rows never decrease (every row-major sorted list; find_local_minima's) gives
 // every rank ONE contiguous range, found by binary search; any other list is dealt out seed by seed with explicit colours
 // (the general form).  With edge correction the rank's rows of the PADDED plane are built on the device: a zeroed block and
@@ -990,13 +1117,22 @@ struct HostLists {
   uint64_t *offsets, *uncoloured;
 };
 
+// the tree and (stats: nullable) the catalogue, wanted from a host-buffer tiled call (ws_merge_tree_tiled); weight null: the image
+struct HostTree {
+  ws_tree_node *tree;
+  ws_lake_stats *stats;
+  TreeWeights wt;
+};
+
 static int segment_tiled_host(ws_group *g, const uint8_t *img, size_t h, size_t w, size_t stride, const uint64_t *seeds_rc, size_t n_seeds,
-                              const ws_options *opt, int merging, uint64_t *out_labels, uint32_t *exchange_rounds, const HostLists *lists) {
+                              const ws_options *opt, int merging, uint64_t *out_labels, uint32_t *exchange_rounds, const HostLists *lists,
+                              const HostTree *tree = nullptr) {
   int rc = check_group_call(g, opt);
   if (rc) return rc;
   if ((!img && h * w) || (!seeds_rc && n_seeds) || stride < w) return gfail(g, WS_ERR_BAD_ARG, "bad argument");
   const size_t e = opt->edge_correction ? 2 : 0, ph = h + e, pw = w + e, shift = opt->edge_correction && opt->seed_shift ? 1 : 0;
-  if (!lists && !out_labels && ph * pw) return gfail(g, WS_ERR_BAD_ARG, "out_labels is null");
+  if (!lists && !tree && !out_labels && ph * pw) return gfail(g, WS_ERR_BAD_ARG, "out_labels is null");
+  if (tree && (rc = check_tree_weights(g, tree->stats != nullptr, tree->wt, true, w, ph, pw))) return rc;
   if (n_seeds >= 0x7FFFFFFFull) return gfail(g, WS_ERR_TOO_LARGE, "too many seeds");
   if (ph > 0x7FFFFFF0ull || pw > 0x7FFFFFF0ull) return gfail(g, WS_ERR_TOO_LARGE, "plane too large");
   if (exchange_rounds) *exchange_rounds = 0;
@@ -1069,9 +1205,46 @@ static int segment_tiled_host(ws_group *g, const uint8_t *img, size_t h, size_t 
     b.first_colour = first_colour;
     b.d_labels = (uint32_t *)me.labels.p;
     const size_t i = (size_t)(me.rank - g->first_local);
-    if (world == 1) rc2 = single_rank(g, me, ph, pw, b, &plain, lists ? 0 : merging);
-    else rc2 = tiled_rank(g, me, ph, pw, n_seeds, b, &plain, lists ? 0 : merging, &rounds[i]);
+    if (world == 1) rc2 = single_rank(g, me, ph, pw, b, &plain, lists || tree ? 0 : merging);
+    else rc2 = tiled_rank(g, me, ph, pw, n_seeds, b, &plain, lists || tree ? 0 : merging, &rounds[i]);
     if (rc2) return rc2;
+    if (tree) {      // merge_tree: the planes to rank 0 as for the lists, the records from the arrival form there (see the device form)
+      const bool stats = tree->stats != nullptr;
+      const size_t n = ph * pw, elem = stats && tree->wt.weight && tree->wt.dtype == WS_U16 ? 2 : 1;
+      const size_t tree_bytes = (n_seeds + 1) * sizeof(ws_tree_node);
+      if (me.rank == 0) {      // every buffer of rank 0 before the first gather
+        if (world > 1 && (rc2 = reserve_tree_root(g, me, n, n_seeds, stats))) return rc2;
+        if ((rc2 = grow(g, me.out64, tree_bytes + (stats ? (n_seeds + 1) * sizeof(ws_lake_stats) : 0)))) return rc2;
+        if (stats && (rc2 = grow(g, me.weight, (n ? n : 1) * elem))) return rc2;
+      }
+      const uint32_t *keys = (const uint32_t *)me.keys.p, *full_k = keys, *full_l = b.d_labels;
+      if (world == 1) {
+        size_t kh = 0, kw = 0;
+        G_WS(g, me, ws_last_arrival_device(me.ctx, &full_k, &kh, &kw));
+      } else {
+        Exchange x{g, me};
+        G_HIP(g, hipStreamSynchronize(s));
+        if ((rc2 = x.gather_rows(keys + (r0 - lo) * pw, ph, pw, (uint32_t *)me.full_keys.p))) return rc2;
+        if ((rc2 = x.gather_rows(b.d_labels + (r0 - lo) * pw, ph, pw, (uint32_t *)me.full_labels.p))) return rc2;
+        full_k = (const uint32_t *)me.full_keys.p;
+        full_l = (const uint32_t *)me.full_labels.p;
+      }
+      if (me.rank != 0) return WS_OK;
+      if (stats) {      // the weights of the (padded) plane: the caller's plane, or the image, one pixel in under edge correction; the ring weighs 0
+        const uint8_t *src = tree->wt.weight ? (const uint8_t *)tree->wt.weight : img;
+        const size_t src_stride = tree->wt.weight ? tree->wt.stride : stride, off = e ? 1 : 0;
+        if (e) G_HIP(g, hipMemsetAsync(me.weight.p, 0, (n ? n : 1) * elem, s));
+        if (h * w)
+          G_HIP(g, hipMemcpy2DAsync((uint8_t *)me.weight.p + (off * pw + off) * elem, pw * elem, src, src_stride * elem, w * elem, h, hipMemcpyHostToDevice, s));
+      }
+      ws_tree_node *d_tree = (ws_tree_node *)me.out64.p;
+      ws_lake_stats *d_stats = stats ? (ws_lake_stats *)((uint8_t *)me.out64.p + tree_bytes) : nullptr;
+      G_WS(g, me, ws_merge_tree_from_arrival_device(me.ctx, full_k, full_l, ph, pw, n_seeds, &plain, me.weight.p, elem == 2 ? WS_U16 : WS_U8, pw, d_tree, d_stats));
+      G_HIP(g, hipMemcpyAsync(tree->tree, d_tree, tree_bytes, hipMemcpyDeviceToHost, s));
+      if (stats) G_HIP(g, hipMemcpyAsync(tree->stats, d_stats, (n_seeds + 1) * sizeof(ws_lake_stats), hipMemcpyDeviceToHost, s));
+      G_HIP(g, hipStreamSynchronize(s));
+      return WS_OK;
+    }
     if (lists) {      // transform_to_list: the arrival planes of the owned rows to rank 0, the records of all levels there (see the device form)
       const uint32_t *keys = (const uint32_t *)me.keys.p, *full_k = keys, *full_l = b.d_labels;
       if (world == 1) {
@@ -1138,6 +1311,17 @@ int ws_transform_to_list_tiled(ws_group *g, int merging, const uint8_t *img, siz
   *n_lakes = 0;
   const HostLists lists{lakes, cap, n_lakes, offsets, uncoloured};
   return segment_tiled_host(g, img, h, w, stride, seeds_rc, n_seeds, opt, merging, nullptr, exchange_rounds, &lists);
+}
+
+// merge_tree (and the catalogue) of a host field over the ranks of the group: as ws_transform_to_list_tiled up to the gathers, then
+// ws_merge_tree_from_arrival_device on rank 0, whose records go to the caller's host buffers.
+int ws_merge_tree_tiled(ws_group *g, const uint8_t *img, size_t h, size_t w, size_t stride, const uint64_t *seeds_rc, size_t n_seeds,
+                        const ws_options *opt, const void *weight, int weight_dtype, size_t weight_row_stride, ws_tree_node *tree,
+                        ws_lake_stats *stats, uint32_t *exchange_rounds) {
+  if (!g) return WS_ERR_BAD_ARG;
+  if (!tree && g->first_local == 0) return gfail(g, WS_ERR_BAD_ARG, "null pointer");
+  const HostTree want{tree, stats, TreeWeights{weight, weight_dtype, weight_row_stride}};
+  return segment_tiled_host(g, img, h, w, stride, seeds_rc, n_seeds, opt, 0, nullptr, exchange_rounds, nullptr, &want);
 }
 
 // ... in py x px tiles: every local rank uploads its tile of the (padded) image, takes the seeds that fall on its plane with

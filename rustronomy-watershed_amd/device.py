@@ -350,6 +350,38 @@ class DeviceEngine:
                                                              labels.data_ptr() if want_labels else None))
         return (out, out_stats, labels) if want_labels else (out, out_stats)
 
+    def merge_tree_from_arrival(self, keys, labels, n_seeds, max_level=254, weights=None, want_stats=False):
+        """merge_tree -- with want_stats, merge_tree_stats -- of a segmenting transform that has already run, without a second
+        flood (ws_merge_tree_from_arrival_device): keys = its arrival stamps (last_arrival()), labels = its labels, both 2-D int32
+        device tensors of the (padded) plane's shape, contiguous (views into larger buffers are fine); n_seeds = the number of
+        colours.  Returns the tree tensor of merge_tree, or (tree, stats) as merge_tree_stats.  weights (needed with want_stats:
+        this form has no image): a uint8 or int16 / uint16 device tensor of the PLANE's shape with contiguous rows."""
+        if keys.dim() != 2 or tuple(keys.shape) != tuple(labels.shape):
+            raise ValueError("keys and labels must be 2-D tensors of the same shape")
+        assert keys.dtype == torch.int32 and labels.dtype == torch.int32 and keys.is_cuda and labels.is_cuda
+        assert keys.numel() == 0 or (keys.is_contiguous() and labels.is_contiguous())
+        h, w = keys.shape
+        ns = int(n_seeds)
+        dtype, wstride = 0, 0
+        if want_stats:
+            if weights is None:
+                raise ValueError("merge_tree_from_arrival has no image: the catalogue needs weights")
+            u16 = {torch.int16, getattr(torch, "uint16", torch.int16)}
+            if weights.dtype != torch.uint8 and weights.dtype not in u16:
+                raise TypeError("weights must be a uint8, uint16 or int16 (u16 bits) tensor")
+            if not weights.is_cuda or weights.dim() != 2 or tuple(weights.shape) != (h, w) or (w > 1 and weights.stride(1) != 1):
+                raise ValueError(f"weights must be a device tensor of shape {(h, w)} with contiguous rows")
+            dtype = _ffi.WS_DTYPES["uint8" if weights.dtype == torch.uint8 else "uint16"]
+            wstride = weights.stride(0) if h > 1 else w
+        out = torch.empty((ns + 1, 4), dtype=torch.int32, device=self.device)
+        out_stats = torch.empty((ns + 1, 9), dtype=torch.int64, device=self.device) if want_stats else None
+        opt = self.options(max_level, False)
+        self.ctx.check(_ffi.lib().ws_merge_tree_from_arrival_device(self.ctx.handle, keys.data_ptr() if h * w else None,
+                                                                    labels.data_ptr() if h * w else None, h, w, ns, ctypes.byref(opt),
+                                                                    weights.data_ptr() if want_stats else None, dtype, wstride,
+                                                                    out.data_ptr(), out_stats.data_ptr() if want_stats else None))
+        return (out, out_stats) if want_stats else out
+
     def merge_tree_batch(self, cube, seeds, seed_offsets, max_level=254, edge=False, seed_shift=False, want_labels=False, out=None):
         """merge_tree of every slice of a cube with everything in HBM (ws_merge_tree_batch_device); cube, seeds and seed_offsets as
         transform_to_list_batch.  Returns an (n_seeds_total + S, 4) int32 tensor: slice k's n_k + 1 rows start at

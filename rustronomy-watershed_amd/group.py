@@ -136,6 +136,34 @@ class Group:
                     "ws_transform_to_list_tiled_device")
         return n.value, offsets, uncoloured, rounds.value
 
+    @staticmethod
+    def _tree_args(n_seeds_total, weights, want_stats, device):
+        """Outputs and weight arguments of the tiled tree forms: (tree, stats or None, weight pointer, dtype, row stride)."""
+        tree = torch.empty((n_seeds_total + 1, 4), dtype=torch.int32, device=device)
+        stats = torch.empty((n_seeds_total + 1, 9), dtype=torch.int64, device=device) if want_stats else None
+        if weights is None:
+            return tree, stats, None, 0, 0
+        if weights.dtype != torch.uint8 and weights.dtype not in {torch.int16, getattr(torch, "uint16", torch.int16)}:
+            raise TypeError("weights must be a uint8, uint16 or int16 (u16 bits) tensor")
+        if not weights.is_cuda or weights.dim() != 2 or (weights.shape[1] > 1 and weights.stride(1) != 1):
+            raise ValueError("weights must be a 2-D device tensor with contiguous rows")
+        dtype = _ffi.WS_DTYPES["uint8" if weights.dtype == torch.uint8 else "uint16"]
+        return tree, stats, weights.data_ptr(), dtype, weights.stride(0) if weights.shape[0] > 1 else weights.shape[1]
+
+    def merge_tree_tiled_device(self, field_rows, width, n_seeds_total, blocks, max_level=254, weights=None, want_stats=False, device=None):
+        """merge_tree -- with want_stats, merge_tree_stats -- of a field in row blocks (ws_merge_tree_tiled_device): `blocks` as for
+        segment_tiled_device; weights (needed with want_stats) the whole field's uint8 or int16 / uint16 plane on rank 0's device.
+        Returns (tree, stats or None, rounds): the tensors of DeviceEngine.merge_tree_stats on `device` (rank 0's; default: the
+        weights' or the current one), meaningful in the process that holds rank 0."""
+        device = device if device is not None else (weights.device if weights is not None else torch.device("cuda", torch.cuda.current_device()))
+        tree, stats, wp, dtype, wstride = self._tree_args(n_seeds_total, weights, want_stats, device)
+        opt = _ffi.Options(max_level)
+        rounds = ctypes.c_uint32(0)
+        self._check(_ffi.lib().ws_merge_tree_tiled_device(self._h, field_rows, width, n_seeds_total, blocks, ctypes.byref(opt), wp, dtype, wstride,
+                                                          tree.data_ptr(), stats.data_ptr() if want_stats else None, ctypes.byref(rounds)),
+                    "ws_merge_tree_tiled_device")
+        return tree, stats, rounds.value
+
     # ---- one field in py x px tiles (both directions) ------------------------------------------------------------------------------
     @staticmethod
     def tile_grid(h, w, rank, py, px):
@@ -175,6 +203,18 @@ class Group:
         self._check(_ffi.lib().ws_segment_tiled2d_device(self._h, field_h, field_w, py, px, n_seeds_total, blocks, ctypes.byref(opt), int(merging),
                                                          ctypes.byref(rounds)), "ws_segment_tiled2d_device")
         return rounds.value
+
+    def merge_tree_tiled2d_device(self, field_h, field_w, py, px, n_seeds_total, blocks, max_level=254, weights=None, want_stats=False,
+                                  device=None):
+        """merge_tree_tiled_device over py x px tiles (ws_merge_tree_tiled2d_device): `blocks` as for segment_tiled2d_device."""
+        device = device if device is not None else (weights.device if weights is not None else torch.device("cuda", torch.cuda.current_device()))
+        tree, stats, wp, dtype, wstride = self._tree_args(n_seeds_total, weights, want_stats, device)
+        opt = _ffi.Options(max_level)
+        rounds = ctypes.c_uint32(0)
+        self._check(_ffi.lib().ws_merge_tree_tiled2d_device(self._h, field_h, field_w, py, px, n_seeds_total, blocks, ctypes.byref(opt), wp, dtype,
+                                                            wstride, tree.data_ptr(), stats.data_ptr() if want_stats else None, ctypes.byref(rounds)),
+                    "ws_merge_tree_tiled2d_device")
+        return tree, stats, rounds.value
 
     # ---- a batch of independent slices ------------------------------------------------------------------------------------------
     def segment_batch(self, h, w, parts, max_level=254):
