@@ -682,6 +682,12 @@ int ws_group_selftest(ws_group *g);
  * plus one halo row on every side that has a neighbour.  WS_ERR_BAD_ARG when h < world (every rank must own a row). */
 int ws_tile_rows(size_t h, int rank, int world, size_t *r0, size_t *r1, size_t *lo, size_t *hi);
 
+/* The ws_*_tiled* calls below.  A call that is wrong in several ways reports the first of: the group and the options (a null
+ * options pointer, ws_options_validate, the sweep engine on more than one rank); a null `blocks` or host output pointer; py * px
+ * against the group's ranks; edge correction on a device form (WS_ERR_UNSUPPORTED: pad first, the host forms do); a field with
+ * fewer rows (tiles: or columns) than ranks; a seed count of 2^31 - 1 or more (WS_ERR_TOO_LARGE); a null device output on the
+ * process that holds rank 0; the catalogue's weights; a block descriptor.  A refused call has queued no work. */
+
 /* One field tiled over the ranks of a group, host buffers in and out -- what a caller of transform(ArrayView2<u8>, &seeds)
  * (lib.rs:1810) has.  Every rank of the group calls it with the SAME arguments (local: one call drives all ranks); rank r
  * uploads its rows of the image, takes its part of the seed list (any list: one that is not strictly increasing, or a
