@@ -70,7 +70,9 @@ typedef enum ws_status {
   WS_ERR_OOM = -6,           /* device or host allocation failed */
   WS_ERR_NO_DEVICE = -7,
   WS_ERR_CAPACITY = -8,      /* output buffer too small; *n_found still holds the true count */
-  WS_ERR_RING_OVERFLOW = -9, /* > 2^24-1 flood rings inside one level (needs > 16.7 M pixel corridor) */
+  WS_ERR_RING_OVERFLOW = -9, /* a flood reached ring 2^24-1 inside one level: the last ring allowed is 2^24-2, at every level
+                                (from seeds that needs a corridor of 16.7 M pixels).  The flood is refused one ring BEFORE the 24-bit
+                                field would carry: out of level 254 the carry itself is 0xFF000000, "never coloured" */
   WS_ERR_TOO_LARGE = -10,    /* plane has >= 2^32 pixels or seeds */
   WS_ERR_UNSUPPORTED = -11,
   WS_ERR_RCCL = -12          /* an RCCL call failed, or librccl.so could not be loaded; see ws_group_last_error */

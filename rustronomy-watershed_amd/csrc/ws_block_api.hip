@@ -59,7 +59,7 @@ int ws_block_relax(ws_ctx *c, const uint8_t *d_img, size_t h, size_t w, size_t s
   HIP_TRY(c, hipMemcpyAsync(&c->pinned[FLAG_OVERFLOW], flags + FLAG_OVERFLOW, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(&c->pinned[FLAG_ANY], flags + FLAG_ANY, FLAG_SLOT * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (c->pinned[FLAG_OVERFLOW]) return fail(c, WS_ERR_RING_OVERFLOW, "more than 2^24-1 flood rings inside one level");
+  if (c->pinned[FLAG_OVERFLOW]) return fail(c, WS_ERR_RING_OVERFLOW, "a flood reached ring 2^24-1 inside one level (the last allowed is 2^24-2)");
   *changed = slot_nonzero(&c->pinned[FLAG_ANY]);
   return WS_OK;
 }
@@ -114,7 +114,7 @@ int ws_block_resolve_ring(ws_ctx *c, const uint32_t *d_keys, uint32_t *d_labels,
   HIP_TRY(c, resolve_two_launch(c->stream, job));
   HIP_TRY(c, hipMemcpyAsync(&c->pinned[FLAG_OVERFLOW], flags + FLAG_OVERFLOW, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (c->pinned[FLAG_OVERFLOW]) return fail(c, WS_ERR_RING_OVERFLOW, "more than 2^24-1 flood rings inside one level");
+  if (c->pinned[FLAG_OVERFLOW]) return fail(c, WS_ERR_RING_OVERFLOW, "a flood reached ring 2^24-1 inside one level (the last allowed is 2^24-2)");
   return WS_OK;
 }
 
@@ -236,7 +236,7 @@ int ws_block_resolve_local(ws_ctx *c, const uint32_t *d_keys, uint32_t *d_labels
   HIP_TRY(c, resolve_two_launch(c->stream, job));
   HIP_TRY(c, hipMemcpyAsync(&c->pinned[FLAG_OVERFLOW], flags + FLAG_OVERFLOW, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (c->pinned[FLAG_OVERFLOW]) return fail(c, WS_ERR_RING_OVERFLOW, "more than 2^24-1 flood rings inside one level");
+  if (c->pinned[FLAG_OVERFLOW]) return fail(c, WS_ERR_RING_OVERFLOW, "a flood reached ring 2^24-1 inside one level (the last allowed is 2^24-2)");
   c->misc_clean = true;
   return WS_OK;
 }

@@ -173,7 +173,7 @@ const char *ws_strerror(int status) {
     case WS_ERR_OOM: return "out of memory";
     case WS_ERR_NO_DEVICE: return "no HIP device";
     case WS_ERR_CAPACITY: return "output buffer too small";
-    case WS_ERR_RING_OVERFLOW: return "ring counter overflow";
+    case WS_ERR_RING_OVERFLOW: return "ring counter overflow (a flood reached ring 2^24-1 inside one level)";
     case WS_ERR_TOO_LARGE: return "input too large";
     case WS_ERR_UNSUPPORTED: return "unsupported";
     case WS_ERR_RCCL: return "RCCL error";

@@ -829,8 +829,8 @@ const uint8_t *__restrict__ img, size_t img_stride, uint32_t *keys,
       }
       if (check_carry) {               // kernel uniform
 #pragma unroll
-        for (int c = 0; c < RX_P; ++c)   // a finite non-seed stamp with ring 0 can only come from a carry out of the ring field
-          ovf |= (T[r][c] != 0u && T[r][c] < KEY_INF && (T[r][c] & RING_MASK) == 0u);
+        for (int c = 0; c < RX_P; ++c)   // a finite non-seed stamp with ring 0 (a carry) or 2^24 - 1 (the last before one: out of level 254 the carry is KEY_INF)
+          ovf |= (T[r][c] != 0u && T[r][c] < KEY_INF && ((T[r][c] + 1u) & RING_MASK) <= 1u);
       }
     }
     e |= 16u;
@@ -899,7 +899,7 @@ const uint8_t *__restrict__ img, size_t img_stride, uint32_t *keys,
   }
   // PERSIST: every wave's stamps have left for memory before the workgroup's barrier, and so before wave 0 flags a neighbour
   if (PERSIST) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (ovf) atomicExch(pf.overflow, 1u);      // never taken on sane inputs
+  if (ovf) atomicExch(pf.overflow, 1u);      // never taken on sane inputs (tests/test_gpu_planted_stamps.py plants the others)
   if (unfinished && (write_same || SEAM == 1 || chunk == 3)) e |= 32u;      // (chunk == 3: pass 0 of a seam-repair transform)
   if (e) atomicOr(&s_edges, e);
   __syncthreads();
@@ -1290,12 +1290,12 @@ __global__ __launch_bounds__(64 * RX_NW, 4) void k_relax0_tall(const uint8_t *__
       if (gy < H) *reinterpret_cast<u32x4_t *>(keys + (size_t)gy * W + gx0) = u32x4_t{T[r][0], T[r][1], T[r][2], T[r][3]};
       if (check_carry) {               // kernel uniform
 #pragma unroll
-        for (int c = 0; c < RX_P; ++c)   // a finite non-seed stamp with ring 0 can only come from a carry out of the ring field
-          ovf |= (T[r][c] != 0u && T[r][c] < KEY_INF && (T[r][c] & RING_MASK) == 0u);
+        for (int c = 0; c < RX_P; ++c)   // a finite non-seed stamp with ring 0 (a carry) or 2^24 - 1 (the last before one: out of level 254 the carry is KEY_INF)
+          ovf |= (T[r][c] != 0u && T[r][c] < KEY_INF && ((T[r][c] + 1u) & RING_MASK) <= 1u);
       }
     }
   }
-  if (ovf) atomicExch(pf.overflow, 1u);      // never taken on sane inputs
+  if (ovf) atomicExch(pf.overflow, 1u);      // never taken on sane inputs (and by no test: this kernel starts from seeds only)
   const uint32_t stripe = (blockIdx.x % NSTRIPE) * STRIPE_STRIDE;
   // A changed border pixel matters to the tile across the border when it can lower the pixel it touches there, which this
   // tile holds as its halo (`matters`).  No copy of the border as loaded is kept: a border pixel starts as a seed (0, for ever) or at
@@ -1539,13 +1539,13 @@ __global__ __launch_bounds__(64 * RX_NW, 4) void k_relax_strips_tall(const uint8
       if (gy < H) *reinterpret_cast<u32x4_t *>(keys + (size_t)gy * W + gx0) = u32x4_t{T[r][0], T[r][1], T[r][2], T[r][3]};
       if (check_carry) {               // kernel uniform
 #pragma unroll
-        for (int c = 0; c < RX_P; ++c)   // a finite non-seed stamp with ring 0 can only come from a carry out of the ring field
-          ovf |= (T[r][c] != 0u && T[r][c] < KEY_INF && (T[r][c] & RING_MASK) == 0u);
+        for (int c = 0; c < RX_P; ++c)   // a finite non-seed stamp with ring 0 (a carry) or 2^24 - 1 (the last before one: out of level 254 the carry is KEY_INF)
+          ovf |= (T[r][c] != 0u && T[r][c] < KEY_INF && ((T[r][c] + 1u) & RING_MASK) <= 1u);
       }
     }
     e |= 16u;
   }
-  if (ovf) atomicExch(pf.overflow, 1u);      // never taken on sane inputs
+  if (ovf) atomicExch(pf.overflow, 1u);      // never taken on sane inputs (and by no test: this kernel follows a pass 0 from seeds only)
   // Flags: the word that pass 2 reads for anchored tile (x, y), word 3 of entry (x, y) of the shifted grid's stamps.
   // Why they are a superset of the pixels whose equation can be violated, on slices of 64 rows: when the strips start, an
   // equation can only be violated next to a vertical seam (pass 0's tiles and the bands are fixpoints of their own pixels, and

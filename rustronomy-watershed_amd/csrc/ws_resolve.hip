@@ -310,7 +310,7 @@ __global__ __launch_bounds__(NTHREADS, 5) void k_resolve_local(const uint32_t *_
   // root of the in-tile forest (a seed, or a halo cell = where the chain leaves the tile): such a
   // pixel never enters the jumping rounds.  Roots point at themselves.
   uint32_t P[4][4];
-  uint32_t carried = 0xFFFFFFFFu;
+  uint32_t carried = 0u;
   uint32_t live = 0;                             // pixels whose pointer may still move
   {
     const u32x4_r up4 = *reinterpret_cast<const u32x4_r *>(&sB[(ly0 - 1) * RL_P + lx0]);
@@ -341,10 +341,13 @@ __global__ __launch_bounds__(NTHREADS, 5) void k_resolve_local(const uint32_t *_
         // never coloured and the stamp alone says "not flooded"; only a row block's halo rows hold finite stamps on a border
         // row (a neighbour rank's): BLOCK keeps the masks.
         const uint32_t flood = BLOCK ? (uint32_t)(k - 1u < KEY_INF - 1u) & row_int[r] & col_int[c] : (uint32_t)(k - 1u < KEY_INF - 1u);
-        // a finite stamp of a flooded pixel with ring 0: a carry out of the 24-bit ring field (the relaxation of a whole
-        // transform leaves this test to the one kernel that reads the finished plane)
-        // (smallest, over the flooded pixels, of the ring field moved to the top of the word: 0 = a carry; two ops per pixel)
-        carried = min(carried, (k << 8) | (flood ^ 1u));
+        // a finite stamp of a flooded pixel with ring 0 -- a carry out of the 24-bit ring field -- or with ring 2^24 - 1, the
+        // last before one: out of level 254 the carry itself is KEY_INF, "never coloured", and shows nowhere (the relaxation
+        // of a whole transform leaves this test to the one kernel that reads the finished plane)
+        // (largest, over the flooded pixels, of the ring field of stamp - 1 moved to the top of the word: 0xFFFFFF00 = ring 0,
+        // 0xFFFFFE00 = ring 2^24 - 1, every other ring less; stamp - 1 is there already, for `flood`: a shift, a select and the
+        // maximum per pixel.  The same test on stamp + 1 with a minimum flipped this kernel's register allocation.)
+        carried = max(carried, flood ? (k - 1u) << 8 : 0u);
         const uint32_t d = r == 3 ? dn[c] : K[r + 1][c];
         const uint32_t rr = c == 3 ? Rc[r] : K[r][c + 1];
         const uint32_t l = c == 0 ? Lc[r] : K[r][c - 1];
@@ -367,7 +370,7 @@ __global__ __launch_bounds__(NTHREADS, 5) void k_resolve_local(const uint32_t *_
       }
     }
   }
-  if (carry_flag && carried == 0u) atomicExch(carry_flag, 1u);      // never taken on sane inputs
+  if (carry_flag && carried >= 0xFFFFFE00u) atomicExch(carry_flag, 1u);      // never taken on sane inputs (tests/test_gpu_planted_stamps.py plants the others)
   __syncthreads();                               // every stamp has been read: the tile becomes pointers
 #pragma unroll
   for (int r = 0; r < 4; ++r)

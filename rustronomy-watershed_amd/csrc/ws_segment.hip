@@ -264,7 +264,7 @@ int run_fused_form(ws_ctx *c, const uint8_t *d_img, size_t stride, int ph, int p
     *mispredicted = true;
     return WS_OK;
   }
-  if (c->pinned[FLAG_OVERFLOW]) return fail(c, WS_ERR_RING_OVERFLOW, "more than 2^24-1 flood rings inside one level");
+  if (c->pinned[FLAG_OVERFLOW]) return fail(c, WS_ERR_RING_OVERFLOW, "a flood reached ring 2^24-1 inside one level (the last allowed is 2^24-2)");
   c->misc_clean = c->pinned[FLAG_UNSORTED] == 0 && c->pinned[FLAG_NONSTRICT] == 0;
   c->graph_sufficed = graph_mode != 0 && converged_at == GRAPH_PASSES - 1;
   c->have_keys = true;

@@ -60,6 +60,12 @@ class NumpyBlockEngine:
                 break
             k[:] = new.astype(np.uint32)
             changed = True
+        # WS_ERR_RING_OVERFLOW (include/ws_hip.h): a flooded pixel -- interior, finite, no seed -- whose ring is 2^24 - 1, the
+        # last before a carry (out of level 254 the carry itself is KEY_INF and shows nowhere), or 0, a carry that happened
+        fin = k.astype(np.int64)
+        flooded = np.zeros((self.h, self.w), dtype=bool)
+        flooded[1:-1, 1:-1] = (fin[1:-1, 1:-1] != 0) & (fin[1:-1, 1:-1] < INF)
+        self.ring_overflow = bool((flooded & (((fin + 1) & 0xFFFFFF) <= 1)).any())
         return changed
 
     def resolve(self):
