@@ -91,8 +91,6 @@ struct PassFlags {
 
 // --- launch wrappers (ws_kernels.hip) ---------------------------------------------------
 hipError_t fill_u32(hipStream_t s, uint32_t *p, size_t n, uint32_t v);
-// host_a / host_b: DEVICE pointers to pinned host memory (hipHostGetDevicePointer)
-hipError_t words_to_host(hipStream_t s, const uint32_t *a, uint32_t na, uint32_t *host_a, const uint32_t *b, uint32_t nb, uint32_t *host_b);
 hipError_t zero3(hipStream_t s, uint32_t *a, size_t na, uint32_t *b, size_t nb, uint32_t *c, size_t nc);   // one launch
 hipError_t random_field(hipStream_t s, uint8_t *img, size_t stride, int h, int w, uint64_t seed);
 hipError_t scatter_seeds(hipStream_t s, const uint32_t *seeds_rc, const uint32_t *colours, size_t n, int ph, int pw,
@@ -145,6 +143,12 @@ hipError_t resolve_pass(hipStream_t s, const uint32_t *keys, uint32_t *labels, i
                         uint32_t pass, uint32_t *stamps, PassFlags pf);
 // label resolve without a launch loop (pointer jumping in LDS + reference chase); needs h*w < 2^31
 size_t resolve_ref_capacity(int h, int w);
+// A run of device words that k_resolve_chase copies into device-visible host memory (hipHostGetDevicePointer) on its way.
+struct ReadBack {
+  const uint32_t *src = nullptr;
+  uint32_t count = 0;
+  uint32_t *host = nullptr;
+};
 // One two-launch resolve: a caller fills what it uses.
 struct ResolveJob {
   const uint32_t *keys = nullptr;           // the finished stamp plane
@@ -158,6 +162,7 @@ struct ResolveJob {
   const uint32_t *gate = nullptr;           // speculative launch: a pass's convergence slot; both kernels leave if it is set
   uint32_t *carry_flag = nullptr;           // set when a stamp carried out of its ring field (relax_pass with carry_checked_later leaves the test to this kernel)
   const uint32_t *seed_err = nullptr;       // seed_tables()' three error words: both kernels leave when the tables are invalid
+  ReadBack read_back[2];                    // optional (count 0: none): words that are final before the chase starts, copied by its block 0 even when the gate is closed
   int halo_flags = 0;                       // row block: 1 / 2 = the first / last row is a neighbour's (chains stop there); 4, without seed tables: a tile of a field cut both ways, the plane's border RING holds other ranks' pixels (roots like seeds, not flooded here)
 };
 hipError_t resolve_two_launch(hipStream_t s, const ResolveJob &job);

@@ -570,19 +570,9 @@ hipError_t snapshot_level(hipStream_t s, const uint32_t *keys, const uint32_t *l
   return hipGetLastError();
 }
 
-// Two short runs of flag words into the host's pinned mirror (device-visible host memory) by ONE small launch: inside a
-// replayed graph two device-to-host copy nodes were blit kernels of their own with barriers around them, idle time at the
-// end of every transform.
-__global__ void k_words_to_host(const uint32_t *__restrict__ a, uint32_t na, uint32_t *ha, const uint32_t *__restrict__ b, uint32_t nb,
-                                uint32_t *hb) {
-  for (uint32_t i = threadIdx.x; i < na; i += blockDim.x) ha[i] = a[i];
-  for (uint32_t i = threadIdx.x; i < nb; i += blockDim.x) hb[i] = b[i];
-}
-
-hipError_t words_to_host(hipStream_t s, const uint32_t *a, uint32_t na, uint32_t *host_a, const uint32_t *b, uint32_t nb, uint32_t *host_b) {
-  k_words_to_host<<<1, 64, 0, s>>>(a, na, host_a, b, nb, host_b);
-  return hipGetLastError();
-}
+// (the flag words a replayed graph sends to the host's pinned mirror: no kernel of their own any more -- inside a graph two
+// device-to-host copy nodes were blit kernels with barriers around them, then one small launch here, idle time at the end
+// of every transform either way; k_resolve_chase copies them now, ResolveJob::read_back)
 
 typedef uint32_t u32x4_r __attribute__((ext_vector_type(4)));
 

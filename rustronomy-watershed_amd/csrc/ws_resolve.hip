@@ -196,6 +196,12 @@ hipError_t resolve_pass(hipStream_t s, const uint32_t *keys, uint32_t *labels, i
 // (every image-interior pixel coloured) and a colour to stand for it -- both are lying around here: tile_min[tile] =
 // a colour of the tile that is not a reference (0: not one lake; RL_TILE_UNDECIDED: one lake, but every pixel's
 // chain leaves the tile, k_tile_scan looks at the finished labels).  Saves a 268 MB pass over the label plane.
+// With halo seeds' colours (below) tile_min may be the colour of a seed in the NEIGHBOURING tile.  It is still a colour that
+// some pixel of this tile holds in the finished plane, and nothing in ws_merge.hip asks for more: k_tile_scan, the same
+// word's other source, takes the smallest colour of the finished labels, foreign ones included; k_tile_links and k_tile_roots
+// join and replace colours; k_union_seeds joins every seed of the tile with it (one lake: all of the tile is one set, whichever
+// member names it); k_tile_edges joins the edge pixels' colours with it.  A corner pixel is never flooded, so it never holds a
+// halo's colour and stays out as before.
 // BLOCK: the plane's first / last row (a row block of a larger field, ws_block_*: halo_flags bit 0 / 1) or its whole border
 // ring (a tile of a field cut both ways) holds other ranks' pixels: finite stamps that are not flooded here (phase 2 keeps
 // the border masks).  With TABLES a halo pixel that some flood reached (finite, non-zero stamp) has a colour only its owner
@@ -209,8 +215,9 @@ hipError_t resolve_pass(hipStream_t s, const uint32_t *keys, uint32_t *labels, i
 //   1  load           stamps of the patch and the halo ring -> registers and LDS; labels or table words -> registers
 //   2  parents        the branch-free parent pointer of every pixel, the carry test; the tile becomes pointers
 //   3  jump           barrier-free pointer jumping
-//   4  colours        seed colours from the tables (TABLES), halo rows' references (BLOCK && TABLES)
-//   5  store          colours and halo references through LDS, refmask, the stores
+//   4  colours        seed colours from the tables (TABLES), halo rows' references (BLOCK && TABLES); TABLES && !BLOCK: ahead of
+//                     phase 3's closing barrier (it touches no LDS but the halo colours it publishes)
+//   5  store          colours and halo references -- or, TABLES && !BLOCK, halo seeds' colours -- through LDS, refmask, the stores
 //   6  classify       tile_min (MERGE)
 //   7  references     per-wave count word and list
 // They are sections of this body, not functions: a function is simplified by the compiler on its own before it is inlined,
@@ -225,7 +232,8 @@ __global__ __launch_bounds__(NTHREADS, 5) void k_resolve_local(const uint32_t *_
                                                             const uint32_t *__restrict__ gate, int SH, uint32_t *carry_flag,
                                                             const uint32_t *__restrict__ seed_err, int halo_flags) {
   // One LDS tile, used three times: stamps (+ halo ring) -> parent pointers -> painted colours.
-  __shared__ __attribute__((aligned(16))) uint32_t sB[RL_ROWS * RL_P];
+  // (HALO_SEEDS, below: one word per halo cell behind the tile)
+  __shared__ __attribute__((aligned(16))) uint32_t sB[RL_ROWS * RL_P + (TABLES && !BLOCK ? NTHREADS : 0)];
   // Side tables built from a seed list that turned out not to be strictly increasing, or to leave the plane, describe
   // some other list: nothing may be computed from them (the host repeats the transform once it has read the same words).
   // k_seed_tables has finished before this kernel starts, so the words are final: [0] out of bounds, [2] not strict.
@@ -245,6 +253,13 @@ __global__ __launch_bounds__(NTHREADS, 5) void k_resolve_local(const uint32_t *_
 
   // ---- phase 1, load.  Unconditional loads on clamped addresses (see ws_relax.hip)
   uint32_t K[4][4], Lb[4][4];
+  // A halo cell that is a SEED of the plane holds the seed's colour instead of a reference (phases 4 and 5): with the tables,
+  // on the 16-byte path, outside a row block.
+  constexpr bool HALO_SEEDS = TABLES && !BLOCK;
+  // ... sHaloColour[tid]: the colour halo cell (side, t) = (tid >> 6, tid & 63) would have as a seed, published ahead of barriers
+  // that exist anyway -- top and bottom rows by the halo threads in phase 1, left and right columns by the lanes of the
+  // tile's first and last patch column in phase 4 -- and picked up by the halo threads in phase 5.
+  uint32_t *const sHaloColour = sB + RL_ROWS * RL_P;      // (16-byte aligned: RL_ROWS * RL_P % 4 == 0)
   uint32_t seedbits = 0;                         // TABLES: which pixels of the patch are seeds
   uint32_t tab_mask[4] = {0u, 0u, 0u, 0u}, tab_base[4] = {0u, 0u, 0u, 0u};   // TABLES, vec: the table words of the 4 patch rows
   const bool vec = (W & 3) == 0 && ((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(labels)) & 15u) == 0;
@@ -286,6 +301,10 @@ __global__ __launch_bounds__(NTHREADS, 5) void k_resolve_local(const uint32_t *_
     const size_t hg = (size_t)min(max(hy, 0), H - 1) * W + min(max(hx, 0), W - 1);
     const uint32_t hv = keys[hg];
     const bool hok = hy >= 0 && hy < H && hx >= 0 && hx < W;
+    // the table words of a top / bottom halo row: requested with the stamps, two coalesced loads in waves 0 and 1 only (`side`
+    // is wave uniform; the row's 64 cells lie in two or three consecutive words, one cache line per table)
+    uint32_t hmask = 0u, hbase = 0u;
+    if (HALO_SEEDS && vec && side < 2) { hmask = seed_mask[hg >> 5]; hbase = word_base[hg >> 5]; }
     // (workgroup uniform: a tile that lies wholly inside the plane has nothing to mask -- this kernel is bound by vector issue)
     if (!(x0 + TS <= W && y0 + TS <= H)) {
 #pragma unroll
@@ -302,6 +321,8 @@ __global__ __launch_bounds__(NTHREADS, 5) void k_resolve_local(const uint32_t *_
       *reinterpret_cast<u32x4_r *>(&sB[(ly0 + r) * RL_P + lx0]) = u32x4_r{K[r][0], K[r][1], K[r][2], K[r][3]};
     }
     sB[(hy - (y0 - 1)) * RL_P + (hx - (x0 - 1)) + (RL_X0 - 1)] = hok ? hv : KEY_INF;
+    // phase 4's formula gives the colour of any pixel that is a seed
+    if (HALO_SEEDS && vec && side < 2) sHaloColour[tid] = hbase + __popc(hmask & ((1u << (hg & 31u)) - 1u)) + 1u;
   }
   __syncthreads();
   WS_STAMP(1);
@@ -399,10 +420,11 @@ __global__ __launch_bounds__(NTHREADS, 5) void k_resolve_local(const uint32_t *_
       }
     WS_STAMP_VALUE(6, it + 1);
   }
-  __syncthreads();
+  if (!HALO_SEEDS) __syncthreads();
   WS_STAMP(3);
   if (TABLES) {      // ---- phase 4, colours
     // seed colours from the side tables; with W % 4 == 0 a patch row sits in one mask word
+    uint32_t side_first[4] = {0u, 0u, 0u, 0u};      // HALO_SEEDS, vec: `first` of the 4 patch rows
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int gyc = min(gy0 + r, H - 1);
@@ -419,6 +441,7 @@ __global__ __launch_bounds__(NTHREADS, 5) void k_resolve_local(const uint32_t *_
         Lb[r][1] = nib & 2u ? first + (nib & 1u) : 0u;
         Lb[r][2] = nib & 4u ? first + __popc(nib & 3u) : 0u;
         Lb[r][3] = nib & 8u ? first + __popc(nib & 7u) : 0u;
+        if (HALO_SEEDS) side_first[r] = first;
       } else {
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -428,7 +451,18 @@ __global__ __launch_bounds__(NTHREADS, 5) void k_resolve_local(const uint32_t *_
         }
       }
     }
+    // The left and right halo columns' colours.  The list is strictly increasing, so colours are consecutive along a row:
+    // `first` is the number of seeds before the patch row's first pixel g, plus one.  Left, (y, x0 - 1): if g - 1 is a seed it
+    // is the last seed before g, colour first - 1.  Right, (y, x0 + 64): the seeds of the patch row x0 + 60 .. 63 come
+    // first, colour first + popc(nibble).  Same row, hence the same slice of a stack and the same colour base.
+    if (HALO_SEEDS && vec && (pc == 0 || pc == 15)) {
+      uint32_t cand[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) cand[r] = pc == 0 ? side_first[r] - 1u : side_first[r] + __popc((seedbits >> (r * 4)) & 15u);
+      *reinterpret_cast<u32x4_r *>(&sHaloColour[(pc == 0 ? 128 : 192) + pr * 4]) = u32x4_r{cand[0], cand[1], cand[2], cand[3]};
+    }
   }
+  if (HALO_SEEDS) __syncthreads();      // (phase 4 ahead of phase 3's closing barrier: it touches no LDS but sHaloColour)
   if (BLOCK && TABLES) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -448,10 +482,21 @@ __global__ __launch_bounds__(NTHREADS, 5) void k_resolve_local(const uint32_t *_
     const int hy = side == 0 ? y0 - 1 : (side == 1 ? y0 + TS : y0 + t);
     const int hx = side == 2 ? x0 - 1 : (side == 3 ? x0 + TS : x0 + t);
     const int hyc = min(max(hy, 0), H - 1), hxc = min(max(hx, 0), W - 1);
-    // (tried: a halo cell that is a SEED holds the seed's colour, from the side tables, instead of a reference -- half of the
-    // leaving chains of a random field end there: k_resolve_chase 41 -> 27 us, and this kernel 170 -> 183 us for the two
-    // table words per halo cell, the left and right columns' a cache line each)
-    sB[(hy - (y0 - 1)) * RL_P + (hx - (x0 - 1)) + (RL_X0 - 1)] = REF_BIT | (uint32_t)((size_t)hyc * W + hxc);
+    // HALO_SEEDS, 16-byte path: a halo cell that is a SEED of the plane holds the seed's colour instead -- a third of the
+    // leaving chains of a random field end there (8192^2 bench field: 34 %, tools/count_halo_seed_refs.py), read a colour
+    // without REF_BIT and so drop out of refmask, the lists and the chase.  The cell still holds the halo pixel's stamp
+    // (phases 2 and 3 rewrite patch cells only; outside the plane it is KEY_INF): stamp 0 means seed.  The colour costs no
+    // load of its own for the left and right columns (phase 4) and two coalesced ones per top / bottom row (phase 1).
+    // 8192^2 bench field, per launch: k_resolve_chase 37.1 -> 29.3 us (77 -> 55 MB fetched, 37 -> 27 MB written) and this
+    // kernel 168.9 -> 160.5 us (profiles/halo_seeds_kernel_stats_*.csv, halo_seeds_pmc_hbm_bytes.json; the first form, with
+    // two table words loaded per halo cell, the left and right columns' a cache line each, was chase 41 -> 27 us and this
+    // kernel 170 -> 183 us and was dropped).
+    if (HALO_SEEDS && vec) {
+      const int cell = (hy - (y0 - 1)) * RL_P + (hx - (x0 - 1)) + (RL_X0 - 1);
+      sB[cell] = sB[cell] == 0u ? sHaloColour[tid] : REF_BIT | (uint32_t)((size_t)hyc * W + hxc);
+    } else {
+      sB[(hy - (y0 - 1)) * RL_P + (hx - (x0 - 1)) + (RL_X0 - 1)] = REF_BIT | (uint32_t)((size_t)hyc * W + hxc);
+    }
   }
 #pragma unroll
   for (int r = 0; r < 4; ++r)
@@ -563,12 +608,24 @@ __global__ __launch_bounds__(NTHREADS, 5) void k_resolve_local(const uint32_t *_
 // them before it waits (one region at a time, four per wave one after the other: 48 us at 8192^2, 75 MB of traffic; this
 // form 41 us, whatever CH_R and CH_U: reading the lists is 6 us of it, the scattered 4-byte loads of the first hop ~10-17 and
 // the scattered 4-byte stores ~18-28 -- partial writes into lines k_resolve_local has just sent to HBM; profiles/r2_v7_chase_ab.log).
+// With halo seeds' colours written by k_resolve_local a region of the bench field holds ~24 references for ~37 and this
+// kernel is 29 us for 37; CH_R / CH_U looked at again with the shorter lists (profiles/halo_seeds_chase_pairs.txt): 4 / 4
+// 27.5-29.1 us, 4 / 2 27.4, 8 / 4 31.7, 8 / 2 34.6, 2 / 4 34.8 -- 4 / 4 stays.
 // (groups of 8 regions balance badly on smooth maps, where every pixel is a reference and a region holds 1024: 8192^2 at
 // correlation 64 / 256 px 344 / 212 us against 301 / 144 with 4 and 269 / 259 for the old one-region walk; bench field 38 us either way)
 __global__ __launch_bounds__(256) void k_resolve_chase(uint32_t *labels, const uint32_t *__restrict__ ref_count,
                                 const uint32_t *__restrict__ ref_list, size_t nregions, size_t n,
                                 const uint32_t *__restrict__ gate, const uint32_t *__restrict__ seed_err,
-                                size_t follow_from, size_t follow_to, int H, int W, int tilesX, uint32_t ntiles, int halve) {
+                                size_t follow_from, size_t follow_to, int H, int W, int tilesX, uint32_t ntiles, int halve,
+                                ReadBack rb0, ReadBack rb1) {
+  // The read-backs of a replayed transform (ResolveJob::read_back: the lookahead pass's convergence slot, the error words) ride
+  // here instead of in a launch of their own behind this one: every such word is final before this kernel starts (the slot
+  // by the last pass, the seed errors by k_seed_tables, the carry word by k_resolve_local; nothing below raises one).  Ahead
+  // of both early returns: a closed gate is exactly when the host needs the slot.
+  if (blockIdx.x == 0) {
+    for (uint32_t i = threadIdx.x; i < rb0.count; i += blockDim.x) rb0.host[i] = rb0.src[i];
+    for (uint32_t i = threadIdx.x; i < rb1.count; i += blockDim.x) rb1.host[i] = rb1.src[i];
+  }
   // [follow_from, follow_to): the pixels a chain may be followed THROUGH -- the whole plane [0, n), or, for a row block
   // whose halo rows still hold references to themselves, the plane without those rows: a chain stops at a halo pixel.
   const int lane = threadIdx.x & 63;
@@ -746,7 +803,7 @@ hipError_t resolve_two_launch(hipStream_t s, const ResolveJob &job) {
   const size_t from = (halo_rows & 1) ? (size_t)job.w : 0, to = (halo_rows & 2) ? n - (size_t)job.w : n;
   k_resolve_chase<<<chase_grid(nregions), 256, 0, s>>>(job.labels, job.ref_scratch, job.ref_scratch + nregions, nregions, n, job.gate,
                                                        tables ? job.seed_err : nullptr, from, to, job.h, job.w, tx, (uint32_t)(tx * ty),
-                                                       halo_rows == 0 && !ring ? 1 : 0);
+                                                       halo_rows == 0 && !ring ? 1 : 0, job.read_back[0], job.read_back[1]);
   return hipGetLastError();
 }
 
@@ -756,7 +813,8 @@ hipError_t resolve_chase_again(hipStream_t s, uint32_t *labels, int h, int w, ui
   const size_t n = (size_t)h * w;
   if (n == 0) return hipSuccess;
   const size_t nregions = (size_t)tiles_of(w) * tiles_of(h) * (NTHREADS / 64);
-  k_resolve_chase<<<chase_grid(nregions), 256, 0, s>>>(labels, ref_scratch, ref_scratch + nregions, nregions, n, nullptr, nullptr, 0, n, h, w, tiles_of(w), (uint32_t)(tiles_of(w) * tiles_of(h)), 0);
+  k_resolve_chase<<<chase_grid(nregions), 256, 0, s>>>(labels, ref_scratch, ref_scratch + nregions, nregions, n, nullptr, nullptr, 0, n, h, w, tiles_of(w), (uint32_t)(tiles_of(w) * tiles_of(h)), 0,
+                                                       ReadBack(), ReadBack());
   return hipGetLastError();
 }
 

@@ -131,12 +131,15 @@ int run_fused_form(ws_ctx *c, const uint8_t *d_img, size_t stride, int ph, int p
     hipError_t e = make_tables();
     for (uint32_t pass = 0; pass < GRAPH_PASSES && e == hipSuccess; ++pass) e = relax_pass(c->stream, captured, pass);
     const uint32_t last = GRAPH_PASSES - 1;
+    // the read-backs: the lookahead pass's convergence slot and the error words.  With a device-visible mirror they ride on
+    // the resolve's last kernel (k_resolve_chase copies them whether its gate is open or not): no launch of their own
+    ResolveJob job = resolve_job(edge_slot(flags, last));
+    if (c->pinned_dev) {
+      job.read_back[0] = {edge_slot(flags, last), (uint32_t)FLAG_SLOT, c->pinned_dev + FLAG_EDGE + (last % COUNTER_RING) * FLAG_SLOT};
+      job.read_back[1] = {flags + FLAG_OVERFLOW, (uint32_t)(FLAG_NERR + 1), c->pinned_dev + FLAG_OVERFLOW};      // (+ 1: FLAG_TOTAL, the minima's count)
+    }
     if (e == hipSuccess)
-      e = resolve_two_launch(c->stream, resolve_job(edge_slot(flags, last)));
-    // the read-backs: the lookahead pass's convergence slot and the error words
-    if (e == hipSuccess && c->pinned_dev)
-      e = words_to_host(c->stream, edge_slot(flags, last), FLAG_SLOT, c->pinned_dev + FLAG_EDGE + (last % COUNTER_RING) * FLAG_SLOT,
-                        flags + FLAG_OVERFLOW, FLAG_NERR + 1, c->pinned_dev + FLAG_OVERFLOW);      // (+ 1: FLAG_TOTAL, the minima's count)
+      e = resolve_two_launch(c->stream, job);
     if (e == hipSuccess && !c->pinned_dev)
       e = hipMemcpyAsync(&c->pinned[FLAG_EDGE + (last % COUNTER_RING) * FLAG_SLOT], edge_slot(flags, last), FLAG_SLOT * sizeof(uint32_t),
                          hipMemcpyDeviceToHost, c->stream);
