@@ -29,6 +29,7 @@ hipError_t fill_u32(hipStream_t s, uint32_t *p, size_t n, uint32_t v) {
 // label plane, the tile-edge stamps and the flag words, and every separate memset is a launch plus
 // a dependency gap (~10 us each).
 typedef uint32_t u32x4_z __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2_z __attribute__((ext_vector_type(2)));
 __global__ void k_zero3(uint32_t *a, size_t na, uint32_t *b, size_t nb, uint32_t *c, size_t nc) {
   const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, step = (size_t)gridDim.x * blockDim.x;
   size_t head = (size_t)((16u - (unsigned)(reinterpret_cast<uintptr_t>(a) & 15u)) & 15u) >> 2;   // words up to 16-byte alignment
@@ -390,6 +391,238 @@ __global__ __launch_bounds__(64 * PAINT_WAVES) void k_seed_tables(const uint32_t
   }
 }
 
+// ---- the same tables in LIST order: one read of the list, no search on the way to it ----------------
+//
+// k_seed_tables gives a wave 8192 pixels, so the wave must FIND its seeds: two 64-ary lower bounds, 4-5 dependent round
+// trips before the first useful load.  For a dense list ownership can go by list position instead: a wave takes the
+// STREAM_E entries [i0, i0 + STREAM_E), all their loads in flight at once, plus entry i0 - 1 and 32 entries of look-ahead.
+//   - a mask word belongs to the wave whose window holds the word's FIRST seed: the wave skips its leading entries that
+//     fall into the word of entry i0 - 1 and takes from the look-ahead the entries of its own last word (a word holds at
+//     most 32 seeds, so it is shared by two windows at the most);
+//   - a run of empty words belongs to the wave that holds the next seed after it, the run behind the last seed to the
+//     last wave; the base of an empty word is the number of seeds before it, as in k_seed_tables (k_resolve_local reads
+//     `first` from such words);
+//   - the wave walks its span of words in pieces of STREAM_ROW words through an LDS row (bits by atomicOr, one wave scan of
+//     the popcounts); a run of empty words before the next seed is written straight from registers, (0, base).
+// One window may own a very long run (all seeds in one half of the plane), which one wave would write alone.  So every
+// aligned chunk of STREAM_BIG words that lies wholly inside one run is left to the plane waves of the same launch: one wave
+// per chunk, the first blocks of the grid, each with one double lower bound (equal ends: the chunk is empty, and the bound
+// is its base).  Chunks that the list waves reach through their rows are written twice, with the same words.
+// The walk is the proof of the list, as in k_seed_tables: every entry is tested once for "in the plane" and "after its
+// predecessor", across windows through entry i0 - 1.  A wave that sees anything else raises the error words and writes
+// nothing; a word index is only ever formed from a position inside the plane, and every fill is bounded by nwords.
+constexpr int STREAM_E = 1024;            // list entries per wave: sixteen 8-byte loads per lane
+constexpr int STREAM_K = STREAM_E / 64;
+constexpr int STREAM_ROW = 512;           // words of a wave's LDS row: eight per lane
+constexpr uint32_t STREAM_BIG = 4096;     // words of a chunk that a plane wave fills when no seed lies in it
+constexpr size_t STREAM_PX_PER_SEED = 16; // seed_tables' rule: this kernel for lists of one seed per so many pixels, or denser
+
+// The wave's steps across lanes without LDS (a __shfl is a ds_bpermute; with some eighty of them per wave the CU's one LDS
+// pipe was a good part of the kernel): a lane's value as a scalar, the value of the lane below by a DPP wave shift, the
+// minimum by the DPP row shifts and row broadcasts of wave_inclusive_sum.
+__device__ __forceinline__ uint32_t lane_value(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
+
+// lane l: the value of lane l - 1; lane 0: `first`
+__device__ __forceinline__ uint32_t lane_below_or(uint32_t v, uint32_t first) {
+  return (uint32_t)__builtin_amdgcn_update_dpp((int)first, (int)v, 0x138, 0xF, 0xF, false);      // wave_shr:1
+}
+
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
+#define WS_DPP_MIN(ctrl, rows) v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, ctrl, rows, 0xF, false))
+  WS_DPP_MIN(0x111, 0xF);      // row_shr:1
+  WS_DPP_MIN(0x112, 0xF);      // row_shr:2
+  WS_DPP_MIN(0x114, 0xF);      // row_shr:4
+  WS_DPP_MIN(0x118, 0xF);      // row_shr:8
+  WS_DPP_MIN(0x142, 0xA);      // row_bcast:15
+  WS_DPP_MIN(0x143, 0xC);      // row_bcast:31
+#undef WS_DPP_MIN
+  return lane_value(v, 63);      // lane 63 holds the minimum of all
+}
+
+// the value again, but new to the compiler: what is computed from it inside a loop stays inside (sixteen words and sixteen
+// bit masks hoisted out of the walk below cost the kernel its eighth wave)
+__device__ __forceinline__ uint32_t opaque_u32(uint32_t v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+
+struct TableOut {
+  uint32_t *mask, *word_base;
+  bool vec_ok;                          // both 16-byte aligned
+  const uint32_t *slice_first;          // stack of slices (slice_px % 128 == 0: an aligned quad of words lies in one slice)
+  uint32_t slice_quads, nslices;        // quads of words per slice (npx < 2^32), slices
+  uint32_t colour_bias;
+};
+
+// the base of the first word of the aligned quad q, from the number of list entries before it: exactly k_seed_tables' rule
+__device__ __forceinline__ uint32_t table_base(const TableOut &t, uint32_t before, uint32_t q) {
+  if (t.slice_first) {
+    const uint32_t sf = t.slice_first[min((q >> 2) / t.slice_quads, t.nslices)];
+    before = before >= sf ? before - sf : 0u;
+  }
+  return before + t.colour_bias;
+}
+
+// words q .. q + 3 (q % 4 == 0) of both tables: those inside [lo, hi] only
+__device__ __forceinline__ void store_quad(const TableOut &t, uint32_t q, uint32_t lo, uint32_t hi, u32x4_z m, u32x4_z b) {
+  if (q >= lo && q + 3 <= hi && t.vec_ok) {
+    *reinterpret_cast<u32x4_z *>(t.mask + q) = m;
+    *reinterpret_cast<u32x4_z *>(t.word_base + q) = b;
+  } else {
+    const uint32_t mv[4] = {m.x, m.y, m.z, m.w}, bv[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) if (q + k >= lo && q + k <= hi) { t.mask[q + k] = mv[k]; t.word_base[q + k] = bv[k]; }
+  }
+}
+
+// empty words [a, b) with `before` list entries before them; b <= nwords
+__device__ __forceinline__ void fill_empty(const TableOut &t, uint32_t a, uint32_t b, uint32_t before, int lane) {
+  if (a >= b) return;
+  for (uint32_t q = (a & ~3u) + 4u * lane; q < b; q += 256u) {
+    const uint32_t v = table_base(t, before, q);
+    store_quad(t, q, a, b - 1, u32x4_z{0u, 0u, 0u, 0u}, u32x4_z{v, v, v, v});
+  }
+}
+
+__global__ __launch_bounds__(64 * PAINT_WAVES) void k_seed_tables_stream(const uint32_t *__restrict__ seeds_rc, size_t n, int ph, int pw,
+                                                                        uint32_t *mask, uint32_t *word_base, size_t npx, uint32_t nwords,
+                                                                        uint32_t plane_blocks, uint32_t *flags,
+                                                                        uint32_t *zero_a, size_t n_zero_a, uint32_t *zero_b, size_t n_zero_b,
+                                                                        const uint32_t *__restrict__ slice_first, uint32_t slice_quads, uint32_t nslices,
+                                                                        uint32_t colour_bias) {
+  __shared__ __attribute__((aligned(16))) uint32_t sRow[PAINT_WAVES][STREAM_ROW];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint2 *seeds = reinterpret_cast<const uint2 *>(seeds_rc);
+  {
+    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, step = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = tid; i < n_zero_a; i += step) zero_a[i] = 0u;
+    for (size_t i = tid; i < n_zero_b; i += step) zero_b[i] = 0u;
+  }
+  if (n == 0) return;      // (seed_tables never sends an empty list here)
+  TableOut t;
+  t.mask = mask; t.word_base = word_base;
+  t.vec_ok = ((reinterpret_cast<uintptr_t>(mask) | reinterpret_cast<uintptr_t>(word_base)) & 15u) == 0;
+  t.slice_first = slice_first; t.slice_quads = slice_quads; t.nslices = nslices;
+  t.colour_bias = colour_bias;
+
+  if (blockIdx.x < plane_blocks) {      // ---- a plane wave: one aligned chunk of STREAM_BIG words, filled if it holds no seed
+    const uint32_t c = blockIdx.x * PAINT_WAVES + wave;
+    if (c >= (nwords + STREAM_BIG - 1) / STREAM_BIG) return;
+    const uint32_t a = c * STREAM_BIG, b = min(a + STREAM_BIG, nwords);
+    const unsigned long long p0 = (unsigned long long)a * 32u, p1 = min((unsigned long long)b * 32u, (unsigned long long)npx);
+    size_t lo, hi;
+    seed_lower_bound2(seeds, n, pw, p0, p1, lane, lo, hi);      // inside [0, n] whatever the list
+    if (lo == hi) fill_empty(t, a, b, (uint32_t)lo, lane);
+    return;
+  }
+
+  // ---- a list wave.  Its loads go through a buffer descriptor over entries [i0 - 1, i0 + STREAM_E + 32) of the list, cut at
+  // its end: the hardware's range check is the clamp (a load behind the end returns zeros, and `mine` drops it), and one
+  // 32-bit offset per lane serves all seventeen loads -- with sixteen 64-bit addresses the kernel held 84 VGPRs.
+  const size_t i0 = ((size_t)(blockIdx.x - plane_blocks) * PAINT_WAVES + (size_t)__builtin_amdgcn_readfirstlane(wave)) * STREAM_E;
+  if (i0 >= n) return;
+  const bool last = i0 + STREAM_E >= n;
+  const uint32_t here = (uint32_t)min(n - i0, (size_t)STREAM_E);      // entries of this window
+  const uint32_t lead = i0 ? 1u : 0u;                                  // entry i0 - 1 in front
+  const uint32_t reach = lead + (uint32_t)min(n - i0, (size_t)(STREAM_E + 32));
+  // (the descriptor from wave-uniform words, said so to the compiler: otherwise every load sits in a loop over lanes)
+  const uintptr_t bp = reinterpret_cast<uintptr_t>(seeds + (i0 - lead));
+  const uintptr_t bu = ((uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(bp >> 32)) << 32) |
+                       (uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)bp);
+  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
+      reinterpret_cast<void *>(bu), 0, __builtin_amdgcn_readfirstlane((int)(reach * 8u)), 0x00020000);
+  const uint32_t off = (lead + (uint32_t)lane) * 8u;
+  uint2 ent[STREAM_K];
+#pragma unroll
+  for (int k = 0; k < STREAM_K; ++k) {
+    const u32x2_z v = __builtin_amdgcn_raw_buffer_load_b64(rsrc, off + 512u * k, 0, 0);
+    ent[k] = make_uint2(v.x, v.y);
+  }
+  // lanes 0 .. 31: the look-ahead; lane 63: entry i0 - 1 (offset 0; the list's first entry, not used, in the first window)
+  const u32x2_z vx = __builtin_amdgcn_raw_buffer_load_b64(rsrc, lane < 32 ? off + 8u * STREAM_E : 0u, 0, 0);
+  const uint2 ex = make_uint2(vx.x, vx.y);
+  // positions in 32 bits (npx < 2^32: seed_tables' rule; word p >> 5, bit p & 31), ~0 for an entry outside the plane or behind
+  // the end of the list: that is the word 2^27 - 1, behind every plane, and never "after" anything
+  const uint32_t x32 = ex.x < (uint32_t)ph && ex.y < (uint32_t)pw ? (uint32_t)seed_pos(ex, pw) : 0xFFFFFFFFu;
+  const uint32_t prev32 = lane_value(x32, 63);
+
+  uint32_t p32[STREAM_K];
+  uint32_t bad = 0u;      // bit 0: not after its predecessor; bit 1: outside the plane
+  uint32_t carry = prev32;      // the entry before lane 0's (uniform)
+#pragma unroll
+  for (int k = 0; k < STREAM_K; ++k) {
+    const bool mine = 64u * k + lane < here;
+    const bool inside = ent[k].x < (uint32_t)ph && ent[k].y < (uint32_t)pw;
+    const uint32_t p = mine && inside ? (uint32_t)seed_pos(ent[k], pw) : 0xFFFFFFFFu;
+    const uint32_t before = lane_below_or(p, carry);
+    const bool has_pred = lane > 0 || k > 0 || i0 > 0;
+    bad |= (mine && has_pred && p <= before ? 1u : 0u) | (mine && !inside ? 2u : 0u);      // (a predecessor outside the plane: ~0, "not after" too)
+    carry = lane_value(p, 63);
+    p32[k] = p;
+  }
+  if (__builtin_amdgcn_ballot_w64(bad != 0u) != 0ull) {      // not a strictly increasing in-plane window: nothing is written
+    if (bad & 2u) atomicExch(&flags[0], 1u);
+    if (lane == 0) { flags[1] = 1u; flags[2] = 1u; }
+    return;
+  }
+  if (i0 > 0 && prev32 == 0xFFFFFFFFu) return;      // (entry i0 - 1 outside the plane: its own window has raised the words)
+
+  // from here on the window is strictly increasing, in the plane, and after entry i0 - 1
+  const uint32_t Wf = i0 ? (prev32 >> 5) + 1u : 0u;                                        // first owned word
+  const uint32_t Wl = last ? nwords - 1u : lane_value(p32[STREAM_K - 1], 63) >> 5;      // last owned word
+  if (Wl < Wf) return;      // the whole window in the word of entry i0 - 1: only a list that another wave refuses
+  const bool x_ok = !last && lane < 32 && i0 + STREAM_E + lane < n && (x32 >> 5) == Wl;
+  uint32_t nskip = 0;      // (uniform: popcounts of ballots)
+#pragma unroll
+  for (int k = 0; k < STREAM_K; ++k)
+    nskip += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64((p32[k] >> 5) < Wf));
+
+  uint32_t *row = sRow[wave];
+  uint32_t ws = Wf, running = (uint32_t)i0 + nskip;      // words before ws are done; `running` list entries lie before ws
+  while (ws <= Wl) {
+    uint32_t m = x_ok ? Wl : 0xFFFFFFFFu;      // the next word that holds a seed
+#pragma unroll
+    for (int k = 0; k < STREAM_K; ++k) {
+      const uint32_t w = opaque_u32(p32[k]) >> 5;
+      if (w >= ws && w <= Wl) m = min(m, w);
+    }
+    m = wave_min_u32(m);
+    const uint32_t g = m == 0xFFFFFFFFu ? Wl + 1u : m;
+    {      // the empty run [ws, g), without the aligned STREAM_BIG chunks wholly inside it (the plane waves')
+      const uint32_t cs = (ws + STREAM_BIG - 1u) & ~(STREAM_BIG - 1u), ce = g & ~(STREAM_BIG - 1u);
+      const bool cut = cs < ce;
+#pragma unroll 1
+      for (int part = 0; part < (cut ? 2 : 1); ++part) fill_empty(t, part ? ce : ws, part || !cut ? g : cs, running, lane);
+    }
+    if (g > Wl) break;
+    const uint32_t rb = g & ~3u;                                     // the row starts at an aligned quad; words [g, pe] are written
+    const uint32_t pe = min(rb + (uint32_t)STREAM_ROW - 1u, Wl);
+    *reinterpret_cast<u32x4_z *>(&row[lane * 8]) = u32x4_z{0u, 0u, 0u, 0u};
+    *reinterpret_cast<u32x4_z *>(&row[lane * 8 + 4]) = u32x4_z{0u, 0u, 0u, 0u};
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");      // the zeroed row before the bits
+#pragma unroll
+    for (int k = 0; k < STREAM_K; ++k) {
+      const uint32_t p = opaque_u32(p32[k]), w = p >> 5;
+      if (w >= g && w <= pe) atomicOr(&row[w - rb], 1u << (p & 31u));
+    }
+    if (x_ok && Wl <= pe) atomicOr(&row[Wl - rb], 1u << (x32 & 31u));
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    const u32x4_z wa = *reinterpret_cast<const u32x4_z *>(&row[lane * 8]);
+    const u32x4_z wb = *reinterpret_cast<const u32x4_z *>(&row[lane * 8 + 4]);
+    const uint32_t a0 = __popc(wa.x), a1 = __popc(wa.y), a2 = __popc(wa.z), ca = a0 + a1 + a2 + __popc(wa.w);
+    const uint32_t b0 = __popc(wb.x), b1 = __popc(wb.y), b2 = __popc(wb.z), cnt = ca + b0 + b1 + b2 + __popc(wb.w);
+    const uint32_t incl = wave_inclusive_sum(cnt);
+    const uint32_t before = running + incl - cnt;      // list entries before this lane's eight words
+    const uint32_t q = rb + 8u * lane;
+    const uint32_t ba = table_base(t, before, q), bb = table_base(t, before + ca, q + 4u);
+    store_quad(t, q, g, pe, wa, u32x4_z{ba, ba + a0, ba + a0 + a1, ba + a0 + a1 + a2});
+    store_quad(t, q + 4u, g, pe, wb, u32x4_z{bb, bb + b0, bb + b0 + b1, bb + b0 + b1 + b2});
+    running += lane_value(incl, 63);
+    ws = pe + 1u;
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");      // the row is read before it is zeroed again
+  }
+}
+
 static int paint_steps() {
   static const int steps = [] {
     const char *e = tuning_env("WS_PAINT_STEPS");      // tuning knob, tools/ only
@@ -425,6 +658,25 @@ hipError_t seed_tables(hipStream_t s, const uint32_t *seeds_rc, size_t n, int ph
                        uint32_t *err_flag, uint32_t *zero_a, size_t n_zero_a, uint32_t *zero_b, size_t n_zero_b,
                        const uint32_t *slice_first, size_t slice_px, uint32_t colour_bias) {
   const size_t npx = (size_t)ph * pw;
+  // Which builder: from what the host knows, n and the plane (fixed for a captured graph, which is replayed only when
+  // buffers and n repeat).  The list-order kernel for lists of one seed per STREAM_PX_PER_SEED pixels or denser; an
+  // empty or sparser list keeps the searches, which are cheap on a short list and spread the empty words over the device
+  // (profiles/seed_stream_density.txt).
+  static const int forced = [] { const char *e = tuning_env("WS_SEED_STREAM"); return e ? atoi(e) : -1; }();      // A/B knob for tools/
+  bool stream = n > 0 && n < ((size_t)1 << 32) && npx < ((size_t)1 << 32) && n * STREAM_PX_PER_SEED >= npx;
+  if (forced >= 0) stream = forced > 0 && n > 0 && n < ((size_t)1 << 32) && npx < ((size_t)1 << 32);
+  if (stream) {
+    const uint32_t nwords = (uint32_t)((npx + 31) / 32);
+    const uint32_t plane_blocks = ((nwords + STREAM_BIG - 1) / STREAM_BIG + PAINT_WAVES - 1) / PAINT_WAVES;
+    const size_t list_blocks = ((n + STREAM_E - 1) / STREAM_E + PAINT_WAVES - 1) / PAINT_WAVES;
+    // slices in quads of words (slice_px % 128 == 0), and their number: k_seed_tables' clamp of the slice index
+    const uint32_t slice_quads = slice_first ? (uint32_t)std::max<size_t>(std::min<size_t>(slice_px / 128, 0xFFFFFFFFu), 1) : 1u;
+    const uint32_t nslices = slice_first ? (uint32_t)((npx + slice_px - 1) / slice_px) : 0u;
+    k_seed_tables_stream<<<(unsigned)(plane_blocks + list_blocks), 64 * PAINT_WAVES, 0, s>>>(
+        seeds_rc, n, ph, pw, mask, word_base, npx, nwords, plane_blocks, err_flag, zero_a, n_zero_a, zero_b, n_zero_b, slice_first,
+        slice_quads, nslices, colour_bias);
+    return hipGetLastError();
+  }
   const size_t per_wave = (size_t)TAB_WORDS * 32;
   const size_t nchunk = (npx + per_wave - 1) / per_wave;
   const size_t blocks = std::max<size_t>((nchunk + PAINT_WAVES - 1) / PAINT_WAVES, 1);
