@@ -38,7 +38,9 @@
  *     make_colour_map's closure (lib.rs:508-541), which is a function of the order of the pair list
  *     (parallel unstable sort + dedup, lib.rs:440-443) -- deterministic for a given list, but not a
  *     property of the lake.  This engine returns the canonical id: the smallest seed colour whose
- *     seed pixel lies in the lake.  The PARTITION into lakes is the reference's (tested against the
+ *     seed pixel lies in the lake AND still carries it after seeding (a later list entry on the same
+ *     pixel overwrites an earlier one, lib.rs:1670-1677: the earlier colour exists nowhere and is
+ *     nobody's id, in any entry point).  The PARTITION into lakes is the reference's (tested against the
  *     oracle's faithful closure under random tie-breaks); the id values are a documented deviation,
  *     "parity unpinned" by the reference (it has no test or fixture for them).
  */

@@ -1034,8 +1034,14 @@ __global__ void k_tile_roots(uint32_t *tile_min, int ntiles, uint32_t *parent, u
 // reading the slot -- nobody else reads or writes it in this launch: a union names a colour only as the seed's own (this
 // thread) or as a tile root (marked), and a find only passes through colours that something was hooked under.  Every
 // other case takes the union.  (54 -> 45 us at 8192^2: what is left is the 16 B per seed the kernel moves.)
-__global__ void k_union_seeds(const uint32_t *__restrict__ seeds_rc, size_t n_seeds, int H, int W, int tilesX,
-                              const uint32_t *__restrict__ tile_min, uint32_t *parent, const uint32_t *__restrict__ tile_root_mark) {
+// A list entry whose pixel a LATER entry names again has lost its colour (the later one overwrites it, lib.rs:1670-1677):
+// colour i + 1 exists nowhere in the plane and must not become a lake's id.  Hooked under a smaller root it is harmless -- no
+// pixel carries it -- so only the case that would hook the tile's root under it (i + 1 < root) looks: at the final level a
+// seed pixel's label is the colour painted last, one load of `labels` decides, and the plain-store path above keeps its
+// argument (an overwritten colour is unmarked, its own root and nobody's parent, like any untouched one).
+__global__ void k_union_seeds(const uint32_t *__restrict__ labels, const uint32_t *__restrict__ seeds_rc, size_t n_seeds, int H, int W,
+                              int tilesX, const uint32_t *__restrict__ tile_min, uint32_t *parent,
+                              const uint32_t *__restrict__ tile_root_mark) {
   // (four seeds per thread and round, each stage's loads in flight together: the kernel is three dependent loads and a
   // store per seed, and with one seed per thread it was 54 us of waiting for them)
   constexpr int SU = 4;
@@ -1063,7 +1069,7 @@ __global__ void k_union_seeds(const uint32_t *__restrict__ seeds_rc, size_t n_se
       const uint32_t me = (uint32_t)(i0 + u * step + 1);
       if (!ok[u] || cmin[u] == 0u || cmin[u] == me || image_corner((int)rc[u].x, (int)rc[u].y, H, W)) continue;
       if (cmin[u] < me && mark[u] == 0u) parent[me] = cmin[u];      // (unmarked: parent[me] == me still, see k_tile_roots)
-      else uf_union(parent, me, cmin[u]);
+      else if (cmin[u] < me || labels[(size_t)rc[u].x * W + rc[u].y] == me) uf_union(parent, me, cmin[u]);      // (ok[u]: the pixel is in the plane)
     }
   }
 }
@@ -1121,7 +1127,7 @@ hipError_t union_image(hipStream_t s, const uint32_t *labels, const uint32_t *se
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if (n_seeds) {
     const int blocks = (int)std::min<size_t>((n_seeds + 1023) / 1024, 16384);      // four seeds per thread
-    k_union_seeds<<<blocks, 256, 0, s>>>(seeds_rc, n_seeds, h, w, tx, tile_min, parent, tile_root_mark);
+    k_union_seeds<<<blocks, 256, 0, s>>>(labels, seeds_rc, n_seeds, h, w, tx, tile_min, parent, tile_root_mark);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     k_tile_edges<<<tx * ty, 256, 0, s>>>(labels, h, w, tx, ty, tile_min, parent);
     if ((e = hipGetLastError()) != hipSuccess) return e;
