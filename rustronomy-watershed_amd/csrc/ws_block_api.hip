@@ -272,7 +272,7 @@ int ws_block_import_boundary(ws_ctx *c, const uint32_t *d_table, size_t world, s
 //
 // After the tiled segmenting transform (labels of the block final, halo rows included):
 //   ws_block_merge_local    a union-find over ALL n_colours_total seed colours of the field in the caller's d_parent,
-//                           the block's touching colours joined (ws_merge.hip, k_block_union_pixels)
+//                           the block's touching colours joined (ws_merge_final.hip, k_block_union_pixels)
 //   ws_block_merge_export   (colour, root) of the block's boundary and halo rows: 4 * w pairs
 //   all-gather of the pairs (distributed.py)
 //   ws_block_merge_import   joins every gathered pair

@@ -1,5 +1,6 @@
 // ws_lists.hip -- the merging drivers (lib.rs:1328-1522) and transform_to_list (lib.rs:1551-1561, 1837-1847): per-level
-// unions over seed colours, lake areas and sparse lake records (kernels: ws_merge.hip).
+// unions over seed colours, lake areas and sparse lake records (kernels: ws_merge.hip the level loop, ws_merge_final.hip the
+// final labels alone, ws_merge_tree.hip history planes, merge tree and lake statistics; wrappers: ws_merge.hpp).
 #include "ws_ctx.hpp"
 #include "ws_level_plan.hpp"
 

@@ -1,4 +1,5 @@
-// ws_merge.hpp -- launch wrappers of the merging-transform kernels (ws_merge.hip).
+// ws_merge.hpp -- launch wrappers of the merging-transform kernels, in three sources: ws_merge.hip (the level loop),
+// ws_merge_final.hip (final labels only) and ws_merge_tree.hip (what reads the stamped forest); ws_uf.hpp is what they share.
 //
 // The reference's merging driver (lib.rs:1328-1522) floods exactly like the segmenting one
 // and, after every level, merges every pair of touching lakes (find_merge lib.rs:393-445,
@@ -21,34 +22,30 @@ constexpr int NLEVELS = 256;
 
 typedef unsigned long long u64c;
 
+// ==== ws_merge.hip: the level loop -- buckets, unions, areas, lake records, the live-lake list, the stamped unions ====
 // parent[i] = i for i in 0..n, size[i] = 0
 hipError_t uf_init(hipStream_t s, uint32_t *parent, uint32_t *size, size_t n);
 
 // per-level histograms of arriving pixels and of label-crossing edges (256 bins each)
 // slice_base (nullable): the plane is a stack of slices of slice_h rows whose labels restart at 1 in every slice; colour c of
 // slice k is c + slice_base[k] (one numbering for the stack) and no pair crosses a slice border
-hipError_t level_hist(hipStream_t s, const uint32_t *keys, const uint32_t *labels, int h, int w,
-                      u64c *hist_px, u64c *hist_edge, int slice_h = 0, const uint32_t *slice_base = nullptr);
+hipError_t level_hist(hipStream_t s, const uint32_t *keys, const uint32_t *labels, int h, int w, u64c *hist_px, u64c *hist_edge, int slice_h, const uint32_t *slice_base);
 // bucketed scatter: px_items[cursor_px[lvl]++] = colour, edge_items[cursor_edge[lvl]++] = (a,b)
-hipError_t level_scatter(hipStream_t s, const uint32_t *keys, const uint32_t *labels, int h, int w,
-                         u64c *cursor_px, u64c *cursor_edge, uint32_t *px_items, uint2 *edge_items,
-                         int slice_h = 0, const uint32_t *slice_base = nullptr);
+hipError_t level_scatter(hipStream_t s, const uint32_t *keys, const uint32_t *labels, int h, int w, u64c *cursor_px, u64c *cursor_edge,
+                         uint32_t *px_items, uint2 *edge_items, int slice_h, const uint32_t *slice_base);
 
 // exclusive prefix sums of the histograms (NLEVELS + 1 entries each) and the scatter cursors, all on the device
 hipError_t level_offsets(hipStream_t s, const u64c *hist_px, const u64c *hist_ed, u64c *off_px, u64c *off_ed, u64c *cur_px, u64c *cur_ed);
 // the per-level kernels on a bucket whose bounds {first, end} sit in device memory (range = off + level): fixed grid,
 // grid-stride loops -- nothing the host has to read before it launches, so the whole level loop can be captured
+// lock-free union-by-min of the bucket's edges; every node that loses its root status is appended to hooked (nullable)
 hipError_t union_edges_ranged(hipStream_t s, const uint2 *edge_items, const u64c *range, unsigned grid, uint32_t *parent, uint32_t *hooked,
                               uint32_t *hooked_count);
+// areas of the nodes hooked in this level to their roots (hooked may be null: nothing was hooked) + arriving pixels counted
 hipError_t fold_and_add_ranged(hipStream_t s, const uint32_t *hooked, const uint32_t *hooked_count, const uint32_t *px_items,
                                const u64c *range, unsigned grid, uint32_t *parent, uint32_t *size);
-
-// lock-free union-by-min of n edges; every node that loses its root status is appended to hooked
-hipError_t union_edges(hipStream_t s, const uint2 *edges, size_t n, uint32_t *parent, uint32_t *hooked,
-                       uint32_t *hooked_count);
-// areas of the nodes hooked in this level to their roots (hooked may be null: nothing was hooked) + arriving pixels counted
-hipError_t fold_and_add(hipStream_t s, const uint32_t *hooked, const uint32_t *hooked_count, const uint32_t *px_items, size_t n,
-                        uint32_t *parent, uint32_t *size);
+// the same unions of n edges the host holds the count of (the gathered pairs of a tiled field's blocks)
+hipError_t union_edges(hipStream_t s, const uint2 *edges, size_t n, uint32_t *parent, uint32_t *hooked, uint32_t *hooked_count);
 // appends (colour, area) of every root with area > 0 behind the records of the earlier levels; counts past cap too
 // level_counts: one record counter per level, zero on entry; the records of level l start at the sum of
 // level_counts[0 .. l) (earlier launches) and level_counts[l] receives this level's count
@@ -74,6 +71,25 @@ hipError_t emit_alive(hipStream_t s, const uint2 *sd, size_t n_colours, uint32_t
 hipError_t fold_and_add_sd(hipStream_t s, const uint32_t *hooked, const uint32_t *hooked_count, const uint32_t *px_items, const u64c *range,
                            unsigned grid, uint32_t *parent, uint2 *sd);
 
+// out[p] = coloured by `level` ? root(labels[p]) : 0
+hipError_t relabel_u32(hipStream_t s, const uint32_t *keys, const uint32_t *labels, uint32_t *parent, uint32_t *out, size_t n, uint32_t level);
+hipError_t relabel_u64(hipStream_t s, const uint32_t *keys, const uint32_t *labels, uint32_t *parent, uint64_t *out, size_t n, uint32_t level);
+
+// transform_history (ws_transform_history_device): the unions of `level` that also stamp the merge forest -- hook[b] = the root b
+// was hooked under, death[b] = level (death: 0xFFFFFFFF at the start; hook is read only where death is set)
+hipError_t union_stamped_ranged(hipStream_t s, const uint2 *edge_items, const u64c *range, unsigned grid, uint32_t *parent, uint32_t *death,
+                                uint32_t *hook, uint32_t level);
+
+// A stack of n_slices slices of slice_h x w pixels flooded as one plane (labels restart at 1 in every slice; base: n_slices + 1
+// words, colour c of slice k is c + base[k] in the stack's numbering).
+// hist[k * NLEVELS + l] += pixels of slice k that arrive at level l (n_slices * NLEVELS words, zeroed by the caller)
+hipError_t slice_arrivals(hipStream_t s, const uint32_t *keys, size_t plane, size_t n_slices, u64c *hist);
+// the stack's lake records (level-major, off: levels + 1 prefix sums, stack colours) into slice-major bins k * levels + l:
+// scatter false adds the bins' counts into `bins`; true writes every record, as (colour - base[k], area), at out[bins[bin]++]
+hipError_t split_records(hipStream_t s, bool scatter, const uint64_t *rec, size_t n_rec, const u64c *off, uint32_t levels,
+                         const uint32_t *base, uint32_t g, u64c *bins, uint64_t *out);
+
+// ==== ws_merge_final.hip: final labels only (coloured <=> label != 0) ====
 // merging across the row blocks of a tiled field: joins the touching colours of one block (seam pairs to its halo rows
 // included; row0 = field row of the block's first local row, H = rows of the whole field), and the (colour, root) pairs
 // of the block's boundary and halo rows (4 * w of them) that the ranks exchange
@@ -81,25 +97,20 @@ hipError_t block_union_pixels(hipStream_t s, const uint32_t *labels, int h, int 
 hipError_t block_colour_roots2d(hipStream_t s, const uint32_t *labels, int h, int w, uint32_t *parent, uint2 *pairs, size_t n_pairs);      // rows and columns: 4 w + 4 h pairs, (0, 0) after them
 hipError_t block_colour_roots(hipStream_t s, const uint32_t *labels, int h, int w, uint32_t *parent, uint2 *pairs);
 
-// final-only path: union every crossing edge of the whole image in one launch
-// final level only (coloured <=> label != 0); tile_min: union_image_tiles(h, w) words of scratch
+// the whole image: every crossing edge joined, tile by tile; tile_min: union_image_tiles(h, w) words of scratch
+// preclassified: resolve_two_launch filled tile_min; tile_root_mark: n_seeds + 1 zeroed words (k_union_seeds' plain-store hooks)
 size_t union_image_tiles(int h, int w);
 hipError_t union_image(hipStream_t s, const uint32_t *labels, const uint32_t *seeds_rc, size_t n_seeds, int h, int w,
-                       uint32_t *parent, uint32_t *tile_min, bool preclassified = false,      // preclassified: resolve_two_launch filled tile_min
-                       uint32_t *tile_root_mark = nullptr);      // optional: n_seeds + 1 zeroed words (k_union_seeds' plain-store hooks)
+                       uint32_t *parent, uint32_t *tile_min, bool preclassified, uint32_t *tile_root_mark);
 // flattens the forest (n_colours entries, entry 0 = "uncoloured" points at itself) and gathers out[i] = root(labels[i])
 hipError_t relabel_final_u32(hipStream_t s, const uint32_t *labels, uint32_t *parent, size_t n_colours, uint32_t *out, size_t n,
                              uint32_t *tile_min = nullptr, int h = 0, int w = 0);      // tile_min: union_image's classification of the h x w plane's tiles (one-lake tiles are filled)
-// out[p] = coloured by `level` ? root(labels[p]) : 0
-hipError_t relabel_u32(hipStream_t s, const uint32_t *keys, const uint32_t *labels, uint32_t *parent,
-                       uint32_t *out, size_t n, uint32_t level);
-hipError_t relabel_u64(hipStream_t s, const uint32_t *keys, const uint32_t *labels, uint32_t *parent,
-                       uint64_t *out, size_t n, uint32_t level);
+// a stack of slices (as slice_arrivals'): final canonical labels of every slice, in place (parent: n_colours = base[n_slices] + 1
+// words, uf_init'ed)
+hipError_t merge_stack(hipStream_t s, uint32_t *labels, int slice_h, int w, size_t n_slices, const uint32_t *base, uint32_t *parent,
+                       size_t n_colours);
 
-// transform_history (ws_transform_history_device): the unions of `level` that also stamp the merge forest -- hook[b] = the root b
-// was hooked under, death[b] = level (death: 0xFFFFFFFF at the start; hook is read only where death is set)
-hipError_t union_stamped_ranged(hipStream_t s, const uint2 *edge_items, const u64c *range, unsigned grid, uint32_t *parent, uint32_t *death,
-                                uint32_t *hook, uint32_t level);
+// ==== ws_merge_tree.hip: what reads the stamped forest (death / hook) -- history planes, the merge tree, lake statistics ====
 // the requested levels in ascending order: e[j] = level | slot << 8 (slot: the output plane, at out + slot * plane_stride)
 constexpr int HISTORY_MAX_LEVELS = 256;
 struct HistoryTable {
@@ -120,18 +131,6 @@ struct HistoryStack {
 hipError_t render_history_stack(hipStream_t s, bool merging, const uint32_t *keys, const uint32_t *labels, const uint32_t *death,
                                 const uint32_t *hook, const HistoryTable &tab, uint32_t *out, size_t plane_stride, size_t n,
                                 const HistoryStack &st);
-
-// A stack of n_slices slices of slice_h x w pixels flooded as one plane (labels restart at 1 in every slice; base: n_slices + 1
-// words, colour c of slice k is c + base[k] in the stack's numbering).
-// hist[k * NLEVELS + l] += pixels of slice k that arrive at level l (n_slices * NLEVELS words, zeroed by the caller)
-hipError_t slice_arrivals(hipStream_t s, const uint32_t *keys, size_t plane, size_t n_slices, u64c *hist);
-// the stack's lake records (level-major, off: levels + 1 prefix sums, stack colours) into slice-major bins k * levels + l:
-// scatter false adds the bins' counts into `bins`; true writes every record, as (colour - base[k], area), at out[bins[bin]++]
-hipError_t split_records(hipStream_t s, bool scatter, const uint64_t *rec, size_t n_rec, const u64c *off, uint32_t levels,
-                         const uint32_t *base, uint32_t g, u64c *bins, uint64_t *out);
-// merging transform, final canonical labels of every slice, in place (parent: n_colours = base[n_slices] + 1 words, uf_init'ed)
-hipError_t merge_stack(hipStream_t s, uint32_t *labels, int slice_h, int w, size_t n_slices, const uint32_t *base, uint32_t *parent,
-                       size_t n_colours);
 
 // merge tree (ws_merge_tree_device): one record per seed colour from the stamped forest (death / hook) of a merging transform_history
 // run, the flood's stamps and segmenting colours.  The records are their own accumulators: area and n_leaves are added to in place.

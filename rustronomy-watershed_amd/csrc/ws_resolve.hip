@@ -197,7 +197,7 @@ hipError_t resolve_pass(hipStream_t s, const uint32_t *keys, uint32_t *labels, i
 // a colour of the tile that is not a reference (0: not one lake; RL_TILE_UNDECIDED: one lake, but every pixel's
 // chain leaves the tile, k_tile_scan looks at the finished labels).  Saves a 268 MB pass over the label plane.
 // With halo seeds' colours (below) tile_min may be the colour of a seed in the NEIGHBOURING tile.  It is still a colour that
-// some pixel of this tile holds in the finished plane, and nothing in ws_merge.hip asks for more: k_tile_scan, the same
+// some pixel of this tile holds in the finished plane, and nothing in ws_merge_final.hip asks for more: k_tile_scan, the same
 // word's other source, takes the smallest colour of the finished labels, foreign ones included; k_tile_links and k_tile_roots
 // join and replace colours; k_union_seeds joins every seed of the tile with it (one lake: all of the tile is one set, whichever
 // member names it); k_tile_edges joins the edge pixels' colours with it.  A corner pixel is never flooded, so it never holds a

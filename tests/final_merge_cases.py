@@ -1,4 +1,4 @@
-"""Inputs for the final merged labels of ws_merge_device (csrc/ws_merge.hip, union_image): the 64 x 64 "one-lake tile" route of
+"""Inputs for the final merged labels of ws_merge_device (csrc/ws_merge_final.hip, union_image): the 64 x 64 "one-lake tile" route of
 k_tile_scan, k_tile_links, k_tile_roots, k_union_seeds, k_tile_edges, k_union_tiles and k_relabel_tiles, which no other merging
 entry point takes.  Plain numpy, seeded, no GPU, no oracle.  tests/test_final_merge_cases_cpu.py proves on the oracle that every
 family is in its regime; tests/test_gpu_final_merge.py compares the device with the oracle bit for bit.

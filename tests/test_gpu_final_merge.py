@@ -1,4 +1,4 @@
-"""The final merged labels of ws_merge_device (union_image in csrc/ws_merge.hip: the one-lake tile route) on the duplicate seed
+"""The final merged labels of ws_merge_device (union_image in csrc/ws_merge_final.hip: the one-lake tile route) on the duplicate seed
 lists and the long tile runs of tests/final_merge_cases.py, -m gpu.  Every comparison is on all pixels, bit for bit, against the
 CPU oracle (ol.merge_arrival); tests/test_final_merge_cases_cpu.py proves that the inputs are in their regimes.
 
