@@ -34,6 +34,7 @@ constexpr int TS = 64;        // tile side of the label-resolve kernels
 constexpr int LP = TS + 2;    // LDS tile side including the 1-px halo
 constexpr int STRIP = 16;     // rows per thread there: 256 threads = 64 columns x 4 strips
 constexpr int NTHREADS = 256;
+constexpr int GRID_Y_MAX = 65535;      // the most a launch takes in gridDim.y: what puts rows or slices there goes in runs of this many
 
 // Per-pass convergence words.  Workgroups never share an atomic: a tile that changed stores 1
 // (plain, idempotent) into the stripe blockIdx % NSTRIPE of the pass's slot; stripes sit on their

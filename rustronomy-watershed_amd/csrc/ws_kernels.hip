@@ -843,9 +843,9 @@ __device__ __forceinline__ uint32_t pick_drlu(uint32_t d, uint32_t r, uint32_t l
 // was coloured" word is a plain idempotent store (one shared atomic per workgroup would serialise).
 __global__ __launch_bounds__(256) void k_flood_step(const uint8_t *__restrict__ img, size_t img_stride,
                                                     const uint32_t *__restrict__ lin, uint32_t *__restrict__ lout,
-                                                    int H, int W, uint32_t level, uint32_t *counter, int pad) {
+                                                    int H, int W, uint32_t level, uint32_t *counter, int pad, int y0) {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-  const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+  const int y = y0 + blockIdx.y * 4 + (threadIdx.x >> 6);
   const int xc = min(x, W - 1), yc = min(y, H - 1);
   const int xm = max(xc - 1, 0), xp = min(xc + 1, W - 1), ym = max(yc - 1, 0), yp = min(yc + 1, H - 1);
   const uint32_t c = lin[(size_t)yc * W + xc];
@@ -862,8 +862,8 @@ __global__ __launch_bounds__(256) void k_flood_step(const uint8_t *__restrict__ 
 // as 16-byte vectors, the image as one dword; a workgroup covers 1024 pixels of one row
 __global__ __launch_bounds__(256) void k_flood_step4(const uint8_t *__restrict__ img, size_t img_stride,
                                                      const uint32_t *__restrict__ lin, uint32_t *__restrict__ lout,
-                                                     int H, int W, uint32_t level, uint32_t *counter) {
-  const int y = blockIdx.y;
+                                                     int H, int W, uint32_t level, uint32_t *counter, int y0) {
+  const int y = y0 + blockIdx.y;
   const int x0 = (blockIdx.x * 256 + threadIdx.x) * 4;
   if (x0 >= W) return;
   const int ym = max(y - 1, 0), yp = min(y + 1, H - 1);
@@ -888,15 +888,21 @@ __global__ __launch_bounds__(256) void k_flood_step4(const uint8_t *__restrict__
   if (any) *counter = 1u;
 }
 
+// (gridDim.y holds at most GRID_Y_MAX rows -- row groups of four in the scalar form: a taller plane goes in runs of rows, every
+// run the same kernel from its first row y0 on; a plane below that height is one launch as before)
 hipError_t flood_step(hipStream_t s, const uint8_t *img, size_t img_stride, const uint32_t *lin,
                       uint32_t *lout, int h, int w, uint32_t level, uint32_t *counter, bool padded) {
   if (h == 0 || w == 0) return hipSuccess;
   if (!padded && (w & 3) == 0 && ((reinterpret_cast<uintptr_t>(img) | img_stride) & 3u) == 0) {
-    dim3 grid((w / 4 + 255) / 256, h);
-    k_flood_step4<<<grid, 256, 0, s>>>(img, img_stride, lin, lout, h, w, level, counter);
+    for (long long y0 = 0; y0 < h; y0 += GRID_Y_MAX) {
+      dim3 grid((w / 4 + 255) / 256, (unsigned)std::min<long long>(h - y0, GRID_Y_MAX));
+      k_flood_step4<<<grid, 256, 0, s>>>(img, img_stride, lin, lout, h, w, level, counter, (int)y0);
+    }
   } else {
-    dim3 grid((w + 63) / 64, (h + 3) / 4);
-    k_flood_step<<<grid, 256, 0, s>>>(img, img_stride, lin, lout, h, w, level, counter, padded ? 1 : 0);
+    for (long long y0 = 0; y0 < h; y0 += 4 * GRID_Y_MAX) {
+      dim3 grid((w + 63) / 64, (unsigned)((std::min<long long>(h - y0, 4 * GRID_Y_MAX) + 3) / 4));
+      k_flood_step<<<grid, 256, 0, s>>>(img, img_stride, lin, lout, h, w, level, counter, padded ? 1 : 0, (int)y0);
+    }
   }
   return hipGetLastError();
 }

@@ -711,7 +711,11 @@ __global__ __launch_bounds__(256) void k_slice_arrivals(const uint32_t *__restri
 hipError_t slice_arrivals(hipStream_t s, const uint32_t *keys, size_t plane, size_t n_slices, u64c *hist) {
   if (plane == 0 || n_slices == 0) return hipSuccess;
   const unsigned bx = (unsigned)std::min<size_t>(std::max<size_t>(plane / (4 * 256 * 16), 1), 256);      // ~16 words a thread
-  k_slice_arrivals<<<dim3(bx, (unsigned)n_slices), 256, 0, s>>>(keys, plane, hist);
+  // gridDim.y holds at most GRID_Y_MAX slices: a stack of more (thumbnails: stackable() groups up to 2^24 of them) goes in runs
+  for (size_t k0 = 0; k0 < n_slices; k0 += GRID_Y_MAX) {
+    const size_t run = std::min<size_t>(n_slices - k0, GRID_Y_MAX);
+    k_slice_arrivals<<<dim3(bx, (unsigned)run), 256, 0, s>>>(keys + k0 * plane, plane, hist + k0 * NLEVELS);
+  }
   return hipGetLastError();
 }
 
