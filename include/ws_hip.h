@@ -492,6 +492,54 @@ int ws_merge_tree_stats(ws_ctx *ctx, const uint8_t *img, size_t h, size_t w, siz
 int ws_merge_tree_from_arrival_device(ws_ctx *ctx, const uint32_t *d_keys, const uint32_t *d_seg_labels, size_t h, size_t w,
                                       size_t n_seeds, const ws_options *opt, const void *d_weight, int weight_dtype,
                                       size_t weight_row_stride, ws_tree_node *d_tree, ws_lake_stats *d_stats);
+/* One cut of a merge tree (ws_tree_cut_device).  12 bytes. */
+typedef struct ws_tree_cut {
+  uint32_t min_area;    /* a lake that was swallowed counts only if it had reached this many pixels ... */
+  uint32_t min_leaves;  /* ... and held this many seed colours; lakes that never died always count */
+  uint8_t show_level;   /* pixels that arrive after this water level are 0; <= 254 */
+  uint8_t merge_level;  /* every merge up to this water level is applied; <= 254 */
+  uint8_t reserved[2];  /* must be zero */
+} ws_tree_cut;
+/* Label planes and lake lists of a merge tree pruned by lake size, number of leaves and level, from a tree the caller holds in HBM
+ * and the two planes of the flood it came from -- no image, no second run of the level loop.  d_tree: n_seeds + 1 records as
+ * ws_merge_tree*_device writes them; d_keys: the arrival stamps (level << 24 | ring, 0xFF000000 never coloured); d_seg_labels: the
+ * segmenting labels; both h x w u32 planes taken as they stand (a padded plane is passed padded, as ws_lists_from_arrival_device;
+ * views off 16-byte alignment fall back to scalar loads).  Node a is KEPT by a cut iff death_level[a] == WS_TREE_ALIVE or
+ * (area[a] >= min_area and n_leaves[a] >= min_leaves).  For pixel p with c = d_seg_labels[p] and t = d_keys[p] >> 24:
+ *   out[p] = 0 if c == 0 or t > show_level; otherwise the first a on the chain c, parent[c], parent[parent[c]], ... that is kept
+ *   and has death_level[a] > max(t, merge_level) (an alive node has).
+ * min_area = min_leaves = 0 and show_level = merge_level = L is the merging history plane of level L (ws_transform_history_device);
+ * show_level = 254, merge_level = 0, min_area = A sends every pixel to the smallest lake it ever belonged to that reached A pixels
+ * before it was swallowed.  The regions of a cut need not be connected.
+ * cuts: 1 <= n_cuts <= 32 on the HOST, in any order, repeats allowed; n_cuts == 0 runs nothing and writes nothing.  Plane k goes to
+ * d_out + k * plane_stride (plane_stride >= h * w; 16-byte stores when d_out is 16-byte aligned and plane_stride % 4 == 0,
+ * otherwise every pixel is stored on its own); d_out == NULL: lists only.  d_lakes != NULL: the records d_lakes[offsets[k] ..
+ * offsets[k + 1]) are (colour a, pixels with out_k == a) for every a != 0 with pixels, in INCREASING colour; hidden[k] = pixels
+ * with out_k == 0; offsets (n_cuts + 1) and hidden (n_cuts) on the host; *n_lakes and WS_ERR_CAPACITY as
+ * ws_transform_to_list_device (on overflow only *n_lakes is meaningful).  d_lakes == NULL with d_out != NULL: planes only, and
+ * n_lakes, offsets and hidden may be NULL.
+ * Refused with WS_ERR_BAD_ARG before any walk runs, outputs untouched: null pointers with non-zero sizes, both outputs NULL, a
+ * level above 254, non-zero reserved, more than 32 cuts, a short plane_stride, d_out equal to d_keys or d_seg_labels, a context
+ * that holds a begun transform, and a tree that is no merge tree -- one pass over the records (it reads no index above n_seeds)
+ * wants of every record either death_level == WS_TREE_ALIVE and parent == 0, or death_level <= 254, 0 < parent < c and
+ * death_level[parent] > death_level[c]; the host reads its verdict before anything else is launched.  A label above n_seeds is
+ * compared before it indexes anything, written as 0, and the call returns WS_ERR_BAD_ARG with the outputs unspecified.
+ * WS_ERR_TOO_LARGE: a plane of 2^32 pixels or more, and, with lists, n_cuts * (n_seeds + 1) >= 2^32 (the counters are indexed in 32 bits).
+ * n_seeds == 0 or h * w == 0: the planes are zero, the lists empty, hidden = h * w.  Stream ordered; returns with the host
+ * arrays complete.  ws_last_arrival_device keeps reporting what it reported before.  Workspace kept by the context: 4 B per
+ * colour per cut (the tables), 4 B per colour per cut with lists (the counters, and 12 B per 1024 of them), and four flag words
+ * (DESIGN.md section 4.4). */
+int ws_tree_cut_device(ws_ctx *ctx, const ws_tree_node *d_tree, size_t n_seeds, const uint32_t *d_keys, const uint32_t *d_seg_labels,
+                       size_t h, size_t w, const ws_tree_cut *cuts, size_t n_cuts, uint32_t *d_out, size_t plane_stride,
+                       ws_lake *d_lakes, size_t cap, size_t *n_lakes, uint64_t *offsets, uint64_t *hidden);
+/* The whole route from and into HOST memory (the host ws_merge_tree hands back no stamps): upload, ws_merge_tree, ws_tree_cut_device
+ * on its labels and stamps, download.  Image, seeds, edge correction, seed_shift and duplicate seeds as ws_merge_tree; tree
+ * (nullable): the n_seeds + 1 records; out (nullable): n_cuts contiguous u64 planes of the padded shape; lakes (nullable: planes
+ * only), cap, n_lakes, offsets, hidden as above, in host memory.  Keeps the planes as u32 (4 B per pixel and cut) and cap records
+ * on the device. */
+int ws_merge_tree_cut(ws_ctx *ctx, const uint8_t *img, size_t h, size_t w, size_t row_stride, const uint64_t *seeds_rc, size_t n_seeds,
+                      const ws_options *opt, const ws_tree_cut *cuts, size_t n_cuts, ws_tree_node *tree, uint64_t *out, ws_lake *lakes,
+                      size_t cap, size_t *n_lakes, uint64_t *offsets, uint64_t *hidden);
 /* transform_history of every slice of a cube for a list of water levels (tests/integration.rs:267,356 take a cube apart slice by
  * slice), everything in HBM.  Slices, seeds, seed_offsets (n_slices + 1 entries, on the HOST), edge correction, duplicate seeds
  * and *failed_slice as ws_transform_to_list_batch_device; levels, n_levels (0: nothing runs, nothing is written), merging and the

@@ -388,7 +388,50 @@ class MergingWatershed : public Watershed<T> {        // lib.rs:1297-1562
       }
       return root;
     }
+    // colour -> the first node of its parent chain that `cut` keeps: alive, or area >= min_area and n_leaves >= min_leaves
+    std::vector<std::uint32_t> cut_table(const ws_tree_cut &cut) const {
+      std::vector<std::uint32_t> node(nodes.size());
+      for (std::size_t c = 0; c < nodes.size(); ++c) {
+        std::uint32_t x = std::uint32_t(c);
+        while (nodes[x].death_level != ALIVE && (nodes[x].area < cut.min_area || nodes[x].n_leaves < cut.min_leaves)) x = nodes[x].parent;
+        node[c] = x;
+      }
+      return node;
+    }
   };
+  // one cut of a merge tree (ws_tree_cut): thresholds on a swallowed lake's pixels and seed colours, the last level shown, the
+  // last level whose merges are applied
+  static ws_tree_cut cut(std::uint32_t min_area = 0, std::uint32_t min_leaves = 0, std::uint8_t show_level = 254, std::uint8_t merge_level = 0) {
+    return ws_tree_cut{min_area, min_leaves, show_level, merge_level, {0, 0}};
+  }
+  // not in the reference: the label planes of the merge tree pruned by `cuts` (at most 32), the whole route in one call
+  // (ws_merge_tree_cut): planes[k] shows every pixel the lake cuts[k] leaves it in, 0 where it is hidden; lakes[offsets[k] ..
+  // offsets[k + 1]) are cut k's (colour, pixels) records in increasing colour and hidden[k] its pixels that show 0
+  struct TreeCut {
+    MergeTree tree;
+    std::vector<Array2<usize>> planes;
+    std::vector<ws_lake> lakes;
+    std::vector<std::uint64_t> offsets, hidden;
+  };
+  TreeCut tree_cut(ArrayView2<std::uint8_t> input, const std::vector<Seed> &seeds, const std::vector<ws_tree_cut> &cuts) const {
+    const std::size_t e = this->opt_.edge_correction ? 2 : 0, prow = input.rows + e, pcol = input.cols + e, k = cuts.size();
+    TreeCut t{MergeTree{std::vector<ws_tree_node>(seeds.size() + 1), Array2<usize>(0, 0)}, {}, {}, std::vector<std::uint64_t>(k + 1, 0),
+              std::vector<std::uint64_t>(k, 0)};
+    if (k == 0) throw std::invalid_argument("tree_cut needs at least one cut");
+    auto packed = detail::pack(seeds);
+    std::vector<usize> flat(k * prow * pcol);
+    std::size_t cap = std::max<std::size_t>(std::min(seeds.size(), prow * pcol), 1) * k, total = 0;      // a cut shows no more colours than there are, or pixels
+    t.lakes.resize(cap);
+    this->ctx_->check(ws_merge_tree_cut(this->ctx_->get(), input.ptr, input.rows, input.cols, input.row_stride, packed.data(), seeds.size(),
+                                        &this->opt_, cuts.data(), k, t.tree.nodes.data(), flat.data(), t.lakes.data(), cap, &total,
+                                        t.offsets.data(), t.hidden.data()));
+    t.lakes.resize(total);
+    for (std::size_t j = 0; j < k; ++j) {
+      t.planes.emplace_back(prow, pcol);
+      std::copy(flat.begin() + j * prow * pcol, flat.begin() + (j + 1) * prow * pcol, t.planes.back().data.begin());
+    }
+    return t;
+  }
   MergeTree merge_tree(ArrayView2<std::uint8_t> input, const std::vector<Seed> &seeds, bool want_labels = false) const {
     const std::size_t e = this->opt_.edge_correction ? 2 : 0;
     MergeTree t{std::vector<ws_tree_node>(seeds.size() + 1), Array2<usize>(want_labels ? input.rows + e : 0, want_labels ? input.cols + e : 0)};

@@ -547,9 +547,60 @@ impl MergeTree {
             })
             .collect()
     }
+    /// colour -> the first node of its parent chain that `cut` keeps: alive, or `area >= min_area` and `n_leaves >= min_leaves`.
+    pub fn cut_table(&self, cut: &hip_ffi::ws_tree_cut) -> Vec<u32> {
+        (0..self.nodes.len() as u32)
+            .map(|c| {
+                let mut x = c;
+                loop {
+                    let n = &self.nodes[x as usize];
+                    if n.death_level == Self::ALIVE || (n.area >= cut.min_area && n.n_leaves >= cut.min_leaves) {
+                        break x;
+                    }
+                    x = n.parent;
+                }
+            })
+            .collect()
+    }
+}
+
+/// What `MergingWatershed::tree_cut` returns: `planes[k]` shows every pixel the lake `cuts[k]` leaves it in (0: hidden);
+/// `lakes[offsets[k] .. offsets[k + 1]]` are cut k's (colour, pixels) records in increasing colour, `hidden[k]` its pixels that show 0.
+pub struct TreeCut {
+    pub tree: MergeTree,
+    pub planes: Vec<nd::Array2<usize>>,
+    pub lakes: Vec<hip_ffi::ws_lake>,
+    pub offsets: Vec<u64>,
+    pub hidden: Vec<u64>,
 }
 
 impl<T> MergingWatershed<T> {
+    /// Not in the reference: the label planes and lake lists of the merge tree pruned by `cuts` (1 ..= 32 of them), the whole
+    /// route in one call (`ws_merge_tree_cut`).
+    pub fn tree_cut(&self, input: nd::ArrayView2<u8>, seeds: &[(usize, usize)], cuts: &[hip_ffi::ws_tree_cut]) -> TreeCut {
+        assert!(!cuts.is_empty() && cuts.len() <= 32, "tree_cut takes 1 ..= 32 cuts");
+        let (h, w) = input.dim();
+        let (std_img, stride) = shim::standard(&input);
+        let packed = shim::pack_seeds(seeds);
+        let o = self.opt.ffi();
+        let (ph, pw) = self.opt.plane(h, w);
+        let k = cuts.len();
+        let mut nodes = vec![hip_ffi::ws_tree_node::default(); seeds.len() + 1];
+        let mut flat = vec![0u64; k * ph * pw];
+        let cap = seeds.len().min(ph * pw).max(1) * k;      // a cut shows no more colours than there are, or pixels
+        let mut lakes = vec![hip_ffi::ws_lake { colour: 0, area: 0 }; cap];
+        let (mut offsets, mut hidden, mut total) = (vec![0u64; k + 1], vec![0u64; k], 0usize);
+        shim::with_ctx(|ctx| unsafe {
+            let rc = hip_ffi::ws_merge_tree_cut(ctx, std_img.as_ptr(), h, w, stride, packed.as_ptr(), seeds.len(), &o, cuts.as_ptr(), k,
+                                                nodes.as_mut_ptr(), flat.as_mut_ptr(), lakes.as_mut_ptr(), cap, &mut total,
+                                                offsets.as_mut_ptr(), hidden.as_mut_ptr());
+            shim::check(ctx, rc, "ws_merge_tree_cut");
+        });
+        lakes.truncate(total);
+        let planes = flat.chunks((ph * pw).max(1)).map(|p| nd::Array2::from_shape_vec((ph, pw), p.iter().map(|&v| v as usize).collect()).expect("plane shape")).collect();
+        TreeCut { tree: MergeTree { nodes, labels: None }, planes, lakes, offsets, hidden }
+    }
+
     /// Not in the reference: the merging `transform_to_list(cube[k], &find_local_minima(cube[k]))` of every slice of a cube as one
     /// call; as `SegmentingWatershed::transform_to_list_cube`.
     pub fn transform_to_list_cube(&self, cube: nd::ArrayView3<u8>) -> (Vec<SparseLists>, Vec<usize>) {

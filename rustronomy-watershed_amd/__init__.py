@@ -3,9 +3,9 @@ smups/rustronomy-watershed.  The directory name carries a hyphen
 through `__graft_entry__.load_package()` (registers it as `rustronomy_watershed_amd`)."""
 from . import _ffi
 from .api import (ALWAYS_FILL, ENGINE_AUTO, ENGINE_FUSED, ENGINE_SWEEP, NEVER_FILL, NORMAL_MAX, UNCOLOURED, BuildErr,
-                  Context, HookCtx, MaxToHigh, MaxToLow, MergeTree, MergingWatershed, SeedOutOfBounds, SegmentingWatershed,
+                  Context, Cut, HookCtx, MaxToHigh, MaxToLow, MergeTree, MergingWatershed, SeedOutOfBounds, SegmentingWatershed,
                   TransformBuilder, WatershedError, WatershedUtils, centroids, default_context)
 
 __all__ = ["ALWAYS_FILL", "ENGINE_AUTO", "ENGINE_FUSED", "ENGINE_SWEEP", "NEVER_FILL", "NORMAL_MAX", "UNCOLOURED",
-           "BuildErr", "Context", "HookCtx", "MaxToHigh", "MaxToLow", "MergeTree", "MergingWatershed", "SeedOutOfBounds",
+           "BuildErr", "Context", "Cut", "HookCtx", "MaxToHigh", "MaxToLow", "MergeTree", "MergingWatershed", "SeedOutOfBounds",
            "SegmentingWatershed", "TransformBuilder", "WatershedError", "WatershedUtils", "centroids", "default_context", "_ffi"]

@@ -194,6 +194,48 @@ def centroids(stats):
     return row, col
 
 
+class Cut:
+    """One cut of a merge tree (ws_tree_cut): a swallowed lake stands on its own iff it had reached `min_area` pixels and
+    `min_leaves` seed colours; pixels that arrive after `show_level` are 0; every merge up to `merge_level` is applied.
+    Checked here, before any device work.  Cut(show_level=L, merge_level=L) is the merging history plane of level L."""
+    __slots__ = ("min_area", "min_leaves", "show_level", "merge_level")
+
+    def __init__(self, min_area=0, min_leaves=0, show_level=254, merge_level=0):
+        for name, v, top in (("min_area", min_area, 0xFFFFFFFF), ("min_leaves", min_leaves, 0xFFFFFFFF),
+                             ("show_level", show_level, 254), ("merge_level", merge_level, 254)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"{name} must be an integer")
+            if not 0 <= int(v) <= top:
+                raise ValueError(f"{name} must lie in 0..={top}, not {v}")
+            object.__setattr__(self, name, int(v))
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a Cut is immutable")
+
+    def __repr__(self):
+        return f"Cut(min_area={self.min_area}, min_leaves={self.min_leaves}, show_level={self.show_level}, merge_level={self.merge_level})"
+
+    def __eq__(self, other):
+        return isinstance(other, Cut) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
+
+    def __hash__(self):
+        return hash(tuple(getattr(self, k) for k in self.__slots__))
+
+
+def _as_cuts(cuts):
+    """(ctypes array of ws_tree_cut, n) of a Cut or a sequence of at most 32 of them, checked before any device work."""
+    lst = [cuts] if isinstance(cuts, Cut) else list(cuts)
+    if len(lst) > 32:
+        raise ValueError(f"at most 32 cuts per call, not {len(lst)}")
+    for c in lst:
+        if not isinstance(c, Cut):
+            raise TypeError("cuts must be Cut values")
+    arr = (_ffi.TreeCut * max(len(lst), 1))()
+    for k, c in enumerate(lst):
+        arr[k].min_area, arr[k].min_leaves, arr[k].show_level, arr[k].merge_level = c.min_area, c.min_leaves, c.show_level, c.merge_level
+    return arr, len(lst)
+
+
 class MergeTree:
     """The merging transform's lake hierarchy (ws_merge_tree): numpy arrays indexed by seed colour, 0 .. n_seeds.
     `parent`: canonical id of the lake that swallowed the colour (0: none); `death_level`: the first water level after which the
@@ -218,6 +260,20 @@ class MergeTree:
             root[dead] = self.parent[root[dead]]
             dead = self.death_level[root] <= level
         return root
+
+    def cut_table(self, cut):
+        """colour -> the first node of its parent chain that `cut` keeps: alive, or area >= min_area and n_leaves >= min_leaves.
+        A pixel of colour c that arrived at level t then shows the end of the walk from cut_table(cut)[c] along `parent` while
+        death_level <= max(t, cut.merge_level) (ws_tree_cut_device)."""
+        node = np.arange(self.parent.size, dtype=np.uint32)
+
+        def folded(a):
+            return (self.death_level[a] != self.ALIVE) & ((self.area[a] < cut.min_area) | (self.n_leaves[a] < cut.min_leaves))
+        gone = folded(node)
+        while gone.any():          # areas grow strictly along `parent`, and the chain ends alive: at most one step per level
+            node[gone] = self.parent[node[gone]]
+            gone = folded(node)
+        return node
 
     def children(self):
         """{colour: sorted array of the colours it swallowed}, for the colours that swallowed any."""
@@ -654,6 +710,38 @@ class MergingWatershed(_Transform):
         ctx.check(_ffi.lib().ws_merge_tree(ctx.handle, a.ctypes.data, h, w, stride, s.ctypes.data, ns, ctypes.byref(self._opt),
                                            tree.ctypes.data, labels.ctypes.data if want_labels else None))
         return MergeTree(tree[:, 0].copy(), tree[:, 1].copy(), tree[:, 2].copy(), tree[:, 3].copy(), labels)
+
+    def merge_tree_cut(self, input, seeds, cuts, want_tree=False, want_lakes=False):
+        """Not in the reference: the label planes of the merge tree pruned by `cuts` (a Cut or up to 32 of them), the whole route
+        in one call (ws_merge_tree_cut): a (K, H', W') u64 array whose plane k shows every pixel the lake cuts[k] leaves it in,
+        0 where it is hidden.  want_tree: also the MergeTree.  want_lakes: also (lakes, offsets, hidden) -- lakes[offsets[k] :
+        offsets[k + 1]] are cut k's (colour, pixels) records in increasing colour, hidden[k] its pixels that show 0.
+        Returns planes, or (planes[, tree][, (lakes, offsets, hidden)])."""
+        arr, k = _as_cuts(cuts)
+        if k == 0:
+            raise ValueError("merge_tree_cut needs at least one cut")
+        a, stride = _as_image(input)
+        s, ns = _as_seeds(seeds)
+        h, w = a.shape
+        ph, pw = self._shape(a)
+        planes = np.empty((k, ph, pw), dtype=np.uint64)
+        tree = np.empty((ns + 1, 4), dtype=np.uint32) if want_tree else None
+        offsets = np.zeros(k + 1, dtype=np.uint64)
+        hidden = np.zeros(k, dtype=np.uint64)
+        n = ctypes.c_size_t(0)
+        cap = max(min(ns, ph * pw), 1) * k if want_lakes else 0      # a cut shows no more colours than there are, or pixels
+        lakes = np.empty((max(cap, 1), 2), dtype=np.uint64)
+        ctx = self._ctx()
+        ctx.check(_ffi.lib().ws_merge_tree_cut(ctx.handle, a.ctypes.data, h, w, stride, s.ctypes.data, ns, ctypes.byref(self._opt),
+                                               arr, k, tree.ctypes.data if want_tree else None, planes.ctypes.data,
+                                               lakes.ctypes.data if want_lakes else None, cap, ctypes.byref(n),
+                                               offsets.ctypes.data, hidden.ctypes.data))
+        out = [planes]
+        if want_tree:
+            out.append(MergeTree(tree[:, 0].copy(), tree[:, 1].copy(), tree[:, 2].copy(), tree[:, 3].copy()))
+        if want_lakes:
+            out.append((lakes[: n.value].copy(), offsets, hidden))
+        return out[0] if len(out) == 1 else tuple(out)
 
     def merge_tree_stats(self, input, seeds, weights=None, want_labels=False):
         """Not in the reference: merge_tree and a catalogue of its lakes from the same flood (ws_merge_tree_stats).  Returns

@@ -382,6 +382,43 @@ class DeviceEngine:
                                                                     out.data_ptr(), out_stats.data_ptr() if want_stats else None))
         return (out, out_stats) if want_stats else out
 
+    def tree_cut(self, tree, keys, labels, cuts, out=None, want_lakes=False):
+        """The label planes -- with want_lakes, also the lake lists -- of a merge tree pruned by `cuts` (an api.Cut or up to 32),
+        everything in HBM (ws_tree_cut_device): tree = the (n_seeds + 1, 4) int32 tensor of merge_tree, keys = the arrival stamps
+        (last_arrival()) and labels = the segmenting labels (merge_tree(want_labels=True)) of the same flood, 2-D int32 device
+        tensors of one shape, contiguous (views into larger buffers are fine).  Returns a (K, H', W') int32 tensor whose plane k
+        shows every pixel the lake cuts[k] leaves it in, 0 where it is hidden; with want_lakes (planes, lakes, offsets, hidden):
+        lakes an (n, 2) int64 device tensor, lakes[offsets[k] : offsets[k + 1]] cut k's (colour, pixels) records in increasing
+        colour, hidden[k] its pixels that show 0 (numpy).  `out`: a reusable contiguous (K, H', W') int32 device tensor."""
+        import numpy as np
+        from .api import _as_cuts
+        arr, k = _as_cuts(cuts)
+        if keys.dim() != 2 or tuple(keys.shape) != tuple(labels.shape):
+            raise ValueError("keys and labels must be 2-D tensors of the same shape")
+        if tree.dim() != 2 or tree.shape[0] < 1 or tree.shape[1] != 4:
+            raise ValueError("tree must be an (n_seeds + 1, 4) tensor")
+        assert tree.dtype == torch.int32 and tree.is_cuda and tree.is_contiguous()
+        assert keys.dtype == torch.int32 and labels.dtype == torch.int32 and keys.is_cuda and labels.is_cuda
+        assert keys.numel() == 0 or (keys.is_contiguous() and labels.is_contiguous())
+        h, w = keys.shape
+        ns = tree.shape[0] - 1
+        if out is None:
+            out = torch.empty((k, h, w), dtype=torch.int32, device=self.device)
+        elif out.dtype != torch.int32 or not out.is_contiguous() or tuple(out.shape) != (k, h, w):
+            raise ValueError(f"out must be a contiguous int32 tensor of shape {(k, h, w)}")
+        offsets = np.zeros(k + 1, dtype=np.uint64)
+        hidden = np.zeros(max(k, 1), dtype=np.uint64)
+        n = ctypes.c_size_t(0)
+        lakes = None
+        cap = max(min(ns, h * w), 1) * max(k, 1) if want_lakes else 0      # a cut shows no more colours than there are, or pixels
+        if want_lakes:
+            lakes = torch.empty((cap, 2), dtype=torch.int64, device=self.device)
+        if k and h * w:      # (no cut or no pixel: nothing to run, no plane word to write, empty lists)
+            self.ctx.check(_ffi.lib().ws_tree_cut_device(self.ctx.handle, tree.data_ptr(), ns, keys.data_ptr(), labels.data_ptr(), h, w,
+                                                         arr, k, out.data_ptr(), h * w, lakes.data_ptr() if want_lakes else None, cap,
+                                                         ctypes.byref(n), offsets.ctypes.data, hidden.ctypes.data))
+        return (out, lakes[: n.value], offsets, hidden[:k]) if want_lakes else out
+
     def merge_tree_batch(self, cube, seeds, seed_offsets, max_level=254, edge=False, seed_shift=False, want_labels=False, out=None):
         """merge_tree of every slice of a cube with everything in HBM (ws_merge_tree_batch_device); cube, seeds and seed_offsets as
         transform_to_list_batch.  Returns an (n_seeds_total + S, 4) int32 tensor: slice k's n_k + 1 rows start at
