@@ -540,6 +540,49 @@ int ws_tree_cut_device(ws_ctx *ctx, const ws_tree_node *d_tree, size_t n_seeds, 
 int ws_merge_tree_cut(ws_ctx *ctx, const uint8_t *img, size_t h, size_t w, size_t row_stride, const uint64_t *seeds_rc, size_t n_seeds,
                       const ws_options *opt, const ws_tree_cut *cuts, size_t n_cuts, ws_tree_node *tree, uint64_t *out, ws_lake *lakes,
                       size_t cap, size_t *n_lakes, uint64_t *offsets, uint64_t *hidden);
+/* One cut of a merge tree by catalogue quantities as well (ws_tree_cut_stats_device).  32 bytes. */
+typedef struct ws_lake_cut {
+  uint64_t min_sum_w;   /* a lake that was swallowed counts only if its weights summed to this much (ws_lake_stats.sum_w) ... */
+  uint32_t min_area;    /* ... it had reached this many pixels ... */
+  uint32_t min_leaves;  /* ... held this many seed colours ... */
+  uint32_t min_w_max;   /* ... its largest weight was at least this (ws_lake_stats.w_max) ... */
+  uint32_t min_depth;   /* ... and it died this far above its smallest weight (below); lakes that never died always count */
+  uint8_t show_level;   /* as ws_tree_cut */
+  uint8_t merge_level;  /* as ws_tree_cut */
+  uint8_t reserved[6];  /* must be zero */
+} ws_lake_cut;
+/* ws_tree_cut_device with three more thresholds, on the lake catalogue of the same flood: d_stats is n_seeds + 1 records as
+ * ws_merge_tree_stats*_device (or ws_merge_tree_from_arrival_device) writes them, in HBM, 8-byte aligned.  For node a with tree
+ * record t and catalogue record s let depth(a) = t.death_level - s.w_min if t.death_level != WS_TREE_ALIVE and t.death_level >
+ * s.w_min, else 0 -- with the image as the weight plane, the basin's depth below its spill level.  Node a is KEPT iff it is alive,
+ * or area >= min_area and n_leaves >= min_leaves and s.sum_w >= min_sum_w (a 64-bit compare) and s.w_max >= min_w_max and
+ * depth(a) >= min_depth.  The plane of a cut is DEFINED as table, then walk: T[c] = the first kept node on the chain c, parent[c],
+ * ...; a pixel with c = d_seg_labels[p] != 0 and t = d_keys[p] >> 24 <= show_level starts at T[c] and goes up while death_level
+ * <= max(t, merge_level); it is 0 if c == 0 or t > show_level.  For the catalogue of the tree's own flood every one of the five
+ * quantities is monotone up the chain (a parent's pixels contain the child's, and it dies later), so the plane is also "the first
+ * node that is kept and dies after max(t, merge_level)", as ws_tree_cut_device states it.  A catalogue that belongs to ANOTHER flood
+ * is not detected and is not unsafe: the check of the tree bounds every walk whatever d_stats holds, and the planes are then what
+ * table-then-walk gives on those numbers.
+ * Everything else is ws_tree_cut_device's: the cuts (1 .. 32 on the host, any order, repeats allowed), the planes, the lists,
+ * hidden, capacity, the refusals with the outputs untouched, the check of the tree with its verdict read on the host before
+ * anything walks, the late report of a label above n_seeds, WS_ERR_TOO_LARGE, the empty cases and the refusal of a context that
+ * holds a begun transform.  On top: non-zero reserved bytes, and a cut with a non-zero min_sum_w, min_w_max or min_depth while
+ * d_stats == NULL, are WS_ERR_BAD_ARG before anything runs.  d_stats may be NULL when no cut has such a threshold; d_stats is
+ * then never read, and the call launches exactly what ws_tree_cut_device launches for the same cuts.  One table per distinct
+ * five thresholds.  Workspace on top of ws_tree_cut_device's, only when two or more tables of the call have a catalogue threshold:
+ * 16 B a colour, what the keep test reads of a record (sum_w, w_max, depth) packed by one pass over d_stats; a single such
+ * table reads d_stats itself. */
+int ws_tree_cut_stats_device(ws_ctx *ctx, const ws_tree_node *d_tree, const ws_lake_stats *d_stats, size_t n_seeds, const uint32_t *d_keys,
+                             const uint32_t *d_seg_labels, size_t h, size_t w, const ws_lake_cut *cuts, size_t n_cuts, uint32_t *d_out,
+                             size_t plane_stride, ws_lake *d_lakes, size_t cap, size_t *n_lakes, uint64_t *offsets, uint64_t *hidden);
+/* The whole route from and into HOST memory, as ws_merge_tree_cut with ws_merge_tree_stats in the place of ws_merge_tree: image,
+ * seeds and options as there, the weight plane as ws_merge_tree_stats (NULL: the image itself); tree and stats (both nullable):
+ * the n_seeds + 1 records each; out, lakes, cap, n_lakes, offsets, hidden as ws_merge_tree_cut.  The catalogue always runs, whatever
+ * the thresholds.  Keeps on the device what both of those calls keep. */
+int ws_merge_tree_stats_cut(ws_ctx *ctx, const uint8_t *img, size_t h, size_t w, size_t row_stride, const uint64_t *seeds_rc, size_t n_seeds,
+                            const ws_options *opt, const void *weight, int weight_dtype, size_t weight_row_stride, const ws_lake_cut *cuts,
+                            size_t n_cuts, ws_tree_node *tree, ws_lake_stats *stats, uint64_t *out, ws_lake *lakes, size_t cap,
+                            size_t *n_lakes, uint64_t *offsets, uint64_t *hidden);
 /* transform_history of every slice of a cube for a list of water levels (tests/integration.rs:267,356 take a cube apart slice by
  * slice), everything in HBM.  Slices, seeds, seed_offsets (n_slices + 1 entries, on the HOST), edge correction, duplicate seeds
  * and *failed_slice as ws_transform_to_list_batch_device; levels, n_levels (0: nothing runs, nothing is written), merging and the

@@ -398,6 +398,26 @@ class MergingWatershed : public Watershed<T> {        // lib.rs:1297-1562
       }
       return node;
     }
+    // the same with catalogue thresholds (ws_lake_cut): `stats` is the catalogue of the tree's flood (merge_tree_stats); a node is
+    // also kept only if its sum_w, w_max and depth -- death_level - w_min where that is positive, else 0 -- reach the cut's
+    std::vector<std::uint32_t> cut_table(const ws_lake_cut &cut, const std::vector<ws_lake_stats> &stats) const {
+      if (stats.size() != nodes.size()) throw std::invalid_argument("one catalogue record per tree record");
+      auto kept = [&](std::uint32_t x) {
+        const ws_tree_node &t = nodes[x];
+        const ws_lake_stats &s = stats[x];
+        if (t.death_level == ALIVE) return true;
+        const std::uint32_t depth = t.death_level > s.w_min ? t.death_level - s.w_min : 0;
+        return t.area >= cut.min_area && t.n_leaves >= cut.min_leaves && s.sum_w >= cut.min_sum_w && s.w_max >= cut.min_w_max &&
+               depth >= cut.min_depth;
+      };
+      std::vector<std::uint32_t> node(nodes.size());
+      for (std::size_t c = 0; c < nodes.size(); ++c) {
+        std::uint32_t x = std::uint32_t(c);
+        while (!kept(x)) x = nodes[x].parent;
+        node[c] = x;
+      }
+      return node;
+    }
   };
   // one cut of a merge tree (ws_tree_cut): thresholds on a swallowed lake's pixels and seed colours, the last level shown, the
   // last level whose merges are applied
@@ -431,6 +451,30 @@ class MergingWatershed : public Watershed<T> {        // lib.rs:1297-1562
       std::copy(flat.begin() + j * prow * pcol, flat.begin() + (j + 1) * prow * pcol, t.planes.back().data.begin());
     }
     return t;
+  }
+  // one cut by catalogue quantities as well (ws_lake_cut): the lake's weights summed to min_sum_w, its largest weight reached
+  // min_w_max, and it died min_depth above its smallest weight
+  static ws_lake_cut lake_cut(std::uint64_t min_sum_w = 0, std::uint32_t min_w_max = 0, std::uint32_t min_depth = 0, std::uint32_t min_area = 0,
+                              std::uint32_t min_leaves = 0, std::uint8_t show_level = 254, std::uint8_t merge_level = 0) {
+    return ws_lake_cut{min_sum_w, min_area, min_leaves, min_w_max, min_depth, show_level, merge_level, {0, 0, 0, 0, 0, 0}};
+  }
+  // tree_cut with the lake catalogue of the same flood (ws_merge_tree_stats_cut): the cuts may carry catalogue thresholds, and the
+  // catalogue comes back with the tree.  Weights: a u8 or u16 plane of the image's shape; without one the image itself weighs.
+  struct LakeCut : TreeCut {
+    std::vector<ws_lake_stats> stats;
+  };
+  LakeCut tree_cut(ArrayView2<std::uint8_t> input, const std::vector<Seed> &seeds, const std::vector<ws_lake_cut> &cuts) const {
+    return lake_cut_run(input, seeds, cuts, nullptr, 0, 0);
+  }
+  LakeCut tree_cut(ArrayView2<std::uint8_t> input, const std::vector<Seed> &seeds, const std::vector<ws_lake_cut> &cuts,
+                   ArrayView2<std::uint8_t> weights) const {
+    if (weights.rows != input.rows || weights.cols != input.cols) throw std::invalid_argument("weights must have the image's shape");
+    return lake_cut_run(input, seeds, cuts, weights.ptr, WS_U8, weights.row_stride);
+  }
+  LakeCut tree_cut(ArrayView2<std::uint8_t> input, const std::vector<Seed> &seeds, const std::vector<ws_lake_cut> &cuts,
+                   ArrayView2<std::uint16_t> weights) const {
+    if (weights.rows != input.rows || weights.cols != input.cols) throw std::invalid_argument("weights must have the image's shape");
+    return lake_cut_run(input, seeds, cuts, weights.ptr, WS_U16, weights.row_stride);
   }
   MergeTree merge_tree(ArrayView2<std::uint8_t> input, const std::vector<Seed> &seeds, bool want_labels = false) const {
     const std::size_t e = this->opt_.edge_correction ? 2 : 0;
@@ -585,6 +629,29 @@ class MergingWatershed : public Watershed<T> {        // lib.rs:1297-1562
     }
     if (n_seeds) *n_seeds = counts;
     return out;
+  }
+  LakeCut lake_cut_run(ArrayView2<std::uint8_t> input, const std::vector<Seed> &seeds, const std::vector<ws_lake_cut> &cuts, const void *weights,
+                       int dtype, std::size_t weight_stride) const {
+    const std::size_t e = this->opt_.edge_correction ? 2 : 0, prow = input.rows + e, pcol = input.cols + e, k = cuts.size();
+    if (k == 0) throw std::invalid_argument("tree_cut needs at least one cut");
+    LakeCut t;
+    t.tree = MergeTree{std::vector<ws_tree_node>(seeds.size() + 1), Array2<usize>(0, 0)};
+    t.offsets.assign(k + 1, 0);
+    t.hidden.assign(k, 0);
+    t.stats.resize(seeds.size() + 1);
+    auto packed = detail::pack(seeds);
+    std::vector<usize> flat(k * prow * pcol);
+    std::size_t cap = std::max<std::size_t>(std::min(seeds.size(), prow * pcol), 1) * k, total = 0;      // a cut shows no more colours than there are, or pixels
+    t.lakes.resize(cap);
+    this->ctx_->check(ws_merge_tree_stats_cut(this->ctx_->get(), input.ptr, input.rows, input.cols, input.row_stride, packed.data(), seeds.size(),
+                                              &this->opt_, weights, dtype, weight_stride, cuts.data(), k, t.tree.nodes.data(), t.stats.data(),
+                                              flat.data(), t.lakes.data(), cap, &total, t.offsets.data(), t.hidden.data()));
+    t.lakes.resize(total);
+    for (std::size_t j = 0; j < k; ++j) {
+      t.planes.emplace_back(prow, pcol);
+      std::copy(flat.begin() + j * prow * pcol, flat.begin() + (j + 1) * prow * pcol, t.planes.back().data.begin());
+    }
+    return t;
   }
   LakeCatalogue lake_catalogue(ArrayView2<std::uint8_t> input, const std::vector<Seed> &seeds, const void *weights, int dtype,
                                std::size_t weight_stride, bool want_labels) const {

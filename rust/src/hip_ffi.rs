@@ -59,6 +59,32 @@ impl Default for ws_tree_cut {
     }
 }
 
+/// One cut of a merge tree by catalogue quantities as well (ws_tree_cut_stats_device), 32 bytes.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct ws_lake_cut {
+    pub min_sum_w: u64,
+    pub min_area: u32,
+    pub min_leaves: u32,
+    pub min_w_max: u32,
+    pub min_depth: u32,
+    pub show_level: u8,
+    pub merge_level: u8,
+    pub reserved: [u8; 6],
+}
+
+impl Default for ws_lake_cut {
+    fn default() -> Self {
+        ws_lake_cut { min_sum_w: 0, min_area: 0, min_leaves: 0, min_w_max: 0, min_depth: 0, show_level: 254, merge_level: 0, reserved: [0; 6] }
+    }
+}
+
+impl From<ws_tree_cut> for ws_lake_cut {
+    fn from(c: ws_tree_cut) -> Self {
+        ws_lake_cut { min_area: c.min_area, min_leaves: c.min_leaves, show_level: c.show_level, merge_level: c.merge_level, ..Default::default() }
+    }
+}
+
 /// One lake of that hierarchy measured (ws_merge_tree_stats), 72 bytes; record c belongs to seed colour c.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
@@ -296,6 +322,13 @@ extern "C" {
     pub fn ws_merge_tree_cut(ctx: *mut ws_ctx, img: *const u8, h: usize, w: usize, row_stride: usize, seeds_rc: *const u64,
         n_seeds: usize, opt: *const ws_options, cuts: *const ws_tree_cut, n_cuts: usize, tree: *mut ws_tree_node, out: *mut u64,
         lakes: *mut ws_lake, cap: usize, n_lakes: *mut usize, offsets: *mut u64, hidden: *mut u64) -> c_int;
+    pub fn ws_tree_cut_stats_device(ctx: *mut ws_ctx, d_tree: *const ws_tree_node, d_stats: *const ws_lake_stats, n_seeds: usize,
+        d_keys: *const u32, d_seg_labels: *const u32, h: usize, w: usize, cuts: *const ws_lake_cut, n_cuts: usize, d_out: *mut u32,
+        plane_stride: usize, d_lakes: *mut ws_lake, cap: usize, n_lakes: *mut usize, offsets: *mut u64, hidden: *mut u64) -> c_int;
+    pub fn ws_merge_tree_stats_cut(ctx: *mut ws_ctx, img: *const u8, h: usize, w: usize, row_stride: usize, seeds_rc: *const u64,
+        n_seeds: usize, opt: *const ws_options, weight: *const c_void, weight_dtype: c_int, weight_row_stride: usize,
+        cuts: *const ws_lake_cut, n_cuts: usize, tree: *mut ws_tree_node, stats: *mut ws_lake_stats, out: *mut u64, lakes: *mut ws_lake,
+        cap: usize, n_lakes: *mut usize, offsets: *mut u64, hidden: *mut u64) -> c_int;
     pub fn ws_merge_tree_batch_device(ctx: *mut ws_ctx, d_cube: *const u8, n_slices: usize, h: usize, w: usize, row_stride: usize,
         slice_stride: usize, d_seeds_rc: *const u32, seed_offsets: *const usize, opt: *const ws_options, d_tree: *mut ws_tree_node,
         d_labels: *mut u32, failed_slice: *mut usize) -> c_int;

@@ -562,6 +562,28 @@ impl MergeTree {
             })
             .collect()
     }
+    /// The same with catalogue thresholds (`ws_lake_cut`): `stats` is the catalogue of the tree's flood (`merge_tree_stats`); a
+    /// node is also kept only if its `sum_w`, `w_max` and depth -- `death_level - w_min` where that is positive, else 0 -- reach
+    /// the cut's.
+    pub fn cut_table_stats(&self, cut: &hip_ffi::ws_lake_cut, stats: &[hip_ffi::ws_lake_stats]) -> Vec<u32> {
+        assert_eq!(stats.len(), self.nodes.len(), "one catalogue record per tree record");
+        (0..self.nodes.len() as u32)
+            .map(|c| {
+                let mut x = c;
+                loop {
+                    let (n, s) = (&self.nodes[x as usize], &stats[x as usize]);
+                    let depth = if n.death_level != Self::ALIVE && n.death_level > s.w_min { n.death_level - s.w_min } else { 0 };
+                    if n.death_level == Self::ALIVE
+                        || (n.area >= cut.min_area && n.n_leaves >= cut.min_leaves && s.sum_w >= cut.min_sum_w && s.w_max >= cut.min_w_max
+                            && depth >= cut.min_depth)
+                    {
+                        break x;
+                    }
+                    x = n.parent;
+                }
+            })
+            .collect()
+    }
 }
 
 /// What `MergingWatershed::tree_cut` returns: `planes[k]` shows every pixel the lake `cuts[k]` leaves it in (0: hidden);
@@ -574,7 +596,50 @@ pub struct TreeCut {
     pub hidden: Vec<u64>,
 }
 
+/// What `MergingWatershed::tree_cut_stats` returns: a `TreeCut` and the lake catalogue of the same flood.
+pub struct LakeCut {
+    pub cut: TreeCut,
+    pub stats: Vec<hip_ffi::ws_lake_stats>,
+}
+
 impl<T> MergingWatershed<T> {
+    /// Not in the reference: `tree_cut` with the lake catalogue of the same flood (`ws_merge_tree_stats_cut`): the cuts may also
+    /// ask for a summed weight, a peak and a depth (`ws_lake_cut`).  `weights`: a u16 plane of the image's shape (`None`: the image
+    /// itself weighs).
+    pub fn tree_cut_stats(&self, input: nd::ArrayView2<u8>, seeds: &[(usize, usize)], weights: Option<nd::ArrayView2<u16>>,
+                          cuts: &[hip_ffi::ws_lake_cut]) -> LakeCut {
+        assert!(!cuts.is_empty() && cuts.len() <= 32, "tree_cut_stats takes 1 ..= 32 cuts");
+        let (h, w) = input.dim();
+        let (std_img, stride) = shim::standard(&input);
+        let packed = shim::pack_seeds(seeds);
+        let o = self.opt.ffi();
+        let (ph, pw) = self.opt.plane(h, w);
+        let k = cuts.len();
+        let plane = weights.map(|a| {
+            assert_eq!(a.dim(), (h, w), "weights must have the image's shape");
+            a.as_standard_layout().into_owned()
+        });
+        let (wt_ptr, wt_dtype) = match plane.as_ref() {
+            Some(a) => (a.as_ptr() as *const std::ffi::c_void, hip_ffi::WS_U16),
+            None => (std::ptr::null(), 0),
+        };
+        let mut nodes = vec![hip_ffi::ws_tree_node::default(); seeds.len() + 1];
+        let mut stats = vec![hip_ffi::ws_lake_stats::default(); seeds.len() + 1];
+        let mut flat = vec![0u64; k * ph * pw];
+        let cap = seeds.len().min(ph * pw).max(1) * k;      // a cut shows no more colours than there are, or pixels
+        let mut lakes = vec![hip_ffi::ws_lake { colour: 0, area: 0 }; cap];
+        let (mut offsets, mut hidden, mut total) = (vec![0u64; k + 1], vec![0u64; k], 0usize);
+        shim::with_ctx(|ctx| unsafe {
+            let rc = hip_ffi::ws_merge_tree_stats_cut(ctx, std_img.as_ptr(), h, w, stride, packed.as_ptr(), seeds.len(), &o, wt_ptr, wt_dtype, w,
+                                                      cuts.as_ptr(), k, nodes.as_mut_ptr(), stats.as_mut_ptr(), flat.as_mut_ptr(),
+                                                      lakes.as_mut_ptr(), cap, &mut total, offsets.as_mut_ptr(), hidden.as_mut_ptr());
+            shim::check(ctx, rc, "ws_merge_tree_stats_cut");
+        });
+        lakes.truncate(total);
+        let planes = flat.chunks((ph * pw).max(1)).map(|p| nd::Array2::from_shape_vec((ph, pw), p.iter().map(|&v| v as usize).collect()).expect("plane shape")).collect();
+        LakeCut { cut: TreeCut { tree: MergeTree { nodes, labels: None }, planes, lakes, offsets, hidden }, stats }
+    }
+
     /// Not in the reference: the label planes and lake lists of the merge tree pruned by `cuts` (1 ..= 32 of them), the whole
     /// route in one call (`ws_merge_tree_cut`).
     pub fn tree_cut(&self, input: nd::ArrayView2<u8>, seeds: &[(usize, usize)], cuts: &[hip_ffi::ws_tree_cut]) -> TreeCut {

@@ -81,6 +81,13 @@ class TreeCut(ctypes.Structure):
                 ("merge_level", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 2)]
 
 
+class LakeCut(ctypes.Structure):
+    """ws_lake_cut: one cut of a merge tree by catalogue quantities as well (ws_tree_cut_stats_device), 32 bytes."""
+    _fields_ = [("min_sum_w", ctypes.c_uint64), ("min_area", ctypes.c_uint32), ("min_leaves", ctypes.c_uint32),
+                ("min_w_max", ctypes.c_uint32), ("min_depth", ctypes.c_uint32), ("show_level", ctypes.c_uint8),
+                ("merge_level", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 6)]
+
+
 class LakeStats(ctypes.Structure):
     """ws_lake_stats: one lake of the hierarchy measured (ws_merge_tree_stats), 72 bytes."""
     _fields_ = [("sum_w", ctypes.c_uint64), ("sum_wr", ctypes.c_uint64), ("sum_wc", ctypes.c_uint64), ("sum_r", ctypes.c_uint64),
@@ -171,6 +178,9 @@ SIGNATURES = {
     "ws_merge_tree_from_arrival_device": (ctypes.c_int, [vp, vp, vp, sz, sz, sz, ctypes.POINTER(Options), vp, ctypes.c_int, sz, vp, vp]),
     "ws_tree_cut_device": (ctypes.c_int, [vp, vp, sz, vp, vp, sz, sz, vp, sz, vp, sz, vp, sz, szp, vp, vp]),
     "ws_merge_tree_cut": (ctypes.c_int, [vp, vp, sz, sz, sz, vp, sz, ctypes.POINTER(Options), vp, sz, vp, vp, vp, sz, szp, vp, vp]),
+    "ws_tree_cut_stats_device": (ctypes.c_int, [vp, vp, vp, sz, vp, vp, sz, sz, vp, sz, vp, sz, vp, sz, szp, vp, vp]),
+    "ws_merge_tree_stats_cut": (ctypes.c_int, [vp, vp, sz, sz, sz, vp, sz, ctypes.POINTER(Options), vp, ctypes.c_int, sz, vp, sz, vp, vp, vp, vp, sz,
+                                               szp, vp, vp]),
     "ws_merge_tree_batch_device": (ctypes.c_int, [vp, vp, sz, sz, sz, sz, sz, vp, szp, ctypes.POINTER(Options), vp, vp, szp]),
     "ws_merge_tree_batch": (ctypes.c_int, [vp, vp, sz, sz, sz, sz, sz, vp, szp, ctypes.POINTER(Options), vp, sz, szp, vp, szp, szp]),
     "ws_merge_tree_stats_batch_device": (ctypes.c_int, [vp, vp, sz, sz, sz, sz, sz, vp, szp, ctypes.POINTER(Options), vp, ctypes.c_int, sz, sz,

@@ -197,12 +197,16 @@ def centroids(stats):
 class Cut:
     """One cut of a merge tree (ws_tree_cut): a swallowed lake stands on its own iff it had reached `min_area` pixels and
     `min_leaves` seed colours; pixels that arrive after `show_level` are 0; every merge up to `merge_level` is applied.
-    Checked here, before any device work.  Cut(show_level=L, merge_level=L) is the merging history plane of level L."""
-    __slots__ = ("min_area", "min_leaves", "show_level", "merge_level")
+    Checked here, before any device work.  Cut(show_level=L, merge_level=L) is the merging history plane of level L.
+    With a lake catalogue (ws_lake_cut) three more thresholds: the lake's weights summed to `min_sum_w` (64 bits), its largest
+    weight reached `min_w_max`, and it died `min_depth` above its smallest weight."""
+    __slots__ = ("min_area", "min_leaves", "show_level", "merge_level", "min_sum_w", "min_w_max", "min_depth")
 
-    def __init__(self, min_area=0, min_leaves=0, show_level=254, merge_level=0):
+    def __init__(self, min_area=0, min_leaves=0, show_level=254, merge_level=0, min_sum_w=0, min_w_max=0, min_depth=0):
         for name, v, top in (("min_area", min_area, 0xFFFFFFFF), ("min_leaves", min_leaves, 0xFFFFFFFF),
-                             ("show_level", show_level, 254), ("merge_level", merge_level, 254)):
+                             ("show_level", show_level, 254), ("merge_level", merge_level, 254),
+                             ("min_sum_w", min_sum_w, 0xFFFFFFFFFFFFFFFF), ("min_w_max", min_w_max, 0xFFFFFFFF),
+                             ("min_depth", min_depth, 0xFFFFFFFF)):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
                 raise TypeError(f"{name} must be an integer")
             if not 0 <= int(v) <= top:
@@ -212,8 +216,14 @@ class Cut:
     def __setattr__(self, name, value):
         raise AttributeError("a Cut is immutable")
 
+    @property
+    def catalogue(self):
+        """Whether the cut has a threshold on a catalogue quantity (and so needs the lake statistics)."""
+        return bool(self.min_sum_w or self.min_w_max or self.min_depth)
+
     def __repr__(self):
-        return f"Cut(min_area={self.min_area}, min_leaves={self.min_leaves}, show_level={self.show_level}, merge_level={self.merge_level})"
+        more = f", min_sum_w={self.min_sum_w}, min_w_max={self.min_w_max}, min_depth={self.min_depth}" if self.catalogue else ""
+        return f"Cut(min_area={self.min_area}, min_leaves={self.min_leaves}, show_level={self.show_level}, merge_level={self.merge_level}{more})"
 
     def __eq__(self, other):
         return isinstance(other, Cut) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
@@ -222,17 +232,35 @@ class Cut:
         return hash(tuple(getattr(self, k) for k in self.__slots__))
 
 
-def _as_cuts(cuts):
-    """(ctypes array of ws_tree_cut, n) of a Cut or a sequence of at most 32 of them, checked before any device work."""
+def _cut_list(cuts):
+    """The Cut values of a Cut or a sequence of at most 32 of them, checked before any device work."""
     lst = [cuts] if isinstance(cuts, Cut) else list(cuts)
     if len(lst) > 32:
         raise ValueError(f"at most 32 cuts per call, not {len(lst)}")
     for c in lst:
         if not isinstance(c, Cut):
             raise TypeError("cuts must be Cut values")
+    return lst
+
+
+def _as_cuts(cuts):
+    """(ctypes array of ws_tree_cut, n) of a Cut or a sequence of at most 32 of them, none with a catalogue threshold."""
+    lst = _cut_list(cuts)
+    if any(c.catalogue for c in lst):
+        raise ValueError("a cut has a catalogue threshold: this call takes none")
     arr = (_ffi.TreeCut * max(len(lst), 1))()
     for k, c in enumerate(lst):
         arr[k].min_area, arr[k].min_leaves, arr[k].show_level, arr[k].merge_level = c.min_area, c.min_leaves, c.show_level, c.merge_level
+    return arr, len(lst)
+
+
+def _as_lake_cuts(cuts):
+    """(ctypes array of ws_lake_cut, n) of a Cut or a sequence of at most 32 of them."""
+    lst = _cut_list(cuts)
+    arr = (_ffi.LakeCut * max(len(lst), 1))()
+    for k, c in enumerate(lst):
+        arr[k].min_area, arr[k].min_leaves, arr[k].show_level, arr[k].merge_level = c.min_area, c.min_leaves, c.show_level, c.merge_level
+        arr[k].min_sum_w, arr[k].min_w_max, arr[k].min_depth = c.min_sum_w, c.min_w_max, c.min_depth
     return arr, len(lst)
 
 
@@ -261,18 +289,25 @@ class MergeTree:
             dead = self.death_level[root] <= level
         return root
 
-    def cut_table(self, cut):
-        """colour -> the first node of its parent chain that `cut` keeps: alive, or area >= min_area and n_leaves >= min_leaves.
+    def cut_table(self, cut, stats=None):
+        """colour -> the first node of its parent chain that `cut` keeps: alive, or area >= min_area and n_leaves >= min_leaves
+        -- and, for a cut with catalogue thresholds, stats (the records of merge_tree_stats) with sum_w >= min_sum_w, w_max >=
+        min_w_max and depth >= min_depth, depth = death_level - w_min where that is positive, else 0.
         A pixel of colour c that arrived at level t then shows the end of the walk from cut_table(cut)[c] along `parent` while
-        death_level <= max(t, cut.merge_level) (ws_tree_cut_device)."""
+        death_level <= max(t, cut.merge_level) (ws_tree_cut_device, ws_tree_cut_stats_device)."""
+        if cut.catalogue and stats is None:
+            raise ValueError("a cut with a catalogue threshold needs the lake statistics")
         node = np.arange(self.parent.size, dtype=np.uint32)
-
-        def folded(a):
-            return (self.death_level[a] != self.ALIVE) & ((self.area[a] < cut.min_area) | (self.n_leaves[a] < cut.min_leaves))
-        gone = folded(node)
-        while gone.any():          # areas grow strictly along `parent`, and the chain ends alive: at most one step per level
+        keep = (self.death_level == self.ALIVE) | ((self.area >= cut.min_area) & (self.n_leaves >= cut.min_leaves))
+        if cut.catalogue:
+            death, w_min = self.death_level.astype(np.int64), stats["w_min"].astype(np.int64)
+            depth = np.where((self.death_level != self.ALIVE) & (death > w_min), death - w_min, 0)
+            keep &= (self.death_level == self.ALIVE) | ((stats["sum_w"] >= np.uint64(cut.min_sum_w)) & (stats["w_max"] >= cut.min_w_max) &
+                                                         (depth >= cut.min_depth))
+        gone = ~keep[node]
+        while gone.any():          # the chain ends alive: at most one step per level
             node[gone] = self.parent[node[gone]]
-            gone = folded(node)
+            gone = ~keep[node]
         return node
 
     def children(self):
@@ -711,15 +746,19 @@ class MergingWatershed(_Transform):
                                            tree.ctypes.data, labels.ctypes.data if want_labels else None))
         return MergeTree(tree[:, 0].copy(), tree[:, 1].copy(), tree[:, 2].copy(), tree[:, 3].copy(), labels)
 
-    def merge_tree_cut(self, input, seeds, cuts, want_tree=False, want_lakes=False):
+    def merge_tree_cut(self, input, seeds, cuts, want_tree=False, want_lakes=False, weights=None, want_stats=False):
         """Not in the reference: the label planes of the merge tree pruned by `cuts` (a Cut or up to 32 of them), the whole route
         in one call (ws_merge_tree_cut): a (K, H', W') u64 array whose plane k shows every pixel the lake cuts[k] leaves it in,
         0 where it is hidden.  want_tree: also the MergeTree.  want_lakes: also (lakes, offsets, hidden) -- lakes[offsets[k] :
         offsets[k + 1]] are cut k's (colour, pixels) records in increasing colour, hidden[k] its pixels that show 0.
-        Returns planes, or (planes[, tree][, (lakes, offsets, hidden)])."""
-        arr, k = _as_cuts(cuts)
+        A cut with a catalogue threshold (min_sum_w, min_w_max, min_depth), `weights` (a u8 or u16 plane of the image's shape;
+        None: the image itself) or want_stats (also the catalogue, as merge_tree_stats returns it) take the route with the lake
+        statistics (ws_merge_tree_stats_cut).  Returns planes, or (planes[, tree][, stats][, (lakes, offsets, hidden)])."""
+        lst = _cut_list(cuts)
+        k = len(lst)
         if k == 0:
             raise ValueError("merge_tree_cut needs at least one cut")
+        with_stats = want_stats or weights is not None or any(c.catalogue for c in lst)
         a, stride = _as_image(input)
         s, ns = _as_seeds(seeds)
         h, w = a.shape
@@ -732,13 +771,27 @@ class MergingWatershed(_Transform):
         cap = max(min(ns, ph * pw), 1) * k if want_lakes else 0      # a cut shows no more colours than there are, or pixels
         lakes = np.empty((max(cap, 1), 2), dtype=np.uint64)
         ctx = self._ctx()
-        ctx.check(_ffi.lib().ws_merge_tree_cut(ctx.handle, a.ctypes.data, h, w, stride, s.ctypes.data, ns, ctypes.byref(self._opt),
-                                               arr, k, tree.ctypes.data if want_tree else None, planes.ctypes.data,
-                                               lakes.ctypes.data if want_lakes else None, cap, ctypes.byref(n),
-                                               offsets.ctypes.data, hidden.ctypes.data))
+        stats = None
+        if with_stats:
+            arr, _ = _as_lake_cuts(lst)
+            wt, dtype, wstride = _as_weights(weights, a.shape)
+            stats = np.empty(ns + 1, dtype=LAKE_STATS_DTYPE) if want_stats else None
+            ctx.check(_ffi.lib().ws_merge_tree_stats_cut(ctx.handle, a.ctypes.data, h, w, stride, s.ctypes.data, ns, ctypes.byref(self._opt),
+                                                         wt.ctypes.data if wt is not None else None, dtype, wstride, arr, k,
+                                                         tree.ctypes.data if want_tree else None, stats.ctypes.data if want_stats else None,
+                                                         planes.ctypes.data, lakes.ctypes.data if want_lakes else None, cap, ctypes.byref(n),
+                                                         offsets.ctypes.data, hidden.ctypes.data))
+        else:
+            arr, _ = _as_cuts(lst)
+            ctx.check(_ffi.lib().ws_merge_tree_cut(ctx.handle, a.ctypes.data, h, w, stride, s.ctypes.data, ns, ctypes.byref(self._opt),
+                                                   arr, k, tree.ctypes.data if want_tree else None, planes.ctypes.data,
+                                                   lakes.ctypes.data if want_lakes else None, cap, ctypes.byref(n),
+                                                   offsets.ctypes.data, hidden.ctypes.data))
         out = [planes]
         if want_tree:
             out.append(MergeTree(tree[:, 0].copy(), tree[:, 1].copy(), tree[:, 2].copy(), tree[:, 3].copy()))
+        if want_stats:
+            out.append(stats)
         if want_lakes:
             out.append((lakes[: n.value].copy(), offsets, hidden))
         return out[0] if len(out) == 1 else tuple(out)

@@ -65,8 +65,9 @@ struct ws_ctx {
   // ws_merge_tree_from_arrival_device: the seed pairs recovered from the planes (8 B a colour: seed_pixels_from_planes)
   wsapi::DevBuf tree_seed_px;
   // ws_tree_cut_device: the tables T (4 B a colour and distinct pair of thresholds), with lists the counters (4 B a colour and cut)
-  // and the compaction's block sums, the flag words; ws_merge_tree_cut: its u32 planes and its records before they cross the bus
-  wsapi::DevBuf cut_tables, cut_counts, cut_blocks, cut_flags, cut_planes, cut_lakes;
+  // and the compaction's block sums, the flag words; ws_merge_tree_cut: its u32 planes and its records before they cross the bus;
+  // ws_tree_cut_stats_device: the packed catalogue keys (16 B a colour), only for calls with two or more catalogue tables
+  wsapi::DevBuf cut_tables, cut_counts, cut_blocks, cut_flags, cut_planes, cut_lakes, cut_keys;
   uint32_t *pinned = nullptr;      // FLAG_WORDS words of pinned host memory: the host's mirror of the flag block
   uint32_t *pinned_dev = nullptr;  // the same words as the device sees them (nullptr: not mapped, copies only)
   hipEvent_t ring_ev[wsk::COUNTER_RING]{};   // flag slot copied to the host

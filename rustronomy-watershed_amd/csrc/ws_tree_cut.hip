@@ -9,8 +9,17 @@
 //
 // Nothing walks before k_cut_check has passed the records: parent < c bounds every walk and every index, and the host reads
 // the verdict before the next launch.  A label above n_seeds is compared before it indexes anything.
+//
+// ws_tree_cut_stats_device / ws_merge_tree_stats_cut (section 4.4.1) add three thresholds on the lake catalogue of the same flood
+// (ws_lake_cut): sum_w, w_max and depth = death_level - w_min.  The plane is DEFINED as table, then walk, so it is total whatever
+// the catalogue holds; for the catalogue of the tree's own flood all five kept-quantities are monotone up the chain and the
+// argument above stands.  Only the tables change: k_cut_keys packs what the keep test reads of a 72-byte record into 16 bytes a
+// colour, and the table kernel gathers that next to the tree record; a call with a single such table reads the records themselves
+// (cut_source).  Both entry points share one driver (cut_run).
 #include "ws_ctx.hpp"
 #include "ws_uf.hpp"
+
+#include <type_traits>
 
 namespace wsk {
 
@@ -31,8 +40,17 @@ struct CutEntry {
 struct CutPlan {
   uint32_t n, n_tables;
   CutEntry e[CUT_MAX];
-  uint32_t min_area[CUT_MAX], min_leaves[CUT_MAX];      // per table
+  uint32_t min_area[CUT_MAX], min_leaves[CUT_MAX], min_w_max[CUT_MAX], min_depth[CUT_MAX];      // per table
+  u64c min_sum_w[CUT_MAX];
 };
+// What the keep test reads of colour c's catalogue record, as one 16-byte load: sum_w, w_max and the depth, which needs the tree
+// record (death_level - w_min where the lake died above its smallest weight, else 0) and is therefore folded in once, here.
+struct alignas(16) CutKey {
+  u64c sum_w;
+  uint32_t w_max, depth;
+};
+// how the table kernel tests the catalogue thresholds: not at all, from the packed keys, or from the records themselves
+enum CutSource { CUT_TREE_ONLY = 0, CUT_KEYS = 1, CUT_RECORDS = 2 };
 
 // ---- the records, checked ---------------------------------------------------------------------------------------------------------
 // One lane, one record (16 bytes, as one load where the array is 16-byte aligned).  A merge-tree record is either alive with no
@@ -55,16 +73,51 @@ __global__ __launch_bounds__(256) void k_cut_check(const TreeRec *__restrict__ t
 }
 
 // ---- the tables ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t cut_depth(uint32_t death_level, uint32_t w_min) {
+  return death_level != TREE_ALIVE && death_level > w_min ? death_level - w_min : 0u;
+}
+
+// One streaming pass over the catalogue: a lane reads the 16 bytes of its 72-byte record that the keep test needs (two 8-byte
+// loads: the records are 8-byte aligned and no more) and the death level of its tree record, and stores one key.
+__global__ __launch_bounds__(256) void k_cut_keys(const TreeRec *__restrict__ tree, const LakeRec *__restrict__ stats, size_t n_colours, CutKey *keys) {
+  const size_t c = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (c >= n_colours) return;
+  const u64c sum_w = stats[c].sum_w;
+  const uint32_t w_min = stats[c].w_min, w_max = stats[c].w_max;
+  reinterpret_cast<u32x4_m *>(keys)[c] = u32x4_m{(uint32_t)sum_w, (uint32_t)(sum_w >> 32), w_max, cut_depth(tree[c].death_level, w_min)};
+}
+
 // T_j[c] for every table j of the plan (blockIdx.y): up `parent` while the node is not kept.  The chain ends at an alive node,
-// which is kept; at most 255 steps on a checked tree, and the cap holds whatever the records say.
-__global__ __launch_bounds__(256) void k_cut_table(const TreeRec *__restrict__ tree, size_t n_colours, CutPlan plan, uint32_t *tables, uint32_t *flags) {
+// which is kept; at most 255 steps on a checked tree, and the cap holds whatever the records say.  SRC == CUT_KEYS: a table with a
+// catalogue threshold (workgroup uniform) gathers the node's 16-byte key next to its 16-byte tree record, both loads in flight
+// together; a table without one reads the tree alone, as CUT_TREE_ONLY does for every table.  CUT_RECORDS reads sum_w, w_min and
+// w_max from the 72-byte record itself, two cache lines a step: the form of a call with ONE such table (cut_source).
+template <int SRC>
+__global__ __launch_bounds__(256) void k_cut_table(const TreeRec *__restrict__ tree, const CutKey *__restrict__ ckeys, const LakeRec *__restrict__ stats,
+                                                   size_t n_colours, CutPlan plan, uint32_t *tables, uint32_t *flags) {
   const size_t c = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (c >= n_colours) return;
   const uint32_t j = blockIdx.y, min_area = plan.min_area[j], min_leaves = plan.min_leaves[j];
+  const uint32_t min_w_max = SRC != CUT_TREE_ONLY ? plan.min_w_max[j] : 0u, min_depth = SRC != CUT_TREE_ONLY ? plan.min_depth[j] : 0u;
+  const u64c min_sum_w = SRC != CUT_TREE_ONLY ? plan.min_sum_w[j] : 0ull;
+  const bool catalogue = SRC != CUT_TREE_ONLY && (min_sum_w != 0ull || min_w_max != 0u || min_depth != 0u);
   uint32_t a = (uint32_t)c, steps = 0;
   for (;;) {
     const TreeRec r = tree[a];
-    if (r.death_level == TREE_ALIVE || (r.area >= min_area && r.n_leaves >= min_leaves)) break;
+    bool keep = r.area >= min_area && r.n_leaves >= min_leaves;
+    if constexpr (SRC == CUT_KEYS) {
+      if (catalogue) {
+        const u32x4_m k = reinterpret_cast<const u32x4_m *>(ckeys)[a];
+        keep = keep && ((u64c)k.y << 32 | k.x) >= min_sum_w && k.z >= min_w_max && k.w >= min_depth;
+      }
+    } else if constexpr (SRC == CUT_RECORDS) {
+      if (catalogue) {
+        const u64c sum_w = stats[a].sum_w;
+        const uint32_t w_min = stats[a].w_min, w_max = stats[a].w_max;
+        keep = keep && sum_w >= min_sum_w && w_max >= min_w_max && cut_depth(r.death_level, w_min) >= min_depth;
+      }
+    }
+    if (r.death_level == TREE_ALIVE || keep) break;
     if (++steps > CUT_STEPS || r.parent >= a) { atomicOr(&flags[CUT_F_STEPS], 1u); a = 0u; break; }
     a = r.parent;
   }
@@ -286,31 +339,58 @@ namespace {
 using namespace wsapi;
 
 static_assert(sizeof(ws_tree_cut) == 12, "ws_tree_cut is part of the ABI");
+static_assert(sizeof(ws_lake_cut) == 32, "ws_lake_cut is part of the ABI");
 
-// what both forms check of the cuts before anything runs
-int check_cuts(ws_ctx *c, const ws_tree_cut *cuts, size_t n_cuts) {
-  if (n_cuts > (size_t)CUT_MAX) return fail(c, WS_ERR_BAD_ARG, "more than 32 cuts");
-  if (n_cuts && !cuts) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+// The cuts of a call as the driver takes them -- a ws_tree_cut is the ws_lake_cut without catalogue thresholds -- with what the
+// entry points check of them before anything runs: `refused` is the reason, reported where the checks of a call have always stood.
+struct Cuts {
+  ws_lake_cut v[CUT_MAX];
+  size_t n = 0;
+  const char *refused = nullptr;
+  bool catalogue = false;      // some cut has a threshold on sum_w, w_max or depth
+};
+
+template <class C>
+Cuts take_cuts(const C *cuts, size_t n_cuts) {
+  Cuts cs;
+  cs.n = n_cuts;
+  if (n_cuts > (size_t)CUT_MAX) { cs.refused = "more than 32 cuts"; return cs; }
+  if (n_cuts && !cuts) { cs.refused = "null pointer"; return cs; }
   for (size_t k = 0; k < n_cuts; ++k) {
-    if (cuts[k].show_level > 254 || cuts[k].merge_level > 254) return fail(c, WS_ERR_BAD_ARG, "a cut's level is above 254");
-    if (cuts[k].reserved[0] || cuts[k].reserved[1]) return fail(c, WS_ERR_BAD_ARG, "ws_tree_cut.reserved must be zero");
+    const C &in = cuts[k];
+    ws_lake_cut &o = cs.v[k];
+    o = ws_lake_cut{};
+    o.min_area = in.min_area; o.min_leaves = in.min_leaves; o.show_level = in.show_level; o.merge_level = in.merge_level;
+    if constexpr (std::is_same_v<C, ws_lake_cut>) { o.min_sum_w = in.min_sum_w; o.min_w_max = in.min_w_max; o.min_depth = in.min_depth; }
+    if (in.show_level > 254 || in.merge_level > 254) { cs.refused = "a cut's level is above 254"; return cs; }
+    for (uint8_t r : in.reserved)
+      if (r) { cs.refused = "a cut's reserved bytes must be zero"; return cs; }
+    cs.catalogue = cs.catalogue || o.min_sum_w || o.min_w_max || o.min_depth;
   }
-  return WS_OK;
+  return cs;
 }
 
-// one table per distinct (min_area, min_leaves); the entries by table, then merge level (stable: repeats keep their order)
-CutPlan make_plan(const ws_tree_cut *cuts, size_t n_cuts) {
+int check_cuts(ws_ctx *c, const Cuts &cs) { return cs.refused ? fail(c, WS_ERR_BAD_ARG, cs.refused) : WS_OK; }
+
+// one table per distinct five thresholds; the entries by table, then merge level (stable: repeats keep their order)
+CutPlan make_plan(const Cuts &cs) {
   CutPlan p{};
-  p.n = (uint32_t)n_cuts;
-  for (size_t k = 0; k < n_cuts; ++k) {
+  p.n = (uint32_t)cs.n;
+  for (size_t k = 0; k < cs.n; ++k) {
+    const ws_lake_cut &cut = cs.v[k];
     uint32_t j = 0;
-    while (j < p.n_tables && !(p.min_area[j] == cuts[k].min_area && p.min_leaves[j] == cuts[k].min_leaves)) ++j;
+    while (j < p.n_tables && !(p.min_area[j] == cut.min_area && p.min_leaves[j] == cut.min_leaves && p.min_sum_w[j] == cut.min_sum_w &&
+                               p.min_w_max[j] == cut.min_w_max && p.min_depth[j] == cut.min_depth))
+      ++j;
     if (j == p.n_tables) {
-      p.min_area[j] = cuts[k].min_area;
-      p.min_leaves[j] = cuts[k].min_leaves;
+      p.min_area[j] = cut.min_area;
+      p.min_leaves[j] = cut.min_leaves;
+      p.min_sum_w[j] = cut.min_sum_w;
+      p.min_w_max[j] = cut.min_w_max;
+      p.min_depth[j] = cut.min_depth;
       ++p.n_tables;
     }
-    p.e[k] = CutEntry{j, cuts[k].merge_level, cuts[k].show_level, (uint8_t)k, 0};
+    p.e[k] = CutEntry{j, cut.merge_level, cut.show_level, (uint8_t)k, 0};
   }
   std::stable_sort(p.e, p.e + p.n, [](const CutEntry &a, const CutEntry &b) {
     return a.table != b.table ? a.table < b.table : a.merge_level < b.merge_level;
@@ -320,13 +400,26 @@ CutPlan make_plan(const ws_tree_cut *cuts, size_t n_cuts) {
 
 size_t cut_blocks(size_t n_colours) { return (n_colours + CUT_CHUNK - 1) / CUT_CHUNK; }
 
+// Where the table kernel reads the catalogue.  The key pass costs about one table's walk over the records themselves (4096^2, 1.83 M
+// colours: 30 us for the pass, then 27 us a table against 50 - 58 us a table from the 72-byte records: DESIGN.md section 4.4.1), so
+// ONE table with a catalogue threshold reads the records and needs no keys; from two tables on the keys pay.
+CutSource cut_source(const CutPlan &p) {
+  uint32_t n = 0;
+  for (uint32_t j = 0; j < p.n_tables; ++j) n += p.min_sum_w[j] != 0 || p.min_w_max[j] != 0 || p.min_depth[j] != 0;
+  if (n == 0) return CUT_TREE_ONLY;
+  static const char *forced = tuning_env("WS_CUT_TABLE_FROM_RECORDS");      // A/B knob for tools/: 1 always the records, 0 always the keys
+  if (forced) return forced[0] == '1' ? CUT_RECORDS : CUT_KEYS;
+  return n == 1 ? CUT_RECORDS : CUT_KEYS;
+}
+
 // the context's workspace of a call: the tables (4 B a colour and cut at most), with lists the counters (the same) and 12 B per
-// CUT_CHUNK colours and cut for the compaction, and the flag words
-int cut_reserve(ws_ctx *c, size_t n_seeds, size_t n_cuts, bool lists) {
+// CUT_CHUNK colours and cut for the compaction, the flag words, and for CUT_KEYS the packed keys (16 B a colour)
+int cut_reserve(ws_ctx *c, size_t n_seeds, size_t n_cuts, bool lists, CutSource src) {
   const size_t n_colours = n_seeds + 1;
   int rc;
   if ((rc = ensure(c, c->cut_tables, n_cuts * n_colours * sizeof(uint32_t)))) return rc;
   if ((rc = ensure(c, c->cut_flags, CUT_F_WORDS * sizeof(uint32_t)))) return rc;
+  if (src == CUT_KEYS && (rc = ensure(c, c->cut_keys, n_colours * sizeof(CutKey)))) return rc;
   if (lists) {
     if ((rc = ensure(c, c->cut_counts, n_cuts * n_colours * sizeof(uint32_t)))) return rc;
     if ((rc = ensure(c, c->cut_blocks, n_cuts * cut_blocks(n_colours) * (sizeof(uint32_t) + sizeof(u64c)) + n_cuts * sizeof(uint32_t)))) return rc;
@@ -340,20 +433,17 @@ int read_flags(ws_ctx *c, uint32_t *host) {
   return WS_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int ws_tree_cut_device(ws_ctx *c, const ws_tree_node *d_tree, size_t n_seeds, const uint32_t *d_keys, const uint32_t *d_seg_labels, size_t h,
-                       size_t w, const ws_tree_cut *cuts, size_t n_cuts, uint32_t *d_out, size_t plane_stride, ws_lake *d_lakes, size_t cap,
-                       size_t *n_lakes, uint64_t *offsets, uint64_t *hidden) {
-  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
-  if (!c) return WS_ERR_BAD_ARG;
-  const size_t n = h * w;
+// ws_tree_cut_device and ws_tree_cut_stats_device: every check, the tree's verdict, the tables, the render and the lists.  Without a
+// catalogue threshold d_stats is never read and the launches are those of a call that has none.
+int cut_run(ws_ctx *c, const ws_tree_node *d_tree, const ws_lake_stats *d_stats, size_t n_seeds, const uint32_t *d_keys, const uint32_t *d_seg_labels,
+            size_t h, size_t w, const Cuts &cs, uint32_t *d_out, size_t plane_stride, ws_lake *d_lakes, size_t cap, size_t *n_lakes,
+            uint64_t *offsets, uint64_t *hidden) {
+  const size_t n = h * w, n_cuts = cs.n;
   if ((!d_tree && n_seeds) || ((!d_keys || !d_seg_labels) && n)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
   if (!d_out && !d_lakes) return fail(c, WS_ERR_BAD_ARG, "no output: d_out and d_lakes are both null");
   if (d_lakes && (!n_lakes || !offsets || !hidden)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
-  if (int rc = check_cuts(c, cuts, n_cuts)) return rc;
+  if (int rc = check_cuts(c, cs)) return rc;
+  if (cs.catalogue && !d_stats) return fail(c, WS_ERR_BAD_ARG, "a cut has a catalogue threshold and d_stats is null");
   if (h && n / h != w) return fail(c, WS_ERR_TOO_LARGE, "plane too large");
   if (n > 0xFFFFFFFFull || n_seeds >= 0xFFFFFFFFull) return fail(c, WS_ERR_TOO_LARGE, "the plane has 2^32 pixels or more, or too many seeds");
   if (d_out && plane_stride < n) return fail(c, WS_ERR_BAD_ARG, "plane_stride is shorter than the plane");
@@ -373,7 +463,9 @@ int ws_tree_cut_device(ws_ctx *c, const ws_tree_node *d_tree, size_t n_seeds, co
     return WS_OK;
   }
   const size_t n_colours = n_seeds + 1;
-  if (int rc = cut_reserve(c, n_seeds, n_cuts, lists)) return rc;
+  const CutPlan plan = make_plan(cs);
+  const CutSource src = cut_source(plan);
+  if (int rc = cut_reserve(c, n_seeds, n_cuts, lists, src)) return rc;
   const TreeRec *tree = reinterpret_cast<const TreeRec *>(d_tree);
   uint32_t *flags = (uint32_t *)c->cut_flags.p, *tables = (uint32_t *)c->cut_tables.p, *counts = lists ? (uint32_t *)c->cut_counts.p : nullptr;
   uint32_t seen[CUT_F_WORDS];
@@ -384,8 +476,18 @@ int ws_tree_cut_device(ws_ctx *c, const ws_tree_node *d_tree, size_t n_seeds, co
   HIP_TRY(c, hipGetLastError());
   if (int rc = read_flags(c, seen)) return rc;
   if (seen[CUT_F_TREE]) return fail(c, WS_ERR_BAD_ARG, "d_tree is not a merge tree (ws_merge_tree_device's records)");
-  const CutPlan plan = make_plan(cuts, n_cuts);
-  k_cut_table<<<dim3(per_colour, plan.n_tables), 256, 0, c->stream>>>(tree, n_colours, plan, tables, flags);
+  const dim3 table_grid(per_colour, plan.n_tables);
+  const LakeRec *stats = reinterpret_cast<const LakeRec *>(d_stats);
+  if (src == CUT_TREE_ONLY) {
+    k_cut_table<CUT_TREE_ONLY><<<table_grid, 256, 0, c->stream>>>(tree, nullptr, nullptr, n_colours, plan, tables, flags);
+  } else if (src == CUT_RECORDS) {
+    k_cut_table<CUT_RECORDS><<<table_grid, 256, 0, c->stream>>>(tree, nullptr, stats, n_colours, plan, tables, flags);
+  } else {
+    CutKey *ckeys = (CutKey *)c->cut_keys.p;
+    k_cut_keys<<<per_colour, 256, 0, c->stream>>>(tree, stats, n_colours, ckeys);
+    HIP_TRY(c, hipGetLastError());
+    k_cut_table<CUT_KEYS><<<table_grid, 256, 0, c->stream>>>(tree, ckeys, nullptr, n_colours, plan, tables, flags);
+  }
   HIP_TRY(c, hipGetLastError());
   if (lists) HIP_TRY(c, hipMemsetAsync(counts, 0, n_cuts * n_colours * sizeof(uint32_t), c->stream));
   {      // 1024 pixels a step.  Planes alone: one step a workgroup, the finer grain evens out the walks (4096^2, 8 cuts: 1.17 ms
@@ -431,23 +533,31 @@ int ws_tree_cut_device(ws_ctx *c, const ws_tree_node *d_tree, size_t n_seeds, co
   return WS_OK;
 }
 
-int ws_merge_tree_cut(ws_ctx *c, const uint8_t *img, size_t h, size_t w, size_t row_stride, const uint64_t *seeds_rc, size_t n_seeds,
-                      const ws_options *opt, const ws_tree_cut *cuts, size_t n_cuts, ws_tree_node *tree, uint64_t *out, ws_lake *lakes, size_t cap,
-                      size_t *n_lakes, uint64_t *offsets, uint64_t *hidden) {
-  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
-  if (!c) return WS_ERR_BAD_ARG;
+// ws_merge_tree_cut and ws_merge_tree_stats_cut: the transform's host form (with lw: ws_merge_tree_stats, whose catalogue stays on
+// the context next to the records, the labels and the stamps), the device call on what it left there, the download.
+struct CutWeights {
+  const void *weight;
+  int dtype;
+  size_t stride;
+  ws_lake_stats *stats;      // nullable: where the caller wants the catalogue
+};
+
+int merge_tree_cut_host(ws_ctx *c, const uint8_t *img, size_t h, size_t w, size_t row_stride, const uint64_t *seeds_rc, size_t n_seeds,
+                        const ws_options *opt, const CutWeights *lw, const Cuts &cs, ws_tree_node *tree, uint64_t *out, ws_lake *lakes, size_t cap,
+                        size_t *n_lakes, uint64_t *offsets, uint64_t *hidden) {
   if (!opt || (!img && h * w) || (!seeds_rc && n_seeds)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
   if (!out && !lakes) return fail(c, WS_ERR_BAD_ARG, "no output: out and lakes are both null");
   if (lakes && (!n_lakes || !offsets || !hidden)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
-  if (int rc = check_cuts(c, cuts, n_cuts)) return rc;
+  if (int rc = check_cuts(c, cs)) return rc;
   size_t ph = 0, pw = 0;
   if (int rc = check_plane(c, h, w, row_stride, opt, &ph, &pw)) return rc;
   if (n_seeds >= 0xFFFFFFFFull) return fail(c, WS_ERR_TOO_LARGE, "too many seeds");
+  const size_t n_cuts = cs.n;
   if (n_cuts == 0) return WS_OK;
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t n = ph * pw;
   // every buffer before the transform: one that moves afterwards would not disturb it, but the level loop's graphs are keyed by them
-  if (int rc = cut_reserve(c, n_seeds, n_cuts, lakes != nullptr)) return rc;
+  if (int rc = cut_reserve(c, n_seeds, n_cuts, lakes != nullptr, cut_source(make_plan(cs)))) return rc;
   if (out && n)
     if (int rc = ensure(c, c->cut_planes, n_cuts * n * sizeof(uint32_t))) return rc;
   if (lakes)
@@ -455,11 +565,20 @@ int ws_merge_tree_cut(ws_ctx *c, const uint8_t *img, size_t h, size_t w, size_t 
   std::vector<ws_tree_node> own;
   if (!tree) { own.resize(n_seeds + 1); tree = own.data(); }
   // upload, flood, stamped unions and the records; the segmenting labels, the stamps and the records stay on the context
-  if (int rc = ws_merge_tree(c, img, h, w, row_stride, seeds_rc, n_seeds, opt, tree, nullptr)) return rc;
+  const ws_lake_stats *d_stats = nullptr;
+  if (lw) {
+    std::vector<ws_lake_stats> own_stats;
+    ws_lake_stats *stats = lw->stats;
+    if (!stats) { own_stats.resize(n_seeds + 1); stats = own_stats.data(); }
+    if (int rc = ws_merge_tree_stats(c, img, h, w, row_stride, seeds_rc, n_seeds, opt, lw->weight, lw->dtype, lw->stride, tree, stats, nullptr)) return rc;
+    d_stats = (const ws_lake_stats *)c->lake_out.p;
+  } else if (int rc = ws_merge_tree(c, img, h, w, row_stride, seeds_rc, n_seeds, opt, tree, nullptr)) {
+    return rc;
+  }
   uint32_t *planes = out ? (uint32_t *)c->cut_planes.p : nullptr;
   ws_lake *d_lakes = lakes ? (ws_lake *)c->cut_lakes.p : nullptr;
-  if (int rc = ws_tree_cut_device(c, (const ws_tree_node *)c->tree_out.p, n_seeds, (const uint32_t *)c->keys.p, (const uint32_t *)c->labels.p, ph, pw, cuts,
-                                  n_cuts, planes, n, d_lakes, cap, n_lakes, offsets, hidden))
+  if (int rc = cut_run(c, (const ws_tree_node *)c->tree_out.p, d_stats, n_seeds, (const uint32_t *)c->keys.p, (const uint32_t *)c->labels.p, ph, pw, cs,
+                       planes, n, d_lakes, cap, n_lakes, offsets, hidden))
     return rc;
   if (lakes && *n_lakes) HIP_TRY(c, hipMemcpyAsync(lakes, d_lakes, *n_lakes * sizeof(ws_lake), hipMemcpyDeviceToHost, c->stream));
   if (out && n) {
@@ -472,6 +591,48 @@ int ws_merge_tree_cut(ws_ctx *c, const uint8_t *img, size_t h, size_t w, size_t 
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return WS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ws_tree_cut_device(ws_ctx *c, const ws_tree_node *d_tree, size_t n_seeds, const uint32_t *d_keys, const uint32_t *d_seg_labels, size_t h,
+                       size_t w, const ws_tree_cut *cuts, size_t n_cuts, uint32_t *d_out, size_t plane_stride, ws_lake *d_lakes, size_t cap,
+                       size_t *n_lakes, uint64_t *offsets, uint64_t *hidden) {
+  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
+  if (!c) return WS_ERR_BAD_ARG;
+  return cut_run(c, d_tree, nullptr, n_seeds, d_keys, d_seg_labels, h, w, take_cuts(cuts, n_cuts), d_out, plane_stride, d_lakes, cap, n_lakes, offsets,
+                 hidden);
+}
+
+int ws_tree_cut_stats_device(ws_ctx *c, const ws_tree_node *d_tree, const ws_lake_stats *d_stats, size_t n_seeds, const uint32_t *d_keys,
+                             const uint32_t *d_seg_labels, size_t h, size_t w, const ws_lake_cut *cuts, size_t n_cuts, uint32_t *d_out,
+                             size_t plane_stride, ws_lake *d_lakes, size_t cap, size_t *n_lakes, uint64_t *offsets, uint64_t *hidden) {
+  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
+  if (!c) return WS_ERR_BAD_ARG;
+  return cut_run(c, d_tree, d_stats, n_seeds, d_keys, d_seg_labels, h, w, take_cuts(cuts, n_cuts), d_out, plane_stride, d_lakes, cap, n_lakes, offsets,
+                 hidden);
+}
+
+int ws_merge_tree_cut(ws_ctx *c, const uint8_t *img, size_t h, size_t w, size_t row_stride, const uint64_t *seeds_rc, size_t n_seeds,
+                      const ws_options *opt, const ws_tree_cut *cuts, size_t n_cuts, ws_tree_node *tree, uint64_t *out, ws_lake *lakes, size_t cap,
+                      size_t *n_lakes, uint64_t *offsets, uint64_t *hidden) {
+  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
+  if (!c) return WS_ERR_BAD_ARG;
+  return merge_tree_cut_host(c, img, h, w, row_stride, seeds_rc, n_seeds, opt, nullptr, take_cuts(cuts, n_cuts), tree, out, lakes, cap, n_lakes, offsets,
+                             hidden);
+}
+
+int ws_merge_tree_stats_cut(ws_ctx *c, const uint8_t *img, size_t h, size_t w, size_t row_stride, const uint64_t *seeds_rc, size_t n_seeds,
+                            const ws_options *opt, const void *weight, int weight_dtype, size_t weight_row_stride, const ws_lake_cut *cuts,
+                            size_t n_cuts, ws_tree_node *tree, ws_lake_stats *stats, uint64_t *out, ws_lake *lakes, size_t cap, size_t *n_lakes,
+                            uint64_t *offsets, uint64_t *hidden) {
+  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
+  if (!c) return WS_ERR_BAD_ARG;
+  const CutWeights lw{weight, weight_dtype, weight_row_stride, stats};
+  return merge_tree_cut_host(c, img, h, w, row_stride, seeds_rc, n_seeds, opt, &lw, take_cuts(cuts, n_cuts), tree, out, lakes, cap, n_lakes, offsets,
+                             hidden);
 }
 
 }  // extern "C"

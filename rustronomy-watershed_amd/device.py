@@ -382,17 +382,29 @@ class DeviceEngine:
                                                                     out.data_ptr(), out_stats.data_ptr() if want_stats else None))
         return (out, out_stats) if want_stats else out
 
-    def tree_cut(self, tree, keys, labels, cuts, out=None, want_lakes=False):
+    def tree_cut(self, tree, keys, labels, cuts, out=None, want_lakes=False, stats=None):
         """The label planes -- with want_lakes, also the lake lists -- of a merge tree pruned by `cuts` (an api.Cut or up to 32),
         everything in HBM (ws_tree_cut_device): tree = the (n_seeds + 1, 4) int32 tensor of merge_tree, keys = the arrival stamps
         (last_arrival()) and labels = the segmenting labels (merge_tree(want_labels=True)) of the same flood, 2-D int32 device
         tensors of one shape, contiguous (views into larger buffers are fine).  Returns a (K, H', W') int32 tensor whose plane k
         shows every pixel the lake cuts[k] leaves it in, 0 where it is hidden; with want_lakes (planes, lakes, offsets, hidden):
         lakes an (n, 2) int64 device tensor, lakes[offsets[k] : offsets[k + 1]] cut k's (colour, pixels) records in increasing
-        colour, hidden[k] its pixels that show 0 (numpy).  `out`: a reusable contiguous (K, H', W') int32 device tensor."""
+        colour, hidden[k] its pixels that show 0 (numpy).  `out`: a reusable contiguous (K, H', W') int32 device tensor.
+        stats: the (n_seeds + 1, 9) int64 catalogue tensor of merge_tree_stats of the same flood (views into larger buffers are
+        fine); with it the cuts may carry catalogue thresholds (min_sum_w, min_w_max, min_depth: ws_tree_cut_stats_device).  Such
+        a cut without stats is a ValueError before any device work."""
         import numpy as np
-        from .api import _as_cuts
-        arr, k = _as_cuts(cuts)
+        from .api import _as_cuts, _as_lake_cuts, _cut_list
+        lst = _cut_list(cuts)
+        if stats is None:
+            if any(c.catalogue for c in lst):
+                raise ValueError("a cut has a catalogue threshold: pass stats, the catalogue of merge_tree_stats")
+            arr, k = _as_cuts(lst)
+        else:
+            arr, k = _as_lake_cuts(lst)
+            if stats.dim() != 2 or tuple(stats.shape) != (tree.shape[0], 9):
+                raise ValueError("stats must be an (n_seeds + 1, 9) tensor, one row per row of tree")
+            assert stats.dtype == torch.int64 and stats.is_cuda and stats.is_contiguous()
         if keys.dim() != 2 or tuple(keys.shape) != tuple(labels.shape):
             raise ValueError("keys and labels must be 2-D tensors of the same shape")
         if tree.dim() != 2 or tree.shape[0] < 1 or tree.shape[1] != 4:
@@ -413,10 +425,15 @@ class DeviceEngine:
         cap = max(min(ns, h * w), 1) * max(k, 1) if want_lakes else 0      # a cut shows no more colours than there are, or pixels
         if want_lakes:
             lakes = torch.empty((cap, 2), dtype=torch.int64, device=self.device)
-        if k and h * w:      # (no cut or no pixel: nothing to run, no plane word to write, empty lists)
+        if k and h * w and stats is None:      # (no cut or no pixel: nothing to run, no plane word to write, empty lists)
             self.ctx.check(_ffi.lib().ws_tree_cut_device(self.ctx.handle, tree.data_ptr(), ns, keys.data_ptr(), labels.data_ptr(), h, w,
                                                          arr, k, out.data_ptr(), h * w, lakes.data_ptr() if want_lakes else None, cap,
                                                          ctypes.byref(n), offsets.ctypes.data, hidden.ctypes.data))
+        elif k and h * w:
+            self.ctx.check(_ffi.lib().ws_tree_cut_stats_device(self.ctx.handle, tree.data_ptr(), stats.data_ptr(), ns, keys.data_ptr(),
+                                                               labels.data_ptr(), h, w, arr, k, out.data_ptr(), h * w,
+                                                               lakes.data_ptr() if want_lakes else None, cap, ctypes.byref(n),
+                                                               offsets.ctypes.data, hidden.ctypes.data))
         return (out, lakes[: n.value], offsets, hidden[:k]) if want_lakes else out
 
     def merge_tree_batch(self, cube, seeds, seed_offsets, max_level=254, edge=False, seed_shift=False, want_labels=False, out=None):
