@@ -2,8 +2,9 @@
 // buffer helpers, the pass loop.  Kernels and their launch wrappers live in ws_common.hpp / ws_merge.hpp.
 //
 //   ws_ctx.hip        context life cycle, options, seeds (find_local_minima), pre-processor, staging helpers
-//   ws_segment.hip    the segmenting drivers (lib.rs:1638-1808): fused and sweep engines, host / device / begin-end / batch
-//   ws_lists.hip      the merging drivers and transform_to_list (lib.rs:1328-1522, 1551-1561)
+//   ws_segment.hip    the segmenting drivers (lib.rs:1638-1808): fused and sweep engines, host / device / begin-end, host cubes
+//   ws_lists.hip      the merging drivers and transform_to_list (lib.rs:1328-1522, 1551-1561): the per-level driver, single fields
+//   ws_batch.hip      every product for a cube of slices on the device: one batch, one stack decision, one walk (ws_lists.hpp)
 //   ws_block_api.hip  row blocks of a tiled field, one call per step (the caller brings the collectives)
 //   ws_tiled.hip      the same loop driven inside the library: several devices of one process, or one rank of an RCCL job
 #pragma once

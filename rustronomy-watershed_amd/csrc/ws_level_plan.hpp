@@ -54,6 +54,42 @@ struct LevelJob {
 
   bool lists() const { return n_lakes != nullptr; }
   bool device_records() const { return source != LevelSource::HOST; }
+
+  // the three sources; what a job wants on top of its flood is named behind them (with_lists, with_history, cb, out_labels)
+  static LevelJob plane(bool merging, LevelSource source, size_t h, size_t w, size_t stride, size_t n_seeds, const ws_options *opt) {
+    LevelJob j;
+    j.merging = merging; j.source = source; j.h = h; j.w = w; j.stride = stride; j.n_seeds = n_seeds; j.opt = opt;
+    return j;
+  }
+  static LevelJob from_host(bool merging, const uint8_t *img, size_t h, size_t w, size_t stride, const uint64_t *seeds_rc, size_t n_seeds,
+                            const ws_options *opt) {
+    LevelJob j = plane(merging, LevelSource::HOST, h, w, stride, n_seeds, opt);
+    j.img = img; j.seeds_rc = seeds_rc;
+    return j;
+  }
+  static LevelJob from_device(bool merging, const uint8_t *d_img, size_t h, size_t w, size_t stride, const uint32_t *d_seeds_rc, size_t n_seeds,
+                              const ws_options *opt) {
+    LevelJob j = plane(merging, LevelSource::DEVICE, h, w, stride, n_seeds, opt);
+    j.d_img = d_img; j.d_seeds_rc = d_seeds_rc;
+    return j;
+  }
+  static LevelJob from_arrival(bool merging, const uint32_t *d_keys, const uint32_t *d_seg, size_t h, size_t w, size_t n_seeds, const ws_options *opt) {
+    LevelJob j = plane(merging, LevelSource::ARRIVAL, h, w, w, n_seeds, opt);
+    j.d_keys = d_keys; j.d_seg = d_seg;
+    return j;
+  }
+  // records: on the source's side of the bus
+  LevelJob with_lists(ws_lake *records, size_t cap_, size_t *n_lakes_, uint64_t *offsets_, uint64_t *uncoloured_) const {
+    LevelJob j = *this;
+    (j.device_records() ? j.d_lakes : j.lakes) = records;
+    j.cap = cap_; j.n_lakes = n_lakes_; j.offsets = offsets_; j.uncoloured = uncoloured_;
+    return j;
+  }
+  LevelJob with_history() const {
+    LevelJob j = *this;
+    j.history = true;
+    return j;
+  }
 };
 
 // A job that no entry point builds: what is wrong with it (null: nothing).

@@ -1,8 +1,9 @@
 // ws_lists.hip -- the merging drivers (lib.rs:1328-1522) and transform_to_list (lib.rs:1551-1561, 1837-1847): per-level
 // unions over seed colours, lake areas and sparse lake records (kernels: ws_merge.hip the level loop, ws_merge_final.hip the
-// final labels alone, ws_merge_tree.hip history planes, merge tree and lake statistics; wrappers: ws_merge.hpp).
-#include "ws_ctx.hpp"
-#include "ws_level_plan.hpp"
+// final labels alone, ws_merge_tree.hip history planes, merge tree and lake statistics; wrappers: ws_merge.hpp).  The per-level
+// driver merge_host with the single-field entry points; the same products for cubes of slices: ws_batch.hip, which calls what
+// ws_lists.hpp declares.
+#include "ws_lists.hpp"
 
 using namespace wsapi;
 
@@ -48,15 +49,6 @@ int build_buckets(ws_ctx *c, const uint32_t *keys, const uint32_t *seg_labels, i
   if ((rc = ensure(c, c->edge_items, need_ed))) return rc;
   HIP_TRY(c, level_scatter(c->stream, keys, seg_labels, ph, pw, mf + MF_CUR_PX, mf + MF_CUR_ED,
                            (uint32_t *)c->px_items.p, (uint2 *)c->edge_items.p, slice_h, slice_base));
-  return WS_OK;
-}
-
-int ensure_uf(ws_ctx *c, size_t n_colours) {
-  int rc;
-  if ((rc = ensure(c, c->uf_parent, n_colours * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, c->uf_size, n_colours * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, c->uf_hooked, n_colours * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, c->uf_death, n_colours * sizeof(uint32_t)))) return rc;
   return WS_OK;
 }
 
@@ -152,6 +144,7 @@ int level_range(ws_ctx *c, const LevelJob &job, const LevelRun &r, uint32_t l0, 
       }
   return WS_OK;
 }
+}  // namespace
 
 // Records [from, end) of the device array d_rec into the host's `lakes`, on stream `on` (returns with the copy complete when the
 // chunked road is taken; otherwise queued).  A piece of two million records and more (2048^2 planes on) crosses the bus as u32 --
@@ -159,7 +152,7 @@ int level_range(ws_ctx *c, const LevelJob &job, const LevelRun &r, uint32_t l0, 
 // (ws_hostcopy.hip; pieces of at most n records: the narrowed words borrow the u64 label buffer, n x 8 bytes).
 // A piece that is too short for the chunked road must NOT go down it: labels_to_host_u64's other path widens into the very
 // buffer the narrowed words sit in (and may reallocate it).  Such pieces are copied as they are.
-int records_to_host(ws_ctx *c, const ws_lake *d_rec, ws_lake *lakes, size_t from, size_t end, size_t n, hipStream_t on) {
+int wsapi::records_to_host(ws_ctx *c, const ws_lake *d_rec, ws_lake *lakes, size_t from, size_t end, size_t n, hipStream_t on) {
   const bool may_narrow = n < 0x80000000ull && c->out64.p && c->out64.cap >= n * sizeof(uint64_t);
   while (from < end) {
     const size_t piece = std::min<size_t>(end - from, n);
@@ -173,6 +166,8 @@ int records_to_host(ws_ctx *c, const ws_lake *d_rec, ws_lake *lakes, size_t from
   }
   return WS_OK;
 }
+
+namespace {
 
 // ---- merge_host: the per-level driver, stage by stage (the job and its plan: ws_level_plan.hpp) --------------------------------------
 
@@ -371,8 +366,9 @@ int level_epilogue(ws_ctx *c, const LevelJob &job, const LevelRun &r) {
   if (job.lists() && *job.n_lakes > job.cap) return fail(c, WS_ERR_CAPACITY, "lake buffer too small");
   return WS_OK;
 }
+}  // namespace
 
-int merge_host(ws_ctx *c, const LevelJob &job) {
+int wsapi::merge_host(ws_ctx *c, const LevelJob &job) {
   if (!c) return WS_ERR_BAD_ARG;
   int rc = check_job(c, job);
   if (rc) return rc;
@@ -388,7 +384,7 @@ int merge_host(ws_ctx *c, const LevelJob &job) {
   return level_epilogue(c, job, r);
 }
 
-void stats_add(ws_stats &a, const ws_stats &b) {
+void wsapi::stats_add(ws_stats &a, const ws_stats &b) {
   a.relax_passes += b.relax_passes; a.resolve_passes += b.resolve_passes; a.sweep_steps += b.sweep_steps;
   a.merge_levels = std::max(a.merge_levels, b.merge_levels);
   a.tiles_run_relax += b.tiles_run_relax; a.tiles_run_resolve += b.tiles_run_resolve;
@@ -397,227 +393,20 @@ void stats_add(ws_stats &a, const ws_stats &b) {
   a.relax_tile_iterations += b.relax_tile_iterations; a.graph_launches += b.graph_launches;
 }
 
-// The stack of ws_segment_batch_device (same conditions: see the header) for a batch whose every group of slices has a seed;
-// groups of batch_max_px / plane slices.  false: the slice-by-slice loop takes the batch.
-bool stackable(ws_ctx *c, size_t n_slices, size_t h, size_t w, size_t stride, size_t ph, size_t pw, const size_t *seed_offsets,
-               const ws_options *opt, size_t *per_group) {
-  static const bool off = tuning_env("WS_NO_BATCH_STACK") != nullptr || tuning_env("WS_NO_SEED_TABLES") != nullptr;      // A/B knobs for tools/
-  const size_t plane = ph * pw;
-  if (off || n_slices < 2 || pick_engine(opt) != WS_ENGINE_FUSED || !c->expect_sorted || (pw & 3) != 0 || plane == 0 ||
-      plane % 128 != 0 || plane >= 0x40000000ull || stride != w || h * w == 0)
-    return false;
-  if (seed_offsets[n_slices] - seed_offsets[0] >= 0xFFFFFFFFull) return false;
-  *per_group = std::max<size_t>(1, c->batch_max_px / plane);
-  for (size_t k0 = 0; k0 < n_slices; k0 += *per_group)      // (a flood needs a seed)
-    if (seed_offsets[std::min(k0 + *per_group, n_slices)] == seed_offsets[k0]) return false;
-  return true;
-}
-
-// A batch that stacks, as its drivers hand it to flood_group
-struct StackBatch {
-  const uint8_t *d_cube = nullptr;
-  size_t h = 0, stride = 0, ph = 0, pw = 0;
-  const uint32_t *d_seeds_rc = nullptr;
-  const size_t *seed_offsets = nullptr;
-  const ws_options *opt = nullptr;
-};
-
-// The flood of slices [k0, k0 + g) as one stack (flood_stack) into `labels`; first (g + 1): every slice's first seed within the
-// group.  true: flooded, and the statistics span is still OPEN -- the drivers differ in where they close it.  false: the flood
-// failed or mispredicted; the span is closed, the error cleared, and the slice-by-slice loop repeats the work and names the slice.
-bool flood_group(ws_ctx *c, const StackBatch &b, size_t k0, size_t g, uint32_t *labels, std::vector<uint32_t> &first) {
-  const size_t s0 = b.seed_offsets[k0];
-  first.resize(g + 1);
-  for (size_t k = 0; k <= g; ++k) first[k] = (uint32_t)(b.seed_offsets[k0 + k] - s0);
-  stats_begin(c);
-  bool mispredicted = false;
-  const int rc = flood_stack(c, b.d_cube + k0 * b.h * b.stride, b.stride, g, b.ph, b.pw, b.d_seeds_rc + 2 * s0, first.data(), b.opt, labels, &mispredicted);
-  c->have_keys = false;      // the stamps are those of a stack, not of an image
-  if (rc == WS_OK && !mispredicted) return true;
-  (void)stats_end(c);
-  c->err.clear();
-  return false;
-}
-
-// The arrival-form job of a flooded stack of slices of ph rows: the per-level driver over the stack's numbering of colours
-LevelJob stack_job(ws_ctx *c, bool merging, size_t g, size_t ph, size_t pw, size_t n_seeds, const ws_options *opt, const uint32_t *labels,
-                   const uint32_t *d_base) {
-  LevelJob job;
-  job.merging = merging; job.h = g * ph; job.w = pw; job.stride = pw; job.n_seeds = n_seeds; job.opt = opt;
-  job.source = LevelSource::ARRIVAL; job.d_keys = (const uint32_t *)c->keys.p; job.d_seg = labels;
-  job.slice_h = (int)ph; job.d_slice_base = d_base;
-  return job;
-}
-
-// The history job of a device-resident image: the flood and, merging, the stamped level loop; nothing leaves the context
-LevelJob history_job_device(bool merging, const uint8_t *d_img, size_t h, size_t w, size_t stride, const uint32_t *d_seeds_rc, size_t n_seeds,
-                            const ws_options *opt) {
-  LevelJob job;
-  job.merging = merging; job.h = h; job.w = w; job.stride = stride; job.n_seeds = n_seeds; job.opt = opt;
-  job.source = LevelSource::DEVICE; job.d_img = d_img; job.d_seeds_rc = d_seeds_rc; job.history = true;
-  return job;
-}
-
-// ... and of a host image
-LevelJob history_job_host(bool merging, const uint8_t *img, size_t h, size_t w, size_t stride, const uint64_t *seeds_rc, size_t n_seeds,
-                          const ws_options *opt) {
-  LevelJob job;
-  job.merging = merging; job.h = h; job.w = w; job.stride = stride; job.n_seeds = n_seeds; job.opt = opt;
-  job.img = img; job.seeds_rc = seeds_rc; job.history = true;
-  return job;
-}
-
-// ... and of a finished transform's planes (ws_merge_tree_from_arrival_device): no flood, the stamped level loop alone
-LevelJob history_job_arrival(const uint32_t *d_keys, const uint32_t *d_seg, size_t h, size_t w, size_t n_seeds, const ws_options *opt) {
-  LevelJob job;
-  job.merging = true; job.h = h; job.w = w; job.stride = w; job.n_seeds = n_seeds; job.opt = opt;
-  job.source = LevelSource::ARRIVAL; job.d_keys = d_keys; job.d_seg = d_seg; job.history = true;
-  return job;
-}
-
-// ws_transform_to_list_batch_device on a stack: per group of slices, the flood of the stack (flood_stack), the per-level driver
-// over the stack's numbering of colours (merge_host, arrival form: the bucketing adds the slice's base to every colour and pairs
-// no pixels across a slice border), then the split of the group's records (level-major, stack colours) into the caller's
-// slice-major layout in the slices' own colours.  *done = false: nothing was decided, the loop takes the batch.
-int lists_batch_stacked(ws_ctx *c, bool merging, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w, size_t stride,
-                        const uint32_t *d_seeds_rc, const size_t *seed_offsets, const ws_options *opt, ws_lake *d_lakes, size_t cap,
-                        size_t *n_lakes, uint64_t *offsets, uint64_t *uncoloured, bool *done) {
-  *done = false;
-  size_t ph, pw, per_group = 0;
-  int rc = check_plane(c, h, w, stride, opt, &ph, &pw);
-  if (rc) return rc;
-  if (!stackable(c, n_slices, h, w, stride, ph, pw, seed_offsets, opt, &per_group)) return WS_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
-  const size_t plane = ph * pw;
-  const uint32_t levels = (uint32_t)opt->max_water_level + 1;
-  ws_stats acc{};
-  size_t need = 0;      // records of the groups so far; while need <= cap they are in d_lakes[0 .. need)
-  std::vector<uint32_t> first;
-  std::vector<uint64_t> goff(levels + 1), gunc(levels);
-  std::vector<u64c> bins;
-  StackBatch batch;
-  batch.d_cube = d_cube; batch.h = h; batch.stride = stride; batch.ph = ph; batch.pw = pw; batch.d_seeds_rc = d_seeds_rc; batch.seed_offsets = seed_offsets; batch.opt = opt;
-  for (size_t k0 = 0; k0 < n_slices; k0 += per_group) {
-    const size_t g = std::min(per_group, n_slices - k0);
-    const size_t s0 = seed_offsets[k0], ns = seed_offsets[k0 + g] - s0;
-    const size_t gcap = need <= cap ? cap - need : 0, n_bins = g * levels;
-    if ((rc = ensure(c, c->stack_labels, g * plane * sizeof(uint32_t)))) return rc;
-    if ((rc = ensure(c, c->stack_records, std::max<size_t>(gcap, 1) * sizeof(ws_lake)))) return rc;
-    if ((rc = ensure(c, c->stack_bins, (levels + 1 + n_bins + g * NLEVELS) * sizeof(u64c)))) return rc;
-    uint32_t *labels = (uint32_t *)c->stack_labels.p;
-    if (!flood_group(c, batch, k0, g, labels, first)) return WS_OK;      // the loop takes the batch
-    if ((rc = stats_end(c))) return rc;
-    stats_add(acc, c->stats);
-    const uint32_t *d_base = stacked_first(c, ns);
-    u64c *d_off = (u64c *)c->stack_bins.p, *d_bins = d_off + levels + 1, *d_hist = d_bins + n_bins;
-    HIP_TRY(c, hipMemsetAsync(d_bins, 0, (n_bins + g * NLEVELS) * sizeof(u64c), c->stream));
-    HIP_TRY(c, slice_arrivals(c->stream, (const uint32_t *)c->keys.p, plane, g, d_hist));
-    size_t got = 0;
-    LevelJob job = stack_job(c, merging, g, ph, pw, ns, opt, labels, d_base);
-    job.d_lakes = (ws_lake *)c->stack_records.p; job.cap = gcap; job.n_lakes = &got; job.offsets = goff.data(); job.uncoloured = gunc.data();
-    rc = merge_host(c, job);
-    if (rc != WS_OK && rc != WS_ERR_CAPACITY) return rc;
-    stats_add(acc, c->stats);
-    need += got;
-    if (rc == WS_ERR_CAPACITY || need > cap) {      // counted, not written: the caller learns how many records to make room for
-      c->err.clear();
-      continue;
-    }
-    // counts per (slice, level) -> the bins' first records in the caller's layout, which the scatter takes as its cursors.
-    // A bin holds at most one record per colour of its slice; segmenting lists that have ALL of them (every seed owns its pixel
-    // from level 0 on: the usual case) are known without a pass over the records.
-    HIP_TRY(c, hipMemcpyAsync(d_off, goff.data(), (levels + 1) * sizeof(u64c), hipMemcpyHostToDevice, c->stream));
-    const bool full = !merging && got == (size_t)levels * ns;
-    if (!full)
-      HIP_TRY(c, split_records(c->stream, false, (const uint64_t *)c->stack_records.p, got, d_off, levels, d_base, (uint32_t)g, d_bins, nullptr));
-    bins.resize(n_bins + g * NLEVELS);
-    HIP_TRY(c, hipMemcpyAsync(bins.data(), d_bins, bins.size() * sizeof(u64c), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (full)
-      for (size_t k = 0; k < g; ++k)
-        for (uint32_t l = 0; l < levels; ++l) bins[k * levels + l] = first[k + 1] - first[k];
-    u64c at = need - got;
-    for (size_t b = 0; b < n_bins; ++b) {
-      const u64c count = bins[b];
-      offsets[k0 * levels + b] = at;
-      bins[b] = at;
-      at += count;
-    }
-    if (at != need) return fail(c, WS_ERR_HIP, "internal: the split of the stack's records lost some");
-    for (size_t k = 0; k < g; ++k) {      // index 0 of lib.rs:630's vector: the slice's pixels not yet coloured
-      u64c arrived = 0;
-      for (uint32_t l = 0; l < levels; ++l) {
-        arrived += bins[n_bins + k * NLEVELS + l];
-        uncoloured[(k0 + k) * levels + l] = plane - arrived;
-      }
-    }
-    HIP_TRY(c, hipMemcpyAsync(d_bins, bins.data(), n_bins * sizeof(u64c), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, split_records(c->stream, true, (const uint64_t *)c->stack_records.p, got, d_off, levels, d_base, (uint32_t)g, d_bins,
-                             (uint64_t *)d_lakes));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));      // `bins` and `goff` are the next group's
-  }
-  offsets[n_slices * levels] = need;
-  *n_lakes = need;
-  c->stats = acc;
-  *done = true;
-  if (need > cap) return fail(c, WS_ERR_CAPACITY, "lake buffer too small");
-  return WS_OK;
-}
-
-// ws_merge_batch_device on a stack: the flood of each group of slices into the caller's labels, then the unions of the final
-// level over the stack's numbering of colours and a relabel back to every slice's own (merge_stack).
-int merge_batch_stacked(ws_ctx *c, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w, size_t stride, const uint32_t *d_seeds_rc,
-                        const size_t *seed_offsets, const ws_options *opt, uint32_t *d_labels, bool *done) {
-  *done = false;
-  size_t ph, pw, per_group = 0;
-  int rc = check_plane(c, h, w, stride, opt, &ph, &pw);
-  if (rc) return rc;
-  if (!stackable(c, n_slices, h, w, stride, ph, pw, seed_offsets, opt, &per_group)) return WS_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
-  const size_t plane = ph * pw;
-  ws_stats acc{};
-  std::vector<uint32_t> first;
-  StackBatch batch;
-  batch.d_cube = d_cube; batch.h = h; batch.stride = stride; batch.ph = ph; batch.pw = pw; batch.d_seeds_rc = d_seeds_rc; batch.seed_offsets = seed_offsets; batch.opt = opt;
-  for (size_t k0 = 0; k0 < n_slices; k0 += per_group) {
-    const size_t g = std::min(per_group, n_slices - k0);
-    const size_t ns = seed_offsets[k0 + g] - seed_offsets[k0];
-    if ((rc = ensure_uf(c, ns + 1))) return rc;
-    uint32_t *labels = d_labels + k0 * plane;
-    if (!flood_group(c, batch, k0, g, labels, first)) return WS_OK;      // the loop takes the batch
-    HIP_TRY(c, uf_init(c->stream, (uint32_t *)c->uf_parent.p, (uint32_t *)c->uf_size.p, ns + 1));
-    {
-      Span sp(c, KC_OTHER);
-      HIP_TRY(c, merge_stack(c->stream, labels, (int)ph, (int)pw, g, stacked_first(c, ns), (uint32_t *)c->uf_parent.p, ns + 1));
-    }
-    if ((rc = stats_end(c))) return rc;
-    stats_add(acc, c->stats);
-  }
-  c->stats = acc;
-  c->stats.merge_levels = 1;
-  *done = true;
-  return WS_OK;
-}
-
-// the checks the batch entry points share (as ws_segment_batch_device's)
-int check_batch(ws_ctx *c, size_t n_slices, size_t h, size_t row_stride, size_t slice_stride, const size_t *seed_offsets,
-                const ws_options *opt) {
-  if (n_slices && !seed_offsets) return fail(c, WS_ERR_BAD_ARG, "null pointer");
-  if (!opt) return fail(c, WS_ERR_BAD_ARG, "null pointer");
-  if (int v = ws_options_validate(opt)) return fail(c, v, ws_strerror(v));
-  if (n_slices > 1 && slice_stride < h * row_stride) return fail(c, WS_ERR_BAD_ARG, "slice_stride < h * row_stride");
-  for (size_t k = 0; k < n_slices; ++k)
-    if (seed_offsets[k + 1] < seed_offsets[k]) return fail(c, WS_ERR_BAD_ARG, "seed_offsets must not decrease");
+int wsapi::ensure_uf(ws_ctx *c, size_t n_colours) {
+  int rc;
+  if ((rc = ensure(c, c->uf_parent, n_colours * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, c->uf_size, n_colours * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, c->uf_hooked, n_colours * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, c->uf_death, n_colours * sizeof(uint32_t)))) return rc;
   return WS_OK;
 }
 
 // ---- transform_history (lib.rs:1233-1237, 1538-1549, 1824-1835) for a list of levels ------------------------------------------------
 
-constexpr size_t HISTORY_SCRATCH_BYTES = (size_t)256 << 20;      // the host form's u32 planes on the device, at most, per chunk of levels
-
 // n_planes planes of n u32 words, contiguous on the device, into the host's u64 planes: in ONE labels_to_host_u64 where the host
 // threads widen (host_copy_in_chunks), else plane by plane, widened on the device in the u64 buffer the context holds for one plane
-int planes_to_host(ws_ctx *c, const uint32_t *src, uint64_t *dst, size_t n_planes, size_t n) {
+int wsapi::planes_to_host(ws_ctx *c, const uint32_t *src, uint64_t *dst, size_t n_planes, size_t n) {
   if (host_copy_in_chunks(c, n_planes * n)) return labels_to_host_u64(c, src, dst, n_planes * n);
   for (size_t i = 0; i < n_planes; ++i)
     if (int rc = labels_to_host_u64(c, src + i * n, dst + i * n, n)) return rc;
@@ -625,7 +414,7 @@ int planes_to_host(ws_ctx *c, const uint32_t *src, uint64_t *dst, size_t n_plane
 }
 
 // what both forms check before anything runs; *n_px: pixels of the (padded) plane
-int check_history(ws_ctx *c, size_t h, size_t w, size_t stride, const ws_options *opt, const uint8_t *levels, size_t n_levels, size_t *n_px) {
+int wsapi::check_history(ws_ctx *c, size_t h, size_t w, size_t stride, const ws_options *opt, const uint8_t *levels, size_t n_levels, size_t *n_px) {
   size_t ph, pw;
   if (int rc = check_plane(c, h, w, stride, opt, &ph, &pw)) return rc;
   if (n_levels > (size_t)HISTORY_MAX_LEVELS) return fail(c, WS_ERR_BAD_ARG, "more than 256 levels");
@@ -637,7 +426,7 @@ int check_history(ws_ctx *c, size_t h, size_t w, size_t stride, const ws_options
 }
 
 // levels[k0 .. k1) in ascending order (stable: repeats keep their order), each with its plane k - k0
-HistoryTable history_table(const uint8_t *levels, size_t k0, size_t k1) {
+HistoryTable wsapi::history_table(const uint8_t *levels, size_t k0, size_t k1) {
   HistoryTable t{};
   t.n = (uint32_t)(k1 - k0);
   for (size_t k = k0; k < k1; ++k) t.e[k - k0] = (uint32_t)levels[k] | (uint32_t)(k - k0) << 8;
@@ -646,7 +435,7 @@ HistoryTable history_table(const uint8_t *levels, size_t k0, size_t k1) {
 }
 
 // the planes of tab's levels from the transform merge_host(history) has just run on this context
-int render_levels(ws_ctx *c, bool merging, const HistoryTable &tab, uint32_t *d_out, size_t plane_stride, size_t n) {
+int wsapi::render_levels(ws_ctx *c, bool merging, const HistoryTable &tab, uint32_t *d_out, size_t plane_stride, size_t n) {
   HIP_TRY(c, render_history(c->stream, merging, (const uint32_t *)c->keys.p, (const uint32_t *)c->labels.p, (const uint32_t *)c->uf_death.p,
                             (const uint32_t *)c->uf_hook.p, tab, d_out, plane_stride, n));
   return WS_OK;
@@ -656,26 +445,9 @@ int render_levels(ws_ctx *c, bool merging, const HistoryTable &tab, uint32_t *d_
 
 static_assert(sizeof(ws_tree_node) == sizeof(TreeRec) && WS_TREE_ALIVE == TREE_ALIVE, "ws_tree_node is the kernels' TreeRec");
 
-// what both forms check before anything runs
-int check_tree(ws_ctx *c, size_t h, size_t w, size_t stride, const ws_options *opt, size_t n_seeds, size_t *ph, size_t *pw) {
-  if (int rc = check_plane(c, h, w, stride, opt, ph, pw)) return rc;
-  if (n_seeds >= 0xFFFFFFFFull) return fail(c, WS_ERR_TOO_LARGE, "too many seeds");
-  return WS_OK;
-}
-
-// every buffer the tree needs, BEFORE the transform: a buffer that moves bumps the context's generation, and the level loop's
-// captured graphs are keyed by it
-int ensure_tree(ws_ctx *c, size_t n_seeds, bool host_records) {
-  int rc;
-  if ((rc = ensure(c, c->tree_order, (n_seeds + 1) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, c->tree_ws, TREE_WS_WORDS * sizeof(u64c)))) return rc;
-  if (host_records && (rc = ensure(c, c->tree_out, (n_seeds + 1) * sizeof(ws_tree_node)))) return rc;
-  return WS_OK;
-}
-
 // the records from the transform merge_host(merging, history) has just run on this context over the planes keys and seg (the
 // context's own, or the arrival form's); d_seeds: the seed pairs in those planes' coordinates
-int build_tree(ws_ctx *c, const uint32_t *keys, const uint32_t *seg, const uint32_t *d_seeds, size_t n_seeds, const ws_options *opt, size_t ph, size_t pw,
+int wsapi::build_tree(ws_ctx *c, const uint32_t *keys, const uint32_t *seg, const uint32_t *d_seeds, size_t n_seeds, const ws_options *opt, size_t ph, size_t pw,
                ws_tree_node *d_tree) {
   const uint32_t levels = (uint32_t)opt->max_water_level + 1;
   const uint32_t *death = (const uint32_t *)c->uf_death.p, *hook = (const uint32_t *)c->uf_hook.p;
@@ -695,7 +467,7 @@ int build_tree(ws_ctx *c, const uint32_t *keys, const uint32_t *seg, const uint3
 static_assert(sizeof(ws_lake_stats) == 72 && sizeof(ws_lake_stats) == sizeof(LakeRec), "ws_lake_stats is the kernels' LakeRec");
 
 // what both forms check, after check_tree and before anything runs: the weights' type and stride, and that no sum can pass 64 bits
-int check_lake_weights(ws_ctx *c, size_t w, size_t ph, size_t pw, const void *weight, int dtype, size_t weight_stride) {
+int wsapi::check_lake_weights(ws_ctx *c, size_t w, size_t ph, size_t pw, const void *weight, int dtype, size_t weight_stride) {
   uint64_t wmax = 0xFFull;
   if (weight) {
     if (dtype != WS_U8 && dtype != WS_U16) return fail(c, WS_ERR_UNSUPPORTED, "weights are u8 or u16");
@@ -707,21 +479,40 @@ int check_lake_weights(ws_ctx *c, size_t w, size_t ph, size_t pw, const void *we
   return WS_OK;
 }
 
-int ensure_lake(ws_ctx *c, size_t n_seeds, bool host_records) {
-  int rc;
-  if ((rc = ensure(c, c->lake_acc, (n_seeds + 1) * LAKE_ACC_BYTES))) return rc;
-  if (host_records && (rc = ensure(c, c->lake_out, (n_seeds + 1) * sizeof(ws_lake_stats)))) return rc;
-  return WS_OK;
-}
-
 // the statistics of the tree build_tree has just finished at d_tree, from the same transform and planes
-int build_lake_stats(ws_ctx *c, const uint32_t *keys, const uint32_t *seg, const uint32_t *d_seeds, size_t n_seeds, const ws_options *opt, size_t ph,
+int wsapi::build_lake_stats(ws_ctx *c, const uint32_t *keys, const uint32_t *seg, const uint32_t *d_seeds, size_t n_seeds, const ws_options *opt, size_t ph,
                      size_t pw, const ws_tree_node *d_tree, const LakeWeights &wt, ws_lake_stats *d_stats) {
   Span sp(c, KC_OTHER);
   HIP_TRY(c, lake_stats(c->stream, keys, seg, (const uint32_t *)c->uf_death.p,
                         (const uint32_t *)c->uf_hook.p, reinterpret_cast<const TreeRec *>(d_tree), d_seeds, n_seeds + 1,
                         (uint32_t)opt->max_water_level + 1, (const u64c *)c->tree_ws.p, (const uint32_t *)c->tree_order.p, wt, (int)ph, (int)pw,
                         c->lake_acc.p, reinterpret_cast<LakeRec *>(d_stats)));
+  return WS_OK;
+}
+
+namespace {
+
+// what both forms check before anything runs
+int check_tree(ws_ctx *c, size_t h, size_t w, size_t stride, const ws_options *opt, size_t n_seeds, size_t *ph, size_t *pw) {
+  if (int rc = check_plane(c, h, w, stride, opt, ph, pw)) return rc;
+  if (n_seeds >= 0xFFFFFFFFull) return fail(c, WS_ERR_TOO_LARGE, "too many seeds");
+  return WS_OK;
+}
+
+// every buffer the tree needs, BEFORE the transform: a buffer that moves bumps the context's generation, and the level loop's
+// captured graphs are keyed by it
+int ensure_tree(ws_ctx *c, size_t n_seeds, bool host_records) {
+  int rc;
+  if ((rc = ensure(c, c->tree_order, (n_seeds + 1) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, c->tree_ws, TREE_WS_WORDS * sizeof(u64c)))) return rc;
+  if (host_records && (rc = ensure(c, c->tree_out, (n_seeds + 1) * sizeof(ws_tree_node)))) return rc;
+  return WS_OK;
+}
+
+int ensure_lake(ws_ctx *c, size_t n_seeds, bool host_records) {
+  int rc;
+  if ((rc = ensure(c, c->lake_acc, (n_seeds + 1) * LAKE_ACC_BYTES))) return rc;
+  if (host_records && (rc = ensure(c, c->lake_out, (n_seeds + 1) * sizeof(ws_lake_stats)))) return rc;
   return WS_OK;
 }
 
@@ -747,7 +538,7 @@ int merge_tree_device_body(ws_ctx *c, const uint8_t *d_img, size_t h, size_t w, 
   if (int rc = ensure_tree(c, n_seeds, false)) return rc;
   if (ls)
     if (int rc = ensure_lake(c, n_seeds, false)) return rc;
-  if (int rc = merge_host(c, history_job_device(true, d_img, h, w, stride, d_seeds_rc, n_seeds, opt))) return rc;
+  if (int rc = merge_host(c, LevelJob::from_device(true, d_img, h, w, stride, d_seeds_rc, n_seeds, opt).with_history())) return rc;
   // the seed pairs as the flood took them: the caller's, or (shifted_seeds) moved into the padded plane in the context's buffer
   const uint32_t *seeds = seed_shift_of(opt) && n_seeds ? (const uint32_t *)c->seeds.p : d_seeds_rc;
   if (int rc = build_tree(c, (const uint32_t *)c->keys.p, (const uint32_t *)c->labels.p, seeds, n_seeds, opt, ph, pw, d_tree)) return rc;
@@ -778,7 +569,7 @@ int merge_tree_host_body(ws_ctx *c, const uint8_t *img, size_t h, size_t w, size
     if (int rc = ensure(c, c->lake_weight, h * w * elem)) return rc;
     HIP_TRY(c, hipMemcpy2DAsync(c->lake_weight.p, w * elem, ls->weight, ls->stride * elem, w * elem, h, hipMemcpyHostToDevice, c->stream));
   }
-  if (int rc = merge_host(c, history_job_host(true, img, h, w, stride, seeds_rc, n_seeds, opt))) return rc;
+  if (int rc = merge_host(c, LevelJob::from_host(true, img, h, w, stride, seeds_rc, n_seeds, opt).with_history())) return rc;
   const uint32_t *seeds = (const uint32_t *)c->seeds.p;      // stage_inputs: narrowed, shifted where the options say so
   ws_tree_node *d_tree = (ws_tree_node *)c->tree_out.p;
   if (int rc = build_tree(c, (const uint32_t *)c->keys.p, (const uint32_t *)c->labels.p, seeds, n_seeds, opt, ph, pw, d_tree)) return rc;
@@ -832,7 +623,7 @@ int merge_tree_arrival_body(ws_ctx *c, const uint32_t *d_keys, const uint32_t *d
     return WS_OK;
   }
   if (int rc = reserve_tree_arrival(c, n_seeds, ls != nullptr)) return rc;
-  if (int rc = merge_host(c, history_job_arrival(d_keys, d_seg, h, w, n_seeds, &plain))) return rc;
+  if (int rc = merge_host(c, LevelJob::from_arrival(true, d_keys, d_seg, h, w, n_seeds, &plain).with_history())) return rc;
   const uint32_t *seeds = (const uint32_t *)c->tree_seed_px.p;
   {
     Span sp(c, KC_OTHER);
@@ -847,250 +638,6 @@ int merge_tree_arrival_body(ws_ctx *c, const uint32_t *d_keys, const uint32_t *d
   return WS_OK;
 }
 
-// ---- transform_history of a cube of slices (ws_transform_history_batch(_device)) ---------------------------------------------------
-
-// The transform of slices [k_first, k_first + g) of a batch, left on the context for rendering: a stack (labels restart at 1 in every
-// slice; colour c of slice k_first + k is c + base[k] in the merge forest) or one slice of the loop (g == 1, base null)
-struct HistoryGroup {
-  size_t k_first, g;
-  const uint32_t *keys, *labels, *base;
-};
-
-// slices [ka, kb) of the group (plane pixels each), tab's levels, into out: slice ka + r's plane of slot j at out + (r * per_slice + j) * plane_stride
-int render_group(ws_ctx *c, bool merging, const HistoryGroup &grp, size_t plane, size_t ka, size_t kb, const HistoryTable &tab, uint32_t *out,
-                 size_t per_slice, size_t plane_stride) {
-  if (!grp.base) return render_levels(c, merging, tab, out, plane_stride, plane);
-  const HistoryStack st{grp.base + ka, (uint32_t)plane, (uint32_t)per_slice};
-  HIP_TRY(c, render_history_stack(c->stream, merging, grp.keys + ka * plane, grp.labels + ka * plane, (const uint32_t *)c->uf_death.p,
-                                  (const uint32_t *)c->uf_hook.p, tab, out, plane_stride, (kb - ka) * plane, st));
-  return WS_OK;
-}
-
-// The transforms of a batch for transform_history, each handed to emit(HistoryGroup) while its planes can be rendered.  Slices
-// that stack run per group of slices as one flood (flood_stack) and, merging, ONE run of the stamping per-level driver over the
-// stack's numbering of colours (merge_host, arrival form, history: no pair crosses a slice border, so no lake either); anything
-// else -- and a stack that fails or mispredicts, which the loop repeats and whose failing slice it names -- as the single-field
-// transform of ws_transform_history_device slice by slice.  Statistics are summed.
-template <class F>
-int history_batch_run(ws_ctx *c, bool merging, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w, size_t stride, size_t slice_stride,
-                      const uint32_t *d_seeds_rc, const size_t *seed_offsets, const ws_options *opt, size_t *failed_slice, F emit) {
-  size_t ph, pw, per_group = 0;
-  int rc = check_plane(c, h, w, stride, opt, &ph, &pw);
-  if (rc) return rc;
-  HIP_TRY(c, hipSetDevice(c->device));
-  const size_t plane = ph * pw;
-  ws_stats acc{};
-  if (n_slices > 1 && slice_stride == h * stride && d_cube && d_seeds_rc && stackable(c, n_slices, h, w, stride, ph, pw, seed_offsets, opt, &per_group)) {
-    bool stacked = true;
-    std::vector<uint32_t> first;
-    StackBatch batch;
-    batch.d_cube = d_cube; batch.h = h; batch.stride = stride; batch.ph = ph; batch.pw = pw; batch.d_seeds_rc = d_seeds_rc; batch.seed_offsets = seed_offsets; batch.opt = opt;
-    for (size_t k0 = 0; k0 < n_slices && stacked; k0 += per_group) {
-      const size_t g = std::min(per_group, n_slices - k0);
-      const size_t ns = seed_offsets[k0 + g] - seed_offsets[k0];
-      if ((rc = ensure(c, c->stack_labels, g * plane * sizeof(uint32_t)))) return rc;
-      uint32_t *labels = (uint32_t *)c->stack_labels.p;
-      if (!flood_group(c, batch, k0, g, labels, first)) {
-        stacked = false;
-        break;
-      }
-      if ((rc = stats_end(c))) return rc;
-      stats_add(acc, c->stats);
-      const uint32_t *d_base = stacked_first(c, ns);
-      if (merging) {
-        LevelJob job = stack_job(c, true, g, ph, pw, ns, opt, labels, d_base);
-        job.history = true;
-        if ((rc = merge_host(c, job))) return rc;
-        stats_add(acc, c->stats);
-      }
-      if ((rc = emit(HistoryGroup{k0, g, (const uint32_t *)c->keys.p, labels, d_base}))) return rc;
-    }
-    if (stacked) {
-      c->stats = acc;
-      return WS_OK;
-    }
-    acc = ws_stats{};
-  }
-  for (size_t k = 0; k < n_slices; ++k) {
-    const size_t ns = seed_offsets[k + 1] - seed_offsets[k];
-    rc = merge_host(c, history_job_device(merging, d_cube + k * slice_stride, h, w, stride, ns ? d_seeds_rc + 2 * seed_offsets[k] : nullptr, ns, opt));
-    if (rc == WS_OK) {
-      stats_add(acc, c->stats);
-      rc = emit(HistoryGroup{k, 1, (const uint32_t *)c->keys.p, (const uint32_t *)c->labels.p, nullptr});
-    }
-    if (rc != WS_OK) { if (failed_slice) *failed_slice = k; return rc; }
-  }
-  c->stats = acc;
-  c->have_keys = false;      // as after a stacked batch: the stamps are no single slice's business
-  return WS_OK;
-}
-
-// what both batch forms check before anything runs: the batch as ws_transform_to_list_batch(_device), the levels as
-// ws_transform_history(_device); *n_px: pixels of a (padded) slice
-int check_history_batch(ws_ctx *c, size_t n_slices, size_t h, size_t w, size_t row_stride, size_t slice_stride, const size_t *seed_offsets,
-                        const ws_options *opt, const uint8_t *levels, size_t n_levels, size_t *n_px) {
-  if (int rc = check_batch(c, n_slices, h, row_stride, slice_stride, seed_offsets, opt)) return rc;
-  return check_history(c, h, w, row_stride, opt, levels, n_levels, n_px);
-}
-
-// The host form's inputs on the device, as the device forms take them: the cube as contiguous slices (c->batch_cube) and the
-// seeds as u32 pairs (c->batch_seeds) -- seeds_rc == NULL: every slice's own find_local_minima (lib.rs:1178-1197), its seeds
-// behind the previous slices'.  offs (n_slices + 1): the seed offsets into c->batch_seeds; n_seeds (nullable): the counts.
-int upload_batch(ws_ctx *c, const uint8_t *cube, size_t n_slices, size_t h, size_t w, size_t row_stride, size_t slice_stride,
-                 const uint64_t *seeds_rc, const size_t *seed_offsets, std::vector<size_t> &offs, size_t *n_seeds, size_t *failed_slice) {
-  int rc;
-  HIP_TRY(c, hipSetDevice(c->device));
-  const size_t hw = h * w;
-  if ((rc = ensure(c, c->batch_cube, std::max<size_t>(n_slices * hw, 1)))) return rc;
-  uint8_t *d_cube = (uint8_t *)c->batch_cube.p;
-  if (hw && row_stride == w && (n_slices == 1 || slice_stride == hw)) {      // a contiguous cube: one copy
-    HIP_TRY(c, hipMemcpyAsync(d_cube, cube, n_slices * hw, hipMemcpyHostToDevice, c->stream));
-  } else if (hw) {
-    for (size_t k = 0; k < n_slices; ++k)
-      HIP_TRY(c, hipMemcpy2DAsync(d_cube + k * hw, w, cube + k * slice_stride, row_stride, w, h, hipMemcpyHostToDevice, c->stream));
-  }
-  offs.assign(n_slices + 1, 0);
-  if (seeds_rc) {
-    // the u64 pairs cross whole and are narrowed on the device, as stage_inputs does (k_narrow_seeds: the host loop it replaced
-    // took 5 ms for 7.3 M seeds); a coordinate past u32 is out of bounds either way: its pair becomes ~0 and stays so
-    const size_t s0 = seed_offsets[0], total = seed_offsets[n_slices] - s0;
-    if ((rc = ensure(c, c->batch_seeds, std::max<size_t>(total, 1) * 2 * sizeof(uint32_t)))) return rc;
-    if (total) {
-      if ((rc = ensure(c, c->seeds64, total * 2 * sizeof(uint64_t)))) return rc;
-      HIP_TRY(c, hipMemcpyAsync(c->seeds64.p, seeds_rc + 2 * s0, total * 2 * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-      HIP_TRY(c, narrow_seeds(c->stream, (const uint64_t *)c->seeds64.p, total, 0xFFFFFFFFull, 0xFFFFFFFFull, (uint32_t *)c->batch_seeds.p));
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (size_t k = 0; k <= n_slices; ++k) offs[k] = seed_offsets[k] - s0;
-  } else {
-    const size_t bound = h >= 3 && w >= 3 ? ((h - 1) / 2 + 1) * ((w - 1) / 2 + 1) : 0;
-    if ((rc = ensure(c, c->batch_seeds, std::max<size_t>(n_slices * bound, 1) * 2 * sizeof(uint32_t)))) return rc;
-    for (size_t k = 0; k < n_slices; ++k) {
-      size_t found = 0;
-      if (bound && (rc = ws_find_local_minima_device(c, d_cube + k * hw, h, w, w, (uint32_t *)c->batch_seeds.p + 2 * offs[k], bound, &found))) {
-        if (failed_slice) *failed_slice = k;
-        return rc;
-      }
-      offs[k + 1] = offs[k] + found;
-    }
-  }
-  if (n_seeds)
-    for (size_t k = 0; k < n_slices; ++k) n_seeds[k] = offs[k + 1] - offs[k];
-  return WS_OK;
-}
-
-// ---- merge_tree of a cube of slices (ws_merge_tree_batch(_device)) ----------------------------------------
-
-// the records of a stacked group from the transform history_batch_run has just run on this context, into the caller's layout at d_tree
-int build_tree_stack(ws_ctx *c, const HistoryGroup &grp, size_t ns, const ws_options *opt, size_t ph, size_t pw, ws_tree_node *d_tree) {
-  const uint32_t levels = (uint32_t)opt->max_water_level + 1;
-  const size_t plane = ph * pw;
-  const uint32_t *death = (const uint32_t *)c->uf_death.p, *hook = (const uint32_t *)c->uf_hook.p;
-  u64c *ws = (u64c *)c->tree_ws.p, *hist = ws + TREE_WS_WORDS;      // (behind the fold's counters: arrivals per (slice, level))
-  TreeRec *forest = (TreeRec *)c->tree_forest.p;
-  const TreeStack st{grp.base, (uint32_t)grp.g, (uint32_t)plane};
-  Span sp(c, KC_OTHER);
-  HIP_TRY(c, hipMemsetAsync(ws, 0, (TREE_WS_WORDS + grp.g * NLEVELS) * sizeof(u64c), c->stream));
-  HIP_TRY(c, slice_arrivals(c->stream, grp.keys, plane, grp.g, hist));
-  HIP_TRY(c, tree_init_stack(c->stream, death, hook, (const uint32_t *)c->seed_stack.p, grp.labels, (int)(grp.g * ph), (int)pw, forest, ns + 1, ws, st));
-  HIP_TRY(c, tree_own_counts_stack(c->stream, grp.keys, grp.labels, death, hook, forest, grp.g * plane, st));
-  HIP_TRY(c, tree_fold(c->stream, forest, ns + 1, levels, ws, (uint32_t *)c->tree_order.p));      // ONE launch per level for the group
-  HIP_TRY(c, tree_unstack(c->stream, forest, ns, grp.base, grp.g, hist, levels, plane, reinterpret_cast<TreeRec *>(d_tree)));
-  return WS_OK;
-}
-
-// ---- merge_tree_stats of a cube of slices (ws_merge_tree_stats_batch(_device)) ------------------------------
-
-// the statistics request of a batch: the weight cube on the device (null: the image cube itself, u8) with its strides in
-// elements, and where the records go (device; the layout of d_tree)
-struct LakeBatchWanted {
-  const void *weight = nullptr;
-  int dtype = 0;
-  size_t stride = 0, slice_stride = 0;
-  ws_lake_stats *d_stats = nullptr;
-};
-
-// what both forms check after check_batch and check_plane, before anything runs: the weights as check_lake_weights for one slice's
-// plane (the 64-bit bound is a slice's: rows and columns restart in every slice), their slice stride as check_batch treats the cube's
-int check_lake_batch(ws_ctx *c, size_t n_slices, size_t h, size_t w, size_t ph, size_t pw, const void *weight, int dtype, size_t weight_stride,
-                     size_t weight_slice_stride) {
-  if (int rc = check_lake_weights(c, w, ph, pw, weight, dtype, weight_stride)) return rc;
-  if (weight && n_slices > 1 && weight_slice_stride < h * weight_stride) return fail(c, WS_ERR_BAD_ARG, "weight_slice_stride < h * weight_row_stride");
-  return WS_OK;
-}
-
-// the weights of slices k .. of the batch: the request's cube, or the image cube read as u8 with its own strides
-LakeWeights lake_weights_from(const LakeBatchWanted &ls, const uint8_t *d_cube, size_t stride, size_t slice_stride, size_t k, size_t h, size_t w,
-                              const ws_options *opt) {
-  const uint32_t off = opt->edge_correction ? 1u : 0u;
-  if (!ls.weight) return LakeWeights{d_cube + k * slice_stride, stride, (uint32_t)h, (uint32_t)w, off, 0, slice_stride};
-  const size_t elem = ls.dtype == WS_U16 ? 2 : 1;
-  return LakeWeights{(const uint8_t *)ls.weight + k * ls.slice_stride * elem, ls.stride, (uint32_t)h, (uint32_t)w, off, ls.dtype == WS_U16, ls.slice_stride};
-}
-
-// the statistics of the forest build_tree_stack has just folded in c->tree_forest (tree_fold's buckets are still in c->tree_ws and
-// c->tree_order), into the caller's layout at d_stats
-int build_lake_stats_stack(ws_ctx *c, const HistoryGroup &grp, size_t ns, const ws_options *opt, size_t ph, size_t pw, const LakeWeights &wt,
-                           ws_lake_stats *d_stats) {
-  const TreeStack st{grp.base, (uint32_t)grp.g, (uint32_t)(ph * pw)};
-  Span sp(c, KC_OTHER);
-  HIP_TRY(c, lake_stats_stack(c->stream, grp.keys, grp.labels, (const uint32_t *)c->uf_death.p, (const uint32_t *)c->uf_hook.p,
-                              (const TreeRec *)c->tree_forest.p, (const uint32_t *)c->seed_stack.p, ns + 1, (uint32_t)opt->max_water_level + 1,
-                              (const u64c *)c->tree_ws.p, (const uint32_t *)c->tree_order.p, wt, st, (int)pw, c->lake_acc.p,
-                              reinterpret_cast<LakeRec *>(d_stats)));
-  return WS_OK;
-}
-
-// The trees of a batch into d_tree (device; slice k's n_k + 1 records from (seed_offsets[k] - seed_offsets[0]) + k on), every group's
-// segmenting labels handed to labels(HistoryGroup) while they are on the context; with ls, every group's statistics into
-// ls->d_stats in the same layout -- a stacked group's from the forest (lake_stats_stack: one fold launch per level for the group),
-// a looped slice's as ws_merge_tree_stats_device's with that slice's weight plane.  Every buffer the tree and statistics kernels
-// need is sized for the largest group BEFORE the first transform (as ensure_tree: nothing moves under the level loop's captured graphs).
-template <class F>
-int tree_batch_run(ws_ctx *c, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w, size_t stride, size_t slice_stride,
-                   const uint32_t *d_seeds_rc, const size_t *seed_offsets, const ws_options *opt, size_t ph, size_t pw, ws_tree_node *d_tree,
-                   size_t *failed_slice, F labels, const LakeBatchWanted *ls = nullptr) {
-  HIP_TRY(c, hipSetDevice(c->device));
-  size_t per_group = 0, most = 0, most_group = 0;
-  for (size_t k = 0; k < n_slices; ++k) most = std::max(most, seed_offsets[k + 1] - seed_offsets[k]);
-  const bool stack = n_slices > 1 && slice_stride == h * stride && d_cube && d_seeds_rc &&
-                     stackable(c, n_slices, h, w, stride, ph, pw, seed_offsets, opt, &per_group);
-  if (!stack) per_group = 0;
-  if (stack) {
-    per_group = std::min(per_group, n_slices);
-    for (size_t k0 = 0; k0 < n_slices; k0 += per_group) most_group = std::max(most_group, seed_offsets[std::min(k0 + per_group, n_slices)] - seed_offsets[k0]);
-  }
-  int rc;
-  if ((rc = ensure(c, c->tree_order, (std::max(most, most_group) + 1) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, c->tree_ws, (TREE_WS_WORDS + per_group * NLEVELS) * sizeof(u64c)))) return rc;
-  if (stack) {
-    if ((rc = ensure(c, c->tree_forest, (most_group + 1) * sizeof(TreeRec)))) return rc;
-    if ((rc = ensure(c, c->seed_stack, (most_group * 2 + per_group + 1) * sizeof(uint32_t)))) return rc;      // (flood_stack's, for its largest group)
-  }
-  // (the accumulator planes: a group's colours, the forest's entry 0 and one record 0 per slice of the group)
-  if (ls && (rc = ensure(c, c->lake_acc, (std::max(most, most_group) + 1 + per_group) * LAKE_ACC_BYTES))) return rc;
-  const size_t s0 = seed_offsets[0];
-  return history_batch_run(c, true, d_cube, n_slices, h, w, stride, slice_stride, d_seeds_rc, seed_offsets, opt, failed_slice,
-                           [&](const HistoryGroup &grp) -> int {
-                             const size_t k = grp.k_first, ns = seed_offsets[k + grp.g] - seed_offsets[k];
-                             ws_tree_node *out = d_tree + (seed_offsets[k] - s0) + k;
-                             ws_lake_stats *out_stats = ls ? ls->d_stats + (seed_offsets[k] - s0) + k : nullptr;
-                             if (grp.base) {
-                               if (int rc_t = build_tree_stack(c, grp, ns, opt, ph, pw, out)) return rc_t;
-                               if (ls)
-                                 if (int rc_t = build_lake_stats_stack(c, grp, ns, opt, ph, pw, lake_weights_from(*ls, d_cube, stride, slice_stride, k, h, w, opt), out_stats))
-                                   return rc_t;
-                             } else {
-                               // the seed pairs as the flood took them: the caller's, or (shifted_seeds) moved into the padded plane
-                               const uint32_t *seeds = seed_shift_of(opt) && ns ? (const uint32_t *)c->seeds.p : d_seeds_rc + 2 * seed_offsets[k];
-                               if (int rc_t = build_tree(c, grp.keys, grp.labels, seeds, ns, opt, ph, pw, out)) return rc_t;
-                               if (ls)
-                                 if (int rc_t = build_lake_stats(c, grp.keys, grp.labels, seeds, ns, opt, ph, pw, out, lake_weights_from(*ls, d_cube, stride, slice_stride, k, h, w, opt), out_stats))
-                                   return rc_t;
-                             }
-                             return labels(grp);
-                           });
-}
 
 }  // namespace
 
@@ -1114,7 +661,7 @@ int ws_transform_history_device(ws_ctx *c, int merging, const uint8_t *d_img, si
   if (plane_stride < n) return fail(c, WS_ERR_BAD_ARG, "plane_stride is shorter than the plane");
   if (n_levels == 0) return WS_OK;
   if (!d_out && n) return fail(c, WS_ERR_BAD_ARG, "null pointer");
-  if (int rc = merge_host(c, history_job_device(merging != 0, d_img, h, w, stride, d_seeds_rc, n_seeds, opt))) return rc;
+  if (int rc = merge_host(c, LevelJob::from_device(merging != 0, d_img, h, w, stride, d_seeds_rc, n_seeds, opt).with_history())) return rc;
   return render_levels(c, merging != 0, history_table(levels, 0, n_levels), d_out, plane_stride, n);
 }
 
@@ -1127,7 +674,7 @@ int ws_transform_history(ws_ctx *c, int merging, const uint8_t *img, size_t h, s
   if (int rc = check_history(c, h, w, stride, opt, levels, n_levels, &n)) return rc;
   if (n_levels == 0) return WS_OK;
   if (!out && n) return fail(c, WS_ERR_BAD_ARG, "null pointer");
-  if (int rc = merge_host(c, history_job_host(merging != 0, img, h, w, stride, seeds_rc, n_seeds, opt))) return rc;
+  if (int rc = merge_host(c, LevelJob::from_host(merging != 0, img, h, w, stride, seeds_rc, n_seeds, opt).with_history())) return rc;
   if (n == 0) return WS_OK;
   // chunks of levels rendered into bounded scratch; a chunk's planes are contiguous there and in `out`, so a chunk of 2^21 words
   // and more crosses the bus in ONE labels_to_host_u64 as u32, widened by the host threads while its next pieces are in flight.
@@ -1289,9 +836,7 @@ int ws_merge_device_end(ws_ctx *c) {
 int ws_merge_with_hook(ws_ctx *c, const uint8_t *img, size_t h, size_t w, size_t stride, const uint64_t *seeds_rc,
                        size_t n_seeds, const ws_options *opt, ws_level_cb cb, void *user, uint64_t *out_labels) {
   if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
-  LevelJob job;
-  job.merging = true; job.h = h; job.w = w; job.stride = stride; job.n_seeds = n_seeds; job.opt = opt;
-  job.img = img; job.seeds_rc = seeds_rc;
+  LevelJob job = LevelJob::from_host(true, img, h, w, stride, seeds_rc, n_seeds, opt);
   job.cb = cb; job.user = user; job.out_labels = out_labels;
   return merge_host(c, job);
 }
@@ -1302,11 +847,7 @@ int ws_transform_to_list_device(ws_ctx *c, int merging, const uint8_t *d_img, si
   if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
   if (!n_lakes || !offsets || !uncoloured || (!d_lakes && cap) || (!d_img && h * w) || (!d_seeds_rc && n_seeds))
     return fail(c, WS_ERR_BAD_ARG, "null pointer");
-  LevelJob job;
-  job.merging = merging != 0; job.h = h; job.w = w; job.stride = stride; job.n_seeds = n_seeds; job.opt = opt;
-  job.source = LevelSource::DEVICE; job.d_img = d_img; job.d_seeds_rc = d_seeds_rc;
-  job.d_lakes = d_lakes; job.cap = cap; job.n_lakes = n_lakes; job.offsets = offsets; job.uncoloured = uncoloured;
-  return merge_host(c, job);
+  return merge_host(c, LevelJob::from_device(merging != 0, d_img, h, w, stride, d_seeds_rc, n_seeds, opt).with_lists(d_lakes, cap, n_lakes, offsets, uncoloured));
 }
 
 int ws_lists_from_arrival_device(ws_ctx *c, int merging, const uint32_t *d_keys, const uint32_t *d_seg_labels, size_t h, size_t w,
@@ -1324,11 +865,7 @@ int ws_lists_from_arrival_device(ws_ctx *c, int merging, const uint32_t *d_keys,
     offsets[(size_t)opt->max_water_level + 1] = 0;
     return WS_OK;
   }
-  LevelJob job;
-  job.merging = merging != 0; job.h = h; job.w = w; job.stride = w; job.n_seeds = n_seeds; job.opt = opt;
-  job.source = LevelSource::ARRIVAL; job.d_keys = d_keys; job.d_seg = d_seg_labels;
-  job.d_lakes = d_lakes; job.cap = cap; job.n_lakes = n_lakes; job.offsets = offsets; job.uncoloured = uncoloured;
-  return merge_host(c, job);
+  return merge_host(c, LevelJob::from_arrival(merging != 0, d_keys, d_seg_labels, h, w, n_seeds, opt).with_lists(d_lakes, cap, n_lakes, offsets, uncoloured));
 }
 
 int ws_transform_to_list(ws_ctx *c, int merging, const uint8_t *img, size_t h, size_t w, size_t stride,
@@ -1336,311 +873,7 @@ int ws_transform_to_list(ws_ctx *c, int merging, const uint8_t *img, size_t h, s
                          size_t *n_lakes, uint64_t *offsets, uint64_t *uncoloured) {
   if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
   if (!n_lakes || !offsets || !uncoloured || (!lakes && cap)) return fail(c, WS_ERR_BAD_ARG, "null output pointer");
-  LevelJob job;
-  job.merging = merging != 0; job.h = h; job.w = w; job.stride = stride; job.n_seeds = n_seeds; job.opt = opt;
-  job.img = img; job.seeds_rc = seeds_rc;
-  job.lakes = lakes; job.cap = cap; job.n_lakes = n_lakes; job.offsets = offsets; job.uncoloured = uncoloured;
-  return merge_host(c, job);
-}
-
-int ws_transform_to_list_batch_device(ws_ctx *c, int merging, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w,
-                                      size_t row_stride, size_t slice_stride, const uint32_t *d_seeds_rc, const size_t *seed_offsets,
-                                      const ws_options *opt, ws_lake *d_lakes, size_t cap, size_t *n_lakes, uint64_t *offsets,
-                                      uint64_t *uncoloured, size_t *failed_slice) {
-  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
-  if (!c) return WS_ERR_BAD_ARG;
-  if (failed_slice) *failed_slice = 0;
-  if (!n_lakes || !offsets || !uncoloured || (!d_lakes && cap)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
-  if (int rc = check_batch(c, n_slices, h, row_stride, slice_stride, seed_offsets, opt)) return rc;
-  if (n_slices && ((!d_cube && h * w) || (!d_seeds_rc && seed_offsets[n_slices] > seed_offsets[0]))) return fail(c, WS_ERR_BAD_ARG, "null pointer");
-  const size_t levels = (size_t)opt->max_water_level + 1;
-  if (n_slices > 1 && slice_stride == h * row_stride && d_cube && d_seeds_rc) {
-    bool done = false;
-    const int rc = lists_batch_stacked(c, merging != 0, d_cube, n_slices, h, w, row_stride, d_seeds_rc, seed_offsets, opt, d_lakes, cap,
-                                       n_lakes, offsets, uncoloured, &done);
-    if (done || (rc != WS_OK && rc != WS_ERR_CAPACITY)) return rc;
-  }
-  // the loop: one ws_transform_to_list_device per slice, its records behind the previous slices'
-  std::vector<uint64_t> off(levels + 1);
-  ws_stats acc{};
-  size_t need = 0;
-  for (size_t k = 0; k < n_slices; ++k) {
-    const size_t ns = seed_offsets[k + 1] - seed_offsets[k];
-    const bool room = need <= cap;
-    size_t got = 0;
-    const int rc = ws_transform_to_list_device(c, merging, d_cube + k * slice_stride, h, w, row_stride, ns ? d_seeds_rc + 2 * seed_offsets[k] : nullptr,
-                                               ns, opt, room ? d_lakes + need : nullptr, room ? cap - need : 0, &got, off.data(),
-                                               uncoloured + k * levels);
-    if (rc != WS_OK && rc != WS_ERR_CAPACITY) { if (failed_slice) *failed_slice = k; return rc; }
-    stats_add(acc, c->stats);
-    for (size_t l = 0; l < levels; ++l) offsets[k * levels + l] = need + off[l];
-    need += got;
-  }
-  offsets[n_slices * levels] = need;
-  *n_lakes = need;
-  c->stats = acc;
-  c->have_keys = false;      // as after a stacked batch: the stamps are no single slice's business
-  if (need > cap) return fail(c, WS_ERR_CAPACITY, "lake buffer too small");
-  c->err.clear();
-  return WS_OK;
-}
-
-int ws_transform_to_list_batch(ws_ctx *c, int merging, const uint8_t *cube, size_t n_slices, size_t h, size_t w, size_t row_stride,
-                               size_t slice_stride, const uint64_t *seeds_rc, const size_t *seed_offsets, const ws_options *opt,
-                               ws_lake *lakes, size_t cap, size_t *n_lakes, uint64_t *offsets, uint64_t *uncoloured, size_t *n_seeds,
-                               size_t *failed_slice) {
-  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
-  if (!c) return WS_ERR_BAD_ARG;
-  if (failed_slice) *failed_slice = 0;
-  if (!n_lakes || !offsets || !uncoloured || (!lakes && cap) || (!cube && h * w && n_slices)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
-  if (int rc = check_batch(c, seeds_rc ? n_slices : 0, h, row_stride, slice_stride, seed_offsets, opt)) return rc;
-  size_t ph, pw;
-  int rc = check_plane(c, h, w, row_stride, opt, &ph, &pw);
-  if (rc) return rc;
-  const size_t hw = h * w, plane = ph * pw;
-  // the cube as contiguous slices, the seeds as u32 pairs (the device form's inputs), then the records back as ws_transform_to_list's are
-  std::vector<size_t> offs;
-  if ((rc = upload_batch(c, cube, n_slices, h, w, row_stride, slice_stride, seeds_rc, seed_offsets, offs, n_seeds, failed_slice))) return rc;
-  uint8_t *d_cube = (uint8_t *)c->batch_cube.p;
-  if ((rc = ensure(c, c->lakes, std::max<size_t>(cap, 1) * sizeof(ws_lake)))) return rc;
-  if ((rc = ensure(c, c->out64, std::max<size_t>(plane, 1) * sizeof(uint64_t)))) return rc;      // (the narrowed records' staging)
-  rc = ws_transform_to_list_batch_device(c, merging, d_cube, n_slices, h, w, w, hw, (const uint32_t *)c->batch_seeds.p, offs.data(), opt,
-                                         (ws_lake *)c->lakes.p, cap, n_lakes, offsets, uncoloured, failed_slice);
-  if (rc) return rc;
-  if ((rc = records_to_host(c, (const ws_lake *)c->lakes.p, lakes, 0, *n_lakes, std::max<size_t>(plane, 1), c->stream))) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return WS_OK;
-}
-
-int ws_merge_batch_device(ws_ctx *c, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w, size_t row_stride, size_t slice_stride,
-                          const uint32_t *d_seeds_rc, const size_t *seed_offsets, const ws_options *opt, uint32_t *d_labels,
-                          size_t *failed_slice) {
-  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
-  if (!c) return WS_ERR_BAD_ARG;
-  if (failed_slice) *failed_slice = 0;
-  if (int rc = check_batch(c, n_slices, h, row_stride, slice_stride, seed_offsets, opt)) return rc;
-  const size_t e = opt->edge_correction ? 2 : 0, plane = (h + e) * (w + e);
-  if (n_slices > 1 && slice_stride == h * row_stride && d_cube && d_seeds_rc && d_labels) {
-    bool done = false;
-    const int rc = merge_batch_stacked(c, d_cube, n_slices, h, w, row_stride, d_seeds_rc, seed_offsets, opt, d_labels, &done);
-    if (rc != WS_OK) return rc;
-    if (done) return WS_OK;
-  }
-  ws_stats acc{};
-  for (size_t k = 0; k < n_slices; ++k) {
-    const size_t ns = seed_offsets[k + 1] - seed_offsets[k];
-    const int rc = ws_merge_device(c, d_cube + k * slice_stride, h, w, row_stride, ns ? d_seeds_rc + 2 * seed_offsets[k] : nullptr, ns, opt,
-                                   d_labels + k * plane);
-    if (rc != WS_OK) { if (failed_slice) *failed_slice = k; return rc; }
-    stats_add(acc, c->stats);
-  }
-  c->stats = acc;
-  c->have_keys = false;
-  return WS_OK;
-}
-
-int ws_transform_history_batch_device(ws_ctx *c, int merging, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w, size_t row_stride,
-                                      size_t slice_stride, const uint32_t *d_seeds_rc, const size_t *seed_offsets, const ws_options *opt,
-                                      const uint8_t *levels, size_t n_levels, uint32_t *d_out, size_t plane_stride, size_t *failed_slice) {
-  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
-  if (!c) return WS_ERR_BAD_ARG;
-  if (failed_slice) *failed_slice = 0;
-  size_t n = 0;
-  if (int rc = check_history_batch(c, n_slices, h, w, row_stride, slice_stride, seed_offsets, opt, levels, n_levels, &n)) return rc;
-  if (plane_stride < n) return fail(c, WS_ERR_BAD_ARG, "plane_stride is shorter than the plane");
-  if (n_levels == 0 || n_slices == 0) return WS_OK;
-  if ((!d_cube && h * w) || (!d_seeds_rc && seed_offsets[n_slices] > seed_offsets[0]) || (!d_out && n)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
-  // every slice's planes at once, straight into the caller's buffer
-  const HistoryTable tab = history_table(levels, 0, n_levels);
-  return history_batch_run(c, merging != 0, d_cube, n_slices, h, w, row_stride, slice_stride, d_seeds_rc, seed_offsets, opt, failed_slice,
-                           [&](const HistoryGroup &grp) {
-                             return render_group(c, merging != 0, grp, n, 0, grp.g, tab, d_out + grp.k_first * n_levels * plane_stride, n_levels,
-                                                 plane_stride);
-                           });
-}
-
-int ws_transform_history_batch(ws_ctx *c, int merging, const uint8_t *cube, size_t n_slices, size_t h, size_t w, size_t row_stride,
-                               size_t slice_stride, const uint64_t *seeds_rc, const size_t *seed_offsets, const ws_options *opt,
-                               const uint8_t *levels, size_t n_levels, uint64_t *out, size_t *n_seeds, size_t *failed_slice) {
-  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
-  if (!c) return WS_ERR_BAD_ARG;
-  if (failed_slice) *failed_slice = 0;
-  size_t n = 0;
-  if (int rc = check_history_batch(c, seeds_rc ? n_slices : 0, h, w, row_stride, slice_stride, seed_offsets, opt, levels, n_levels, &n)) return rc;
-  if (n_levels == 0 || n_slices == 0) return WS_OK;
-  if ((!cube && h * w) || (!out && n)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
-  std::vector<size_t> offs;
-  int rc = upload_batch(c, cube, n_slices, h, w, row_stride, slice_stride, seeds_rc, seed_offsets, offs, n_seeds, failed_slice);
-  if (rc) return rc;
-  if (n == 0)      // (no pixel: the transforms still run, for their errors)
-    return history_batch_run(c, merging != 0, (const uint8_t *)c->batch_cube.p, n_slices, h, w, w, h * w, (const uint32_t *)c->batch_seeds.p,
-                             offs.data(), opt, failed_slice, [](const HistoryGroup &) { return (int)WS_OK; });
-  // The planes are rendered into bounded scratch and cross the bus chunk by chunk.  Where a slice's planes fit, a chunk is a run
-  // of whole slices -- contiguous in `out` as in the scratch, so it crosses in ONE labels_to_host_u64 (u32 words widened by the
-  // host threads); where they do not, a chunk is a run of one slice's levels, as in ws_transform_history.
-  const size_t scratch_words = HISTORY_SCRATCH_BYTES / sizeof(uint32_t), slice_words = n_levels * n;
-  const size_t slices_per = slice_words <= scratch_words ? std::min(n_slices, scratch_words / slice_words) : 0;
-  const size_t levels_per = std::max<size_t>(1, std::min(n_levels, scratch_words / n));
-  if ((rc = ensure(c, c->history_planes, (slices_per ? slices_per * slice_words : levels_per * n) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, c->out64, n * sizeof(uint64_t)))) return rc;      // (the plane-by-plane copy widens there)
-  uint32_t *planes = (uint32_t *)c->history_planes.p;
-  const HistoryTable all = history_table(levels, 0, n_levels);
-  return history_batch_run(c, merging != 0, (const uint8_t *)c->batch_cube.p, n_slices, h, w, w, h * w, (const uint32_t *)c->batch_seeds.p,
-                           offs.data(), opt, failed_slice, [&](const HistoryGroup &grp) -> int {
-                             if (slices_per) {
-                               for (size_t ka = 0; ka < grp.g; ka += slices_per) {
-                                 const size_t kb = std::min(ka + slices_per, grp.g);
-                                 if (int rc_r = render_group(c, merging != 0, grp, n, ka, kb, all, planes, n_levels, n)) return rc_r;
-                                 if (int rc_c = planes_to_host(c, planes, out + (grp.k_first + ka) * slice_words, (kb - ka) * n_levels, n)) return rc_c;
-                               }
-                               return (int)WS_OK;
-                             }
-                             for (size_t k = 0; k < grp.g; ++k)
-                               for (size_t j0 = 0; j0 < n_levels; j0 += levels_per) {
-                                 const size_t j1 = std::min(j0 + levels_per, n_levels);
-                                 if (int rc_r = render_group(c, merging != 0, grp, n, k, k + 1, history_table(levels, j0, j1), planes, 0, n)) return rc_r;
-                                 if (int rc_c = planes_to_host(c, planes, out + (grp.k_first + k) * slice_words + j0 * n, j1 - j0, n)) return rc_c;
-                               }
-                             return (int)WS_OK;
-                           });
-}
-
-int ws_merge_tree_batch_device(ws_ctx *c, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w, size_t row_stride, size_t slice_stride,
-                               const uint32_t *d_seeds_rc, const size_t *seed_offsets, const ws_options *opt, ws_tree_node *d_tree,
-                               uint32_t *d_labels, size_t *failed_slice) {
-  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
-  if (!c) return WS_ERR_BAD_ARG;
-  if (failed_slice) *failed_slice = 0;
-  if (int rc = check_batch(c, n_slices, h, row_stride, slice_stride, seed_offsets, opt)) return rc;
-  size_t ph = 0, pw = 0;
-  if (int rc = check_plane(c, h, w, row_stride, opt, &ph, &pw)) return rc;
-  if (n_slices == 0) return WS_OK;
-  const size_t total = seed_offsets[n_slices] - seed_offsets[0], plane = ph * pw;
-  if (total >= 0xFFFFFFFFull) return fail(c, WS_ERR_TOO_LARGE, "too many seeds");
-  if (!d_tree || (!d_cube && h * w) || (!d_seeds_rc && total)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
-  if (int rc = tree_batch_run(c, d_cube, n_slices, h, w, row_stride, slice_stride, d_seeds_rc, seed_offsets, opt, ph, pw, d_tree, failed_slice,
-                              [&](const HistoryGroup &grp) -> int {
-                                if (d_labels && plane)
-                                  HIP_TRY(c, hipMemcpyAsync(d_labels + grp.k_first * plane, grp.labels, grp.g * plane * sizeof(uint32_t),
-                                                            hipMemcpyDeviceToDevice, c->stream));
-                                return (int)WS_OK;
-                              }))
-    return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return WS_OK;
-}
-
-int ws_merge_tree_batch(ws_ctx *c, const uint8_t *cube, size_t n_slices, size_t h, size_t w, size_t row_stride, size_t slice_stride,
-                        const uint64_t *seeds_rc, const size_t *seed_offsets, const ws_options *opt, ws_tree_node *tree, size_t cap,
-                        size_t *n_records, uint64_t *labels, size_t *n_seeds, size_t *failed_slice) {
-  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
-  if (!c) return WS_ERR_BAD_ARG;
-  if (failed_slice) *failed_slice = 0;
-  if (int rc = check_batch(c, seeds_rc ? n_slices : 0, h, row_stride, slice_stride, seed_offsets, opt)) return rc;
-  size_t ph = 0, pw = 0;
-  int rc = check_plane(c, h, w, row_stride, opt, &ph, &pw);
-  if (rc) return rc;
-  if (n_slices == 0) {
-    if (n_records) *n_records = 0;
-    return WS_OK;
-  }
-  if ((!cube && h * w) || (!tree && cap)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
-  if (seeds_rc && seed_offsets[n_slices] - seed_offsets[0] >= 0xFFFFFFFFull) return fail(c, WS_ERR_TOO_LARGE, "too many seeds");
-  std::vector<size_t> offs;
-  if ((rc = upload_batch(c, cube, n_slices, h, w, row_stride, slice_stride, seeds_rc, seed_offsets, offs, n_seeds, failed_slice))) return rc;
-  const size_t total = offs[n_slices] + n_slices, plane = ph * pw;
-  if (n_records) *n_records = total;
-  if (offs[n_slices] >= 0xFFFFFFFFull) return fail(c, WS_ERR_TOO_LARGE, "too many seeds");
-  if (cap < total) return fail(c, WS_ERR_CAPACITY, "tree buffer too small");      // counted, nothing flooded: the caller learns how many records to make room for
-  if ((rc = ensure(c, c->tree_out, total * sizeof(ws_tree_node)))) return rc;
-  if (labels && (rc = ensure(c, c->out64, std::max<size_t>(plane, 1) * sizeof(uint64_t)))) return rc;      // (the plane-by-plane copy widens there)
-  rc = tree_batch_run(c, (const uint8_t *)c->batch_cube.p, n_slices, h, w, w, h * w, (const uint32_t *)c->batch_seeds.p, offs.data(), opt, ph, pw,
-                      (ws_tree_node *)c->tree_out.p, failed_slice, [&](const HistoryGroup &grp) -> int {
-                        if (!labels || !plane) return (int)WS_OK;
-                        return planes_to_host(c, grp.labels, labels + grp.k_first * plane, grp.g, plane);
-                      });
-  if (rc) return rc;
-  HIP_TRY(c, hipMemcpyAsync(tree, c->tree_out.p, total * sizeof(ws_tree_node), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return WS_OK;
-}
-
-int ws_merge_tree_stats_batch_device(ws_ctx *c, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w, size_t row_stride,
-                                     size_t slice_stride, const uint32_t *d_seeds_rc, const size_t *seed_offsets, const ws_options *opt,
-                                     const void *d_weight, int weight_dtype, size_t weight_row_stride, size_t weight_slice_stride,
-                                     ws_tree_node *d_tree, ws_lake_stats *d_stats, uint32_t *d_labels, size_t *failed_slice) {
-  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
-  if (!c) return WS_ERR_BAD_ARG;
-  if (failed_slice) *failed_slice = 0;
-  if (int rc = check_batch(c, n_slices, h, row_stride, slice_stride, seed_offsets, opt)) return rc;
-  size_t ph = 0, pw = 0;
-  if (int rc = check_plane(c, h, w, row_stride, opt, &ph, &pw)) return rc;
-  if (int rc = check_lake_batch(c, n_slices, h, w, ph, pw, d_weight, weight_dtype, weight_row_stride, weight_slice_stride)) return rc;
-  if (n_slices == 0) return WS_OK;
-  const size_t total = seed_offsets[n_slices] - seed_offsets[0], plane = ph * pw;
-  if (total >= 0xFFFFFFFFull) return fail(c, WS_ERR_TOO_LARGE, "too many seeds");
-  if (!d_tree || !d_stats || (!d_cube && h * w) || (!d_seeds_rc && total)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
-  LakeBatchWanted ls;
-  ls.weight = h * w ? d_weight : nullptr; ls.dtype = weight_dtype; ls.stride = weight_row_stride; ls.slice_stride = weight_slice_stride; ls.d_stats = d_stats;
-  if (int rc = tree_batch_run(c, d_cube, n_slices, h, w, row_stride, slice_stride, d_seeds_rc, seed_offsets, opt, ph, pw, d_tree, failed_slice,
-                              [&](const HistoryGroup &grp) -> int {
-                                if (d_labels && plane)
-                                  HIP_TRY(c, hipMemcpyAsync(d_labels + grp.k_first * plane, grp.labels, grp.g * plane * sizeof(uint32_t),
-                                                            hipMemcpyDeviceToDevice, c->stream));
-                                return (int)WS_OK;
-                              }, &ls))
-    return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return WS_OK;
-}
-
-int ws_merge_tree_stats_batch(ws_ctx *c, const uint8_t *cube, size_t n_slices, size_t h, size_t w, size_t row_stride, size_t slice_stride,
-                              const uint64_t *seeds_rc, const size_t *seed_offsets, const ws_options *opt, const void *weight, int weight_dtype,
-                              size_t weight_row_stride, size_t weight_slice_stride, ws_tree_node *tree, ws_lake_stats *stats, size_t cap,
-                              size_t *n_records, uint64_t *labels, size_t *n_seeds, size_t *failed_slice) {
-  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
-  if (!c) return WS_ERR_BAD_ARG;
-  if (failed_slice) *failed_slice = 0;
-  if (int rc = check_batch(c, seeds_rc ? n_slices : 0, h, row_stride, slice_stride, seed_offsets, opt)) return rc;
-  size_t ph = 0, pw = 0;
-  int rc = check_plane(c, h, w, row_stride, opt, &ph, &pw);
-  if (rc) return rc;
-  if ((rc = check_lake_batch(c, n_slices, h, w, ph, pw, weight, weight_dtype, weight_row_stride, weight_slice_stride))) return rc;
-  if (n_slices == 0) {
-    if (n_records) *n_records = 0;
-    return WS_OK;
-  }
-  if ((!cube && h * w) || ((!tree || !stats) && cap)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
-  if (seeds_rc && seed_offsets[n_slices] - seed_offsets[0] >= 0xFFFFFFFFull) return fail(c, WS_ERR_TOO_LARGE, "too many seeds");
-  std::vector<size_t> offs;
-  if ((rc = upload_batch(c, cube, n_slices, h, w, row_stride, slice_stride, seeds_rc, seed_offsets, offs, n_seeds, failed_slice))) return rc;
-  const size_t total = offs[n_slices] + n_slices, plane = ph * pw;
-  if (n_records) *n_records = total;
-  if (offs[n_slices] >= 0xFFFFFFFFull) return fail(c, WS_ERR_TOO_LARGE, "too many seeds");
-  if (cap < total) return fail(c, WS_ERR_CAPACITY, "record buffers too small");      // counted, nothing flooded
-  if ((rc = ensure(c, c->tree_out, total * sizeof(ws_tree_node)))) return rc;
-  if ((rc = ensure(c, c->lake_out, total * sizeof(ws_lake_stats)))) return rc;
-  if (labels && (rc = ensure(c, c->out64, std::max<size_t>(plane, 1) * sizeof(uint64_t)))) return rc;      // (the plane-by-plane copy widens there)
-  LakeBatchWanted ls;
-  ls.d_stats = (ws_lake_stats *)c->lake_out.p;
-  if (weight && h * w) {      // the weight cube contiguous on the context, before the first transform: nothing moves under the level loop's graphs
-    const size_t elem = weight_dtype == WS_U16 ? 2 : 1;
-    if ((rc = ensure(c, c->lake_weight, n_slices * h * w * elem))) return rc;
-    for (size_t k = 0; k < n_slices; ++k)
-      HIP_TRY(c, hipMemcpy2DAsync((uint8_t *)c->lake_weight.p + k * h * w * elem, w * elem, (const uint8_t *)weight + k * weight_slice_stride * elem,
-                                  weight_row_stride * elem, w * elem, h, hipMemcpyHostToDevice, c->stream));
-    ls.weight = c->lake_weight.p; ls.dtype = weight_dtype; ls.stride = w; ls.slice_stride = h * w;
-  }
-  rc = tree_batch_run(c, (const uint8_t *)c->batch_cube.p, n_slices, h, w, w, h * w, (const uint32_t *)c->batch_seeds.p, offs.data(), opt, ph, pw,
-                      (ws_tree_node *)c->tree_out.p, failed_slice, [&](const HistoryGroup &grp) -> int {
-                        if (!labels || !plane) return (int)WS_OK;
-                        return planes_to_host(c, grp.labels, labels + grp.k_first * plane, grp.g, plane);
-                      }, &ls);
-  if (rc) return rc;
-  HIP_TRY(c, hipMemcpyAsync(tree, c->tree_out.p, total * sizeof(ws_tree_node), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(stats, c->lake_out.p, total * sizeof(ws_lake_stats), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return WS_OK;
+  return merge_host(c, LevelJob::from_host(merging != 0, img, h, w, stride, seeds_rc, n_seeds, opt).with_lists(lakes, cap, n_lakes, offsets, uncoloured));
 }
 
 }  // extern "C"

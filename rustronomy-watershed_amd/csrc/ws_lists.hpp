@@ -1,0 +1,25 @@
+// ws_lists.hpp -- what the cube drivers (ws_batch.hip) call of the per-level driver and the single-field forms (ws_lists.hip).
+#pragma once
+
+#include "ws_ctx.hpp"
+#include "ws_level_plan.hpp"
+
+namespace wsapi {
+
+constexpr size_t HISTORY_SCRATCH_BYTES = (size_t)256 << 20;      // the host forms' u32 planes on the device, at most, per chunk of levels
+
+int merge_host(ws_ctx *c, const LevelJob &job);
+int ensure_uf(ws_ctx *c, size_t n_colours);
+void stats_add(ws_stats &a, const ws_stats &b);
+int records_to_host(ws_ctx *c, const ws_lake *d_rec, ws_lake *lakes, size_t from, size_t end, size_t n, hipStream_t on);
+int planes_to_host(ws_ctx *c, const uint32_t *src, uint64_t *dst, size_t n_planes, size_t n);
+int check_history(ws_ctx *c, size_t h, size_t w, size_t stride, const ws_options *opt, const uint8_t *levels, size_t n_levels, size_t *n_px);
+HistoryTable history_table(const uint8_t *levels, size_t k0, size_t k1);
+int render_levels(ws_ctx *c, bool merging, const HistoryTable &tab, uint32_t *d_out, size_t plane_stride, size_t n);
+int check_lake_weights(ws_ctx *c, size_t w, size_t ph, size_t pw, const void *weight, int dtype, size_t weight_stride);
+int build_tree(ws_ctx *c, const uint32_t *keys, const uint32_t *seg, const uint32_t *d_seeds, size_t n_seeds, const ws_options *opt, size_t ph, size_t pw,
+               ws_tree_node *d_tree);
+int build_lake_stats(ws_ctx *c, const uint32_t *keys, const uint32_t *seg, const uint32_t *d_seeds, size_t n_seeds, const ws_options *opt, size_t ph,
+                     size_t pw, const ws_tree_node *d_tree, const LakeWeights &wt, ws_lake_stats *d_stats);
+
+}  // namespace wsapi

@@ -678,7 +678,7 @@ hipError_t union_stamped_ranged(hipStream_t s, const uint2 *edge_items, const u6
   return hipGetLastError();
 }
 
-// ---- a stack of slices flooded as ONE plane (ws_transform_to_list_batch_device; ws_segment.hip, segment_batch_stacked) --------
+// ---- a stack of slices flooded as ONE plane (ws_transform_to_list_batch_device; ws_batch.hip, run_batch) ---------------------
 
 // level of record i: the l in [lo, hi] with off[l] <= i < off[l + 1] (off: prefix sums of the levels' record counts)
 __device__ __forceinline__ uint32_t level_of_record(const u64c *__restrict__ off, uint32_t lo, uint32_t hi, u64c i) {

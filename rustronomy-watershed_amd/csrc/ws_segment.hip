@@ -1,5 +1,7 @@
 // ws_segment.hip -- the segmenting drivers: the reference's transform_with_hook body (lib.rs:1638-1808) restated as launch
 // sequences on one HIP stream, in the fused form (all levels at once) and the literal sweep form.
+// Cubes: the flood of a stack of slices (flood_stack) and the host-lane form ws_segment_batch are here, the device form
+// ws_segment_batch_device with the other cube drivers in ws_batch.hip.
 #include "ws_ctx.hpp"
 #include "ws_relax_plan.hpp"
 
@@ -622,77 +624,6 @@ int ws_level_snapshot_device(ws_ctx *c, const uint32_t *d_labels, uint8_t water_
   if (!c->have_keys) return fail(c, WS_ERR_UNSUPPORTED, "no arrival stamps: the last call was not a fused-engine ws_segment_device / ws_merge_device");
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, snapshot_level_u32(c->stream, (const uint32_t *)c->keys.p, d_labels, d_out, c->last_h * c->last_w, water_level));
-  return WS_OK;
-}
-
-// Final canonical labels only: one union pass over the whole image, no level buckets.
-// A batch of equal-sized independent slices.  Fast path: the slices are stacked into ONE plane of S * h rows whose slice
-// border rows are walls (they are image-border rows of their slices: never flooded), the seed lists are moved to stacked
-// coordinates and the whole batch runs as a single transform -- one set of launches and one host round trip instead of
-// S of each (8 x 4096^2: 2.0 -> ~1.4 ms; 16 x 1024^2: 2.2 ms -> ~0.3 ms).  Needs strictly increasing seed lists (the
-// side-table form), w % 4 == 0, h * w % 128 == 0 and contiguous slices; anything else, and any error (so that the
-// failing slice can be named), takes the slice-by-slice loop.
-static int segment_batch_stacked(ws_ctx *c, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w, size_t stride,
-                                 const uint32_t *d_seeds_rc, const size_t *seed_offsets, const ws_options *opt,
-                                 uint32_t *d_labels, bool *done) {
-  *done = false;
-  size_t ph, pw;
-  int rc = check_plane(c, h, w, stride, opt, &ph, &pw);
-  if (rc) return rc;
-  static const bool off = tuning_env("WS_NO_BATCH_STACK") != nullptr || tuning_env("WS_NO_SEED_TABLES") != nullptr;      // A/B knobs for tools/
-  const size_t plane = ph * pw;
-  if (off || n_slices < 2 || pick_engine(opt) != WS_ENGINE_FUSED || !c->expect_sorted || (pw & 3) != 0 || plane == 0 ||
-      plane % 128 != 0 || plane >= 0x40000000ull || stride != w || h * w == 0)
-    return WS_OK;
-  if (seed_offsets[n_slices] - seed_offsets[0] >= 0xFFFFFFFFull) return WS_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
-  const size_t max_px = c->batch_max_px;      // <= 2^31 - 1: the two-launch resolve indexes pixels with 31 bits
-  const size_t per_group = std::max<size_t>(1, max_px / plane);
-  std::vector<uint32_t> first;
-  for (size_t k0 = 0; k0 < n_slices; k0 += per_group) {
-    const size_t g = std::min(per_group, n_slices - k0);
-    const size_t s0 = seed_offsets[k0], ns = seed_offsets[k0 + g] - s0;
-    if (ns == 0) return WS_OK;
-    stats_begin(c);
-    first.resize(g + 1);
-    for (size_t k = 0; k <= g; ++k) first[k] = (uint32_t)(seed_offsets[k0 + k] - s0);
-    bool mispredicted = false;
-    rc = flood_stack(c, d_cube + k0 * h * stride, stride, g, ph, pw, d_seeds_rc + 2 * s0, first.data(), opt, d_labels + k0 * plane,
-                     &mispredicted);
-    if (rc != WS_OK || mispredicted) {      // the loop repeats the work and names the slice
-      (void)stats_end(c);                   // closes the span opened above; the loop's transforms keep their own statistics
-      c->err.clear();
-      return WS_OK;
-    }
-    c->have_keys = false;      // the stamps are those of a stack, not of an image
-    if ((rc = stats_end(c))) return rc;
-  }
-  *done = true;
-  return WS_OK;
-}
-
-int ws_segment_batch_device(ws_ctx *c, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w, size_t stride,
-                            size_t slice_stride, const uint32_t *d_seeds_rc, const size_t *seed_offsets,
-                            const ws_options *opt, uint32_t *d_labels, size_t *failed_slice) {
-  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
-  if (!c) return WS_ERR_BAD_ARG;
-  if (failed_slice) *failed_slice = 0;
-  if (n_slices && (!seed_offsets || !opt)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
-  if (n_slices > 1 && slice_stride < h * stride) return fail(c, WS_ERR_BAD_ARG, "slice_stride < h * row_stride");
-  const size_t e = opt && opt->edge_correction ? 2 : 0, plane = (h + e) * (w + e);
-  for (size_t k = 0; k < n_slices; ++k)
-    if (seed_offsets[k + 1] < seed_offsets[k]) return fail(c, WS_ERR_BAD_ARG, "seed_offsets must not decrease");
-  if (n_slices > 1 && slice_stride == h * stride && d_cube && d_seeds_rc && d_labels) {
-    bool done = false;
-    const int rc = segment_batch_stacked(c, d_cube, n_slices, h, w, stride, d_seeds_rc, seed_offsets, opt, d_labels, &done);
-    if (rc != WS_OK) return rc;
-    if (done) return WS_OK;
-  }
-  for (size_t k = 0; k < n_slices; ++k) {
-    const int rc = ws_segment_device(c, d_cube + k * slice_stride, h, w, stride, d_seeds_rc + 2 * seed_offsets[k],
-                                     seed_offsets[k + 1] - seed_offsets[k], opt, d_labels + k * plane);
-    if (rc != WS_OK) { if (failed_slice) *failed_slice = k; return rc; }
-  }
   return WS_OK;
 }
 

@@ -164,21 +164,14 @@ void test_job_check() {
   static const uint32_t words32[4] = {};
   static ws_options opt{};
   // what the entry points build
-  LevelJob host;
-  host.merging = true; host.h = 2; host.w = 2; host.stride = 2; host.n_seeds = 1; host.opt = &opt;
-  host.img = px; host.seeds_rc = seeds64;
-  LevelJob dev;
-  dev.h = 2; dev.w = 2; dev.stride = 2; dev.n_seeds = 1; dev.opt = &opt;
-  dev.source = LevelSource::DEVICE; dev.d_img = px; dev.d_seeds_rc = words32;
-  LevelJob arr;
-  arr.h = 2; arr.w = 2; arr.stride = 2; arr.n_seeds = 1; arr.opt = &opt;
-  arr.source = LevelSource::ARRIVAL; arr.d_keys = words32; arr.d_seg = words32;
-  const auto with_lists = [](LevelJob j) {
-    (j.device_records() ? j.d_lakes : j.lakes) = lake_recs;
-    j.cap = 1; j.n_lakes = &n_lakes_word; j.offsets = words; j.uncoloured = words + 2;
-    return j;
-  };
-  const auto with_history = [](LevelJob j) { j.history = true; return j; };
+  const LevelJob host = LevelJob::from_host(true, px, 2, 2, 2, seeds64, 1, &opt);
+  const LevelJob dev = LevelJob::from_device(false, px, 2, 2, 2, words32, 1, &opt);
+  const LevelJob arr = LevelJob::from_arrival(false, words32, words32, 2, 2, 1, &opt);
+  CHECK(host.source == LevelSource::HOST && dev.source == LevelSource::DEVICE && arr.source == LevelSource::ARRIVAL && arr.stride == 2, "the named sources");
+  const auto with_lists = [](const LevelJob &j) { return j.with_lists(lake_recs, 1, &n_lakes_word, words, words + 2); };
+  const auto with_history = [](const LevelJob &j) { return j.with_history(); };
+  CHECK(with_lists(host).lakes == lake_recs && !with_lists(host).d_lakes && with_lists(dev).d_lakes == lake_recs && !with_lists(dev).lakes,
+        "records on the source's side of the bus");
   LevelJob hooked = host;
   hooked.cb = a_hook; hooked.out_labels = words;
   LevelJob stack = arr;

@@ -8,7 +8,7 @@ against the oracle (ol.segment; ol.merge_arrival for ws_merge_device).
                    tile row only two rows high
   61 x 67          the 4-byte path: unchanged references
   3 x 50 x 132     a stack of slices through ws_segment_batch_device.  50 * 132 is no
-                   multiple of 128, so these slices run one by one (segment_batch_stacked, csrc/ws_segment.hip); they stay,
+                   multiple of 128, so these slices run one by one (stackable, csrc/ws_batch.hip); they stay,
                    and ...
   3 x 96 x 132     ... is the stack that does run as ONE plane (96 * 132 = 99 * 128): tile rows straddle slice borders and
                    the top halo row of the tile row at 192 belongs to another slice (no tile row of 50-row slices starts on

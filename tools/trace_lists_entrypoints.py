@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Calls every entry point of csrc/ws_lists.hip three times in a row (plain launches, capture, replay) on one small case -- a
-48 x 64 random field and a stack of 3 slices of 32 x 64, edge correction off and on -- for a run under `rocprofv3 --kernel-trace`;
-and compares two such traces launch by launch.
+"""Calls every entry point of csrc/ws_lists.hip and csrc/ws_batch.hip three times in a row (plain launches, capture, replay) on one
+small case -- a 48 x 64 random field and a stack of 3 slices of 32 x 64, edge correction off and on; the cube entry points also in
+two groups of slices and with the middle slice's seed list shuffled -- for a run under `rocprofv3 --kernel-trace`; and compares
+two such traces launch by launch.
 
   rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 tools/trace_lists_entrypoints.py      (WS_HIP_LIB: another build)
   tools/trace_lists_entrypoints.py --list TRACE.csv         kernel name, grid and block of every launch, in dispatch order
@@ -93,6 +94,22 @@ def drive():
                 eng.merge_begin(img, seeds, out, edge=edge)
                 eng.merge_end()
 
+            def batch_calls(bs, hl):      # every cube entry point, device seeds bs / host lists hl
+                return [
+                    ("ws_transform_to_list_batch_device seg", lambda: eng.transform_to_list_batch(cube, bs, offs, merging=False, edge=edge, lakes=lakes)),
+                    ("ws_transform_to_list_batch_device mer", lambda: eng.transform_to_list_batch(cube, bs, offs, merging=True, edge=edge, lakes=lakes)),
+                    ("ws_transform_to_list_batch", lambda: mer.transform_to_list_cube(hcube, hl)),
+                    ("ws_merge_batch_device", lambda: eng.merge_batch(cube, bs, offs, edge=edge, out=bout)),
+                    ("ws_transform_history_batch_device seg", lambda: eng.transform_history_batch(cube, bs, offs, merging=False, edge=edge)),
+                    ("ws_transform_history_batch_device mer", lambda: eng.transform_history_batch(cube, bs, offs, merging=True, edge=edge)),
+                    ("ws_transform_history_batch", lambda: mer.transform_history_cube(hcube, hl, levels=[0, 100, 254])),
+                    ("ws_merge_tree_batch_device", lambda: eng.merge_tree_batch(cube, bs, offs, edge=edge, want_labels=True)),
+                    ("ws_merge_tree_batch", lambda: mer.merge_tree_cube(hcube, hl, want_labels=True)),
+                    ("ws_merge_tree_stats_batch_device", lambda: eng.merge_tree_stats_batch(cube, bs, offs, edge=edge, want_labels=True)),
+                    ("ws_merge_tree_stats_batch", lambda: mer.merge_tree_stats_cube(hcube, hl, want_labels=True)),
+                    ("ws_segment_batch_device", lambda: eng.segment_batch(cube, bs, offs, edge=edge, out=bout)),
+                ]
+
             calls = [
                 ("ws_transform_history_device seg", lambda: eng.transform_history(img, seeds, merging=False, edge=edge)),
                 ("ws_transform_history_device mer", lambda: eng.transform_history(img, seeds, merging=True, edge=edge)),
@@ -112,31 +129,27 @@ def drive():
                 ("ws_lists_from_arrival_device mer", lambda: from_arrival(1)),
                 ("ws_transform_to_list seg", lambda: seg.transform_to_list_sparse(himg, hseeds)),
                 ("ws_transform_to_list mer", lambda: mer.transform_to_list_sparse(himg, hseeds)),
-                ("ws_transform_to_list_batch_device seg", lambda: eng.transform_to_list_batch(cube, bseeds, offs, merging=False, edge=edge, lakes=lakes)),
-                ("ws_transform_to_list_batch_device mer", lambda: eng.transform_to_list_batch(cube, bseeds, offs, merging=True, edge=edge, lakes=lakes)),
-                ("ws_transform_to_list_batch", lambda: mer.transform_to_list_cube(hcube, hlists)),
-                ("ws_merge_batch_device", lambda: eng.merge_batch(cube, bseeds, offs, edge=edge, out=bout)),
-                ("ws_transform_history_batch_device seg", lambda: eng.transform_history_batch(cube, bseeds, offs, merging=False, edge=edge)),
-                ("ws_transform_history_batch_device mer", lambda: eng.transform_history_batch(cube, bseeds, offs, merging=True, edge=edge)),
-                ("ws_transform_history_batch", lambda: mer.transform_history_cube(hcube, hlists, levels=[0, 100, 254])),
-                ("ws_merge_tree_batch_device", lambda: eng.merge_tree_batch(cube, bseeds, offs, edge=edge, want_labels=True)),
-                ("ws_merge_tree_batch", lambda: mer.merge_tree_cube(hcube, hlists, want_labels=True)),
-                ("ws_merge_tree_stats_batch_device", lambda: eng.merge_tree_stats_batch(cube, bseeds, offs, edge=edge, want_labels=True)),
-                ("ws_merge_tree_stats_batch", lambda: mer.merge_tree_stats_cube(hcube, hlists, want_labels=True)),
-            ]
+            ] + batch_calls(bseeds, hlists)
             # the live-list form of the merging lists, with the threshold lowered (1: the lowest that can be set)
             live = [c for c in calls if c[0] in ("ws_transform_to_list_device mer", "ws_lists_from_arrival_device mer", "ws_transform_to_list mer",
                                                  "ws_transform_to_list_batch_device mer")]
-            for phase, todo in (("", calls), (" live", live)):
-                eng.ctx.check(L.ws_ctx_set_live_list_min_colours(eng.ctx.handle, 1 if phase else 0))
+            # the cube entry points again in two groups of slices, 2 + 1; and with the middle slice's list shuffled: the stack is
+            # abandoned after a flooded group and the slice-by-slice loop takes the batch
+            shuffled = [l[np.random.default_rng(5).permutation(len(l))] if k == SLICES // 2 else l for k, l in enumerate(hlists)]
+            bshuffled = torch.from_numpy(np.concatenate(shuffled).astype(np.int32)).to(eng.device).contiguous()
+            for phase, todo, live_min, limit in ((" ", calls, 0, 0), (" live", live, 1, 0), (" groups", batch_calls(bseeds, hlists), 0, 2 * SLICE_H * W),
+                                                 (" shuffled", batch_calls(bshuffled, shuffled), 0, 2 * SLICE_H * W)):
+                eng.ctx.check(L.ws_ctx_set_live_list_min_colours(eng.ctx.handle, live_min))
+                eng.ctx.set_batch_pixel_limit(limit)
                 for name, fn in todo:
                     launched = []
                     for _ in range(3):
                         fn()
                         torch.cuda.synchronize()
                         launched.append(eng.stats()["graph_launches"])
-                    print(f"edge {int(edge)} {name}{phase}: graph_launches {launched}", flush=True)
+                    print(f"edge {int(edge)} {name}{phase.rstrip()}: graph_launches {launched}", flush=True)
             eng.ctx.check(L.ws_ctx_set_live_list_min_colours(eng.ctx.handle, 0))
+            eng.ctx.set_batch_pixel_limit(0)
 
 
 if __name__ == "__main__":
