@@ -583,6 +583,46 @@ int ws_merge_tree_stats_cut(ws_ctx *ctx, const uint8_t *img, size_t h, size_t w,
                             const ws_options *opt, const void *weight, int weight_dtype, size_t weight_row_stride, const ws_lake_cut *cuts,
                             size_t n_cuts, ws_tree_node *tree, ws_lake_stats *stats, uint64_t *out, ws_lake *lakes, size_t cap,
                             size_t *n_lakes, uint64_t *offsets, uint64_t *hidden);
+/* ws_tree_cut_stats_device, and the regions its cuts show MEASURED in the same call: the source list of a cut, not only its label
+ * plane.  Everything ws_tree_cut_stats_device takes and does stays as it is -- the cuts, the planes, the lists in increasing colour,
+ * hidden, the capacity rule, the check of the tree before anything walks, the late report of a label above n_seeds, every refusal
+ * with its outputs untouched, d_stats nullable when no cut has a catalogue threshold.  On top:
+ *   d_region_stats[i] (device, 8-byte aligned, cap records next to d_lakes) is the ws_lake_stats of the pixels d_lakes[i] counts: the
+ *   region {p : out_k(p) == d_lakes[i].colour} of the cut k whose range offsets[k] .. offsets[k + 1] holds i.  Field meanings and
+ *   the coordinates are those of ws_merge_tree_stats_device, over the plane as it is passed; peak_pixel is the FIRST pixel in
+ *   row-major order with v == w_max; reserved is 0; the region's pixel count is d_lakes[i].area.
+ *   hidden_stats[k] (HOST, n_cuts records) is the same fold over the pixels with out_k == 0, the identity of the fold (as
+ *   ws_merge_tree_stats_device states it) when there are none.
+ * This is NOT a row of the catalogue d_stats: record c there measures M_c, the lake as it was when it died, while a region depends
+ * on every pixel's arrival level, on show_level and merge_level and on which descendants the cut keeps as regions of their own.
+ * The two coincide only for zero thresholds, show_level = merge_level = L and a node that dies at L + 1 (or never, at L = max).
+ * d_weight: an h x w plane of the shape passed, no offset, weight_row_stride ELEMENTS a row, WS_U8 or WS_U16 (anything else:
+ * WS_ERR_UNSUPPORTED), as ws_merge_tree_from_arrival_device; NULL is WS_ERR_BAD_ARG (there is no image), a short stride too, and a
+ * plane too large for 64-bit moments is WS_ERR_TOO_LARGE by the same division.  d_region_stats and hidden_stats are both nullable:
+ * d_region_stats != NULL needs d_lakes (else WS_ERR_BAD_ARG before anything runs); with BOTH NULL the weight arguments are not
+ * looked at and the call is ws_tree_cut_stats_device, launch for launch.  On WS_ERR_CAPACITY only *n_lakes is meaningful and no
+ * measuring kernel has run: d_region_stats is untouched.  n_seeds == 0 with h * w > 0: the lists are empty and hidden_stats[k] is the
+ * record of the whole plane (the fold still runs); h * w == 0: the identity.  n_cuts == 0 runs nothing and writes nothing.
+ * Integer sums, minima and maxima only: every record is reproducible to the bit.  Stream ordered; returns with the host arrays
+ * complete.  The walk runs a second time for the measuring (no plane is read back, so d_out == NULL works).  Workspace kept by the
+ * context on top of ws_tree_cut_stats_device's, reserved before anything runs: 68 B per accumulator entry, of which there are
+ * min(cap, n_cuts * min(n_seeds, h * w)) + n_cuts with d_region_stats (the records a call can end with, and one per cut) and
+ * n_cuts without, and 72 B per cut. */
+int ws_tree_cut_catalogue_device(ws_ctx *ctx, const ws_tree_node *d_tree, const ws_lake_stats *d_stats, size_t n_seeds,
+                                 const uint32_t *d_keys, const uint32_t *d_seg_labels, size_t h, size_t w, const void *d_weight,
+                                 int weight_dtype, size_t weight_row_stride, const ws_lake_cut *cuts, size_t n_cuts, uint32_t *d_out,
+                                 size_t plane_stride, ws_lake *d_lakes, ws_lake_stats *d_region_stats, size_t cap, size_t *n_lakes,
+                                 uint64_t *offsets, uint64_t *hidden, ws_lake_stats *hidden_stats);
+/* The whole route from and into HOST memory, as ws_merge_tree_stats_cut: image, seeds, options, cuts, tree, stats, out, lakes, cap,
+ * n_lakes, offsets and hidden as there; the weight plane as ws_merge_tree_stats (h x w, unpadded, NULL: the image itself; under
+ * edge correction the ring weighs 0 and rows and columns are those of the padded plane).  region_stats (nullable, needs lakes): cap
+ * records, record i measured over the pixels lakes[i] counts; hidden_stats (nullable): n_cuts records.  Keeps on the device what
+ * ws_merge_tree_stats_cut and ws_tree_cut_catalogue_device keep, and cap records of 72 B. */
+int ws_merge_tree_cut_catalogue(ws_ctx *ctx, const uint8_t *img, size_t h, size_t w, size_t row_stride, const uint64_t *seeds_rc,
+                                size_t n_seeds, const ws_options *opt, const void *weight, int weight_dtype, size_t weight_row_stride,
+                                const ws_lake_cut *cuts, size_t n_cuts, ws_tree_node *tree, ws_lake_stats *stats, uint64_t *out,
+                                ws_lake *lakes, ws_lake_stats *region_stats, size_t cap, size_t *n_lakes, uint64_t *offsets,
+                                uint64_t *hidden, ws_lake_stats *hidden_stats);
 /* transform_history of every slice of a cube for a list of water levels (tests/integration.rs:267,356 take a cube apart slice by
  * slice), everything in HBM.  Slices, seeds, seed_offsets (n_slices + 1 entries, on the HOST), edge correction, duplicate seeds
  * and *failed_slice as ws_transform_to_list_batch_device; levels, n_levels (0: nothing runs, nothing is written), merging and the

@@ -476,6 +476,25 @@ class MergingWatershed : public Watershed<T> {        // lib.rs:1297-1562
     if (weights.rows != input.rows || weights.cols != input.cols) throw std::invalid_argument("weights must have the image's shape");
     return lake_cut_run(input, seeds, cuts, weights.ptr, WS_U16, weights.row_stride);
   }
+  // tree_cut with the regions the cuts show MEASURED in the same call (ws_merge_tree_cut_catalogue): region_stats[i] holds the
+  // moments, the box, the extrema and the first peak pixel of the pixels lakes[i] counts -- the region of that colour in its cut, not
+  // stats[colour], which measures the lake as it was when it died -- and hidden_stats[k] those of the pixels cut k shows as 0.
+  struct CutCatalogue : LakeCut {
+    std::vector<ws_lake_stats> region_stats, hidden_stats;
+  };
+  CutCatalogue tree_cut_catalogue(ArrayView2<std::uint8_t> input, const std::vector<Seed> &seeds, const std::vector<ws_lake_cut> &cuts) const {
+    return cut_catalogue_run(input, seeds, cuts, nullptr, 0, 0);
+  }
+  CutCatalogue tree_cut_catalogue(ArrayView2<std::uint8_t> input, const std::vector<Seed> &seeds, const std::vector<ws_lake_cut> &cuts,
+                                  ArrayView2<std::uint8_t> weights) const {
+    if (weights.rows != input.rows || weights.cols != input.cols) throw std::invalid_argument("weights must have the image's shape");
+    return cut_catalogue_run(input, seeds, cuts, weights.ptr, WS_U8, weights.row_stride);
+  }
+  CutCatalogue tree_cut_catalogue(ArrayView2<std::uint8_t> input, const std::vector<Seed> &seeds, const std::vector<ws_lake_cut> &cuts,
+                                  ArrayView2<std::uint16_t> weights) const {
+    if (weights.rows != input.rows || weights.cols != input.cols) throw std::invalid_argument("weights must have the image's shape");
+    return cut_catalogue_run(input, seeds, cuts, weights.ptr, WS_U16, weights.row_stride);
+  }
   MergeTree merge_tree(ArrayView2<std::uint8_t> input, const std::vector<Seed> &seeds, bool want_labels = false) const {
     const std::size_t e = this->opt_.edge_correction ? 2 : 0;
     MergeTree t{std::vector<ws_tree_node>(seeds.size() + 1), Array2<usize>(want_labels ? input.rows + e : 0, want_labels ? input.cols + e : 0)};
@@ -647,6 +666,33 @@ class MergingWatershed : public Watershed<T> {        // lib.rs:1297-1562
                                               &this->opt_, weights, dtype, weight_stride, cuts.data(), k, t.tree.nodes.data(), t.stats.data(),
                                               flat.data(), t.lakes.data(), cap, &total, t.offsets.data(), t.hidden.data()));
     t.lakes.resize(total);
+    for (std::size_t j = 0; j < k; ++j) {
+      t.planes.emplace_back(prow, pcol);
+      std::copy(flat.begin() + j * prow * pcol, flat.begin() + (j + 1) * prow * pcol, t.planes.back().data.begin());
+    }
+    return t;
+  }
+  CutCatalogue cut_catalogue_run(ArrayView2<std::uint8_t> input, const std::vector<Seed> &seeds, const std::vector<ws_lake_cut> &cuts,
+                                 const void *weights, int dtype, std::size_t weight_stride) const {
+    const std::size_t e = this->opt_.edge_correction ? 2 : 0, prow = input.rows + e, pcol = input.cols + e, k = cuts.size();
+    if (k == 0) throw std::invalid_argument("tree_cut_catalogue needs at least one cut");
+    CutCatalogue t;
+    t.tree = MergeTree{std::vector<ws_tree_node>(seeds.size() + 1), Array2<usize>(0, 0)};
+    t.offsets.assign(k + 1, 0);
+    t.hidden.assign(k, 0);
+    t.stats.resize(seeds.size() + 1);
+    t.hidden_stats.resize(k);
+    auto packed = detail::pack(seeds);
+    std::vector<usize> flat(k * prow * pcol);
+    std::size_t cap = std::max<std::size_t>(std::min(seeds.size(), prow * pcol), 1) * k, total = 0;      // a cut shows no more colours than there are, or pixels
+    t.lakes.resize(cap);
+    t.region_stats.resize(cap);
+    this->ctx_->check(ws_merge_tree_cut_catalogue(this->ctx_->get(), input.ptr, input.rows, input.cols, input.row_stride, packed.data(), seeds.size(),
+                                                  &this->opt_, weights, dtype, weight_stride, cuts.data(), k, t.tree.nodes.data(), t.stats.data(),
+                                                  flat.data(), t.lakes.data(), t.region_stats.data(), cap, &total, t.offsets.data(), t.hidden.data(),
+                                                  t.hidden_stats.data()));
+    t.lakes.resize(total);
+    t.region_stats.resize(total);
     for (std::size_t j = 0; j < k; ++j) {
       t.planes.emplace_back(prow, pcol);
       std::copy(flat.begin() + j * prow * pcol, flat.begin() + (j + 1) * prow * pcol, t.planes.back().data.begin());

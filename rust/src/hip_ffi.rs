@@ -329,6 +329,16 @@ extern "C" {
         n_seeds: usize, opt: *const ws_options, weight: *const c_void, weight_dtype: c_int, weight_row_stride: usize,
         cuts: *const ws_lake_cut, n_cuts: usize, tree: *mut ws_tree_node, stats: *mut ws_lake_stats, out: *mut u64, lakes: *mut ws_lake,
         cap: usize, n_lakes: *mut usize, offsets: *mut u64, hidden: *mut u64) -> c_int;
+    pub fn ws_tree_cut_catalogue_device(ctx: *mut ws_ctx, d_tree: *const ws_tree_node, d_stats: *const ws_lake_stats, n_seeds: usize,
+        d_keys: *const u32, d_seg_labels: *const u32, h: usize, w: usize, d_weight: *const c_void, weight_dtype: c_int,
+        weight_row_stride: usize, cuts: *const ws_lake_cut, n_cuts: usize, d_out: *mut u32, plane_stride: usize, d_lakes: *mut ws_lake,
+        d_region_stats: *mut ws_lake_stats, cap: usize, n_lakes: *mut usize, offsets: *mut u64, hidden: *mut u64,
+        hidden_stats: *mut ws_lake_stats) -> c_int;
+    pub fn ws_merge_tree_cut_catalogue(ctx: *mut ws_ctx, img: *const u8, h: usize, w: usize, row_stride: usize, seeds_rc: *const u64,
+        n_seeds: usize, opt: *const ws_options, weight: *const c_void, weight_dtype: c_int, weight_row_stride: usize,
+        cuts: *const ws_lake_cut, n_cuts: usize, tree: *mut ws_tree_node, stats: *mut ws_lake_stats, out: *mut u64, lakes: *mut ws_lake,
+        region_stats: *mut ws_lake_stats, cap: usize, n_lakes: *mut usize, offsets: *mut u64, hidden: *mut u64,
+        hidden_stats: *mut ws_lake_stats) -> c_int;
     pub fn ws_merge_tree_batch_device(ctx: *mut ws_ctx, d_cube: *const u8, n_slices: usize, h: usize, w: usize, row_stride: usize,
         slice_stride: usize, d_seeds_rc: *const u32, seed_offsets: *const usize, opt: *const ws_options, d_tree: *mut ws_tree_node,
         d_labels: *mut u32, failed_slice: *mut usize) -> c_int;

@@ -602,7 +602,57 @@ pub struct LakeCut {
     pub stats: Vec<hip_ffi::ws_lake_stats>,
 }
 
+/// What `MergingWatershed::tree_cut_catalogue` returns: a `LakeCut`, `region_stats[i]` the record of the pixels `cut.lakes[i]`
+/// counts -- the region of that colour in its cut, which is not the catalogue's record of the colour -- and `hidden_stats[k]` the
+/// record of the pixels cut k shows as 0.
+pub struct CutCatalogue {
+    pub cut: LakeCut,
+    pub region_stats: Vec<hip_ffi::ws_lake_stats>,
+    pub hidden_stats: Vec<hip_ffi::ws_lake_stats>,
+}
+
 impl<T> MergingWatershed<T> {
+    /// Not in the reference: `tree_cut_stats` with the regions the cuts show measured in the same call
+    /// (`ws_merge_tree_cut_catalogue`): the source list of every cut.  `weights` as `tree_cut_stats`.
+    pub fn tree_cut_catalogue(&self, input: nd::ArrayView2<u8>, seeds: &[(usize, usize)], weights: Option<nd::ArrayView2<u16>>,
+                              cuts: &[hip_ffi::ws_lake_cut]) -> CutCatalogue {
+        assert!(!cuts.is_empty() && cuts.len() <= 32, "tree_cut_catalogue takes 1 ..= 32 cuts");
+        let (h, w) = input.dim();
+        let (std_img, stride) = shim::standard(&input);
+        let packed = shim::pack_seeds(seeds);
+        let o = self.opt.ffi();
+        let (ph, pw) = self.opt.plane(h, w);
+        let k = cuts.len();
+        let plane = weights.map(|a| {
+            assert_eq!(a.dim(), (h, w), "weights must have the image's shape");
+            a.as_standard_layout().into_owned()
+        });
+        let (wt_ptr, wt_dtype) = match plane.as_ref() {
+            Some(a) => (a.as_ptr() as *const std::ffi::c_void, hip_ffi::WS_U16),
+            None => (std::ptr::null(), 0),
+        };
+        let mut nodes = vec![hip_ffi::ws_tree_node::default(); seeds.len() + 1];
+        let mut stats = vec![hip_ffi::ws_lake_stats::default(); seeds.len() + 1];
+        let mut flat = vec![0u64; k * ph * pw];
+        let cap = seeds.len().min(ph * pw).max(1) * k;      // a cut shows no more colours than there are, or pixels
+        let mut lakes = vec![hip_ffi::ws_lake { colour: 0, area: 0 }; cap];
+        let mut region_stats = vec![hip_ffi::ws_lake_stats::default(); cap];
+        let mut hidden_stats = vec![hip_ffi::ws_lake_stats::default(); k];
+        let (mut offsets, mut hidden, mut total) = (vec![0u64; k + 1], vec![0u64; k], 0usize);
+        shim::with_ctx(|ctx| unsafe {
+            let rc = hip_ffi::ws_merge_tree_cut_catalogue(ctx, std_img.as_ptr(), h, w, stride, packed.as_ptr(), seeds.len(), &o, wt_ptr, wt_dtype, w,
+                                                          cuts.as_ptr(), k, nodes.as_mut_ptr(), stats.as_mut_ptr(), flat.as_mut_ptr(),
+                                                          lakes.as_mut_ptr(), region_stats.as_mut_ptr(), cap, &mut total, offsets.as_mut_ptr(),
+                                                          hidden.as_mut_ptr(), hidden_stats.as_mut_ptr());
+            shim::check(ctx, rc, "ws_merge_tree_cut_catalogue");
+        });
+        lakes.truncate(total);
+        region_stats.truncate(total);
+        let planes = flat.chunks((ph * pw).max(1)).map(|p| nd::Array2::from_shape_vec((ph, pw), p.iter().map(|&v| v as usize).collect()).expect("plane shape")).collect();
+        CutCatalogue { cut: LakeCut { cut: TreeCut { tree: MergeTree { nodes, labels: None }, planes, lakes, offsets, hidden }, stats }, region_stats,
+                       hidden_stats }
+    }
+
     /// Not in the reference: `tree_cut` with the lake catalogue of the same flood (`ws_merge_tree_stats_cut`): the cuts may also
     /// ask for a summed weight, a peak and a depth (`ws_lake_cut`).  `weights`: a u16 plane of the image's shape (`None`: the image
     /// itself weighs).

@@ -181,6 +181,9 @@ SIGNATURES = {
     "ws_tree_cut_stats_device": (ctypes.c_int, [vp, vp, vp, sz, vp, vp, sz, sz, vp, sz, vp, sz, vp, sz, szp, vp, vp]),
     "ws_merge_tree_stats_cut": (ctypes.c_int, [vp, vp, sz, sz, sz, vp, sz, ctypes.POINTER(Options), vp, ctypes.c_int, sz, vp, sz, vp, vp, vp, vp, sz,
                                                szp, vp, vp]),
+    "ws_tree_cut_catalogue_device": (ctypes.c_int, [vp, vp, vp, sz, vp, vp, sz, sz, vp, ctypes.c_int, sz, vp, sz, vp, sz, vp, vp, sz, szp, vp, vp, vp]),
+    "ws_merge_tree_cut_catalogue": (ctypes.c_int, [vp, vp, sz, sz, sz, vp, sz, ctypes.POINTER(Options), vp, ctypes.c_int, sz, vp, sz, vp, vp, vp, vp, vp,
+                                                   sz, szp, vp, vp, vp]),
     "ws_merge_tree_batch_device": (ctypes.c_int, [vp, vp, sz, sz, sz, sz, sz, vp, szp, ctypes.POINTER(Options), vp, vp, szp]),
     "ws_merge_tree_batch": (ctypes.c_int, [vp, vp, sz, sz, sz, sz, sz, vp, szp, ctypes.POINTER(Options), vp, sz, szp, vp, szp, szp]),
     "ws_merge_tree_stats_batch_device": (ctypes.c_int, [vp, vp, sz, sz, sz, sz, sz, vp, szp, ctypes.POINTER(Options), vp, ctypes.c_int, sz, sz,

@@ -796,6 +796,48 @@ class MergingWatershed(_Transform):
             out.append((lakes[: n.value].copy(), offsets, hidden))
         return out[0] if len(out) == 1 else tuple(out)
 
+    def merge_tree_cut_catalogue(self, input, seeds, cuts, weights=None, want_tree=False, want_stats=False, want_planes=True):
+        """Not in the reference: merge_tree_cut with the regions its cuts show MEASURED -- the source list of every cut from one
+        call (ws_merge_tree_cut_catalogue).  Returns (planes | None, lakes, region_stats, offsets, hidden, hidden_stats[, tree]
+        [, stats]): planes, lakes, offsets and hidden as merge_tree_cut(want_lakes=True); region_stats a structured array
+        (LAKE_STATS_DTYPE) next to lakes, record i the weighted and plain first moments, the box, the extrema and the first peak
+        pixel of the pixels lakes[i] counts -- the region of colour lakes[i, 0] in its cut, which is NOT the catalogue's record of
+        that colour; hidden_stats[k] the same over the pixels cut k shows as 0.  weights as merge_tree_stats (None: the image
+        itself); rows and columns are those of the padded plane.  centroids(region_stats) gives the weighted centroids.
+        want_planes=False: no plane is rendered or downloaded.  want_tree / want_stats: also the MergeTree / the catalogue."""
+        lst = _cut_list(cuts)
+        k = len(lst)
+        if k == 0:
+            raise ValueError("merge_tree_cut_catalogue needs at least one cut")
+        a, stride = _as_image(input)
+        s, ns = _as_seeds(seeds)
+        h, w = a.shape
+        ph, pw = self._shape(a)
+        arr, _ = _as_lake_cuts(lst)
+        wt, dtype, wstride = _as_weights(weights, a.shape)
+        planes = np.empty((k, ph, pw), dtype=np.uint64) if want_planes else None
+        tree = np.empty((ns + 1, 4), dtype=np.uint32) if want_tree else None
+        stats = np.empty(ns + 1, dtype=LAKE_STATS_DTYPE) if want_stats else None
+        offsets = np.zeros(k + 1, dtype=np.uint64)
+        hidden = np.zeros(k, dtype=np.uint64)
+        n = ctypes.c_size_t(0)
+        cap = max(min(ns, ph * pw), 1) * k      # a cut shows no more colours than there are, or pixels
+        lakes = np.empty((cap, 2), dtype=np.uint64)
+        region = np.empty(cap, dtype=LAKE_STATS_DTYPE)
+        hidden_stats = np.empty(k, dtype=LAKE_STATS_DTYPE)
+        ctx = self._ctx()
+        ctx.check(_ffi.lib().ws_merge_tree_cut_catalogue(ctx.handle, a.ctypes.data, h, w, stride, s.ctypes.data, ns, ctypes.byref(self._opt),
+                                                         wt.ctypes.data if wt is not None else None, dtype, wstride, arr, k,
+                                                         tree.ctypes.data if want_tree else None, stats.ctypes.data if want_stats else None,
+                                                         planes.ctypes.data if want_planes else None, lakes.ctypes.data, region.ctypes.data, cap,
+                                                         ctypes.byref(n), offsets.ctypes.data, hidden.ctypes.data, hidden_stats.ctypes.data))
+        out = [planes, lakes[: n.value].copy(), region[: n.value].copy(), offsets, hidden, hidden_stats]
+        if want_tree:
+            out.append(MergeTree(tree[:, 0].copy(), tree[:, 1].copy(), tree[:, 2].copy(), tree[:, 3].copy()))
+        if want_stats:
+            out.append(stats)
+        return tuple(out)
+
     def merge_tree_stats(self, input, seeds, weights=None, want_labels=False):
         """Not in the reference: merge_tree and a catalogue of its lakes from the same flood (ws_merge_tree_stats).  Returns
         (MergeTree, stats): stats is a numpy structured array (LAKE_STATS_DTYPE) of n_seeds + 1 records, record c the weighted

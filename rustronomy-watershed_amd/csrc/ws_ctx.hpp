@@ -69,6 +69,9 @@ struct ws_ctx {
   // and the compaction's block sums, the flag words; ws_merge_tree_cut: its u32 planes and its records before they cross the bus;
   // ws_tree_cut_stats_device: the packed catalogue keys (16 B a colour), only for calls with two or more catalogue tables
   wsapi::DevBuf cut_tables, cut_counts, cut_blocks, cut_flags, cut_planes, cut_lakes, cut_keys;
+  // ws_tree_cut_catalogue_device: the accumulator planes (68 B per list record the call can hold, and per cut) and the cuts' hidden
+  // records before they cross the bus; ws_merge_tree_cut_catalogue: the regions' records (72 B each, cap of them)
+  wsapi::DevBuf cut_acc, cut_hidden, cut_region;
   uint32_t *pinned = nullptr;      // FLAG_WORDS words of pinned host memory: the host's mirror of the flag block
   uint32_t *pinned_dev = nullptr;  // the same words as the device sees them (nullptr: not mapped, copies only)
   hipEvent_t ring_ev[wsk::COUNTER_RING]{};   // flag slot copied to the host

@@ -16,8 +16,15 @@
 // argument above stands.  Only the tables change: k_cut_keys packs what the keep test reads of a 72-byte record into 16 bytes a
 // colour, and the table kernel gathers that next to the tree record; a call with a single such table reads the records themselves
 // (cut_source).  Both entry points share one driver (cut_run).
+//
+// ws_tree_cut_catalogue_device / ws_merge_tree_cut_catalogue (section 4.4.2) measure the regions the cuts show: after the lists are
+// compacted the counters hold every record's position (k_cut_compact<CUT_INDEX>), k_cut_measure walks again and folds every pixel
+// into the accumulator entry of its region's record (the LakePart fold of ws_lake_part.hpp), and k_cut_measure_write turns the
+// entries into ws_lake_stats records next to d_lakes, the cuts' hidden pixels behind them.  The same driver, with a CutMeasure.
 #include "ws_ctx.hpp"
 #include "ws_uf.hpp"
+#include "ws_lake_part.hpp"
+#include "ws_lists.hpp"
 
 #include <type_traits>
 
@@ -161,13 +168,92 @@ __device__ __forceinline__ void cut_count(uint32_t *s_key, uint32_t *s_cnt, uint
   }
 }
 
+// ---- a thread's four pixels: the loads, the guard, the table entry and the walks, as k_render_cut and k_cut_measure share them -----
+// Stamps and colours of the quad at pixels 4 * q .. 4 * q + 3: 16-byte loads where vec_in (keys and labels 16-byte aligned) and the
+// quad is whole, pixel by pixel otherwise, with the same result.
+__device__ __forceinline__ void cut_load(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ labels, size_t n, size_t q, bool vec_in,
+                                         uint32_t (&arr)[4], uint32_t (&col)[4], bool (&in)[4]) {
+  const size_t i0 = 4 * q;
+  if (vec_in && i0 + 3 < n) {
+    const u32x4_m k = reinterpret_cast<const u32x4_m *>(keys)[q], l = reinterpret_cast<const u32x4_m *>(labels)[q];
+    arr[0] = k.x >> 24; arr[1] = k.y >> 24; arr[2] = k.z >> 24; arr[3] = k.w >> 24;
+    col[0] = l.x; col[1] = l.y; col[2] = l.z; col[3] = l.w;
+    in[0] = in[1] = in[2] = in[3] = true;
+  } else {
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      in[p] = i0 + p < n;
+      arr[p] = in[p] ? keys[i0 + p] >> 24 : 0xFFu;
+      col[p] = in[p] ? labels[i0 + p] : 0u;
+    }
+  }
+}
+
+// The walk of one quad through the cuts of a plan: a pixel keeps the node it stands on and that node's parent and death level in
+// registers, so a step of the walk is ONE dependent load; the four walks of a thread run side by side (one after the other they
+// wait for each other's gathers); a cut of the same table as the one before it walks on from where that one stopped (merge levels
+// ascend within a table), and a new table starts from its own entry.
+struct CutWalk {
+  uint32_t arr[4], col[4];
+  bool walks[4];      // coloured: the pixel has a chain to walk
+  uint32_t a[4], up[4], d[4];      // the node, its parent, its death level
+  uint32_t table;
+
+  __device__ __forceinline__ void start(uint32_t n_seeds, uint32_t *flags) {
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      if (col[p] > n_seeds) {      // before it indexes anything
+        atomicOr(&flags[CUT_F_LABEL], 1u);
+        col[p] = 0u;
+      }
+      walks[p] = col[p] != 0u && arr[p] != 0xFFu;      // (0xFF: never coloured, above every show_level)
+      a[p] = up[p] = 0u;
+      d[p] = TREE_ALIVE;
+    }
+    table = 0xFFFFFFFFu;
+  }
+
+  // the lakes v[] the four pixels show under cut e
+  __device__ __forceinline__ void cut(const TreeRec *__restrict__ tree, const uint32_t *__restrict__ tables, size_t n_colours, const CutEntry e,
+                                      uint32_t *flags, uint32_t (&v)[4]) {
+    if (e.table != table) {
+#pragma unroll
+      for (int p = 0; p < 4; ++p)
+        if (walks[p]) a[p] = tables[(size_t)e.table * n_colours + col[p]];
+#pragma unroll
+      for (int p = 0; p < 4; ++p)
+        if (walks[p]) { up[p] = tree[a[p]].parent; d[p] = tree[a[p]].death_level; }
+      table = e.table;
+    }
+    bool shown[4];
+    uint32_t until[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      shown[p] = walks[p] && arr[p] <= (uint32_t)e.show_level;
+      until[p] = max(arr[p], (uint32_t)e.merge_level);
+    }
+    for (uint32_t hops = 0;; ++hops) {      // the four walks side by side
+      bool go[4];
+#pragma unroll
+      for (int p = 0; p < 4; ++p) go[p] = shown[p] && d[p] <= until[p];
+      if (!(go[0] || go[1] || go[2] || go[3])) break;
+      if (hops >= CUT_STEPS) { atomicOr(&flags[CUT_F_STEPS], 1u); break; }
+#pragma unroll
+      for (int p = 0; p < 4; ++p)
+        if (go[p]) a[p] = up[p];      // (k_cut_check: below the node it leaves, so inside the records)
+#pragma unroll
+      for (int p = 0; p < 4; ++p)
+        if (go[p]) { up[p] = tree[a[p]].parent; d[p] = tree[a[p]].death_level; }
+    }
+#pragma unroll
+    for (int p = 0; p < 4; ++p) v[p] = shown[p] ? a[p] : 0u;
+  }
+};
+
 // A workgroup takes `steps` consecutive runs of 1024 pixels, a thread four consecutive pixels of each: their stamps and colours once
-// (16-byte loads where keys and labels are 16-byte aligned), then cut after cut in the plan's order, and every plane gets its four
-// pixels as one 16-byte store where out and plane_stride allow it.  A pixel keeps the node it stands on and that node's parent and
-// death level in registers: a step of the walk is ONE dependent load, the four walks of a thread run side by side (one after the
-// other they wait for each other's gathers), a cut of the same table as the one before it walks on from where that one stopped
-// (merge levels ascend within a table), and a new table starts from its own entry.  The last, short quad of a plane and planes
-// off 16-byte alignment load and store pixel by pixel, with the same result.
+// (cut_load), then cut after cut in the plan's order (CutWalk), and every plane gets its four pixels as one 16-byte store where out
+// and plane_stride allow it.  The last, short quad of a plane and planes off 16-byte alignment load and store pixel by pixel, with
+// the same result.
 // LISTS: the counters of every cut, through the workgroup's table; it is written out when a step leaves it more than half full
 // and at the end.  Every trip count and barrier is the same for all threads of a workgroup.
 template <bool LISTS>
@@ -188,68 +274,14 @@ __global__ __launch_bounds__(256) void k_render_cut(const TreeRec *__restrict__ 
   for (size_t st = 0; st < steps; ++st) {      // workgroup uniform
     const size_t q = ((size_t)blockIdx.x * steps + st) * 256 + threadIdx.x, i0 = 4 * q;
     const bool whole = i0 + 3 < n;
-    uint32_t arr[4], col[4];
+    CutWalk wk;
     bool in[4];
-    if (vec_in && whole) {
-      const u32x4_m k = reinterpret_cast<const u32x4_m *>(keys)[q], l = reinterpret_cast<const u32x4_m *>(labels)[q];
-      arr[0] = k.x >> 24; arr[1] = k.y >> 24; arr[2] = k.z >> 24; arr[3] = k.w >> 24;
-      col[0] = l.x; col[1] = l.y; col[2] = l.z; col[3] = l.w;
-      in[0] = in[1] = in[2] = in[3] = true;
-    } else {
-#pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        in[p] = i0 + p < n;
-        arr[p] = in[p] ? keys[i0 + p] >> 24 : 0xFFu;
-        col[p] = in[p] ? labels[i0 + p] : 0u;
-      }
-    }
-    bool walks[4];      // coloured: the pixel has a chain to walk
-    uint32_t a[4], up[4], d[4];      // the node, its parent, its death level
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      if (col[p] > n_seeds) {      // before it indexes anything
-        atomicOr(&flags[CUT_F_LABEL], 1u);
-        col[p] = 0u;
-      }
-      walks[p] = col[p] != 0u && arr[p] != 0xFFu;      // (0xFF: never coloured, above every show_level)
-      a[p] = up[p] = 0u;
-      d[p] = TREE_ALIVE;
-    }
-    uint32_t table = 0xFFFFFFFFu;
+    cut_load(keys, labels, n, q, vec_in, wk.arr, wk.col, in);
+    wk.start(n_seeds, flags);
     for (uint32_t j = 0; j < plan.n; ++j) {
       const CutEntry e = plan.e[j];
-      if (e.table != table) {
-#pragma unroll
-        for (int p = 0; p < 4; ++p)
-          if (walks[p]) a[p] = tables[(size_t)e.table * n_colours + col[p]];
-#pragma unroll
-        for (int p = 0; p < 4; ++p)
-          if (walks[p]) { up[p] = tree[a[p]].parent; d[p] = tree[a[p]].death_level; }
-        table = e.table;
-      }
-      bool shown[4];
-      uint32_t until[4];
-#pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        shown[p] = walks[p] && arr[p] <= (uint32_t)e.show_level;
-        until[p] = max(arr[p], (uint32_t)e.merge_level);
-      }
-      for (uint32_t hops = 0;; ++hops) {      // the four walks side by side
-        bool go[4];
-#pragma unroll
-        for (int p = 0; p < 4; ++p) go[p] = shown[p] && d[p] <= until[p];
-        if (!(go[0] || go[1] || go[2] || go[3])) break;
-        if (hops >= CUT_STEPS) { atomicOr(&flags[CUT_F_STEPS], 1u); break; }
-#pragma unroll
-        for (int p = 0; p < 4; ++p)
-          if (go[p]) a[p] = up[p];      // (k_cut_check: below the node it leaves, so inside the records)
-#pragma unroll
-        for (int p = 0; p < 4; ++p)
-          if (go[p]) { up[p] = tree[a[p]].parent; d[p] = tree[a[p]].death_level; }
-      }
       uint32_t v[4];
-#pragma unroll
-      for (int p = 0; p < 4; ++p) v[p] = shown[p] ? a[p] : 0u;
+      wk.cut(tree, tables, n_colours, e, flags, v);
       if (out) {
         uint32_t *plane = out + (size_t)e.slot * plane_stride;
         if (vec_out && whole) {
@@ -294,16 +326,20 @@ __global__ __launch_bounds__(256) void k_render_cut(const TreeRec *__restrict__ 
 
 // ---- the lists ----------------------------------------------------------------------------------------------------------------------
 // The counters in colour order are the records in colour order: a workgroup takes CUT_CHUNK colours of one cut (blockIdx.y),
-// counts those with pixels (pass 0: block_n), and, once the host has summed the blocks into bases, writes them behind its base.
+// counts those with pixels (CUT_COUNT: block_n), and, once the host has summed the blocks into bases, writes them behind its base
+// (CUT_WRITE).  CUT_INDEX (ws_tree_cut_catalogue_device) writes them too, where there is a list, and then OVERWRITES counter
+// (k, a) of every colour with pixels with the record's position in the lists, and counter 0 of cut k with total + k: the index the
+// measuring kernel looks a pixel's lake up in.  A thread reads its four counters before it writes them, and nobody else reads them.
 constexpr int CUT_PER_THREAD = 4;
 constexpr int CUT_CHUNK = 256 * CUT_PER_THREAD;
+enum CutCompact { CUT_COUNT = 0, CUT_WRITE = 1, CUT_INDEX = 2 };
 
-template <bool WRITE>
+template <int MODE>
 __global__ __launch_bounds__(256) void k_cut_compact(const uint32_t *__restrict__ counts, size_t n_colours, uint32_t blocks_per_cut, uint32_t *block_n,
-                                                     const u64c *__restrict__ block_base, ws_lake *lakes) {
+                                                     const u64c *__restrict__ block_base, ws_lake *lakes, uint32_t *index, uint32_t total) {
   __shared__ uint32_t s_n[256];
   const uint32_t k = blockIdx.y, t = threadIdx.x;
-  const uint32_t *cnt = counts + (size_t)k * n_colours;
+  const uint32_t *cnt = (MODE == CUT_INDEX ? index : counts) + (size_t)k * n_colours;      // (CUT_INDEX: the counters, read and written through ONE pointer)
   const size_t c0 = (size_t)blockIdx.x * CUT_CHUNK + (size_t)t * CUT_PER_THREAD;
   uint32_t area[CUT_PER_THREAD], mine = 0;
 #pragma unroll
@@ -321,15 +357,121 @@ __global__ __launch_bounds__(256) void k_cut_compact(const uint32_t *__restrict_
     __syncthreads();
   }
   const size_t b = (size_t)k * blocks_per_cut + blockIdx.x;
-  if constexpr (!WRITE) {
+  if constexpr (MODE == CUT_COUNT) {
     if (t == 255) block_n[b] = s_n[255];
     if (t == 0 && blockIdx.x == 0) block_n[(size_t)gridDim.y * blocks_per_cut + k] = cnt[0];      // behind the blocks: the cut's hidden pixels
   } else {
     u64c at = block_base[b] + (s_n[t] - mine);
 #pragma unroll
     for (int j = 0; j < CUT_PER_THREAD; ++j)
-      if (area[j] != 0u) lakes[at++] = ws_lake{(uint64_t)(c0 + j), (uint64_t)area[j]};
+      if (area[j] != 0u) {
+        if (MODE == CUT_WRITE || lakes) lakes[at] = ws_lake{(uint64_t)(c0 + j), (uint64_t)area[j]};
+        if constexpr (MODE == CUT_INDEX) index[(size_t)k * n_colours + c0 + j] = (uint32_t)at;
+        ++at;
+      }
+    if constexpr (MODE == CUT_INDEX)
+      if (c0 == 0) index[(size_t)k * n_colours] = total + k;
   }
+}
+
+// ---- the regions measured (ws_tree_cut_catalogue_device) ---------------------------------------------------
+// The fold of k_lake_own over the REGIONS of every cut: pixel p of cut k goes to accumulator entry index[k * n_colours + out_k(p)]
+// -- the position of the region's record in the lists, total + k for the hidden pixels -- so the accumulators are sized by records
+// (n_rec = total + n_cuts entries of LAKE_ACC_BYTES), not by cuts x colours.  The loads, the guard, the table entry and the walks
+// are k_render_cut's (cut_load, CutWalk): the kernel walks again and reads no plane, so it does not need one.  A pixel's weight,
+// row and column are taken once a step; per cut a lane joins the pixels of its quad that agree, a wave joins the lanes that agree
+// with its first live lane, the rest goes to the workgroup's LAKE_SLOTS-entry table keyed by accumulator entry (lake_add:
+// LAKE_PROBES, then memory itself), and the table is written out when a cut of a step leaves it more than half full and at the
+// end (lake_flush; k_lake_own looks once a step).  index == nullptr (no record wanted: the hidden pixels alone): a hidden pixel of cut k goes to
+// entry k and the others sit out.  n_seeds == 0: every pixel is hidden, no label is looked at.  Every trip count and barrier is the
+// same for all threads of a workgroup.
+template <typename T>
+__global__ __launch_bounds__(256) void k_cut_measure(const TreeRec *__restrict__ tree, uint32_t n_seeds, const uint32_t *__restrict__ tables,
+                                                     const uint32_t *__restrict__ keys, const uint32_t *__restrict__ labels, size_t n, size_t steps,
+                                                     CutPlan plan, const uint32_t *__restrict__ index, LakeWeights wt, uint32_t W, u64c *sum,
+                                                     uint32_t *box, size_t n_rec, uint32_t *flags) {
+  __shared__ u64c s_sum[6 * LAKE_SLOTS];
+  __shared__ uint32_t s_box[5 * LAKE_SLOTS], s_key[LAKE_SLOTS], s_used;
+  for (int j = threadIdx.x; j < LAKE_SLOTS; j += 256) {
+    s_key[j] = LAKE_EMPTY;
+    lake_store(s_sum, s_box, LAKE_SLOTS, j, lake_none());
+  }
+  if (threadIdx.x == 0) s_used = 0;
+  __syncthreads();
+  const size_t n_colours = (size_t)n_seeds + 1;
+  const int lane = threadIdx.x & 63;
+  const bool vec_in = ((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(labels)) & 15u) == 0;
+  uint32_t flushed_at = 0;      // slots taken, over the run, when the table was last written out
+  for (size_t st = 0; st < steps; ++st) {      // workgroup uniform
+    const size_t q = ((size_t)blockIdx.x * steps + st) * 256 + threadIdx.x, i0 = 4 * q;
+    CutWalk wk;
+    bool in[4];
+    cut_load(keys, labels, n, q, vec_in, wk.arr, wk.col, in);
+    if (n_seeds == 0u) wk.col[0] = wk.col[1] = wk.col[2] = wk.col[3] = 0u;
+    wk.start(n_seeds, flags);
+    uint32_t wv[4], yy[4], xx[4];      // the four pixels' weights, rows and columns
+    {
+      uint32_t y = i0 < n ? (uint32_t)i0 / W : 0u, x = i0 < n ? (uint32_t)i0 % W : 0u;      // (n < 2^32)
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        wv[p] = in[p] ? lake_weight<T>(wt, y, x) : 0u;
+        yy[p] = y; xx[p] = x;
+        if (++x == W) { x = 0; ++y; }
+      }
+    }
+    for (uint32_t j = 0; j < plan.n; ++j) {
+      const CutEntry e = plan.e[j];
+      uint32_t v[4];
+      wk.cut(tree, tables, n_colours, e, flags, v);
+      bool live[4];
+#pragma unroll
+      for (int p = 0; p < 4; ++p) live[p] = in[p] && (index != nullptr || v[p] == 0u);
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {      // one part at a time: the first pixel of a lake takes the later ones of its quad (a quad mostly lies in one lake)
+        LakePart part = lake_pixel(wv[p], yy[p], xx[p], (uint32_t)i0 + (uint32_t)p);
+#pragma unroll
+        for (int r = p + 1; r < 4; ++r)
+          if (live[p] && live[r] && v[r] == v[p]) {
+            lake_join(part, lake_pixel(wv[r], yy[r], xx[r], (uint32_t)i0 + (uint32_t)r));
+            live[r] = false;
+          }
+        const unsigned long long todo = __builtin_amdgcn_ballot_w64(live[p]);
+        if (todo == 0) continue;      // wave uniform
+        const uint32_t at = !live[p] ? 0u : index ? index[(size_t)e.slot * n_colours + v[p]] : (uint32_t)e.slot;      // ONE look-up a lake and lane
+        const int leader = (int)__builtin_ctzll(todo);
+        const uint32_t at0 = (uint32_t)__builtin_amdgcn_readlane((int)at, leader);
+        const bool same = live[p] && at == at0;
+        if (__popcll(__builtin_amdgcn_ballot_w64(same)) > 1) {      // wave uniform
+          const LakePart total = lake_wave_total(same ? part : lake_none());
+          if (lane == leader) lake_add(s_key, s_sum, s_box, &s_used, sum, box, n_rec, at0, total);
+          else if (live[p] && !same) lake_add(s_key, s_sum, s_box, &s_used, sum, box, n_rec, at, part);
+        } else if (live[p]) {
+          lake_add(s_key, s_sum, s_box, &s_used, sum, box, n_rec, at, part);
+        }
+      }
+      // after every CUT, not every step: the entries of one cut are of no use to the next (its regions have entries of their own),
+      // so the table fills by the regions of a run times the cuts, and a table that the cuts of one step have filled sends the
+      // next step's newcomers to memory field by field (measured: DESIGN.md section 4.4.2)
+      __syncthreads();
+      const uint32_t used = s_used;      // (nobody inserts between the two barriers: workgroup uniform)
+      const bool full = used - flushed_at > LAKE_SLOTS / 2;
+      if (full || (st + 1 == steps && j + 1 == plan.n)) lake_flush(s_key, s_sum, s_box, sum, box, n_rec);
+      if (full) flushed_at = used;
+      __syncthreads();
+    }
+  }
+}
+
+// The accumulator entries as records: entry i < total is the record of d_lakes[i], entry total + k the hidden pixels of cut k, which
+// go to a buffer of their own that the host reads.  An entry nobody added to is the identity of the fold, and so is its record.
+__global__ __launch_bounds__(256) void k_cut_measure_write(const u64c *__restrict__ sum, const uint32_t *__restrict__ box, size_t n_rec, size_t total,
+                                                           LakeRec *region, LakeRec *hidden) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_rec) return;
+  const LakePart a = lake_load(sum, box, n_rec, i);
+  const LakeRec r{a.w, a.wr, a.wc, a.r, a.c, a.r_min, a.r_max, a.c_min, a.c_max, a.w_min, (uint32_t)(a.peak >> 32), 0xFFFFFFFFu - (uint32_t)a.peak, 0u};
+  if (i < total) region[i] = r;
+  else hidden[i - total] = r;
 }
 
 }  // namespace wsk
@@ -412,7 +554,7 @@ CutSource cut_source(const CutPlan &p) {
   return n == 1 ? CUT_RECORDS : CUT_KEYS;
 }
 
-// the context's workspace of a call: the tables (4 B a colour and cut at most), with lists the counters (the same) and 12 B per
+// the context's workspace of a call without measuring (with: measure_reserve on top): the tables (4 B a colour and cut at most), with lists the counters (the same) and 12 B per
 // CUT_CHUNK colours and cut for the compaction, the flag words, and for CUT_KEYS the packed keys (16 B a colour)
 int cut_reserve(ws_ctx *c, size_t n_seeds, size_t n_cuts, bool lists, CutSource src) {
   const size_t n_colours = n_seeds + 1;
@@ -433,15 +575,64 @@ int read_flags(ws_ctx *c, uint32_t *host) {
   return WS_OK;
 }
 
-// ws_tree_cut_device and ws_tree_cut_stats_device: every check, the tree's verdict, the tables, the render and the lists.  Without a
-// catalogue threshold d_stats is never read and the launches are those of a call that has none.
+// What ws_tree_cut_catalogue_device adds to a call: the weights and where the records go.  region (nullable): the caller's device
+// records, next to d_lakes; hidden (nullable): n_cuts records on the HOST.
+struct CutMeasure {
+  LakeWeights wt;
+  ws_lake_stats *region, *hidden;
+};
+
+const ws_lake_stats LAKE_IDENTITY{0, 0, 0, 0, 0, 0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u};
+
+// the most accumulator entries a measuring call can need: a record per list entry -- no more than cap, or a call would have
+// ended with WS_ERR_CAPACITY before it measured, and no more than a cut shows (a colour, or a pixel, each) -- and one per cut
+size_t measure_entries(size_t n_seeds, size_t n, size_t n_cuts, bool records, size_t cap) {
+  return (records ? std::min(cap, n_cuts * std::min(n_seeds, n)) : 0) + n_cuts;
+}
+
+// the context's workspace of the measuring: LAKE_ACC_BYTES an entry, and the cuts' hidden records before they cross the bus
+int measure_reserve(ws_ctx *c, size_t entries, size_t n_cuts) {
+  if (int rc = ensure(c, c->cut_acc, entries * LAKE_ACC_BYTES)) return rc;
+  return ensure(c, c->cut_hidden, n_cuts * sizeof(ws_lake_stats));
+}
+
+// The regions of plan's cuts measured into m.region[0 .. total) and, behind them, the hidden pixels of cut k into entry total + k:
+// accumulators to the identity, the fold, the records; m.hidden is on its way when this returns (the caller waits for the stream).
+// index: the counters as CUT_INDEX left them, or nullptr with total == 0 (the hidden records alone).
+int measure_cuts(ws_ctx *c, const TreeRec *tree, size_t n_seeds, const uint32_t *tables, const uint32_t *d_keys, const uint32_t *d_seg_labels, size_t n,
+                 size_t w, const CutPlan &plan, size_t n_cuts, const uint32_t *index, size_t total, const CutMeasure &m, uint32_t *flags) {
+  const size_t n_rec = total + n_cuts;
+  u64c *sum = (u64c *)c->cut_acc.p;
+  uint32_t *box = (uint32_t *)(sum + 6 * n_rec);
+  LakeRec *d_hidden = (LakeRec *)c->cut_hidden.p;
+  const unsigned per_entry = (unsigned)((n_rec + 255) / 256);
+  k_lake_init<<<per_entry, 256, 0, c->stream>>>(sum, box, n_rec);
+  HIP_TRY(c, hipGetLastError());
+  // the grid of the render with lists: a workgroup's table serves a run of several steps on a large plane
+  const size_t runs = (n + 1023) / 1024, steps = std::max<size_t>((runs + 4095) / 4096, 1);
+  const unsigned blocks = (unsigned)((runs + steps - 1) / steps);
+  if (m.wt.u16)
+    k_cut_measure<uint16_t><<<blocks, 256, 0, c->stream>>>(tree, (uint32_t)n_seeds, tables, d_keys, d_seg_labels, n, steps, plan, index, m.wt, (uint32_t)w, sum, box, n_rec, flags);
+  else
+    k_cut_measure<uint8_t><<<blocks, 256, 0, c->stream>>>(tree, (uint32_t)n_seeds, tables, d_keys, d_seg_labels, n, steps, plan, index, m.wt, (uint32_t)w, sum, box, n_rec, flags);
+  HIP_TRY(c, hipGetLastError());
+  k_cut_measure_write<<<per_entry, 256, 0, c->stream>>>(sum, box, n_rec, total, reinterpret_cast<LakeRec *>(m.region), d_hidden);
+  HIP_TRY(c, hipGetLastError());
+  if (m.hidden) HIP_TRY(c, hipMemcpyAsync(m.hidden, d_hidden, n_cuts * sizeof(ws_lake_stats), hipMemcpyDeviceToHost, c->stream));
+  return WS_OK;
+}
+
+// ws_tree_cut_device, ws_tree_cut_stats_device and ws_tree_cut_catalogue_device: every check, the tree's verdict, the tables, the
+// render, the lists and, with m, the measuring.  Without a catalogue threshold d_stats is never read and the launches are those of
+// a call that has none; without m they are those of ws_tree_cut_stats_device.
 int cut_run(ws_ctx *c, const ws_tree_node *d_tree, const ws_lake_stats *d_stats, size_t n_seeds, const uint32_t *d_keys, const uint32_t *d_seg_labels,
             size_t h, size_t w, const Cuts &cs, uint32_t *d_out, size_t plane_stride, ws_lake *d_lakes, size_t cap, size_t *n_lakes,
-            uint64_t *offsets, uint64_t *hidden) {
+            uint64_t *offsets, uint64_t *hidden, const CutMeasure *m = nullptr) {
   const size_t n = h * w, n_cuts = cs.n;
   if ((!d_tree && n_seeds) || ((!d_keys || !d_seg_labels) && n)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
   if (!d_out && !d_lakes) return fail(c, WS_ERR_BAD_ARG, "no output: d_out and d_lakes are both null");
   if (d_lakes && (!n_lakes || !offsets || !hidden)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  if (m && m->region && !d_lakes) return fail(c, WS_ERR_BAD_ARG, "d_region_stats needs d_lakes: the records lie next to the lists");
   if (int rc = check_cuts(c, cs)) return rc;
   if (cs.catalogue && !d_stats) return fail(c, WS_ERR_BAD_ARG, "a cut has a catalogue threshold and d_stats is null");
   if (h && n / h != w) return fail(c, WS_ERR_TOO_LARGE, "plane too large");
@@ -452,14 +643,26 @@ int cut_run(ws_ctx *c, const ws_tree_node *d_tree, const ws_lake_stats *d_stats,
   const bool lists = d_lakes != nullptr;
   if (lists && n_cuts * (n_seeds + 1) > 0xFFFFFFFFull) return fail(c, WS_ERR_TOO_LARGE, "lists: cuts x (seeds + 1) must stay below 2^32");
   HIP_TRY(c, hipSetDevice(c->device));
+  if (m)
+    if (int rc = measure_reserve(c, measure_entries(n_seeds, n, n_cuts, m->region != nullptr, cap), n_cuts)) return rc;
   if (n_seeds == 0 || n == 0) {      // no colour or no pixel: nothing is shown
+    const bool fold = m && m->hidden && n;      // ... and every pixel is hidden: one fold of the plane, the same record for every cut
+    if (fold)
+      if (int rc = ensure(c, c->cut_flags, CUT_F_WORDS * sizeof(uint32_t))) return rc;
     for (size_t k = 0; d_out && n && k < n_cuts; ++k) HIP_TRY(c, hipMemsetAsync(d_out + k * plane_stride, 0, n * sizeof(uint32_t), c->stream));
     if (lists) {
       *n_lakes = 0;
       for (size_t k = 0; k < n_cuts; ++k) { offsets[k] = 0; hidden[k] = n; }
       offsets[n_cuts] = 0;
     }
+    if (fold) {
+      CutPlan one{};
+      one.n = one.n_tables = 1;
+      const CutMeasure first{m->wt, nullptr, m->hidden};
+      if (int rc = measure_cuts(c, nullptr, 0, nullptr, d_keys, d_seg_labels, n, w, one, 1, nullptr, 0, first, (uint32_t *)c->cut_flags.p)) return rc;
+    }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (size_t k = fold ? 1 : 0; m && m->hidden && k < n_cuts; ++k) m->hidden[k] = fold ? m->hidden[0] : LAKE_IDENTITY;
     return WS_OK;
   }
   const size_t n_colours = n_seeds + 1;
@@ -504,13 +707,17 @@ int cut_run(ws_ctx *c, const ws_tree_node *d_tree, const ws_lake_stats *d_stats,
     if (int rc = read_flags(c, seen)) return rc;
     if (seen[CUT_F_LABEL]) return fail(c, WS_ERR_BAD_ARG, "a label above n_seeds in d_seg_labels");
     if (seen[CUT_F_STEPS]) return fail(c, WS_ERR_BAD_ARG, "a walk did not end: d_tree changed under the call");
+    if (m) {      // (no list, so no record: the hidden pixels alone)
+      if (int rc = measure_cuts(c, tree, n_seeds, tables, d_keys, d_seg_labels, n, w, plan, n_cuts, nullptr, 0, *m, flags)) return rc;
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
     return WS_OK;
   }
   // the records: nonzero counters per block of colours, summed on the host (which owes the caller the offsets anyway)
   const size_t bpc = cut_blocks(n_colours), nb = n_cuts * bpc;
   uint32_t *block_n = (uint32_t *)((u64c *)c->cut_blocks.p + nb);
   u64c *block_base = (u64c *)c->cut_blocks.p;
-  k_cut_compact<false><<<dim3((unsigned)bpc, (unsigned)n_cuts), 256, 0, c->stream>>>(counts, n_colours, (uint32_t)bpc, block_n, nullptr, nullptr);
+  k_cut_compact<CUT_COUNT><<<dim3((unsigned)bpc, (unsigned)n_cuts), 256, 0, c->stream>>>(counts, n_colours, (uint32_t)bpc, block_n, nullptr, nullptr, nullptr, 0u);
   HIP_TRY(c, hipGetLastError());
   std::vector<uint32_t> host_n(nb + n_cuts);      // (behind the blocks' counts: entry 0 of every cut's counters)
   std::vector<u64c> host_base(nb);
@@ -524,11 +731,17 @@ int cut_run(ws_ctx *c, const ws_tree_node *d_tree, const ws_lake_stats *d_stats,
   if (total > cap) return fail(c, WS_ERR_CAPACITY, "lake buffer too small");
   for (size_t k = 0; k < n_cuts; ++k) { offsets[k] = host_base[k * bpc]; hidden[k] = host_n[nb + k]; }
   offsets[n_cuts] = total;
-  if (total) {
+  const bool records = m && m->region;      // the counters become the records' positions (total == 0: the hidden entries still)
+  if (total || records) {
     HIP_TRY(c, hipMemcpyAsync(block_base, host_base.data(), nb * sizeof(u64c), hipMemcpyHostToDevice, c->stream));
-    k_cut_compact<true><<<dim3((unsigned)bpc, (unsigned)n_cuts), 256, 0, c->stream>>>(counts, n_colours, (uint32_t)bpc, nullptr, block_base, d_lakes);
+    const dim3 grid((unsigned)bpc, (unsigned)n_cuts);
+    if (records) k_cut_compact<CUT_INDEX><<<grid, 256, 0, c->stream>>>(nullptr, n_colours, (uint32_t)bpc, nullptr, block_base, d_lakes, counts, (uint32_t)total);
+    else k_cut_compact<CUT_WRITE><<<grid, 256, 0, c->stream>>>(counts, n_colours, (uint32_t)bpc, nullptr, block_base, d_lakes, nullptr, 0u);
     HIP_TRY(c, hipGetLastError());
   }
+  if (m)
+    if (int rc = measure_cuts(c, tree, n_seeds, tables, d_keys, d_seg_labels, n, w, plan, n_cuts, records ? counts : nullptr, records ? (size_t)total : 0, *m, flags))
+      return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));      // (host_base is read by the copy until here)
   return WS_OK;
 }
@@ -540,6 +753,8 @@ struct CutWeights {
   int dtype;
   size_t stride;
   ws_lake_stats *stats;      // nullable: where the caller wants the catalogue
+  // ws_merge_tree_cut_catalogue: the regions' records next to `lakes` and the cuts' hidden records (host memory, both nullable)
+  ws_lake_stats *region_stats = nullptr, *hidden_stats = nullptr;
 };
 
 int merge_tree_cut_host(ws_ctx *c, const uint8_t *img, size_t h, size_t w, size_t row_stride, const uint64_t *seeds_rc, size_t n_seeds,
@@ -548,6 +763,8 @@ int merge_tree_cut_host(ws_ctx *c, const uint8_t *img, size_t h, size_t w, size_
   if (!opt || (!img && h * w) || (!seeds_rc && n_seeds)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
   if (!out && !lakes) return fail(c, WS_ERR_BAD_ARG, "no output: out and lakes are both null");
   if (lakes && (!n_lakes || !offsets || !hidden)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  const bool measure = lw && (lw->region_stats || lw->hidden_stats);
+  if (measure && lw->region_stats && !lakes) return fail(c, WS_ERR_BAD_ARG, "region_stats needs lakes: the records lie next to the lists");
   if (int rc = check_cuts(c, cs)) return rc;
   size_t ph = 0, pw = 0;
   if (int rc = check_plane(c, h, w, row_stride, opt, &ph, &pw)) return rc;
@@ -562,6 +779,11 @@ int merge_tree_cut_host(ws_ctx *c, const uint8_t *img, size_t h, size_t w, size_
     if (int rc = ensure(c, c->cut_planes, n_cuts * n * sizeof(uint32_t))) return rc;
   if (lakes)
     if (int rc = ensure(c, c->cut_lakes, std::max<size_t>(cap, 1) * sizeof(ws_lake))) return rc;
+  if (measure) {
+    if (int rc = measure_reserve(c, measure_entries(n_seeds, n, n_cuts, lw->region_stats != nullptr, cap), n_cuts)) return rc;
+    if (lw->region_stats)
+      if (int rc = ensure(c, c->cut_region, std::max<size_t>(cap, 1) * sizeof(ws_lake_stats))) return rc;
+  }
   std::vector<ws_tree_node> own;
   if (!tree) { own.resize(n_seeds + 1); tree = own.data(); }
   // upload, flood, stamped unions and the records; the segmenting labels, the stamps and the records stay on the context
@@ -577,10 +799,19 @@ int merge_tree_cut_host(ws_ctx *c, const uint8_t *img, size_t h, size_t w, size_
   }
   uint32_t *planes = out ? (uint32_t *)c->cut_planes.p : nullptr;
   ws_lake *d_lakes = lakes ? (ws_lake *)c->cut_lakes.p : nullptr;
+  CutMeasure m{};
+  if (measure) {      // the weights as ws_merge_tree_stats left them on the device: its own contiguous plane, or the image, w elements a row
+    const bool own_plane = lw->weight && h * w;
+    m = CutMeasure{LakeWeights{own_plane ? c->lake_weight.p : c->img.p, w, (uint32_t)h, (uint32_t)w, opt->edge_correction ? 1u : 0u,
+                               own_plane && lw->dtype == WS_U16},
+                   lw->region_stats ? (ws_lake_stats *)c->cut_region.p : nullptr, lw->hidden_stats};
+  }
   if (int rc = cut_run(c, (const ws_tree_node *)c->tree_out.p, d_stats, n_seeds, (const uint32_t *)c->keys.p, (const uint32_t *)c->labels.p, ph, pw, cs,
-                       planes, n, d_lakes, cap, n_lakes, offsets, hidden))
+                       planes, n, d_lakes, cap, n_lakes, offsets, hidden, measure ? &m : nullptr))
     return rc;
   if (lakes && *n_lakes) HIP_TRY(c, hipMemcpyAsync(lakes, d_lakes, *n_lakes * sizeof(ws_lake), hipMemcpyDeviceToHost, c->stream));
+  if (measure && lw->region_stats && *n_lakes)
+    HIP_TRY(c, hipMemcpyAsync(lw->region_stats, m.region, *n_lakes * sizeof(ws_lake_stats), hipMemcpyDeviceToHost, c->stream));
   if (out && n) {
     if (host_copy_in_chunks(c, n_cuts * n)) {
       if (int rc = labels_to_host_u64(c, planes, out, n_cuts * n)) return rc;
@@ -631,6 +862,37 @@ int ws_merge_tree_stats_cut(ws_ctx *c, const uint8_t *img, size_t h, size_t w, s
   if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
   if (!c) return WS_ERR_BAD_ARG;
   const CutWeights lw{weight, weight_dtype, weight_row_stride, stats};
+  return merge_tree_cut_host(c, img, h, w, row_stride, seeds_rc, n_seeds, opt, &lw, take_cuts(cuts, n_cuts), tree, out, lakes, cap, n_lakes, offsets,
+                             hidden);
+}
+
+int ws_tree_cut_catalogue_device(ws_ctx *c, const ws_tree_node *d_tree, const ws_lake_stats *d_stats, size_t n_seeds, const uint32_t *d_keys,
+                                 const uint32_t *d_seg_labels, size_t h, size_t w, const void *d_weight, int weight_dtype, size_t weight_row_stride,
+                                 const ws_lake_cut *cuts, size_t n_cuts, uint32_t *d_out, size_t plane_stride, ws_lake *d_lakes,
+                                 ws_lake_stats *d_region_stats, size_t cap, size_t *n_lakes, uint64_t *offsets, uint64_t *hidden,
+                                 ws_lake_stats *hidden_stats) {
+  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
+  if (!c) return WS_ERR_BAD_ARG;
+  if (!d_region_stats && !hidden_stats)      // nothing to measure: ws_tree_cut_stats_device, the weights are not looked at
+    return cut_run(c, d_tree, d_stats, n_seeds, d_keys, d_seg_labels, h, w, take_cuts(cuts, n_cuts), d_out, plane_stride, d_lakes, cap, n_lakes, offsets,
+                   hidden);
+  if (!d_weight) return fail(c, WS_ERR_BAD_ARG, "this form has no image: d_weight is null");
+  if (h && h * w / h != w) return fail(c, WS_ERR_TOO_LARGE, "plane too large");
+  if (int rc = check_lake_weights(c, w, h, w, d_weight, weight_dtype, weight_row_stride)) return rc;
+  const CutMeasure m{LakeWeights{d_weight, weight_row_stride, (uint32_t)h, (uint32_t)w, 0u, weight_dtype == WS_U16}, d_region_stats, hidden_stats};
+  return cut_run(c, d_tree, d_stats, n_seeds, d_keys, d_seg_labels, h, w, take_cuts(cuts, n_cuts), d_out, plane_stride, d_lakes, cap, n_lakes, offsets,
+                 hidden, &m);
+}
+
+int ws_merge_tree_cut_catalogue(ws_ctx *c, const uint8_t *img, size_t h, size_t w, size_t row_stride, const uint64_t *seeds_rc, size_t n_seeds,
+                                const ws_options *opt, const void *weight, int weight_dtype, size_t weight_row_stride, const ws_lake_cut *cuts,
+                                size_t n_cuts, ws_tree_node *tree, ws_lake_stats *stats, uint64_t *out, ws_lake *lakes, ws_lake_stats *region_stats,
+                                size_t cap, size_t *n_lakes, uint64_t *offsets, uint64_t *hidden, ws_lake_stats *hidden_stats) {
+  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
+  if (!c) return WS_ERR_BAD_ARG;
+  CutWeights lw{weight, weight_dtype, weight_row_stride, stats};
+  lw.region_stats = region_stats;
+  lw.hidden_stats = hidden_stats;
   return merge_tree_cut_host(c, img, h, w, row_stride, seeds_rc, n_seeds, opt, &lw, take_cuts(cuts, n_cuts), tree, out, lakes, cap, n_lakes, offsets,
                              hidden);
 }

@@ -436,6 +436,66 @@ class DeviceEngine:
                                                                offsets.ctypes.data, hidden.ctypes.data))
         return (out, lakes[: n.value], offsets, hidden[:k]) if want_lakes else out
 
+    def tree_cut_catalogue(self, tree, keys, labels, cuts, weights, stats=None, out=None, want_planes=True):
+        """tree_cut(want_lakes=True) with the regions the cuts show measured in the same call, everything in HBM
+        (ws_tree_cut_catalogue_device): returns (planes | None, lakes, region_stats, offsets, hidden, hidden_stats).  tree, keys,
+        labels, cuts, stats and out as tree_cut, with the same checks; planes, lakes, offsets and hidden as it returns them
+        (want_planes=False: no plane is rendered).  region_stats: an (n, 9) int64 device tensor of raw ws_lake_stats records as
+        merge_tree_stats returns them, row i measured over the pixels lakes[i] counts -- the region of colour lakes[i, 0] in
+        its cut, not the catalogue's record of that colour.  hidden_stats: a (K, 9) int64 numpy array, row k the same over the
+        pixels cut k shows as 0.  weights: a 2-D uint8 or int16 / uint16 (taken as u16 bits) device tensor of the PLANE's shape
+        (keys.shape: a padded plane comes with padded weights) whose rows are contiguous (a row stride in elements is honoured)."""
+        import numpy as np
+        from .api import _as_lake_cuts, _cut_list
+        lst = _cut_list(cuts)
+        if stats is None and any(c.catalogue for c in lst):
+            raise ValueError("a cut has a catalogue threshold: pass stats, the catalogue of merge_tree_stats")
+        arr, k = _as_lake_cuts(lst)
+        if keys.dim() != 2 or tuple(keys.shape) != tuple(labels.shape):
+            raise ValueError("keys and labels must be 2-D tensors of the same shape")
+        if tree.dim() != 2 or tree.shape[0] < 1 or tree.shape[1] != 4:
+            raise ValueError("tree must be an (n_seeds + 1, 4) tensor")
+        if stats is not None:
+            if stats.dim() != 2 or tuple(stats.shape) != (tree.shape[0], 9):
+                raise ValueError("stats must be an (n_seeds + 1, 9) tensor, one row per row of tree")
+            assert stats.dtype == torch.int64 and stats.is_cuda and stats.is_contiguous()
+        assert tree.dtype == torch.int32 and tree.is_cuda and tree.is_contiguous()
+        assert keys.dtype == torch.int32 and labels.dtype == torch.int32 and keys.is_cuda and labels.is_cuda
+        assert keys.numel() == 0 or (keys.is_contiguous() and labels.is_contiguous())
+        h, w = keys.shape
+        ns = tree.shape[0] - 1
+        u16 = {torch.int16, getattr(torch, "uint16", torch.int16)}
+        if weights is None:
+            raise ValueError("tree_cut_catalogue has no image: the records need weights")
+        if weights.dtype != torch.uint8 and weights.dtype not in u16:
+            raise TypeError("weights must be a uint8, uint16 or int16 (u16 bits) tensor")
+        if not weights.is_cuda or weights.dim() != 2 or tuple(weights.shape) != (h, w) or (w > 1 and weights.stride(1) != 1):
+            raise ValueError(f"weights must be a device tensor of shape {(h, w)} with contiguous rows")
+        dtype = _ffi.WS_DTYPES["uint8" if weights.dtype == torch.uint8 else "uint16"]
+        wstride = weights.stride(0) if h > 1 else w
+        if not want_planes:
+            out = None
+        elif out is None:
+            out = torch.empty((k, h, w), dtype=torch.int32, device=self.device)
+        elif out.dtype != torch.int32 or not out.is_contiguous() or tuple(out.shape) != (k, h, w):
+            raise ValueError(f"out must be a contiguous int32 tensor of shape {(k, h, w)}")
+        offsets = np.zeros(k + 1, dtype=np.uint64)
+        hidden = np.zeros(max(k, 1), dtype=np.uint64)
+        hidden_stats = np.zeros((max(k, 1), 9), dtype=np.int64)
+        n = ctypes.c_size_t(0)
+        cap = max(min(ns, h * w), 1) * max(k, 1)      # a cut shows no more colours than there are, or pixels
+        lakes = torch.empty((cap, 2), dtype=torch.int64, device=self.device)
+        region = torch.empty((cap, 9), dtype=torch.int64, device=self.device)
+        if h * w == 0:      # (no pixel: nothing to run, empty lists, every hidden record the identity of the fold)
+            hidden_stats[:] = (0, 0, 0, 0, 0, 0xFFFFFFFF, 0xFFFFFFFF, 0xFFFFFFFF, 0xFFFFFFFF)
+        elif k:
+            self.ctx.check(_ffi.lib().ws_tree_cut_catalogue_device(self.ctx.handle, tree.data_ptr(), stats.data_ptr() if stats is not None else None,
+                                                                   ns, keys.data_ptr(), labels.data_ptr(), h, w,
+                                                                   weights.data_ptr(), dtype, wstride, arr, k, out.data_ptr() if want_planes else None,
+                                                                   h * w, lakes.data_ptr(), region.data_ptr(), cap, ctypes.byref(n),
+                                                                   offsets.ctypes.data, hidden.ctypes.data, hidden_stats.ctypes.data))
+        return out, lakes[: n.value], region[: n.value], offsets, hidden[:k], hidden_stats[:k]
+
     def merge_tree_batch(self, cube, seeds, seed_offsets, max_level=254, edge=False, seed_shift=False, want_labels=False, out=None):
         """merge_tree of every slice of a cube with everything in HBM (ws_merge_tree_batch_device); cube, seeds and seed_offsets as
         transform_to_list_batch.  Returns an (n_seeds_total + S, 4) int32 tensor: slice k's n_k + 1 rows start at
