@@ -702,6 +702,72 @@ int ws_merge_tree_stats_batch(ws_ctx *ctx, const uint8_t *cube, size_t n_slices,
                               const uint64_t *seeds_rc, const size_t *seed_offsets, const ws_options *opt, const void *weight,
                               int weight_dtype, size_t weight_row_stride, size_t weight_slice_stride, ws_tree_node *tree,
                               ws_lake_stats *stats, size_t cap, size_t *n_records, uint64_t *labels, size_t *n_seeds, size_t *failed_slice);
+/* ws_tree_cut_catalogue_device of every slice of a cube in one call, from records and planes held in HBM.
+ * d_tree and d_stats (nullable when no cut has a catalogue threshold) in the slice-major layout ws_merge_tree(_stats)_batch_device
+ * writes: seed_offsets (n_slices + 1 entries, on the HOST), slice k with its n_k = seed_offsets[k + 1] - seed_offsets[k] seeds owns
+ * n_k + 1 records from rb[k] = seed_offsets[k] - seed_offsets[0] + k on, `parent` in the slice's own colours.  d_keys and
+ * d_seg_labels: n_slices contiguous h x w u32 planes each, as they stand (padded planes are passed padded).  d_weight: n_slices
+ * planes of h x w elements, weight_row_stride and weight_slice_stride in ELEMENTS, WS_U8 or WS_U16, nullable exactly as in the single
+ * call (with both measuring outputs NULL the weight arguments are not looked at and nothing that measures is launched).  The cuts:
+ * 1 .. 32 ws_lake_cut on the host.  Outputs, slice-major then cut (as ws_transform_history_batch_device lays out planes): plane
+ * (k, j) at d_out + (k * n_cuts + j) * plane_stride; list (k, j) is d_lakes[offsets[k * n_cuts + j] .. offsets[k * n_cuts + j + 1]),
+ * in the slice's own colours, in increasing colour; offsets (n_slices * n_cuts + 1 entries) and hidden (n_slices * n_cuts) on the
+ * HOST; d_region_stats[i] next to d_lakes[i]; hidden_stats[k * n_cuts + j] on the HOST; rows, columns and peak_pixel are those of
+ * the slice's own plane.  Every plane, record, offset difference, hidden count, region record and hidden record of slice k is
+ * bit-identical to ws_tree_cut_catalogue_device on slice k alone with that slice's records, planes and weight plane and the same
+ * cuts; slice k's lists are that call's, shifted by offsets[k * n_cuts].
+ * Refused with WS_ERR_BAD_ARG before any walk runs, every output untouched: everything the single call refuses, seed_offsets that
+ * decrease, weight_slice_stride < h * weight_row_stride with more than one slice, and a tree that is no merge tree WITHIN ITS SLICE:
+ * record c of slice k is alive with parent 0, or dies at a level <= 254 into 0 < parent < c of the same slice that dies strictly
+ * later (ONE check pass and ONE verdict, read on the host, for the whole cube; the record of a slice without seeds is not read).
+ * A label above ITS OWN slice's n_k -- which may well be a valid record index of the next slice -- is compared before it indexes
+ * anything, written as 0 and reported late as WS_ERR_BAD_ARG; the labels of a slice without seeds are not looked at.
+ * WS_ERR_TOO_LARGE on the cube's totals: n_slices * h * w >= 2^32, seeds + n_slices >= 2^32 - 1, or with lists n_cuts * (seeds +
+ * n_slices) >= 2^32.  n_slices == 0 or n_cuts == 0 writes nothing; slices without seeds and h * w == 0 behave as the single call's
+ * empty cases, per slice.  Records past cap are counted, not written: *n_lakes is the need, WS_ERR_CAPACITY, and no measuring
+ * kernel has run.  Workspace kept by the context: 16 B a record (the records with parents as indices into the whole array), 4 B a
+ * record and table, with lists 4 B a record and cut and 12 B per 1024 of those, 16 B per slice and cut and 4 B a slice; measuring:
+ * 68 B per accumulator entry -- min(cap, n_cuts * min(seeds, pixels)) + n_slices * n_cuts with d_region_stats, n_slices * n_cuts
+ * without -- and 72 B per slice and cut.  No term pads a slice. */
+int ws_tree_cut_catalogue_batch_device(ws_ctx *ctx, const ws_tree_node *d_tree, const ws_lake_stats *d_stats, size_t n_slices,
+                                       const size_t *seed_offsets, const uint32_t *d_keys, const uint32_t *d_seg_labels, size_t h, size_t w,
+                                       const void *d_weight, int weight_dtype, size_t weight_row_stride, size_t weight_slice_stride,
+                                       const ws_lake_cut *cuts, size_t n_cuts, uint32_t *d_out, size_t plane_stride, ws_lake *d_lakes,
+                                       ws_lake_stats *d_region_stats, size_t cap, size_t *n_lakes, uint64_t *offsets, uint64_t *hidden,
+                                       ws_lake_stats *hidden_stats);
+/* Cube in, everything out: ws_merge_tree_stats_batch_device and, group by group while the stamps and the labels of a flood are still
+ * on the context, the cut above.  The cube, the seeds, seed_offsets, the options, the weight cube (unpadded h x w planes, the ring
+ * weighs 0, NULL: the cube itself), d_labels and *failed_slice as ws_merge_tree_stats_batch_device.  d_tree is required; d_stats is
+ * nullable: NULL and no catalogue threshold, the statistics pass does not run; NULL with one, WS_ERR_BAD_ARG before anything runs.
+ * d_keys_out (nullable): the arrival stamps of every slice as n_slices padded planes, each bit-identical to
+ * ws_copy_last_arrival_device after ws_merge_tree_device on that slice alone -- with d_labels what a later
+ * ws_tree_cut_catalogue_batch_device needs to cut the same flood again.  The cut outputs are that call's, over the padded planes.
+ * A stacked group is cut once, as its slices; a looped slice as one slice; lists and region records continue behind the previous
+ * groups'.  Once the lists no longer fit, the remaining groups still flood and count: *n_lakes is the need, WS_ERR_CAPACITY.  A
+ * stack that fails or mispredicts is abandoned and the loop starts over from record 0.  Every buffer is reserved for the largest
+ * group before the first transform. */
+int ws_merge_tree_cut_catalogue_batch_device(ws_ctx *ctx, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w, size_t row_stride,
+                                             size_t slice_stride, const uint32_t *d_seeds_rc, const size_t *seed_offsets,
+                                             const ws_options *opt, const void *d_weight, int weight_dtype, size_t weight_row_stride,
+                                             size_t weight_slice_stride, const ws_lake_cut *cuts, size_t n_cuts, ws_tree_node *d_tree,
+                                             ws_lake_stats *d_stats, uint32_t *d_labels, uint32_t *d_keys_out, uint32_t *d_out,
+                                             size_t plane_stride, ws_lake *d_lakes, ws_lake_stats *d_region_stats, size_t cap,
+                                             size_t *n_lakes, uint64_t *offsets, uint64_t *hidden, ws_lake_stats *hidden_stats,
+                                             size_t *failed_slice);
+/* The same from and into HOST memory: the cube, the seeds (seeds_rc == NULL: every slice's own find_local_minima), the weight cube,
+ * *n_records, n_seeds[] and *failed_slice as ws_merge_tree_stats_batch; the cuts and the cut outputs as the device form, planes as
+ * u64 (plane (k, j) at out + (k * n_cuts + j) * padded h * w).  Two capacities: `tree` (required) and `stats` (nullable: the
+ * statistics still run when a cut has a catalogue threshold) hold record_cap records each -- too few is WS_ERR_CAPACITY once the
+ * minima are found or counted and before any flood, everything else untouched; `lakes` and `region_stats` hold cap records, with the
+ * device form's rule (*n_lakes is the need).  One download per output.  Keeps on the device what ws_merge_tree_stats_batch keeps,
+ * the u32 planes of the whole cube and cap records of 16 B and of 72 B. */
+int ws_merge_tree_cut_catalogue_batch(ws_ctx *ctx, const uint8_t *cube, size_t n_slices, size_t h, size_t w, size_t row_stride,
+                                      size_t slice_stride, const uint64_t *seeds_rc, const size_t *seed_offsets, const ws_options *opt,
+                                      const void *weight, int weight_dtype, size_t weight_row_stride, size_t weight_slice_stride,
+                                      const ws_lake_cut *cuts, size_t n_cuts, ws_tree_node *tree, ws_lake_stats *stats, size_t record_cap,
+                                      size_t *n_records, uint64_t *out, ws_lake *lakes, ws_lake_stats *region_stats, size_t cap,
+                                      size_t *n_lakes, uint64_t *offsets, uint64_t *hidden, ws_lake_stats *hidden_stats, size_t *n_seeds,
+                                      size_t *failed_slice);
 
 /* ---- input preparation (first "next" row) ---------------------------------------
  *

@@ -602,7 +602,94 @@ class MergingWatershed : public Watershed<T> {        // lib.rs:1297-1562
     return lake_catalogue_cube(cube, n_slices, rows, cols, weights, WS_U16, seeds, want_labels, n_seeds);
   }
 
+  // not in the reference: tree_cut_catalogue of every slice of a contiguous cube as ONE call of the library
+  // (ws_merge_tree_cut_catalogue_batch: slices that stack share one flood, and every stacked group is cut once, while its stamps
+  // are on the device).  Every CutCatalogue is what tree_cut_catalogue returns for the slice alone: the slice's own colours, rows,
+  // columns and peak pixels, offsets from 0.  weights, seeds and n_seeds as merge_tree_stats_cube.
+  std::vector<CutCatalogue> merge_tree_cut_catalogue_cube(const std::uint8_t *cube, std::size_t n_slices, std::size_t rows, std::size_t cols,
+                                                          const std::vector<ws_lake_cut> &cuts, const std::vector<std::vector<Seed>> *seeds = nullptr,
+                                                          std::vector<std::size_t> *n_seeds = nullptr) const {
+    return cut_catalogue_cube(cube, n_slices, rows, cols, cuts, nullptr, 0, seeds, n_seeds);
+  }
+  std::vector<CutCatalogue> merge_tree_cut_catalogue_cube(const std::uint8_t *cube, std::size_t n_slices, std::size_t rows, std::size_t cols,
+                                                          const std::vector<ws_lake_cut> &cuts, const std::uint8_t *weights,
+                                                          const std::vector<std::vector<Seed>> *seeds = nullptr,
+                                                          std::vector<std::size_t> *n_seeds = nullptr) const {
+    return cut_catalogue_cube(cube, n_slices, rows, cols, cuts, weights, WS_U8, seeds, n_seeds);
+  }
+  std::vector<CutCatalogue> merge_tree_cut_catalogue_cube(const std::uint8_t *cube, std::size_t n_slices, std::size_t rows, std::size_t cols,
+                                                          const std::vector<ws_lake_cut> &cuts, const std::uint16_t *weights,
+                                                          const std::vector<std::vector<Seed>> *seeds = nullptr,
+                                                          std::vector<std::size_t> *n_seeds = nullptr) const {
+    return cut_catalogue_cube(cube, n_slices, rows, cols, cuts, weights, WS_U16, seeds, n_seeds);
+  }
+
  private:
+  std::vector<CutCatalogue> cut_catalogue_cube(const std::uint8_t *cube, std::size_t n_slices, std::size_t rows, std::size_t cols,
+                                               const std::vector<ws_lake_cut> &cuts, const void *weights, int dtype,
+                                               const std::vector<std::vector<Seed>> *seeds, std::vector<std::size_t> *n_seeds) const {
+    if (seeds && seeds->size() != n_slices) throw std::invalid_argument("one seed list per slice");
+    const std::size_t e = this->opt_.edge_correction ? 2 : 0, prow = rows + e, pcol = cols + e, npx = prow * pcol, k = cuts.size();
+    if (k == 0) throw std::invalid_argument("merge_tree_cut_catalogue_cube needs at least one cut");
+    std::vector<std::uint64_t> packed;
+    std::vector<std::size_t> offs(n_slices + 1, 0), counts(n_slices, 0);
+    if (seeds)
+      for (std::size_t s = 0; s < n_slices; ++s) {
+        const auto one = detail::pack((*seeds)[s]);
+        packed.insert(packed.end(), one.begin(), one.end());
+        offs[s + 1] = offs[s] + (*seeds)[s].size();
+        counts[s] = (*seeds)[s].size();
+      }
+    // (as merge_tree_cube: a too small guess of the records is answered before any flood with the count; of the lists, with the need)
+    std::size_t rec_cap = seeds ? offs[n_slices] + n_slices : n_slices * (rows * cols / 8 + 1), total = 0, failed = 0, got = 0;
+    std::size_t cap = std::max<std::size_t>(std::min(rec_cap, n_slices * npx), 1) * k;
+    std::vector<ws_tree_node> flat(rec_cap);
+    std::vector<ws_lake_stats> records(rec_cap), region(cap), hidden_stats(n_slices * k);
+    std::vector<ws_lake> lakes(cap);
+    std::vector<usize> planes(n_slices * k * npx);
+    std::vector<std::uint64_t> offsets(n_slices * k + 1, 0), hidden(n_slices * k, 0);
+    for (int attempt = 0; attempt < 3; ++attempt) {
+      const int rc = ws_merge_tree_cut_catalogue_batch(this->ctx_->get(), cube, n_slices, rows, cols, cols, rows * cols, seeds ? packed.data() : nullptr,
+                                                       seeds ? offs.data() : nullptr, &this->opt_, weights, dtype, cols, rows * cols, cuts.data(), k,
+                                                       flat.data(), records.data(), rec_cap, &total, planes.data(), lakes.data(), region.data(), cap,
+                                                       &got, offsets.data(), hidden.data(), hidden_stats.data(), counts.data(), &failed);
+      if (rc == WS_ERR_CAPACITY && total > rec_cap && attempt < 2) {
+        rec_cap = total;
+        flat.resize(rec_cap);
+        records.resize(rec_cap);
+        continue;
+      }
+      if (rc == WS_ERR_CAPACITY && got > cap && attempt < 2) {
+        cap = got;
+        lakes.resize(cap);
+        region.resize(cap);
+        continue;
+      }
+      this->ctx_->check(rc);
+      break;
+    }
+    std::vector<CutCatalogue> out;
+    std::size_t at = 0;
+    for (std::size_t s = 0; s < n_slices; ++s) {
+      const std::size_t n = counts[s] + 1, lo = offsets[s * k], hi = offsets[(s + 1) * k];
+      CutCatalogue t;
+      t.tree = MergeTree{std::vector<ws_tree_node>(flat.begin() + at, flat.begin() + at + n), Array2<usize>(0, 0)};
+      t.stats.assign(records.begin() + at, records.begin() + at + n);
+      t.lakes.assign(lakes.begin() + lo, lakes.begin() + hi);
+      t.region_stats.assign(region.begin() + lo, region.begin() + hi);
+      t.hidden.assign(hidden.begin() + s * k, hidden.begin() + (s + 1) * k);
+      t.hidden_stats.assign(hidden_stats.begin() + s * k, hidden_stats.begin() + (s + 1) * k);
+      for (std::size_t j = 0; j <= k; ++j) t.offsets.push_back(offsets[s * k + j] - lo);
+      for (std::size_t j = 0; j < k; ++j) {
+        t.planes.emplace_back(prow, pcol);
+        std::copy(planes.begin() + (s * k + j) * npx, planes.begin() + (s * k + j + 1) * npx, t.planes.back().data.begin());
+      }
+      out.push_back(std::move(t));
+      at += n;
+    }
+    if (n_seeds) *n_seeds = counts;
+    return out;
+  }
   std::vector<LakeCatalogue> lake_catalogue_cube(const std::uint8_t *cube, std::size_t n_slices, std::size_t rows, std::size_t cols,
                                                  const void *weights, int dtype, const std::vector<std::vector<Seed>> *seeds,
                                                  bool want_labels, std::vector<std::size_t> *n_seeds) const {

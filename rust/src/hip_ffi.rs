@@ -353,6 +353,23 @@ extern "C" {
         slice_stride: usize, seeds_rc: *const u64, seed_offsets: *const usize, opt: *const ws_options, weight: *const c_void,
         weight_dtype: c_int, weight_row_stride: usize, weight_slice_stride: usize, tree: *mut ws_tree_node, stats: *mut ws_lake_stats,
         cap: usize, n_records: *mut usize, labels: *mut u64, n_seeds: *mut usize, failed_slice: *mut usize) -> c_int;
+    pub fn ws_tree_cut_catalogue_batch_device(ctx: *mut ws_ctx, d_tree: *const ws_tree_node, d_stats: *const ws_lake_stats, n_slices: usize,
+        seed_offsets: *const usize, d_keys: *const u32, d_seg_labels: *const u32, h: usize, w: usize, d_weight: *const c_void,
+        weight_dtype: c_int, weight_row_stride: usize, weight_slice_stride: usize, cuts: *const ws_lake_cut, n_cuts: usize,
+        d_out: *mut u32, plane_stride: usize, d_lakes: *mut ws_lake, d_region_stats: *mut ws_lake_stats, cap: usize,
+        n_lakes: *mut usize, offsets: *mut u64, hidden: *mut u64, hidden_stats: *mut ws_lake_stats) -> c_int;
+    pub fn ws_merge_tree_cut_catalogue_batch_device(ctx: *mut ws_ctx, d_cube: *const u8, n_slices: usize, h: usize, w: usize,
+        row_stride: usize, slice_stride: usize, d_seeds_rc: *const u32, seed_offsets: *const usize, opt: *const ws_options,
+        d_weight: *const c_void, weight_dtype: c_int, weight_row_stride: usize, weight_slice_stride: usize, cuts: *const ws_lake_cut,
+        n_cuts: usize, d_tree: *mut ws_tree_node, d_stats: *mut ws_lake_stats, d_labels: *mut u32, d_keys_out: *mut u32,
+        d_out: *mut u32, plane_stride: usize, d_lakes: *mut ws_lake, d_region_stats: *mut ws_lake_stats, cap: usize,
+        n_lakes: *mut usize, offsets: *mut u64, hidden: *mut u64, hidden_stats: *mut ws_lake_stats, failed_slice: *mut usize) -> c_int;
+    pub fn ws_merge_tree_cut_catalogue_batch(ctx: *mut ws_ctx, cube: *const u8, n_slices: usize, h: usize, w: usize, row_stride: usize,
+        slice_stride: usize, seeds_rc: *const u64, seed_offsets: *const usize, opt: *const ws_options, weight: *const c_void,
+        weight_dtype: c_int, weight_row_stride: usize, weight_slice_stride: usize, cuts: *const ws_lake_cut, n_cuts: usize,
+        tree: *mut ws_tree_node, stats: *mut ws_lake_stats, record_cap: usize, n_records: *mut usize, out: *mut u64,
+        lakes: *mut ws_lake, region_stats: *mut ws_lake_stats, cap: usize, n_lakes: *mut usize, offsets: *mut u64, hidden: *mut u64,
+        hidden_stats: *mut ws_lake_stats, n_seeds: *mut usize, failed_slice: *mut usize) -> c_int;
     pub fn ws_pre_processor_device(ctx: *mut ws_ctx, d_data: *const c_void, dtype: c_int, n_elems: usize,
         max_value: u8, d_out: *mut u8) -> c_int;
     pub fn ws_random_field_device(ctx: *mut ws_ctx, d_img: *mut u8, h: usize, w: usize, row_stride: usize,

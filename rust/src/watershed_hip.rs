@@ -875,6 +875,83 @@ impl<T> MergingWatershed<T> {
             .collect();
         (out, n_seeds)
     }
+    /// Not in the reference: `tree_cut_catalogue(cube[k], &find_local_minima(cube[k]), weights[k], cuts)` of every slice of a cube
+    /// as one call (`ws_merge_tree_cut_catalogue_batch`: slices that stack share one flood, and every stacked group is cut once,
+    /// while its stamps are on the device).  Returns per slice the `CutCatalogue` of the slice alone -- its own colours, rows,
+    /// columns and peak pixels, offsets from 0 -- and the number of minima of every slice.  `weights` as `merge_tree_stats_cube`.
+    pub fn merge_tree_cut_catalogue_cube(&self, cube: nd::ArrayView3<u8>, weights: Option<nd::ArrayView3<u16>>,
+                                         cuts: &[hip_ffi::ws_lake_cut]) -> (Vec<CutCatalogue>, Vec<usize>) {
+        assert!(!cuts.is_empty() && cuts.len() <= 32, "merge_tree_cut_catalogue_cube takes 1 ..= 32 cuts");
+        let (n, h, w) = cube.dim();
+        let std_cube = cube.as_standard_layout();
+        let o = self.opt.ffi();
+        let (ph, pw) = self.opt.plane(h, w);
+        let k = cuts.len();
+        let planes_w = weights.map(|a| {
+            assert_eq!(a.dim(), (n, h, w), "weights must have the cube's shape");
+            a.as_standard_layout().into_owned()
+        });
+        let (wt_ptr, wt_dtype) = match planes_w.as_ref() {
+            Some(a) => (a.as_ptr() as *const std::ffi::c_void, hip_ffi::WS_U16),
+            None => (std::ptr::null(), 0),
+        };
+        // (as merge_tree_cube: a too small guess of the records is answered with the count before any flood; of the lists, with the need)
+        let mut rec_cap = n * (h * w / 8 + 1);
+        let mut cap = rec_cap.min(n * ph * pw).max(1) * k;
+        let mut flat = vec![hip_ffi::ws_tree_node::default(); rec_cap];
+        let mut records = vec![hip_ffi::ws_lake_stats::default(); rec_cap];
+        let mut lakes = vec![hip_ffi::ws_lake { colour: 0, area: 0 }; cap];
+        let mut region = vec![hip_ffi::ws_lake_stats::default(); cap];
+        let mut hidden_stats = vec![hip_ffi::ws_lake_stats::default(); n * k];
+        let mut planes = vec![0u64; n * k * ph * pw];
+        let (mut offsets, mut hidden) = (vec![0u64; n * k + 1], vec![0u64; n * k]);
+        let mut n_seeds = vec![0usize; n];
+        let (mut total, mut got, mut failed) = (0usize, 0usize, 0usize);
+        shim::with_ctx(|ctx| unsafe {
+            for attempt in 0..3 {
+                let rc = hip_ffi::ws_merge_tree_cut_catalogue_batch(ctx, std_cube.as_ptr(), n, h, w, w, h * w, std::ptr::null(), std::ptr::null(), &o,
+                                                                    wt_ptr, wt_dtype, w, h * w, cuts.as_ptr(), k, flat.as_mut_ptr(),
+                                                                    records.as_mut_ptr(), rec_cap, &mut total, planes.as_mut_ptr(),
+                                                                    lakes.as_mut_ptr(), region.as_mut_ptr(), cap, &mut got, offsets.as_mut_ptr(),
+                                                                    hidden.as_mut_ptr(), hidden_stats.as_mut_ptr(), n_seeds.as_mut_ptr(), &mut failed);
+                if rc == hip_ffi::WS_ERR_CAPACITY && total > rec_cap && attempt < 2 {
+                    rec_cap = total;
+                    flat.resize(rec_cap, hip_ffi::ws_tree_node::default());
+                    records.resize(rec_cap, hip_ffi::ws_lake_stats::default());
+                    continue;
+                }
+                if rc == hip_ffi::WS_ERR_CAPACITY && got > cap && attempt < 2 {
+                    cap = got;
+                    lakes.resize(cap, hip_ffi::ws_lake { colour: 0, area: 0 });
+                    region.resize(cap, hip_ffi::ws_lake_stats::default());
+                    continue;
+                }
+                shim::check(ctx, rc, "ws_merge_tree_cut_catalogue_batch");
+                break;
+            }
+        });
+        let npx = ph * pw;
+        let mut at = 0usize;
+        let out = (0..n)
+            .map(|s| {
+                let nodes = flat[at..at + n_seeds[s] + 1].to_vec();
+                let stats = records[at..at + n_seeds[s] + 1].to_vec();
+                at += n_seeds[s] + 1;
+                let (lo, hi) = (offsets[s * k] as usize, offsets[(s + 1) * k] as usize);
+                let slice_planes = (0..k)
+                    .map(|j| {
+                        let p = &planes[(s * k + j) * npx..(s * k + j + 1) * npx];
+                        nd::Array2::from_shape_vec((ph, pw), p.iter().map(|&v| v as usize).collect()).expect("plane shape")
+                    })
+                    .collect();
+                let cut = TreeCut { tree: MergeTree { nodes, labels: None }, planes: slice_planes, lakes: lakes[lo..hi].to_vec(),
+                                    offsets: offsets[s * k..(s + 1) * k + 1].iter().map(|&x| x - lo as u64).collect(),
+                                    hidden: hidden[s * k..(s + 1) * k].to_vec() };
+                CutCatalogue { cut: LakeCut { cut, stats }, region_stats: region[lo..hi].to_vec(), hidden_stats: hidden_stats[s * k..(s + 1) * k].to_vec() }
+            })
+            .collect();
+        (out, n_seeds)
+    }
     /// Not in the reference: the merged label plane after the last level (canonical ids: the smallest seed colour of
     /// every lake).  The reference's own `transform` is the stub above.
     pub fn transform_final(&self, input: nd::ArrayView2<u8>, seeds: &[(usize, usize)]) -> nd::Array2<usize> {

@@ -190,6 +190,12 @@ SIGNATURES = {
                                                         vp, vp, vp, szp]),
     "ws_merge_tree_stats_batch": (ctypes.c_int, [vp, vp, sz, sz, sz, sz, sz, vp, szp, ctypes.POINTER(Options), vp, ctypes.c_int, sz, sz,
                                                  vp, vp, sz, szp, vp, szp, szp]),
+    "ws_tree_cut_catalogue_batch_device": (ctypes.c_int, [vp, vp, vp, sz, szp, vp, vp, sz, sz, vp, ctypes.c_int, sz, sz, vp, sz, vp, sz, vp, vp, sz, szp,
+                                                          vp, vp, vp]),
+    "ws_merge_tree_cut_catalogue_batch_device": (ctypes.c_int, [vp, vp, sz, sz, sz, sz, sz, vp, szp, ctypes.POINTER(Options), vp, ctypes.c_int, sz, sz,
+                                                                vp, sz, vp, vp, vp, vp, vp, sz, vp, vp, sz, szp, vp, vp, vp, szp]),
+    "ws_merge_tree_cut_catalogue_batch": (ctypes.c_int, [vp, vp, sz, sz, sz, sz, sz, vp, szp, ctypes.POINTER(Options), vp, ctypes.c_int, sz, sz,
+                                                         vp, sz, vp, vp, sz, szp, vp, vp, vp, sz, szp, vp, vp, vp, szp, szp]),
     "ws_pre_processor": (ctypes.c_int, [vp, vp, ctypes.c_int, sz, ctypes.c_uint8, vp]),
     "ws_pre_processor_device": (ctypes.c_int, [vp, vp, ctypes.c_int, sz, ctypes.c_uint8, vp]),
     "ws_block_init": (ctypes.c_int, [vp, sz, sz, vp, vp, sz, vp, vp]),

@@ -838,6 +838,100 @@ class MergingWatershed(_Transform):
             out.append(stats)
         return tuple(out)
 
+    def merge_tree_cut_catalogue_cube(self, cube, seeds=None, cuts=(), weights=None, want_tree=False, want_stats=False, want_planes=True):
+        """merge_tree_cut_catalogue of every slice cube[k] of a 3-D u8 array with seeds[k] -- or, with seeds None, the slice's own
+        find_local_minima -- and the weight plane weights[k] (a u8 or u16 cube of the cube's shape; None: the cube itself) in ONE
+        call of the library (ws_merge_tree_cut_catalogue_batch: slices that stack share one flood, and every stacked group is cut
+        once, while its stamps are on the device).  Returns one tuple per slice, as merge_tree_cut_catalogue returns it for the
+        slice alone: (planes | None, lakes, region_stats, offsets, hidden, hidden_stats[, tree][, stats]) in the slice's own colours,
+        rows, columns and peak pixels, offsets from 0; the arrays are views of one array per output.  Not a method of the
+        reference."""
+        lst = _cut_list(cuts)
+        k = len(lst)
+        if k == 0:
+            raise ValueError("merge_tree_cut_catalogue_cube needs at least one cut")
+        c = np.asarray(cube)
+        if c.ndim != 3:
+            raise ValueError("cube must be 3-D: (slices, rows, columns)")
+        if c.dtype != np.uint8:
+            raise ValueError("cube must be uint8")
+        n = c.shape[0]
+        if seeds is not None and len(seeds) != n:
+            raise ValueError("one seed list per slice")
+        wt, dtype = None, 0
+        if weights is not None:
+            wt = np.asarray(weights)
+            if wt.dtype not in (np.uint8, np.uint16) or wt.ndim != 3:
+                raise TypeError("weights must be a 3-D uint8 or uint16 array (quantise float data first: pre_processor_with_max)")
+            if wt.shape != c.shape:
+                raise ValueError(f"weights must have the cube's shape {c.shape}, not {wt.shape}")
+            wt = np.ascontiguousarray(wt)
+            dtype = _ffi.WS_DTYPES[wt.dtype.name]
+        c = np.ascontiguousarray(c)
+        _, h, w = c.shape
+        e = 2 if self.edge_correction else 0
+        ph, pw = h + e, w + e
+        arr, _ = _as_lake_cuts(lst)
+        if seeds is None:
+            flat, offs = None, None
+            rec_cap = n * (h * w // 8 + 1)      # (as merge_tree_cube: a too small guess costs a second call, before any flood)
+        else:
+            lists = [np.asarray(s, dtype=np.uint64).reshape(-1, 2) for s in seeds]
+            offs = np.zeros(n + 1, dtype=np.uintp)
+            offs[1:] = np.cumsum([len(l) for l in lists])
+            flat = np.ascontiguousarray(np.concatenate(lists, axis=0) if lists else np.zeros((0, 2), dtype=np.uint64))
+            if flat.shape[0] == 0:
+                flat = np.zeros((1, 2), dtype=np.uint64)
+            rec_cap = int(offs[n]) + n
+        counts = np.zeros(max(n, 1), dtype=np.uintp)
+        planes = np.empty((n, k, ph, pw), dtype=np.uint64) if want_planes else None
+        offsets = np.zeros(n * k + 1, dtype=np.uint64)
+        hidden = np.zeros(max(n * k, 1), dtype=np.uint64)
+        hidden_stats = np.empty(max(n * k, 1), dtype=LAKE_STATS_DTYPE)
+        tree = np.empty((max(rec_cap, 1), 4), dtype=np.uint32)
+        stats = np.empty(max(rec_cap, 1), dtype=LAKE_STATS_DTYPE) if want_stats else None
+        cap = max(min(rec_cap, n * ph * pw), 1) * k      # a cut shows no more colours than there are, or pixels
+        lakes = np.empty((cap, 2), dtype=np.uint64)
+        region = np.empty(cap, dtype=LAKE_STATS_DTYPE)
+        got = ctypes.c_size_t(0)
+        if n:
+            ctx = self._ctx()
+            total = ctypes.c_size_t(0)
+            failed = ctypes.c_size_t(0)
+            for attempt in range(3):
+                rc = _ffi.lib().ws_merge_tree_cut_catalogue_batch(
+                    ctx.handle, c.ctypes.data, n, h, w, w, h * w, flat.ctypes.data if flat is not None else None,
+                    offs.ctypes.data_as(_ffi.szp) if offs is not None else None, ctypes.byref(self._opt), wt.ctypes.data if wt is not None else None,
+                    dtype, w, h * w, arr, k, tree.ctypes.data, stats.ctypes.data if want_stats else None, rec_cap, ctypes.byref(total),
+                    planes.ctypes.data if want_planes else None, lakes.ctypes.data, region.ctypes.data, cap, ctypes.byref(got), offsets.ctypes.data,
+                    hidden.ctypes.data, hidden_stats.ctypes.data, counts.ctypes.data_as(_ffi.szp), ctypes.byref(failed))
+                if rc == _ffi.WS_ERR_CAPACITY and total.value > rec_cap and attempt < 2:      # more minima than guessed: before any flood
+                    rec_cap = total.value
+                    tree = np.empty((rec_cap, 4), dtype=np.uint32)
+                    stats = np.empty(rec_cap, dtype=LAKE_STATS_DTYPE) if want_stats else None
+                    continue
+                if rc == _ffi.WS_ERR_CAPACITY and got.value > cap and attempt < 2:
+                    cap = got.value
+                    lakes = np.empty((cap, 2), dtype=np.uint64)
+                    region = np.empty(cap, dtype=LAKE_STATS_DTYPE)
+                    continue
+                ctx.check(rc)
+                break
+        first = np.zeros(n + 1, dtype=np.int64)
+        first[1:] = np.cumsum((counts[:n] if seeds is None else np.diff(offs)).astype(np.int64) + 1)
+        out = []
+        for i in range(n):
+            lo, hi = int(offsets[i * k]), int(offsets[(i + 1) * k])
+            one = [planes[i] if want_planes else None, lakes[lo:hi], region[lo:hi], offsets[i * k:(i + 1) * k + 1] - offsets[i * k],
+                   hidden[i * k:(i + 1) * k], hidden_stats[i * k:(i + 1) * k]]
+            t = tree[first[i]:first[i + 1]]
+            if want_tree:
+                one.append(MergeTree(t[:, 0].copy(), t[:, 1].copy(), t[:, 2].copy(), t[:, 3].copy()))
+            if want_stats:
+                one.append(stats[first[i]:first[i + 1]])
+            out.append(tuple(one))
+        return out
+
     def merge_tree_stats(self, input, seeds, weights=None, want_labels=False):
         """Not in the reference: merge_tree and a catalogue of its lakes from the same flood (ws_merge_tree_stats).  Returns
         (MergeTree, stats): stats is a numpy structured array (LAKE_STATS_DTYPE) of n_seeds + 1 records, record c the weighted

@@ -467,6 +467,19 @@ int tree_batch_device_body(ws_ctx *c, const uint8_t *d_cube, size_t n_slices, si
   return WS_OK;
 }
 
+// the host forms' weight cube contiguous on the context (c->lake_weight), before the first transform: nothing moves under the level
+// loop's graphs; ls then describes it.  No weights or no pixel: ls keeps none (the cube itself weighs)
+int upload_weights(ws_ctx *c, const LakeBatchWanted &want, size_t n_slices, size_t h, size_t w, LakeBatchWanted &ls) {
+  if (!want.weight || h * w == 0) return WS_OK;
+  const size_t elem = want.dtype == WS_U16 ? 2 : 1;
+  if (int rc = ensure(c, c->lake_weight, n_slices * h * w * elem)) return rc;
+  for (size_t k = 0; k < n_slices; ++k)
+    HIP_TRY(c, hipMemcpy2DAsync((uint8_t *)c->lake_weight.p + k * h * w * elem, w * elem, (const uint8_t *)want.weight + k * want.slice_stride * elem,
+                                want.stride * elem, w * elem, h, hipMemcpyHostToDevice, c->stream));
+  ls.weight = c->lake_weight.p; ls.dtype = want.dtype; ls.stride = w; ls.slice_stride = h * w;
+  return WS_OK;
+}
+
 // ws_merge_tree_batch and, with want (host pointers), ws_merge_tree_stats_batch: the inputs to the device, the device form's run
 // into the context's record buffers, the records back.  A cap below the need is counted, nothing flooded: the caller learns how
 // many records to make room for.
@@ -495,14 +508,7 @@ int tree_batch_host_body(ws_ctx *c, const uint8_t *cube, size_t n_slices, size_t
   if (labels && (rc = ensure(c, c->out64, std::max<size_t>(plane, 1) * sizeof(uint64_t)))) return rc;      // (the plane-by-plane copy widens there)
   LakeBatchWanted ls;
   ls.stats = (ws_lake_stats *)c->lake_out.p;
-  if (want && want->weight && h * w) {      // the weight cube contiguous on the context, before the first transform: nothing moves under the level loop's graphs
-    const size_t elem = want->dtype == WS_U16 ? 2 : 1;
-    if ((rc = ensure(c, c->lake_weight, n_slices * h * w * elem))) return rc;
-    for (size_t k = 0; k < n_slices; ++k)
-      HIP_TRY(c, hipMemcpy2DAsync((uint8_t *)c->lake_weight.p + k * h * w * elem, w * elem, (const uint8_t *)want->weight + k * want->slice_stride * elem,
-                                  want->stride * elem, w * elem, h, hipMemcpyHostToDevice, c->stream));
-    ls.weight = c->lake_weight.p; ls.dtype = want->dtype; ls.stride = w; ls.slice_stride = h * w;
-  }
+  if (want && (rc = upload_weights(c, *want, n_slices, h, w, ls))) return rc;
   const auto labels_to_caller = [&](const BatchGroup &grp) -> int {
     if (!labels || !plane) return WS_OK;
     return planes_to_host(c, grp.labels, labels + grp.k_first * plane, grp.g, plane);
@@ -514,9 +520,186 @@ int tree_batch_host_body(ws_ctx *c, const uint8_t *cube, size_t n_slices, size_t
   return WS_OK;
 }
 
+// ---- the cut catalogue of a cube of slices (ws_merge_tree_cut_catalogue_batch(_device)) ---------------------
+
+// what the cube's cut writes, in HBM (the device form: the caller's; the host form: the context's) but for the host arrays
+struct CutBatchOut {
+  const ws_lake_cut *cuts = nullptr;
+  size_t n_cuts = 0;
+  uint32_t *d_keys_out = nullptr, *d_out = nullptr;
+  size_t plane_stride = 0;
+  ws_lake *d_lakes = nullptr;
+  ws_lake_stats *d_region_stats = nullptr;
+  size_t cap = 0, *n_lakes = nullptr;
+  uint64_t *offsets = nullptr, *hidden = nullptr;
+  ws_lake_stats *hidden_stats = nullptr;
+  bool measure() const { return d_region_stats || hidden_stats; }
+};
+
+// the group's part of the request: its records, planes and outputs, lists and records behind `need` records of the groups before
+CutCube cut_cube_of(const Batch &b, const CutBatchOut &o, const LakeBatchWanted &ls, const ws_tree_node *d_tree, const ws_lake_stats *d_stats,
+                    size_t k_first, size_t g, const uint32_t *keys, const uint32_t *labels, size_t need) {
+  const size_t at = k_first ? b.seeds_in(0, k_first) + k_first : 0, i0 = k_first * o.n_cuts, room = need <= o.cap ? o.cap - need : 0;
+  CutCube q;
+  q.d_tree = d_tree ? d_tree + at : nullptr; q.d_stats = d_stats ? d_stats + at : nullptr;
+  q.n_slices = g; q.seed_offsets = b.seed_offsets ? b.seed_offsets + k_first : nullptr; q.d_keys = keys; q.d_seg_labels = labels; q.h = b.ph; q.w = b.pw;
+  q.cuts = o.cuts; q.n_cuts = o.n_cuts;
+  q.d_out = o.d_out ? o.d_out + i0 * o.plane_stride : nullptr; q.plane_stride = o.plane_stride;
+  q.d_lakes = o.d_lakes ? o.d_lakes + (room ? need : 0) : nullptr;
+  q.d_region_stats = o.d_region_stats ? o.d_region_stats + (room ? need : 0) : nullptr;
+  q.cap = room; q.n_lakes = o.n_lakes; q.offsets = o.offsets ? o.offsets + i0 : nullptr; q.hidden = o.hidden ? o.hidden + i0 : nullptr;
+  q.hidden_stats = o.hidden_stats ? o.hidden_stats + i0 : nullptr;
+  q.measure = o.measure();
+  if (q.measure) q.wt = lake_weights_from(ls, b, k_first);
+  return q;
+}
+
+// The trees of a checked batch (tree_batch_run; with ls.stats the catalogue) and, per group while its stamps and labels are on the
+// context, the cut: a stacked group as its g slices in ONE run of the cut's driver, a looped slice as one slice of it.  Lists and
+// region records continue behind the previous groups'; once they no longer fit the remaining groups still flood and count
+// (lists_batch_body's rule).  Every buffer of the cut is reserved for the largest group before the first transform.
+template <class F>
+int cut_batch_run(ws_ctx *c, const Batch &b, const LakeBatchWanted &ls, ws_tree_node *d_tree, const CutBatchOut &o, size_t *failed_slice, F labels) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t plane = b.plane(), n_slices = b.n_slices;
+  {
+    const size_t per_group = std::max<size_t>(std::min(stackable(c, b), n_slices), 1);
+    size_t most = 0;
+    for (size_t k0 = 0; k0 < n_slices; k0 += per_group) most = std::max(most, b.seeds_in(k0, std::min(per_group, n_slices - k0)));
+    for (size_t k = 0; k < n_slices; ++k) most = std::max(most, b.seeds_in(k, 1));
+    if (int rc = cut_cube_reserve(c, per_group, most, per_group * plane, cut_cube_of(b, o, ls, d_tree, ls.stats, 0, per_group, nullptr, nullptr, 0))) return rc;
+  }
+  size_t need = 0;
+  const int rc_run = tree_batch_run(
+      c, b, d_tree, failed_slice,
+      [&](const BatchGroup &grp) -> int {
+        if (int rc = labels(grp)) return rc;
+        if (grp.k_first == 0) need = 0;      // (after an abandoned stack: from the start)
+        if (o.d_keys_out && plane)
+          HIP_TRY(c, hipMemcpyAsync(o.d_keys_out + grp.k_first * plane, grp.keys, grp.g * plane * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+        size_t got = 0;
+        CutCube q = cut_cube_of(b, o, ls, d_tree, ls.stats, grp.k_first, grp.g, grp.keys, grp.labels, need);
+        if (q.d_lakes) q.n_lakes = &got;
+        const int rc = cut_cube_run(c, q);
+        if (rc != WS_OK && rc != WS_ERR_CAPACITY) return rc;
+        if (rc == WS_ERR_CAPACITY) c->err.clear();      // counted, not written
+        else if (q.d_lakes)
+          for (size_t i = 0; i < grp.g * o.n_cuts; ++i) q.offsets[i] += need;
+        need += got;
+        return WS_OK;
+      },
+      ls.stats ? &ls : nullptr);
+  if (rc_run) return rc_run;
+  if (o.d_lakes) {
+    *o.n_lakes = need;
+    if (need > o.cap) return fail(c, WS_ERR_CAPACITY, "lake buffer too small");
+    o.offsets[n_slices * o.n_cuts] = need;
+  }
+  return WS_OK;
+}
+
+// what both forms refuse of the cut before anything runs, after check_batch: the cuts and the outputs as the single call, the
+// weights when something reads them, the totals
+int check_cut_batch(ws_ctx *c, size_t n_slices, const Batch &b, const LakeBatchWanted &ls, bool with_stats, const CutBatchOut &o) {
+  if (int rc = cut_cube_check(c, cut_cube_of(b, o, ls, nullptr, nullptr, 0, 0, nullptr, nullptr, 0), with_stats)) return rc;
+  if (with_stats || o.measure())
+    if (int rc = check_lake_batch(c, n_slices, b, ls)) return rc;
+  const size_t plane = b.plane();
+  if (o.d_out && o.plane_stride < plane) return fail(c, WS_ERR_BAD_ARG, "plane_stride is shorter than the plane");
+  // (the host form without a seed list: its batch has no offsets yet, the seeds are counted once the minima are found)
+  return cut_cube_sizes(c, n_slices, b.n_slices ? b.seeds_in(0, b.n_slices) : 0, plane, o.n_cuts, o.d_lakes != nullptr);
+}
+
 }  // namespace
 
 extern "C" {
+
+int ws_merge_tree_cut_catalogue_batch_device(ws_ctx *c, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w, size_t row_stride, size_t slice_stride,
+                                             const uint32_t *d_seeds_rc, const size_t *seed_offsets, const ws_options *opt, const void *d_weight,
+                                             int weight_dtype, size_t weight_row_stride, size_t weight_slice_stride, const ws_lake_cut *cuts,
+                                             size_t n_cuts, ws_tree_node *d_tree, ws_lake_stats *d_stats, uint32_t *d_labels, uint32_t *d_keys_out,
+                                             uint32_t *d_out, size_t plane_stride, ws_lake *d_lakes, ws_lake_stats *d_region_stats, size_t cap,
+                                             size_t *n_lakes, uint64_t *offsets, uint64_t *hidden, ws_lake_stats *hidden_stats, size_t *failed_slice) {
+  if (int rc_open = open_batch(c, failed_slice)) return rc_open;
+  Batch b;
+  if (int rc = check_batch(c, d_cube, n_slices, h, w, row_stride, slice_stride, d_seeds_rc, seed_offsets, opt, &b)) return rc;
+  LakeBatchWanted ls{d_weight, weight_dtype, weight_row_stride, weight_slice_stride, d_stats};
+  CutBatchOut o;
+  o.cuts = cuts; o.n_cuts = n_cuts; o.d_keys_out = d_keys_out; o.d_out = d_out; o.plane_stride = plane_stride; o.d_lakes = d_lakes;
+  o.d_region_stats = d_region_stats; o.cap = cap; o.n_lakes = n_lakes; o.offsets = offsets; o.hidden = hidden; o.hidden_stats = hidden_stats;
+  if (int rc = check_cut_batch(c, n_slices, b, ls, d_stats != nullptr, o)) return rc;
+  if (n_slices == 0 || n_cuts == 0) return WS_OK;
+  if (!d_tree || b.missing_input()) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  if (h * w == 0) ls.weight = nullptr;
+  const size_t plane = b.plane();
+  const auto labels_to_caller = [&](const BatchGroup &grp) -> int {
+    if (d_labels && plane)
+      HIP_TRY(c, hipMemcpyAsync(d_labels + grp.k_first * plane, grp.labels, grp.g * plane * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+    return WS_OK;
+  };
+  const int rc = cut_batch_run(c, b, ls, d_tree, o, failed_slice, labels_to_caller);
+  if (rc) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return WS_OK;
+}
+
+int ws_merge_tree_cut_catalogue_batch(ws_ctx *c, const uint8_t *cube, size_t n_slices, size_t h, size_t w, size_t row_stride, size_t slice_stride,
+                                      const uint64_t *seeds_rc, const size_t *seed_offsets, const ws_options *opt, const void *weight, int weight_dtype,
+                                      size_t weight_row_stride, size_t weight_slice_stride, const ws_lake_cut *cuts, size_t n_cuts, ws_tree_node *tree,
+                                      ws_lake_stats *stats, size_t record_cap, size_t *n_records, uint64_t *out, ws_lake *lakes,
+                                      ws_lake_stats *region_stats, size_t cap, size_t *n_lakes, uint64_t *offsets, uint64_t *hidden,
+                                      ws_lake_stats *hidden_stats, size_t *n_seeds, size_t *failed_slice) {
+  if (int rc_open = open_batch(c, failed_slice)) return rc_open;
+  Batch b;
+  int rc = check_batch(c, nullptr, seeds_rc ? n_slices : 0, h, w, row_stride, slice_stride, nullptr, seed_offsets, opt, &b);
+  if (rc) return rc;
+  const size_t plane = b.plane();
+  bool catalogue = false;      // a cut with a catalogue threshold: the statistics run whether the caller wants the records or not
+  for (size_t j = 0; cuts && j < std::min<size_t>(n_cuts, 32); ++j) catalogue = catalogue || cuts[j].min_sum_w || cuts[j].min_w_max || cuts[j].min_depth;
+  const bool with_stats = stats || catalogue;
+  const LakeBatchWanted want{weight, weight_dtype, weight_row_stride, weight_slice_stride, stats};
+  CutBatchOut o;      // (the checks look at which outputs are wanted, not at where they are)
+  o.cuts = cuts; o.n_cuts = n_cuts; o.d_out = (uint32_t *)out; o.plane_stride = plane; o.d_lakes = lakes; o.d_region_stats = region_stats;
+  o.cap = cap; o.n_lakes = n_lakes; o.offsets = offsets; o.hidden = hidden; o.hidden_stats = hidden_stats;
+  if ((rc = check_cut_batch(c, n_slices, b, want, with_stats, o))) return rc;
+  if (n_slices == 0 || n_cuts == 0) {
+    if (n_records) *n_records = 0;
+    return WS_OK;
+  }
+  if ((!cube && h * w) || (!tree && record_cap)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  std::vector<size_t> offs;
+  if ((rc = upload_batch(c, cube, n_slices, row_stride, slice_stride, seeds_rc, seed_offsets, b, offs, n_seeds, failed_slice))) return rc;
+  const size_t total = offs[n_slices] + n_slices;
+  if (n_records) *n_records = total;
+  if ((rc = cut_cube_sizes(c, n_slices, offs[n_slices], plane, n_cuts, lakes != nullptr))) return rc;
+  if (record_cap < total) return fail(c, WS_ERR_CAPACITY, "record buffers too small");
+  if ((rc = ensure(c, c->tree_out, total * sizeof(ws_tree_node)))) return rc;
+  if (with_stats && (rc = ensure(c, c->lake_out, total * sizeof(ws_lake_stats)))) return rc;
+  if (out && plane && (rc = ensure(c, c->cut_planes, n_slices * n_cuts * plane * sizeof(uint32_t)))) return rc;
+  if (out && (rc = ensure(c, c->out64, std::max<size_t>(plane, 1) * sizeof(uint64_t)))) return rc;      // (the plane-by-plane copy widens there)
+  if (lakes && (rc = ensure(c, c->cut_lakes, std::max<size_t>(cap, 1) * sizeof(ws_lake)))) return rc;
+  if (region_stats && (rc = ensure(c, c->cut_region, std::max<size_t>(cap, 1) * sizeof(ws_lake_stats)))) return rc;
+  LakeBatchWanted ls;
+  ls.stats = with_stats ? (ws_lake_stats *)c->lake_out.p : nullptr;
+  if ((with_stats || o.measure()) && (rc = upload_weights(c, want, n_slices, h, w, ls))) return rc;
+  o.d_out = out && plane ? (uint32_t *)c->cut_planes.p : nullptr;
+  o.d_lakes = lakes ? (ws_lake *)c->cut_lakes.p : nullptr;
+  o.d_region_stats = region_stats ? (ws_lake_stats *)c->cut_region.p : nullptr;
+  if (!o.d_out && !o.d_lakes) {      // (planes of no pixel were all that was asked for: the transforms still run, for their errors)
+    rc = tree_batch_run(c, b, (ws_tree_node *)c->tree_out.p, failed_slice, [](const BatchGroup &) { return (int)WS_OK; }, with_stats ? &ls : nullptr);
+  } else {
+    rc = cut_batch_run(c, b, ls, (ws_tree_node *)c->tree_out.p, o, failed_slice, [](const BatchGroup &) { return (int)WS_OK; });
+  }
+  if (rc) return rc;
+  HIP_TRY(c, hipMemcpyAsync(tree, c->tree_out.p, total * sizeof(ws_tree_node), hipMemcpyDeviceToHost, c->stream));
+  if (stats) HIP_TRY(c, hipMemcpyAsync(stats, c->lake_out.p, total * sizeof(ws_lake_stats), hipMemcpyDeviceToHost, c->stream));
+  if (lakes && *n_lakes) HIP_TRY(c, hipMemcpyAsync(lakes, o.d_lakes, *n_lakes * sizeof(ws_lake), hipMemcpyDeviceToHost, c->stream));
+  if (region_stats && *n_lakes) HIP_TRY(c, hipMemcpyAsync(region_stats, o.d_region_stats, *n_lakes * sizeof(ws_lake_stats), hipMemcpyDeviceToHost, c->stream));
+  if (o.d_out)
+    if ((rc = planes_to_host(c, o.d_out, out, n_slices * n_cuts, plane))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return WS_OK;
+}
 
 // A stack's labels are final as flooded; one ws_segment_device per slice.  The statistics and the stamps left on the context
 // are the last group's or slice's, as after that many single calls.

@@ -242,7 +242,7 @@ void ws_ctx_destroy(ws_ctx *c) {
                     &c->stack_labels, &c->stack_records, &c->stack_bins, &c->batch_cube, &c->batch_seeds, &c->uf_hook, &c->history_planes,
                     &c->tree_order, &c->tree_ws, &c->tree_out, &c->tree_forest, &c->lake_acc, &c->lake_out, &c->lake_weight, &c->tree_seed_px,
                     &c->cut_tables, &c->cut_counts, &c->cut_blocks, &c->cut_flags, &c->cut_planes, &c->cut_lakes, &c->cut_keys,
-                    &c->cut_acc, &c->cut_hidden, &c->cut_region})
+                    &c->cut_acc, &c->cut_hidden, &c->cut_region, &c->cut_forest, &c->cut_slices})
     if (b->p) (void)hipFree(b->p);
   if (c->pinned) (void)hipHostFree(c->pinned);
   host_copy_release(c);

@@ -72,6 +72,9 @@ struct ws_ctx {
   // ws_tree_cut_catalogue_device: the accumulator planes (68 B per list record the call can hold, and per cut) and the cuts' hidden
   // records before they cross the bus; ws_merge_tree_cut_catalogue: the regions' records (72 B each, cap of them)
   wsapi::DevBuf cut_acc, cut_hidden, cut_region;
+  // ws_tree_cut_catalogue_batch_device: the records of every slice with parents as indices into the whole array (16 B a record);
+  // where every (slice, cut) list begins and what it hides (16 B each) and the slices' first records (4 B a slice)
+  wsapi::DevBuf cut_forest, cut_slices;
   uint32_t *pinned = nullptr;      // FLAG_WORDS words of pinned host memory: the host's mirror of the flag block
   uint32_t *pinned_dev = nullptr;  // the same words as the device sees them (nullptr: not mapped, copies only)
   hipEvent_t ring_ev[wsk::COUNTER_RING]{};   // flag slot copied to the host

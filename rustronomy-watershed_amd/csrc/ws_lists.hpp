@@ -22,4 +22,31 @@ int build_tree(ws_ctx *c, const uint32_t *keys, const uint32_t *seg, const uint3
 int build_lake_stats(ws_ctx *c, const uint32_t *keys, const uint32_t *seg, const uint32_t *d_seeds, size_t n_seeds, const ws_options *opt, size_t ph,
                      size_t pw, const ws_tree_node *d_tree, const LakeWeights &wt, ws_lake_stats *d_stats);
 
+// The cut of a cube of slices, or of one group of it (ws_tree_cut.hip): the records of n_slices trees one
+// behind the other (slice k's from seed_offsets[k] - seed_offsets[0] + k on), their stamps and labels as n_slices contiguous h x w
+// planes, the cuts, and the outputs of ws_tree_cut_catalogue_batch_device.  measure: wt is set and the measuring outputs count.
+struct CutCube {
+  const ws_tree_node *d_tree = nullptr;
+  const ws_lake_stats *d_stats = nullptr;
+  size_t n_slices = 0;
+  const size_t *seed_offsets = nullptr;
+  const uint32_t *d_keys = nullptr, *d_seg_labels = nullptr;
+  size_t h = 0, w = 0;
+  const ws_lake_cut *cuts = nullptr;
+  size_t n_cuts = 0;
+  uint32_t *d_out = nullptr;
+  size_t plane_stride = 0;
+  ws_lake *d_lakes = nullptr;
+  ws_lake_stats *d_region_stats = nullptr;
+  size_t cap = 0, *n_lakes = nullptr;
+  uint64_t *offsets = nullptr, *hidden = nullptr;
+  ws_lake_stats *hidden_stats = nullptr;
+  bool measure = false;
+  LakeWeights wt{};
+};
+int cut_cube_check(ws_ctx *c, const CutCube &q, bool have_stats);      // the cuts and the outputs: the single call's refusals
+int cut_cube_sizes(ws_ctx *c, size_t n_slices, size_t seeds, size_t plane, size_t n_cuts, bool lists);      // WS_ERR_TOO_LARGE on the totals
+int cut_cube_reserve(ws_ctx *c, size_t n_slices, size_t seeds, size_t n, const CutCube &q);      // the workspace of a group that large
+int cut_cube_run(ws_ctx *c, const CutCube &q);      // checked arguments, n_slices and n_cuts > 0; WS_ERR_CAPACITY: *n_lakes is the need
+
 }  // namespace wsapi

@@ -21,6 +21,11 @@
 // compacted the counters hold every record's position (k_cut_compact<CUT_INDEX>), k_cut_measure walks again and folds every pixel
 // into the accumulator entry of its region's record (the LakePart fold of ws_lake_part.hpp), and k_cut_measure_write turns the
 // entries into ws_lake_stats records next to d_lakes, the cuts' hidden pixels behind them.  The same driver, with a CutMeasure.
+//
+// ws_tree_cut_catalogue_batch_device (section 4.4.3) is all of that for a cube of slices in one call: the records of every slice
+// checked within their slice and copied with parents as indices into the whole array (k_cut_check_slices), the tables and the walk
+// unchanged on that forest, a pixel's slice found per pixel (CutQuad), counters slice, then cut, then colour and ONE compaction
+// (k_cut_compact_slices).  Its driver (cube_run) is what the cube forms of ws_batch.hip call per group (cut_cube_run).
 #include "ws_ctx.hpp"
 #include "ws_uf.hpp"
 #include "ws_lake_part.hpp"
@@ -138,6 +143,7 @@ __global__ __launch_bounds__(256) void k_cut_table(const TreeRec *__restrict__ t
 constexpr int CUT_SLOTS = 2048, CUT_PROBES = 4;
 constexpr uint32_t CUT_EMPTY = 0xFFFFFFFFu;
 
+template <bool SLICES = false>      // (an instantiation of its own for the cube's kernels: the single-plane kernels keep their code)
 __device__ __forceinline__ void cut_add(uint32_t *s_key, uint32_t *s_cnt, uint32_t *s_used, uint32_t *counts, uint32_t key, uint32_t k) {
   const uint32_t h0 = (key * 2654435761u) >> 21;      // 11 bits
   for (int j = 0; j < CUT_PROBES; ++j) {
@@ -152,6 +158,7 @@ __device__ __forceinline__ void cut_add(uint32_t *s_key, uint32_t *s_cnt, uint32
 // One pixel slot of every lane (weight k: the pixels of the lane's quad that share the key).  The lanes that agree with the wave's
 // first live lane add once -- a coarse cut sends whole waves to a handful of lakes, a low show_level to entry 0 -- the others for
 // themselves.  Called by whole waves.
+template <bool SLICES = false>
 __device__ __forceinline__ void cut_count(uint32_t *s_key, uint32_t *s_cnt, uint32_t *s_used, uint32_t *counts, bool live, uint32_t key, uint32_t k,
                                           int lane) {
   const unsigned long long todo = __builtin_amdgcn_ballot_w64(live);
@@ -161,10 +168,10 @@ __device__ __forceinline__ void cut_count(uint32_t *s_key, uint32_t *s_cnt, uint
   const bool same = live && key == k0;
   if (__popcll(__builtin_amdgcn_ballot_w64(same)) > 1) {      // wave uniform
     const uint32_t total = wave_sum_u32(same ? k : 0u);
-    if (lane == leader) cut_add(s_key, s_cnt, s_used, counts, k0, total);
-    else if (live && !same) cut_add(s_key, s_cnt, s_used, counts, key, k);
+    if (lane == leader) cut_add<SLICES>(s_key, s_cnt, s_used, counts, k0, total);
+    else if (live && !same) cut_add<SLICES>(s_key, s_cnt, s_used, counts, key, k);
   } else if (live) {
-    cut_add(s_key, s_cnt, s_used, counts, key, k);
+    cut_add<SLICES>(s_key, s_cnt, s_used, counts, key, k);
   }
 }
 
@@ -474,6 +481,309 @@ __global__ __launch_bounds__(256) void k_cut_measure_write(const u64c *__restric
   else hidden[i - total] = r;
 }
 
+// ---- a cube of slices (ws_tree_cut_catalogue_batch_device) -------------------------------------------------
+// The records of n_slices trees lie one behind the other: slice k owns records rb[k] .. rb[k + 1] (rb strictly increases: every
+// slice has its record 0), its pixels are plane * k .. plane * (k + 1) of the stamps and the labels.  k_cut_check_slices checks every
+// record WITHIN its slice and writes a copy whose parents are indices into the whole array (the forest), so the table kernels and
+// CutWalk run on it unchanged; a pixel enters at rb[k] + colour and shows a - rb[k].  The counters lie slice, then cut, then colour
+// -- counter n_cuts * rb[k] + slot * (n_k + 1) + v -- so that ONE compaction in index order writes the caller's layout.
+struct CutSlices {
+  const uint32_t *rb;      // n_slices + 1 entries, device
+  uint32_t n_slices, plane, n_cuts;
+};
+
+// the slice that owns entry f of an array in which slice k's entries begin at mul * rb[k]: the same trip count for every thread
+__device__ __forceinline__ uint32_t cut_slice_of(const CutSlices &sl, uint32_t mul, size_t f) {
+  uint32_t lo = 0;
+  for (uint32_t len = sl.n_slices; len > 1;) {
+    const uint32_t half = len >> 1;
+    if ((size_t)mul * sl.rb[lo + half] <= f) lo += half;
+    len -= half;
+  }
+  return lo;
+}
+
+// One lane, one record, as k_cut_check: record c of slice k is alive with no parent, or dies at a level <= 254 into a smaller colour
+// OF THE SAME SLICE that dies strictly later.  The one record of a slice without seeds is not looked at (the single call reads no
+// tree then).  forest[i]: the record with its parent as an index into the whole array, 16 bytes as one store.
+__global__ __launch_bounds__(256) void k_cut_check_slices(const TreeRec *__restrict__ tree, size_t n_rec, CutSlices sl, bool aligned, TreeRec *forest,
+                                                          uint32_t *flags) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const uint32_t k = cut_slice_of(sl, 1u, i < n_rec ? i : n_rec - 1);
+  if (i >= n_rec) return;
+  const uint32_t base = sl.rb[k], c = (uint32_t)i - base, n_k = sl.rb[k + 1] - base - 1u;
+  TreeRec r;
+  if (aligned) {
+    const u32x4_m v = reinterpret_cast<const u32x4_m *>(tree)[i];
+    r = TreeRec{v.x, v.y, v.z, v.w};
+  } else {
+    r = tree[i];
+  }
+  bool ok = true, dead = false;
+  if (n_k != 0u) {
+    if (r.death_level == TREE_ALIVE) ok = r.parent == 0u;
+    else ok = dead = r.death_level <= 254u && r.parent != 0u && r.parent < c && tree[(size_t)base + r.parent].death_level > r.death_level;
+  }
+  if (!ok) atomicOr(&flags[CUT_F_TREE], 1u);
+  reinterpret_cast<u32x4_m *>(forest)[i] = dead ? u32x4_m{base + r.parent, r.death_level, r.area, r.n_leaves} : u32x4_m{0u, TREE_ALIVE, r.area, r.n_leaves};
+}
+
+// The slices of a thread's four pixels i0 .. i0 + 3: slice, pixel within the slice, first record and seed count.  A quad lies in one
+// slice where plane % 4 == 0; otherwise it may straddle two or more, so every pixel has its own.
+struct CutQuad {
+  uint32_t k[4], r[4], base[4], ns[4];
+  __device__ __forceinline__ void locate(const CutSlices &sl, size_t i0, size_t n) {
+    uint32_t kk = i0 < n ? (uint32_t)i0 / sl.plane : 0u, rr = i0 < n ? (uint32_t)i0 % sl.plane : 0u;      // (n < 2^32)
+    uint32_t b = sl.rb[kk], e = sl.rb[kk + 1];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      k[p] = kk; r[p] = rr; base[p] = b; ns[p] = e - b - 1u;
+      if (++rr == sl.plane && kk + 1u < sl.n_slices) { rr = 0u; ++kk; b = e; e = sl.rb[kk + 1]; }
+    }
+  }
+  // the counter of lake v (0: hidden) of the pixel's slice under the cut at `slot`
+  __device__ __forceinline__ uint32_t counter(const CutSlices &sl, int p, uint32_t slot, uint32_t v) const {
+    return sl.n_cuts * base[p] + slot * (ns[p] + 1u) + v;
+  }
+};
+
+// CutWalk::start for the pixels of a cube: the bound of a label is its OWN slice's seed count -- a label above it may be a valid
+// record of the next slice -- compared before it indexes anything; a slice without seeds shows nothing and its labels are not
+// looked at.  Afterwards col[] is the pixel's record in the forest.
+__device__ __forceinline__ void cut_start_slices(CutWalk &wk, const CutQuad &qd, uint32_t *flags) {
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    if (qd.ns[p] == 0u) {
+      wk.col[p] = 0u;
+    } else if (wk.col[p] > qd.ns[p]) {
+      atomicOr(&flags[CUT_F_LABEL], 1u);
+      wk.col[p] = 0u;
+    }
+    wk.walks[p] = wk.col[p] != 0u && wk.arr[p] != 0xFFu;
+    if (wk.walks[p]) wk.col[p] += qd.base[p];
+    wk.a[p] = wk.up[p] = 0u;
+    wk.d[p] = TREE_ALIVE;
+  }
+  wk.table = 0xFFFFFFFFu;
+}
+
+// k_render_cut over the pixels of every slice: the loads, the walks and the workgroup's counting table are its own; plane (k, slot) is
+// at out + (k * n_cuts + slot) * plane_stride, 16-byte stores where out, plane_stride AND plane allow it (quads then lie in one slice).
+template <bool LISTS>
+__global__ __launch_bounds__(256) void k_render_cut_slices(const TreeRec *__restrict__ forest, size_t n_rec, CutSlices sl, const uint32_t *__restrict__ tables,
+                                                           const uint32_t *__restrict__ keys, const uint32_t *__restrict__ labels, size_t n, size_t steps,
+                                                           CutPlan plan, uint32_t *out, size_t plane_stride, uint32_t *counts, uint32_t *flags) {
+  __shared__ uint32_t s_key[LISTS ? CUT_SLOTS : 1], s_cnt[LISTS ? CUT_SLOTS : 1], s_used;
+  const int lane = threadIdx.x & 63;
+  if constexpr (LISTS) {
+    for (int j = threadIdx.x; j < CUT_SLOTS; j += 256) { s_key[j] = CUT_EMPTY; s_cnt[j] = 0; }
+    if (threadIdx.x == 0) s_used = 0;
+    __syncthreads();
+  }
+  uint32_t flushed_at = 0;
+  const bool vec_in = ((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(labels)) & 15u) == 0;
+  const bool vec_out = out && (reinterpret_cast<uintptr_t>(out) & 15u) == 0 && (plane_stride & 3u) == 0 && (sl.plane & 3u) == 0;
+  for (size_t st = 0; st < steps; ++st) {      // workgroup uniform
+    const size_t q = ((size_t)blockIdx.x * steps + st) * 256 + threadIdx.x, i0 = 4 * q;
+    const bool whole = i0 + 3 < n;
+    CutWalk wk;
+    CutQuad qd;
+    bool in[4];
+    cut_load(keys, labels, n, q, vec_in, wk.arr, wk.col, in);
+    qd.locate(sl, i0, n);
+    cut_start_slices(wk, qd, flags);
+    for (uint32_t j = 0; j < plan.n; ++j) {
+      const CutEntry e = plan.e[j];
+      uint32_t v[4];
+      wk.cut(forest, tables, n_rec, e, flags, v);
+#pragma unroll
+      for (int p = 0; p < 4; ++p) v[p] = v[p] ? v[p] - qd.base[p] : 0u;      // (a shown node is never a slice's record 0)
+      if (out) {
+        if (vec_out && whole) {
+          uint32_t *plane = out + ((size_t)qd.k[0] * sl.n_cuts + e.slot) * plane_stride;
+          reinterpret_cast<u32x4_m *>(plane)[qd.r[0] >> 2] = u32x4_m{v[0], v[1], v[2], v[3]};
+        } else {
+#pragma unroll
+          for (int p = 0; p < 4; ++p)
+            if (in[p]) out[((size_t)qd.k[p] * sl.n_cuts + e.slot) * plane_stride + qd.r[p]] = v[p];
+        }
+      }
+      if constexpr (LISTS) {
+        bool live[4];
+        uint32_t key[4], k[4];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) { live[p] = in[p]; k[p] = 1u; key[p] = qd.counter(sl, p, e.slot, v[p]); }
+#pragma unroll
+        for (int p = 1; p < 4; ++p)
+#pragma unroll
+          for (int r = 0; r < p; ++r)
+            if (live[p] && live[r] && key[p] == key[r]) { k[r] += k[p]; live[p] = false; }
+#pragma unroll
+        for (int p = 0; p < 4; ++p) cut_count<true>(s_key, s_cnt, &s_used, counts, live[p], key[p], k[p], lane);
+      }
+    }
+    if constexpr (LISTS) {
+      __syncthreads();
+      const uint32_t used = s_used;      // (nobody inserts between the two barriers: workgroup uniform)
+      const bool full = used - flushed_at > CUT_SLOTS / 2;
+      if (full || st + 1 == steps)
+        for (int j = threadIdx.x; j < CUT_SLOTS; j += 256)
+          if (s_key[j] != CUT_EMPTY) {
+            atomicAdd(&counts[s_key[j]], s_cnt[j]);
+            s_key[j] = CUT_EMPTY;
+            s_cnt[j] = 0;
+          }
+      if (full) flushed_at = used;
+      __syncthreads();
+    }
+  }
+}
+
+// k_cut_compact over the counters of the whole cube in index order, CUT_CHUNK of them a workgroup: a thread finds the slice, the cut
+// and the colour of its first counter by one search and steps on from there (no segment is empty: a slice has its record 0).  Entry
+// 0 of a (slice, cut) segment is its hidden counter and has no record; it sits exactly where that list begins, so the thread that
+// holds it writes seg_first[k * n_cuts + slot] and seg_hidden[...] in the writing pass, and CUT_INDEX leaves total + k * n_cuts +
+// slot there: the accumulator entry of that cut's hidden pixels.
+template <int MODE>
+__global__ __launch_bounds__(256) void k_cut_compact_slices(const uint32_t *__restrict__ counts, size_t n_counters, CutSlices sl, uint32_t *block_n,
+                                                            const u64c *__restrict__ block_base, ws_lake *lakes, uint32_t *index, uint32_t total,
+                                                            u64c *seg_first, u64c *seg_hidden) {
+  __shared__ uint32_t s_n[256];
+  const uint32_t t = threadIdx.x;
+  const uint32_t *cnt = MODE == CUT_INDEX ? index : counts;      // (CUT_INDEX: the counters, read and written through ONE pointer)
+  const size_t f0 = (size_t)blockIdx.x * CUT_CHUNK + (size_t)t * CUT_PER_THREAD;
+  uint32_t k = cut_slice_of(sl, sl.n_cuts, f0 < n_counters ? f0 : n_counters - 1);
+  uint32_t per = sl.rb[k + 1] - sl.rb[k];      // counters of a cut in this slice
+  const uint32_t rel = (uint32_t)((f0 < n_counters ? f0 : n_counters - 1) - (size_t)sl.n_cuts * sl.rb[k]);
+  uint32_t slot = rel / per, v = rel % per;
+  uint32_t area[CUT_PER_THREAD], colour[CUT_PER_THREAD], seg[CUT_PER_THREAD], mine = 0;
+  bool head[CUT_PER_THREAD];
+#pragma unroll
+  for (int j = 0; j < CUT_PER_THREAD; ++j) {
+    const bool valid = f0 + j < n_counters;
+    const uint32_t n = valid ? cnt[f0 + j] : 0u;
+    head[j] = valid && v == 0u;
+    colour[j] = v;
+    seg[j] = k * sl.n_cuts + slot;
+    area[j] = n;
+    mine += !head[j] && n != 0u;
+    if (++v == per) {
+      v = 0u;
+      if (++slot == sl.n_cuts) {
+        slot = 0u;
+        if (++k < sl.n_slices) per = sl.rb[k + 1] - sl.rb[k];
+      }
+    }
+  }
+  s_n[t] = mine;
+  __syncthreads();
+  for (int o = 1; o < 256; o <<= 1) {
+    const uint32_t x = t >= (uint32_t)o ? s_n[t - o] : 0u;
+    __syncthreads();
+    s_n[t] += x;
+    __syncthreads();
+  }
+  if constexpr (MODE == CUT_COUNT) {
+    if (t == 255) block_n[blockIdx.x] = s_n[255];
+  } else {
+    u64c at = block_base[blockIdx.x] + (s_n[t] - mine);
+#pragma unroll
+    for (int j = 0; j < CUT_PER_THREAD; ++j) {
+      if (head[j]) {
+        seg_first[seg[j]] = at;
+        seg_hidden[seg[j]] = area[j];
+        if constexpr (MODE == CUT_INDEX) index[f0 + j] = total + seg[j];
+      } else if (area[j] != 0u) {
+        if (MODE == CUT_WRITE || lakes) lakes[at] = ws_lake{(uint64_t)colour[j], (uint64_t)area[j]};
+        if constexpr (MODE == CUT_INDEX) index[f0 + j] = (uint32_t)at;
+        ++at;
+      }
+    }
+  }
+}
+
+// k_cut_measure over the pixels of every slice: rows, columns and peak_pixel are those of the pixel's own slice, its weight that of
+// the slice's weight plane (lake_weight_of_slice), its accumulator entry index[its counter]; index == nullptr (the hidden pixels
+// alone): entry k * n_cuts + slot.  Every trip count and barrier is the same for all threads of a workgroup.
+template <typename T>
+__global__ __launch_bounds__(256) void k_cut_measure_slices(const TreeRec *__restrict__ forest, size_t n_colours, CutSlices sl, const uint32_t *__restrict__ tables,
+                                                            const uint32_t *__restrict__ keys, const uint32_t *__restrict__ labels, size_t n, size_t steps,
+                                                            CutPlan plan, const uint32_t *__restrict__ index, LakeWeights wt, uint32_t W, u64c *sum,
+                                                            uint32_t *box, size_t n_rec, uint32_t *flags) {
+  __shared__ u64c s_sum[6 * LAKE_SLOTS];
+  __shared__ uint32_t s_box[5 * LAKE_SLOTS], s_key[LAKE_SLOTS], s_used;
+  for (int j = threadIdx.x; j < LAKE_SLOTS; j += 256) {
+    s_key[j] = LAKE_EMPTY;
+    lake_store(s_sum, s_box, LAKE_SLOTS, j, lake_none());
+  }
+  if (threadIdx.x == 0) s_used = 0;
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const bool vec_in = ((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(labels)) & 15u) == 0;
+  uint32_t flushed_at = 0;
+  for (size_t st = 0; st < steps; ++st) {      // workgroup uniform
+    const size_t q = ((size_t)blockIdx.x * steps + st) * 256 + threadIdx.x, i0 = 4 * q;
+    CutWalk wk;
+    CutQuad qd;
+    bool in[4];
+    cut_load(keys, labels, n, q, vec_in, wk.arr, wk.col, in);
+    qd.locate(sl, i0, n);
+    cut_start_slices(wk, qd, flags);
+    uint32_t wv[4], yy[4], xx[4];      // the four pixels' weights, rows and columns within their slices
+    {
+      uint32_t y = qd.r[0] / W, x = qd.r[0] % W;
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        if (p && qd.r[p] == 0u) y = x = 0u;      // the next slice begins
+        wv[p] = in[p] ? lake_weight_of_slice<T>(wt, qd.k[p], y, x) : 0u;
+        yy[p] = y; xx[p] = x;
+        if (++x == W) { x = 0; ++y; }
+      }
+    }
+    for (uint32_t j = 0; j < plan.n; ++j) {
+      const CutEntry e = plan.e[j];
+      uint32_t v[4], key[4];
+      wk.cut(forest, tables, n_colours, e, flags, v);
+      bool live[4];
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        v[p] = v[p] ? v[p] - qd.base[p] : 0u;
+        live[p] = in[p] && (index != nullptr || v[p] == 0u);
+        key[p] = index ? qd.counter(sl, p, e.slot, v[p]) : qd.k[p] * sl.n_cuts + e.slot;
+      }
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {      // one part at a time, as k_cut_measure
+        LakePart part = lake_pixel(wv[p], yy[p], xx[p], qd.r[p]);
+#pragma unroll
+        for (int r = p + 1; r < 4; ++r)
+          if (live[p] && live[r] && key[r] == key[p]) {
+            lake_join(part, lake_pixel(wv[r], yy[r], xx[r], qd.r[r]));
+            live[r] = false;
+          }
+        const unsigned long long todo = __builtin_amdgcn_ballot_w64(live[p]);
+        if (todo == 0) continue;      // wave uniform
+        const uint32_t at = !live[p] ? 0u : index ? index[key[p]] : key[p];      // ONE look-up a lake and lane
+        const int leader = (int)__builtin_ctzll(todo);
+        const uint32_t at0 = (uint32_t)__builtin_amdgcn_readlane((int)at, leader);
+        const bool same = live[p] && at == at0;
+        if (__popcll(__builtin_amdgcn_ballot_w64(same)) > 1) {      // wave uniform
+          const LakePart total = lake_wave_total(same ? part : lake_none());
+          if (lane == leader) lake_add(s_key, s_sum, s_box, &s_used, sum, box, n_rec, at0, total);
+          else if (live[p] && !same) lake_add(s_key, s_sum, s_box, &s_used, sum, box, n_rec, at, part);
+        } else if (live[p]) {
+          lake_add(s_key, s_sum, s_box, &s_used, sum, box, n_rec, at, part);
+        }
+      }
+      __syncthreads();
+      const uint32_t used = s_used;      // (nobody inserts between the two barriers: workgroup uniform)
+      const bool full = used - flushed_at > LAKE_SLOTS / 2;
+      if (full || (st + 1 == steps && j + 1 == plan.n)) lake_flush(s_key, s_sum, s_box, sum, box, n_rec);
+      if (full) flushed_at = used;
+      __syncthreads();
+    }
+  }
+}
+
 }  // namespace wsk
 
 namespace {
@@ -746,6 +1056,162 @@ int cut_run(ws_ctx *c, const ws_tree_node *d_tree, const ws_lake_stats *d_stats,
   return WS_OK;
 }
 
+// ---- the cut of a cube of slices --------------------------------------------------------------------------
+// The context's workspace of a cube (or of one group of a cube) of n_slices slices with `seeds` seeds and n pixels in all: the
+// forest (16 B a record), the tables and, with lists, the counters (4 B a record and cut each), 12 B per CUT_CHUNK counters, the
+// slices' first records (4 B a slice) and 16 B per slice and cut for where a list begins and what it hides; measuring: the
+// accumulators (68 B per record the call can end with and per slice and cut) and 72 B per slice and cut of hidden records.  No
+// term pads a slice.
+int cube_reserve(ws_ctx *c, size_t n_slices, size_t seeds, size_t n, const Cuts &cs, bool lists, bool measure, bool records, size_t cap) {
+  const size_t n_rec = seeds + n_slices, n_cuts = cs.n, nsc = n_slices * n_cuts;
+  const CutSource src = cut_source(make_plan(cs));
+  int rc;
+  if ((rc = ensure(c, c->cut_forest, n_rec * sizeof(TreeRec)))) return rc;
+  if ((rc = ensure(c, c->cut_slices, 2 * nsc * sizeof(u64c) + (n_slices + 1) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, c->cut_tables, n_cuts * n_rec * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, c->cut_flags, CUT_F_WORDS * sizeof(uint32_t)))) return rc;
+  if (src == CUT_KEYS && (rc = ensure(c, c->cut_keys, n_rec * sizeof(CutKey)))) return rc;
+  if (lists) {
+    if ((rc = ensure(c, c->cut_counts, n_cuts * n_rec * sizeof(uint32_t)))) return rc;
+    if ((rc = ensure(c, c->cut_blocks, cut_blocks(n_cuts * n_rec) * (sizeof(uint32_t) + sizeof(u64c))))) return rc;
+  }
+  if (measure) {
+    const size_t entries = (records ? std::min(cap, n_cuts * std::min(seeds, n)) : 0) + nsc;
+    if ((rc = ensure(c, c->cut_acc, entries * LAKE_ACC_BYTES))) return rc;
+    if ((rc = ensure(c, c->cut_hidden, nsc * sizeof(ws_lake_stats)))) return rc;
+  }
+  return WS_OK;
+}
+
+// What every cube form checks of its cut outputs before anything runs (the single call's refusals)
+int cube_check_outputs(ws_ctx *c, const Cuts &cs, bool have_stats, const uint32_t *d_out, const ws_lake *d_lakes, const ws_lake_stats *region,
+                       const size_t *n_lakes, const uint64_t *offsets, const uint64_t *hidden) {
+  if (!d_out && !d_lakes) return fail(c, WS_ERR_BAD_ARG, "no output: d_out and d_lakes are both null");
+  if (d_lakes && (!n_lakes || !offsets || !hidden)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  if (region && !d_lakes) return fail(c, WS_ERR_BAD_ARG, "d_region_stats needs d_lakes: the records lie next to the lists");
+  if (int rc = check_cuts(c, cs)) return rc;
+  if (cs.catalogue && !have_stats) return fail(c, WS_ERR_BAD_ARG, "a cut has a catalogue threshold and d_stats is null");
+  return WS_OK;
+}
+
+// The driver of the cube forms on checked arguments: q.n_slices > 0, 1 .. 32 cuts, n_slices * h * w < 2^32 and, with lists,
+// n_cuts * (seeds + n_slices) < 2^32.  Order: the slices' first records up, ONE check pass and ONE verdict for all records, the
+// tables over the forest, the render, (lists) count -- host sums -- write, (measuring) init, fold, records.  Lists, offsets and
+// hidden counts are the cube's own, from 0; q.cap too small: *n_lakes is the need, WS_ERR_CAPACITY, nothing else written.
+int cube_run(ws_ctx *c, const CutCube &q, const Cuts &cs) {
+  const size_t plane = q.h * q.w, n = q.n_slices * plane, n_cuts = cs.n, nsc = q.n_slices * n_cuts;
+  const size_t seeds = q.seed_offsets[q.n_slices] - q.seed_offsets[0], n_rec = seeds + q.n_slices;
+  const bool lists = q.d_lakes != nullptr, measure = q.measure && (q.d_region_stats || q.hidden_stats), records = measure && q.d_region_stats;
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (n == 0) {      // no pixel: nothing is shown and nothing is hidden
+    if (lists) {
+      *q.n_lakes = 0;
+      for (size_t i = 0; i < nsc; ++i) q.offsets[i] = q.hidden[i] = 0;
+      q.offsets[nsc] = 0;
+    }
+    for (size_t i = 0; measure && q.hidden_stats && i < nsc; ++i) q.hidden_stats[i] = LAKE_IDENTITY;
+    return WS_OK;
+  }
+  if (int rc = cube_reserve(c, q.n_slices, seeds, n, cs, lists, measure, records, q.cap)) return rc;
+  const CutPlan plan = make_plan(cs);
+  const CutSource src = cut_source(plan);
+  std::vector<uint32_t> rb(q.n_slices + 1);
+  for (size_t k = 0; k <= q.n_slices; ++k) rb[k] = (uint32_t)(q.seed_offsets[k] - q.seed_offsets[0] + k);
+  u64c *seg_first = (u64c *)c->cut_slices.p, *seg_hidden = seg_first + nsc;
+  uint32_t *d_rb = (uint32_t *)(seg_hidden + nsc);
+  const CutSlices sl{d_rb, (uint32_t)q.n_slices, (uint32_t)plane, (uint32_t)n_cuts};
+  const TreeRec *forest = (const TreeRec *)c->cut_forest.p;
+  uint32_t *flags = (uint32_t *)c->cut_flags.p, *tables = (uint32_t *)c->cut_tables.p, *counts = lists ? (uint32_t *)c->cut_counts.p : nullptr;
+  uint32_t seen[CUT_F_WORDS];
+  HIP_TRY(c, hipMemcpyAsync(d_rb, rb.data(), rb.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemsetAsync(flags, 0, CUT_F_WORDS * sizeof(uint32_t), c->stream));
+  if (seeds) {      // the records first, and the verdict on the host before anything walks (no seed at all: nothing walks, no record is read)
+    const unsigned per_rec = (unsigned)((n_rec + 255) / 256);
+    k_cut_check_slices<<<per_rec, 256, 0, c->stream>>>(reinterpret_cast<const TreeRec *>(q.d_tree), n_rec, sl, (reinterpret_cast<uintptr_t>(q.d_tree) & 15u) == 0,
+                                                       (TreeRec *)c->cut_forest.p, flags);
+    HIP_TRY(c, hipGetLastError());
+    if (int rc = read_flags(c, seen)) return rc;
+    if (seen[CUT_F_TREE]) return fail(c, WS_ERR_BAD_ARG, "d_tree is not a merge tree within every slice (ws_merge_tree_batch_device's records)");
+    const dim3 table_grid(per_rec, plan.n_tables);
+    const LakeRec *stats = reinterpret_cast<const LakeRec *>(q.d_stats);
+    if (src == CUT_TREE_ONLY) {
+      k_cut_table<CUT_TREE_ONLY><<<table_grid, 256, 0, c->stream>>>(forest, nullptr, nullptr, n_rec, plan, tables, flags);
+    } else if (src == CUT_RECORDS) {
+      k_cut_table<CUT_RECORDS><<<table_grid, 256, 0, c->stream>>>(forest, nullptr, stats, n_rec, plan, tables, flags);
+    } else {
+      CutKey *ckeys = (CutKey *)c->cut_keys.p;
+      k_cut_keys<<<per_rec, 256, 0, c->stream>>>(forest, stats, n_rec, ckeys);
+      HIP_TRY(c, hipGetLastError());
+      k_cut_table<CUT_KEYS><<<table_grid, 256, 0, c->stream>>>(forest, ckeys, nullptr, n_rec, plan, tables, flags);
+    }
+    HIP_TRY(c, hipGetLastError());
+  }
+  const size_t n_counters = n_cuts * n_rec;
+  if (lists) HIP_TRY(c, hipMemsetAsync(counts, 0, n_counters * sizeof(uint32_t), c->stream));
+  // the grids of cut_run: 1024 pixels a step, with lists at most 4096 workgroups
+  const size_t runs = (n + 1023) / 1024, list_steps = std::max<size_t>((runs + 4095) / 4096, 1), steps = lists ? list_steps : 1;
+  {
+    const unsigned blocks = (unsigned)((runs + steps - 1) / steps);
+    if (lists) k_render_cut_slices<true><<<blocks, 256, 0, c->stream>>>(forest, n_rec, sl, tables, q.d_keys, q.d_seg_labels, n, steps, plan, q.d_out, q.plane_stride, counts, flags);
+    else k_render_cut_slices<false><<<blocks, 256, 0, c->stream>>>(forest, n_rec, sl, tables, q.d_keys, q.d_seg_labels, n, steps, plan, q.d_out, q.plane_stride, nullptr, flags);
+    HIP_TRY(c, hipGetLastError());
+  }
+  const auto measure_slices = [&](const uint32_t *index, size_t total) -> int {
+    const size_t n_acc = total + nsc;
+    u64c *sum = (u64c *)c->cut_acc.p;
+    uint32_t *box = (uint32_t *)(sum + 6 * n_acc);
+    LakeRec *d_hidden = (LakeRec *)c->cut_hidden.p;
+    const unsigned per_entry = (unsigned)((n_acc + 255) / 256), blocks = (unsigned)((runs + list_steps - 1) / list_steps);
+    k_lake_init<<<per_entry, 256, 0, c->stream>>>(sum, box, n_acc);
+    HIP_TRY(c, hipGetLastError());
+    if (q.wt.u16)
+      k_cut_measure_slices<uint16_t><<<blocks, 256, 0, c->stream>>>(forest, n_rec, sl, tables, q.d_keys, q.d_seg_labels, n, list_steps, plan, index, q.wt, (uint32_t)q.w, sum, box, n_acc, flags);
+    else
+      k_cut_measure_slices<uint8_t><<<blocks, 256, 0, c->stream>>>(forest, n_rec, sl, tables, q.d_keys, q.d_seg_labels, n, list_steps, plan, index, q.wt, (uint32_t)q.w, sum, box, n_acc, flags);
+    HIP_TRY(c, hipGetLastError());
+    k_cut_measure_write<<<per_entry, 256, 0, c->stream>>>(sum, box, n_acc, total, reinterpret_cast<LakeRec *>(q.d_region_stats), d_hidden);
+    HIP_TRY(c, hipGetLastError());
+    if (q.hidden_stats) HIP_TRY(c, hipMemcpyAsync(q.hidden_stats, d_hidden, nsc * sizeof(ws_lake_stats), hipMemcpyDeviceToHost, c->stream));
+    return WS_OK;
+  };
+  if (!lists) {
+    if (int rc = read_flags(c, seen)) return rc;
+    if (seen[CUT_F_LABEL]) return fail(c, WS_ERR_BAD_ARG, "a label above its slice's seed count in d_seg_labels");
+    if (seen[CUT_F_STEPS]) return fail(c, WS_ERR_BAD_ARG, "a walk did not end: d_tree changed under the call");
+    if (measure) {      // (no list, so no record: the hidden pixels alone)
+      if (int rc = measure_slices(nullptr, 0)) return rc;
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    return WS_OK;
+  }
+  const size_t nb = cut_blocks(n_counters);
+  u64c *block_base = (u64c *)c->cut_blocks.p;
+  uint32_t *block_n = (uint32_t *)(block_base + nb);
+  k_cut_compact_slices<CUT_COUNT><<<(unsigned)nb, 256, 0, c->stream>>>(counts, n_counters, sl, block_n, nullptr, nullptr, nullptr, 0u, nullptr, nullptr);
+  HIP_TRY(c, hipGetLastError());
+  std::vector<uint32_t> host_n(nb);
+  std::vector<u64c> host_base(nb), host_seg(2 * nsc);
+  HIP_TRY(c, hipMemcpyAsync(host_n.data(), block_n, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  if (int rc = read_flags(c, seen)) return rc;
+  if (seen[CUT_F_LABEL]) return fail(c, WS_ERR_BAD_ARG, "a label above its slice's seed count in d_seg_labels");
+  if (seen[CUT_F_STEPS]) return fail(c, WS_ERR_BAD_ARG, "a walk did not end: d_tree changed under the call");
+  u64c total = 0;
+  for (size_t b = 0; b < nb; ++b) { host_base[b] = total; total += host_n[b]; }
+  *q.n_lakes = (size_t)total;
+  if (total > q.cap) return fail(c, WS_ERR_CAPACITY, "lake buffer too small");
+  HIP_TRY(c, hipMemcpyAsync(block_base, host_base.data(), nb * sizeof(u64c), hipMemcpyHostToDevice, c->stream));
+  if (records) k_cut_compact_slices<CUT_INDEX><<<(unsigned)nb, 256, 0, c->stream>>>(nullptr, n_counters, sl, nullptr, block_base, q.d_lakes, counts, (uint32_t)total, seg_first, seg_hidden);
+  else k_cut_compact_slices<CUT_WRITE><<<(unsigned)nb, 256, 0, c->stream>>>(counts, n_counters, sl, nullptr, block_base, q.d_lakes, nullptr, 0u, seg_first, seg_hidden);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(host_seg.data(), seg_first, 2 * nsc * sizeof(u64c), hipMemcpyDeviceToHost, c->stream));
+  if (measure)
+    if (int rc = measure_slices(records ? counts : nullptr, records ? (size_t)total : 0)) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (size_t i = 0; i < nsc; ++i) { q.offsets[i] = host_seg[i]; q.hidden[i] = host_seg[nsc + i]; }
+  q.offsets[nsc] = total;
+  return WS_OK;
+}
+
 // ws_merge_tree_cut and ws_merge_tree_stats_cut: the transform's host form (with lw: ws_merge_tree_stats, whose catalogue stays on
 // the context next to the records, the labels and the stamps), the device call on what it left there, the download.
 struct CutWeights {
@@ -826,7 +1292,64 @@ int merge_tree_cut_host(ws_ctx *c, const uint8_t *img, size_t h, size_t w, size_
 
 }  // namespace
 
+namespace wsapi {
+
+// what ws_batch.hip calls of the cube's cut (ws_lists.hpp)
+int cut_cube_check(ws_ctx *c, const CutCube &q, bool have_stats) {
+  return cube_check_outputs(c, take_cuts(q.cuts, q.n_cuts), have_stats, q.d_out, q.d_lakes, q.measure ? q.d_region_stats : nullptr, q.n_lakes, q.offsets,
+                            q.hidden);
+}
+
+int cut_cube_sizes(ws_ctx *c, size_t n_slices, size_t seeds, size_t plane, size_t n_cuts, bool lists) {
+  if (plane && n_slices > 0xFFFFFFFFull / plane) return fail(c, WS_ERR_TOO_LARGE, "the cube has 2^32 pixels or more");
+  if (seeds + n_slices >= 0xFFFFFFFFull) return fail(c, WS_ERR_TOO_LARGE, "too many seeds");
+  if (lists && n_cuts * (seeds + n_slices) > 0xFFFFFFFFull) return fail(c, WS_ERR_TOO_LARGE, "lists: cuts x (seeds + slices) must stay below 2^32");
+  return WS_OK;
+}
+
+int cut_cube_reserve(ws_ctx *c, size_t n_slices, size_t seeds, size_t n, const CutCube &q) {
+  const bool measure = q.measure && (q.d_region_stats || q.hidden_stats);
+  return cube_reserve(c, n_slices, seeds, n, take_cuts(q.cuts, q.n_cuts), q.d_lakes != nullptr, measure, measure && q.d_region_stats, q.cap);
+}
+
+int cut_cube_run(ws_ctx *c, const CutCube &q) { return cube_run(c, q, take_cuts(q.cuts, q.n_cuts)); }
+
+}  // namespace wsapi
+
 extern "C" {
+
+int ws_tree_cut_catalogue_batch_device(ws_ctx *c, const ws_tree_node *d_tree, const ws_lake_stats *d_stats, size_t n_slices, const size_t *seed_offsets,
+                                       const uint32_t *d_keys, const uint32_t *d_seg_labels, size_t h, size_t w, const void *d_weight, int weight_dtype,
+                                       size_t weight_row_stride, size_t weight_slice_stride, const ws_lake_cut *cuts, size_t n_cuts, uint32_t *d_out,
+                                       size_t plane_stride, ws_lake *d_lakes, ws_lake_stats *d_region_stats, size_t cap, size_t *n_lakes,
+                                       uint64_t *offsets, uint64_t *hidden, ws_lake_stats *hidden_stats) {
+  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
+  if (!c) return WS_ERR_BAD_ARG;
+  if (n_slices && !seed_offsets) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  for (size_t k = 0; k < n_slices; ++k)
+    if (seed_offsets[k + 1] < seed_offsets[k]) return fail(c, WS_ERR_BAD_ARG, "seed_offsets must not decrease");
+  const size_t seeds = n_slices ? seed_offsets[n_slices] - seed_offsets[0] : 0;
+  if (h && h * w / h != w) return fail(c, WS_ERR_TOO_LARGE, "plane too large");
+  const size_t plane = h * w;
+  if ((!d_tree && seeds) || ((!d_keys || !d_seg_labels) && plane && n_slices)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  CutCube q;
+  q.d_tree = d_tree; q.d_stats = d_stats; q.n_slices = n_slices; q.seed_offsets = seed_offsets; q.d_keys = d_keys; q.d_seg_labels = d_seg_labels;
+  q.h = h; q.w = w; q.cuts = cuts; q.n_cuts = n_cuts; q.d_out = d_out; q.plane_stride = plane_stride; q.d_lakes = d_lakes;
+  q.d_region_stats = d_region_stats; q.cap = cap; q.n_lakes = n_lakes; q.offsets = offsets; q.hidden = hidden; q.hidden_stats = hidden_stats;
+  q.measure = d_region_stats || hidden_stats;
+  if (int rc = cut_cube_check(c, q, d_stats != nullptr)) return rc;
+  if (int rc = cut_cube_sizes(c, n_slices, seeds, plane, n_cuts, d_lakes != nullptr)) return rc;
+  if (d_out && plane_stride < plane) return fail(c, WS_ERR_BAD_ARG, "plane_stride is shorter than the plane");
+  if (d_out && plane && n_slices && (d_out == d_keys || d_out == d_seg_labels)) return fail(c, WS_ERR_BAD_ARG, "d_out must not be an input plane");
+  if (q.measure) {      // (nothing to measure: the weight arguments are not looked at)
+    if (!d_weight) return fail(c, WS_ERR_BAD_ARG, "this form has no image: d_weight is null");
+    if (int rc = check_lake_weights(c, w, h, w, d_weight, weight_dtype, weight_row_stride)) return rc;
+    if (n_slices > 1 && weight_slice_stride < h * weight_row_stride) return fail(c, WS_ERR_BAD_ARG, "weight_slice_stride < h * weight_row_stride");
+    q.wt = LakeWeights{d_weight, weight_row_stride, (uint32_t)h, (uint32_t)w, 0u, weight_dtype == WS_U16, weight_slice_stride};
+  }
+  if (n_slices == 0 || n_cuts == 0) return WS_OK;
+  return cut_cube_run(c, q);
+}
 
 int ws_tree_cut_device(ws_ctx *c, const ws_tree_node *d_tree, size_t n_seeds, const uint32_t *d_keys, const uint32_t *d_seg_labels, size_t h,
                        size_t w, const ws_tree_cut *cuts, size_t n_cuts, uint32_t *d_out, size_t plane_stride, ws_lake *d_lakes, size_t cap,

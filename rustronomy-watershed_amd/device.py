@@ -562,5 +562,128 @@ class DeviceEngine:
                                                                        labels.data_ptr() if want_labels else None, ctypes.byref(failed)))
         return (out, out_stats, labels) if want_labels else (out, out_stats)
 
+    @staticmethod
+    def _cube_weights(weights, shape):
+        """(pointer, dtype, row stride, slice stride) of a 3-D weight tensor of `shape` with contiguous rows."""
+        s, h, w = shape
+        u16 = {torch.int16, getattr(torch, "uint16", torch.int16)}
+        if weights.dtype != torch.uint8 and weights.dtype not in u16:
+            raise TypeError("weights must be a uint8, uint16 or int16 (u16 bits) tensor")
+        if not weights.is_cuda or weights.dim() != 3 or tuple(weights.shape) != (s, h, w) or (w > 1 and weights.stride(2) != 1):
+            raise ValueError(f"weights must be a device tensor of shape {(s, h, w)} with contiguous rows")
+        wrow = weights.stride(1) if h > 1 else w
+        return weights.data_ptr(), _ffi.WS_DTYPES["uint8" if weights.dtype == torch.uint8 else "uint16"], wrow, weights.stride(0) if s > 1 else h * wrow
+
+    def tree_cut_catalogue_batch(self, tree, keys, labels, seed_offsets, cuts, weights=None, stats=None, want_planes=True, want_lakes=True,
+                                 measure=True, cap=None):
+        """tree_cut_catalogue of every slice of a cube in one call, from records and planes in HBM
+        (ws_tree_cut_catalogue_batch_device).  tree (and stats, optional) in the slice-major layout of merge_tree(_stats)_batch;
+        keys and labels: (S, H', W') int32 device tensors, contiguous; seed_offsets: S + 1 host integers; weights: an (S, H', W')
+        uint8 or int16 / uint16 device tensor with contiguous rows (needed when measure).  Returns (planes | None, lakes,
+        region_stats, offsets, hidden, hidden_stats): planes (S, K, H', W') int32; lakes (n, 2) int64 and region_stats (n, 9)
+        int64 device tensors, list (k, j) at offsets[k * K + j] : offsets[k * K + j + 1] in slice k's own colours; offsets
+        (S * K + 1), hidden (S * K) and hidden_stats (S * K, 9) numpy.  measure=False: no region or hidden records (None)."""
+        import numpy as np
+        from .api import _as_lake_cuts, _cut_list
+        lst = _cut_list(cuts)
+        if stats is None and any(c.catalogue for c in lst):
+            raise ValueError("a cut has a catalogue threshold: pass stats, the catalogue of merge_tree_stats_batch")
+        arr, k = _as_lake_cuts(lst)
+        if keys.dim() != 3 or tuple(keys.shape) != tuple(labels.shape):
+            raise ValueError("keys and labels must be 3-D tensors of the same shape")
+        s, h, w = keys.shape
+        offs = np.ascontiguousarray(np.asarray(seed_offsets, dtype=np.uint64))
+        if offs.shape != (s + 1,):
+            raise ValueError("seed_offsets must hold one entry per slice and one more")
+        total = int(offs[-1]) - int(offs[0]) + s
+        if tree.dim() != 2 or tuple(tree.shape) != (total, 4):
+            raise ValueError(f"tree must be a {(total, 4)} tensor")
+        assert tree.dtype == torch.int32 and tree.is_cuda and tree.is_contiguous()
+        if stats is not None:
+            if tuple(stats.shape) != (total, 9):
+                raise ValueError(f"stats must be a {(total, 9)} tensor")
+            assert stats.dtype == torch.int64 and stats.is_cuda and stats.is_contiguous()
+        assert keys.dtype == torch.int32 and labels.dtype == torch.int32 and keys.is_cuda and labels.is_cuda
+        assert keys.numel() == 0 or (keys.is_contiguous() and labels.is_contiguous())
+        if not want_planes and not want_lakes:
+            raise ValueError("nothing asked for: want_planes and want_lakes are both False")
+        if measure and weights is None:
+            raise ValueError("tree_cut_catalogue_batch has no image: the records need weights")
+        wptr, dtype, wrow, wslice = self._cube_weights(weights, (s, h, w)) if measure else (None, 0, 0, 0)
+        out = torch.empty((s, k, h, w), dtype=torch.int32, device=self.device) if want_planes else None
+        offsets = np.zeros(s * k + 1, dtype=np.uint64)
+        hidden = np.zeros(max(s * k, 1), dtype=np.uint64)
+        hidden_stats = np.zeros((max(s * k, 1), 9), dtype=np.int64) if measure else None
+        n = ctypes.c_size_t(0)
+        if cap is None:
+            cap = max(min(total - s, s * h * w), 1) * max(k, 1)
+        lakes = torch.empty((max(cap, 1), 2), dtype=torch.int64, device=self.device) if want_lakes else None
+        region = torch.empty((max(cap, 1), 9), dtype=torch.int64, device=self.device) if want_lakes and measure else None
+        self.ctx.check(_ffi.lib().ws_tree_cut_catalogue_batch_device(
+            self.ctx.handle, tree.data_ptr(), stats.data_ptr() if stats is not None else None, s,
+            offs.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)), keys.data_ptr(), labels.data_ptr(), h, w, wptr, dtype, wrow, wslice, arr, k,
+            out.data_ptr() if want_planes else None, h * w, lakes.data_ptr() if want_lakes else None,
+            region.data_ptr() if region is not None else None, cap if want_lakes else 0, ctypes.byref(n), offsets.ctypes.data, hidden.ctypes.data,
+            hidden_stats.ctypes.data if measure else None))
+        return (out, lakes[: n.value] if want_lakes else None, region[: n.value] if region is not None else None, offsets, hidden[: s * k],
+                hidden_stats[: s * k] if measure else None)
+
+    def merge_tree_cut_catalogue_batch(self, cube, seeds, seed_offsets, cuts, weights=None, max_level=254, edge=False, seed_shift=False,
+                                       want_stats=True, want_labels=False, want_keys=False, want_planes=True, want_lakes=True, measure=True,
+                                       cap=None):
+        """Cube in, everything out (ws_merge_tree_cut_catalogue_batch_device): the trees (and with want_stats the catalogues) of
+        merge_tree_stats_batch and the cut catalogue of every slice in one call, each stacked group cut while its stamps are on
+        the device.  cube, seeds, seed_offsets and weights (None: the cube itself) as merge_tree_stats_batch; cuts as
+        tree_cut_catalogue_batch.  Returns a dict: tree, stats (None without want_stats), labels and keys ((S, H', W') int32, when
+        asked: what tree_cut_catalogue_batch needs to cut the same flood again), planes ((S, K, H', W') | None), lakes,
+        region_stats, offsets, hidden, hidden_stats, and `slices`: per slice a tuple (planes, lakes, region_stats, offsets,
+        hidden, hidden_stats) of views, offsets from 0, as tree_cut_catalogue returns them."""
+        import numpy as np
+        from .api import _as_lake_cuts, _cut_list
+        lst = _cut_list(cuts)
+        if not want_stats and any(c.catalogue for c in lst):
+            raise ValueError("a cut has a catalogue threshold: the catalogue is needed (want_stats)")
+        arr, k = _as_lake_cuts(lst)
+        offs = self._batch_args(cube, seeds, seed_offsets)
+        s, h, w = cube.shape
+        e = 2 if edge else 0
+        ph, pw = h + e, w + e
+        if not want_planes and not want_lakes:
+            raise ValueError("nothing asked for: want_planes and want_lakes are both False")
+        wptr, dtype, wrow, wslice = self._cube_weights(weights, (s, h, w)) if weights is not None else (None, 0, 0, 0)
+        total = int(seed_offsets[-1]) - int(seed_offsets[0]) + s
+        tree = torch.empty((total, 4), dtype=torch.int32, device=self.device)
+        stats = torch.empty((total, 9), dtype=torch.int64, device=self.device) if want_stats else None
+        labels = torch.empty((s, ph, pw), dtype=torch.int32, device=self.device) if want_labels else None
+        keys = torch.empty((s, ph, pw), dtype=torch.int32, device=self.device) if want_keys else None
+        out = torch.empty((s, k, ph, pw), dtype=torch.int32, device=self.device) if want_planes else None
+        offsets = np.zeros(s * k + 1, dtype=np.uint64)
+        hidden = np.zeros(max(s * k, 1), dtype=np.uint64)
+        hidden_stats = np.zeros((max(s * k, 1), 9), dtype=np.int64) if measure else None
+        n = ctypes.c_size_t(0)
+        if cap is None:
+            cap = max(min(total - s, s * ph * pw), 1) * max(k, 1)
+        lakes = torch.empty((max(cap, 1), 2), dtype=torch.int64, device=self.device) if want_lakes else None
+        region = torch.empty((max(cap, 1), 9), dtype=torch.int64, device=self.device) if want_lakes and measure else None
+        opt = self.options(max_level, edge, None, seed_shift)
+        failed = ctypes.c_size_t(0)
+        self.ctx.check(_ffi.lib().ws_merge_tree_cut_catalogue_batch_device(
+            self.ctx.handle, cube.data_ptr(), s, h, w, w, h * w, seeds.data_ptr() if seeds.numel() else None, offs, ctypes.byref(opt),
+            wptr, dtype, wrow, wslice, arr, k, tree.data_ptr(), stats.data_ptr() if want_stats else None,
+            labels.data_ptr() if want_labels else None, keys.data_ptr() if want_keys else None, out.data_ptr() if want_planes else None, ph * pw,
+            lakes.data_ptr() if want_lakes else None, region.data_ptr() if region is not None else None, cap if want_lakes else 0, ctypes.byref(n),
+            offsets.ctypes.data, hidden.ctypes.data, hidden_stats.ctypes.data if measure else None, ctypes.byref(failed)))
+        res = dict(tree=tree, stats=stats, labels=labels, keys=keys, planes=out, lakes=lakes[: n.value] if want_lakes else None,
+                   region_stats=region[: n.value] if region is not None else None, offsets=offsets, hidden=hidden[: s * k],
+                   hidden_stats=hidden_stats[: s * k] if measure else None)
+        per = []
+        for i in range(s):
+            lo, hi = int(offsets[i * k]), int(offsets[(i + 1) * k])
+            per.append((out[i] if want_planes else None, res["lakes"][lo:hi] if want_lakes else None,
+                        res["region_stats"][lo:hi] if region is not None else None, offsets[i * k: (i + 1) * k + 1] - offsets[i * k],
+                        hidden[i * k: (i + 1) * k], hidden_stats[i * k: (i + 1) * k] if measure else None))
+        res["slices"] = per
+        return res
+
     def stats(self):
         return self.ctx.stats()
