@@ -789,6 +789,44 @@ int ws_pre_processor(ws_ctx *ctx, const void *data, int dtype, size_t n_elems, u
 int ws_pre_processor_device(ws_ctx *ctx, const void *d_data, int dtype, size_t n_elems, uint8_t max_value,
                             uint8_t *d_out);
 
+/* ---- the front end of a cube of slices, one call each (tests/integration.rs:267-290, 356-380: pre_processor and
+ * find_local_minima of one slice after the other, before any transform) ----------------------------------------------
+ *
+ * ws_pre_processor_batch_device: slice k of d_out is exactly ws_pre_processor_device (pre_processor_with_max::<MAX>,
+ * lib.rs:1134-1173) of the h x w view whose element (r, c) sits at d_data + k * slice_stride + r * row_stride + c * col_stride --
+ * strides in ELEMENTS of dtype, any non-negative values: its OWN zero-seeded (min, max), then the same quantiser.  d_out is the
+ * contiguous (n_slices, h, w) u8 cube every *_batch_device call takes.  d_minmax (nullable): 2 * n_slices doubles, (min, max) of
+ * every slice as the folds leave them (written before a range refusal too).  A channel-last cube (slice_stride == 1, what slicing
+ * a FITS cube along its last axis gives) is read with lanes along the slice axis (and, with fewer than 64 slices, along
+ * neighbouring pixels too) and transposed on the chip: no copy into contiguous planes is needed first.  max_value and dtype are checked as in the single call.  WS_F64 slices whose max - min is
+ * not finite: WS_ERR_UNSUPPORTED and *failed_slice (nullable) = the lowest such slice, decided by one device word read back once
+ * per call (the stream is waited for once); every other dtype stays asynchronous.  n_slices * h * w == 0 writes nothing.  A
+ * context that holds a begun transform refuses the call.  Scratch kept by the context: at most 1 MiB + 32 B a slice. */
+int ws_pre_processor_batch_device(ws_ctx *ctx, const void *d_data, int dtype, size_t n_slices, size_t h, size_t w,
+                                  size_t slice_stride, size_t row_stride, size_t col_stride, uint8_t max_value, uint8_t *d_out,
+                                  double *d_minmax, size_t *failed_slice);
+/* The same from and into HOST memory: the bytes between the view's first and last element cross in ONE copy and the kernels read
+ * them with the caller's strides; the u8 cube and (nullable) minmax are copied back; returns with both complete. */
+int ws_pre_processor_batch(ws_ctx *ctx, const void *data, int dtype, size_t n_slices, size_t h, size_t w, size_t slice_stride,
+                           size_t row_stride, size_t col_stride, uint8_t max_value, uint8_t *out, double *minmax,
+                           size_t *failed_slice);
+
+/* find_local_minima (lib.rs:1178-1197) of every slice of a u8 cube: slice k (at d_cube + k * slice_stride, row_stride >= w) gives
+ * exactly the list of ws_find_local_minima_device, coordinates local to the slice; the lists lie back to back in d_out_rc -- what
+ * every *_batch_device call takes as d_seeds_rc -- and seed_offsets (HOST, n_slices + 1 entries) is the array those calls take:
+ * slice k's seeds are pairs [seed_offsets[k], seed_offsets[k + 1]).  *n_found = the total; cap smaller than that: WS_ERR_CAPACITY,
+ * the list cut at cap, the offsets complete (d_out_rc may be NULL with cap 0: a count).  One count launch, one scan, one write
+ * launch and ONE readback per run of slices; a run is as many whole slices as stay under ws_ctx_set_batch_pixel_limit, under
+ * 2^31 - 16 stacked rows and under 512 MiB of scratch (256 B per row and 1024 columns).  Slices with h < 3 or w < 3 have no
+ * seeds.  Each slice must have fewer than 2^32 - 1 pixels.  Scratch kept by the context: the nibble plane and the counts of the
+ * largest run (up to 512 MiB + 4.5 B a stacked row).  The host *_batch forms called with seeds_rc == NULL find their seeds with this
+ * call and keep that scratch too (70 001 slices of 8 x 16: 143 MB, where the per-slice loop they ran before kept one slice's). */
+int ws_find_local_minima_batch_device(ws_ctx *ctx, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w, size_t row_stride,
+                                      size_t slice_stride, uint32_t *d_out_rc, size_t cap, size_t *seed_offsets, size_t *n_found);
+/* The same from and into HOST memory, the pairs as uint64_t (what the host *_batch calls take as seeds_rc). */
+int ws_find_local_minima_batch(ws_ctx *ctx, const uint8_t *cube, size_t n_slices, size_t h, size_t w, size_t row_stride,
+                               size_t slice_stride, uint64_t *out_rc, size_t cap, size_t *seed_offsets, size_t *n_found);
+
 /* ---- one field tiled over several GPUs: row blocks with halo rows ----------------------
  *
  * A rank holds its rows of the global field plus one extra (halo) row on every side that has a

@@ -150,6 +150,49 @@ class WatershedUtils {                     // lib.rs:1069-1198
     return out;
   }
 
+  // not in the reference: pre_processor_with_max::<MAX> of every slice of a cube as one call (tests/integration.rs:267-290 normalise
+  // one slice of a FITS cube after the other).  Element (k, r, c) of the view sits at data + k * slice_stride + r * row_stride +
+  // c * col_stride (elements; a channel-last cube has slice_stride 1); the result is the contiguous (n_slices, h, w) u8 cube the
+  // *_cube methods take.  minmax (nullable) receives every slice's zero-seeded (min, max).
+  template <std::uint8_t MAX, class E>
+  std::vector<std::uint8_t> pre_processor_cube_with_max(const E *data, std::size_t n_slices, std::size_t h, std::size_t w, std::size_t slice_stride,
+                                                        std::size_t row_stride, std::size_t col_stride,
+                                                        std::vector<std::pair<double, double>> *minmax = nullptr) const {
+    static_assert(MAX < NEVER_FILL && MAX > ALWAYS_FILL, "lib.rs:1143-1144");
+    std::vector<std::uint8_t> out(n_slices * h * w);
+    std::vector<double> mm(minmax ? 2 * n_slices : 0);
+    std::size_t failed = 0;
+    const int rc = ws_pre_processor_batch(ctx_->get(), data, dtype_of<E>::value, n_slices, h, w, slice_stride, row_stride, col_stride, MAX,
+                                          out.data(), minmax ? mm.data() : nullptr, &failed);
+    if (rc == WS_ERR_UNSUPPORTED)      // a WS_F64 slice whose range is not finite: name it, as the other shims do
+      throw WatershedError(rc, "slice " + std::to_string(failed) + ": " + ws_last_error(ctx_->get()));
+    ctx_->check(rc);
+    if (minmax) {
+      minmax->resize(n_slices);
+      for (std::size_t k = 0; k < n_slices; ++k) (*minmax)[k] = {mm[2 * k], mm[2 * k + 1]};
+    }
+    return out;
+  }
+  template <class E>
+  std::vector<std::uint8_t> pre_processor_cube(const E *data, std::size_t n_slices, std::size_t h, std::size_t w, std::size_t slice_stride,
+                                               std::size_t row_stride, std::size_t col_stride) const {
+    return pre_processor_cube_with_max<NORMAL_MAX, E>(data, n_slices, h, w, slice_stride, row_stride, col_stride);
+  }
+
+  // not in the reference: find_local_minima of every slice of a u8 cube as one call.  Returns the slices' lists back to back;
+  // offsets (n_slices + 1 entries): slice k's seeds are [offsets[k], offsets[k + 1]).
+  std::vector<Seed> find_local_minima_cube(const std::uint8_t *cube, std::size_t n_slices, std::size_t h, std::size_t w, std::size_t row_stride,
+                                           std::size_t slice_stride, std::vector<std::size_t> &offsets) const {
+    const std::size_t cap = ((h ? h - 1 : 0) / 2 + 1) * ((w ? w - 1 : 0) / 2 + 1) * n_slices;
+    std::vector<std::uint64_t> rc(2 * cap + 2);
+    offsets.assign(n_slices + 1, 0);
+    std::size_t n = 0;
+    ctx_->check(ws_find_local_minima_batch(ctx_->get(), cube, n_slices, h, w, row_stride, slice_stride, rc.data(), cap, offsets.data(), &n));
+    std::vector<Seed> out(n);
+    for (std::size_t i = 0; i < n; ++i) out[i] = {rc[2 * i], rc[2 * i + 1]};
+    return out;
+  }
+
  protected:
   explicit WatershedUtils(std::shared_ptr<Context> c) : ctx_(std::move(c)) {}
   std::shared_ptr<Context> ctx_;

@@ -372,6 +372,17 @@ extern "C" {
         hidden_stats: *mut ws_lake_stats, n_seeds: *mut usize, failed_slice: *mut usize) -> c_int;
     pub fn ws_pre_processor_device(ctx: *mut ws_ctx, d_data: *const c_void, dtype: c_int, n_elems: usize,
         max_value: u8, d_out: *mut u8) -> c_int;
+    // ---- the front end of a cube of slices: pre_processor and find_local_minima of every slice, one call each
+    pub fn ws_pre_processor_batch_device(ctx: *mut ws_ctx, d_data: *const c_void, dtype: c_int, n_slices: usize, h: usize, w: usize,
+        slice_stride: usize, row_stride: usize, col_stride: usize, max_value: u8, d_out: *mut u8, d_minmax: *mut f64,
+        failed_slice: *mut usize) -> c_int;
+    pub fn ws_pre_processor_batch(ctx: *mut ws_ctx, data: *const c_void, dtype: c_int, n_slices: usize, h: usize, w: usize,
+        slice_stride: usize, row_stride: usize, col_stride: usize, max_value: u8, out: *mut u8, minmax: *mut f64,
+        failed_slice: *mut usize) -> c_int;
+    pub fn ws_find_local_minima_batch_device(ctx: *mut ws_ctx, d_cube: *const u8, n_slices: usize, h: usize, w: usize,
+        row_stride: usize, slice_stride: usize, d_out_rc: *mut u32, cap: usize, seed_offsets: *mut usize, n_found: *mut usize) -> c_int;
+    pub fn ws_find_local_minima_batch(ctx: *mut ws_ctx, cube: *const u8, n_slices: usize, h: usize, w: usize, row_stride: usize,
+        slice_stride: usize, out_rc: *mut u64, cap: usize, seed_offsets: *mut usize, n_found: *mut usize) -> c_int;
     pub fn ws_random_field_device(ctx: *mut ws_ctx, d_img: *mut u8, h: usize, w: usize, row_stride: usize,
         seed: u64) -> c_int;
 

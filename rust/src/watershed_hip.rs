@@ -219,6 +219,81 @@ pub trait WatershedUtils {
         });
         rc_pairs[..2 * n].chunks_exact(2).map(|p| (p[0] as usize, p[1] as usize)).collect()
     }
+
+    /// Not in the reference: `pre_processor_with_max::<MAX>` of every slice `cube.index_axis(axis, k)` of a cube as one call
+    /// (tests/integration.rs:267-290 slice a FITS cube along its LAST axis and normalise one slice after the other).  The view
+    /// goes to the engine with its own strides -- a channel-last cube needs no copy into planes -- and the result is the
+    /// standard-layout `(n_slices, h, w)` cube the `*_cube` methods take.  Element types outside the ABI's list, and views
+    /// with a negative stride, are first copied (as f64 / into standard layout).
+    fn pre_processor_cube_with_max<const MAX: u8, T>(&self, cube: nd::ArrayView3<T>, axis: nd::Axis) -> nd::Array3<u8>
+    where
+        T: Num + Copy + ToPrimitive + PartialOrd + 'static,
+    {
+        assert!(MAX < NEVER_FILL); // lib.rs:1143
+        assert!(MAX > ALWAYS_FILL); // lib.rs:1144
+        assert!(axis.index() < 3);
+        use std::any::TypeId;
+        let t = TypeId::of::<T>();
+        let dtype = [
+            (TypeId::of::<f32>(), hip_ffi::WS_F32),
+            (TypeId::of::<f64>(), hip_ffi::WS_F64),
+            (TypeId::of::<i32>(), hip_ffi::WS_I32),
+            (TypeId::of::<u16>(), hip_ffi::WS_U16),
+            (TypeId::of::<i16>(), hip_ffi::WS_I16),
+            (TypeId::of::<u8>(), hip_ffi::WS_U8),
+        ]
+        .iter()
+        .find(|(id, _)| *id == t)
+        .map(|&(_, d)| d);
+        let others: Vec<usize> = (0..3).filter(|&a| a != axis.index()).collect();
+        let view = cube.permuted_axes([axis.index(), others[0], others[1]]);
+        let (n, h, w) = view.dim();
+        let mut out = nd::Array3::<u8>::zeros((n, h, w));
+        let out_ptr = out.as_slice_mut().expect("fresh array is contiguous").as_mut_ptr();
+        let mut failed = 0usize;
+        let run = |ptr: *const c_void, d: c_int, st: [usize; 3], failed: &mut usize| {
+            shim::with_ctx(|ctx| unsafe {
+                let rc = hip_ffi::ws_pre_processor_batch(ctx, ptr, d, n, h, w, st[0], st[1], st[2], MAX, out_ptr, std::ptr::null_mut(), failed);
+                shim::check(ctx, rc, "ws_pre_processor_batch");
+            })
+        };
+        let strided = view.strides().iter().all(|&s| s >= 0);
+        match dtype {
+            Some(d) if strided => {
+                let st = view.strides();
+                run(view.as_ptr() as *const c_void, d, [st[0] as usize, st[1] as usize, st[2] as usize], &mut failed)
+            }
+            Some(d) => {
+                let std_view = view.as_standard_layout();
+                run(std_view.as_ptr() as *const c_void, d, [h * w, w, 1], &mut failed)
+            }
+            None => {
+                let wide: Vec<f64> = view.iter().map(|x| x.to_f64().unwrap()).collect();
+                run(wide.as_ptr() as *const c_void, hip_ffi::WS_F64, [h * w, w, 1], &mut failed)
+            }
+        }
+        out
+    }
+
+    /// Not in the reference: `find_local_minima` of every slice of a standard-layout `(n_slices, h, w)` cube as one call.  Returns
+    /// the slices' lists back to back and `n_slices + 1` offsets: slice `k`'s seeds are `seeds[offsets[k]..offsets[k + 1]]`.
+    fn find_local_minima_cube(&self, cube: nd::ArrayView3<u8>) -> (Vec<(usize, usize)>, Vec<usize>) {
+        let (n, h, w) = cube.dim();
+        let mut offsets = vec![0usize; n + 1];
+        if n == 0 || h < 3 || w < 3 {
+            return (Vec::new(), offsets);
+        }
+        let std_cube = cube.as_standard_layout();
+        let cap = ((h - 1) / 2 + 1) * ((w - 1) / 2 + 1) * n;
+        let mut rc_pairs = vec![0u64; 2 * cap];
+        let mut found = 0usize;
+        shim::with_ctx(|ctx| unsafe {
+            let rc = hip_ffi::ws_find_local_minima_batch(ctx, std_cube.as_ptr(), n, h, w, w, h * w, rc_pairs.as_mut_ptr(), cap,
+                                                         offsets.as_mut_ptr(), &mut found);
+            shim::check(ctx, rc, "ws_find_local_minima_batch");
+        });
+        (rc_pairs[..2 * found].chunks_exact(2).map(|p| (p[0] as usize, p[1] as usize)).collect(), offsets)
+    }
 }
 
 impl<T> WatershedUtils for MergingWatershed<T> {}

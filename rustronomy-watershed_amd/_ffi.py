@@ -198,6 +198,10 @@ SIGNATURES = {
                                                          vp, sz, vp, vp, sz, szp, vp, vp, vp, sz, szp, vp, vp, vp, szp, szp]),
     "ws_pre_processor": (ctypes.c_int, [vp, vp, ctypes.c_int, sz, ctypes.c_uint8, vp]),
     "ws_pre_processor_device": (ctypes.c_int, [vp, vp, ctypes.c_int, sz, ctypes.c_uint8, vp]),
+    "ws_pre_processor_batch_device": (ctypes.c_int, [vp, vp, ctypes.c_int, sz, sz, sz, sz, sz, sz, ctypes.c_uint8, vp, vp, szp]),
+    "ws_pre_processor_batch": (ctypes.c_int, [vp, vp, ctypes.c_int, sz, sz, sz, sz, sz, sz, ctypes.c_uint8, vp, vp, szp]),
+    "ws_find_local_minima_batch_device": (ctypes.c_int, [vp, vp, sz, sz, sz, sz, sz, vp, sz, szp, szp]),
+    "ws_find_local_minima_batch": (ctypes.c_int, [vp, vp, sz, sz, sz, sz, sz, vp, sz, szp, szp]),
     "ws_block_init": (ctypes.c_int, [vp, sz, sz, vp, vp, sz, vp, vp]),
     "ws_block_relax": (ctypes.c_int, [vp, vp, sz, sz, sz, ctypes.c_uint8, vp, ctypes.POINTER(ctypes.c_int)]),
     "ws_block_resolve": (ctypes.c_int, [vp, vp, vp, sz, sz, ctypes.POINTER(ctypes.c_int)]),

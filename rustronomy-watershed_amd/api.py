@@ -422,6 +422,59 @@ class WatershedUtils:
         ctx.check(rc)
         return out[: n.value].copy()
 
+    def pre_processor_cube(self, cube, axis=0):
+        """pre_processor of every slice `cube.take(k, axis)` of a 3-D cube as one call (ws_pre_processor_batch): each slice is
+        normalised with its OWN zero-seeded (min, max).  Returns the contiguous (n_slices, h, w) uint8 cube the *_cube methods take."""
+        return self.pre_processor_with_max_cube(cube, NORMAL_MAX, axis)
+
+    def pre_processor_with_max_cube(self, cube, max_value, axis=0):
+        """pre_processor_with_max of every slice along `axis` (tests/integration.rs:267-290 slice a FITS cube along its LAST axis:
+        axis=2).  Any numpy strides that are non-negative multiples of the item size go to the engine as they are -- a channel-last
+        cube is not copied into planes first; anything else is copied contiguous."""
+        a = np.asarray(cube)
+        if a.ndim != 3:
+            raise ValueError("cube must be 3-D")
+        if a.dtype.name not in _ffi.WS_DTYPES:
+            raise TypeError(f"unsupported dtype {a.dtype} (supported: {sorted(_ffi.WS_DTYPES)})")
+        if not 0 <= int(max_value) <= 255:
+            raise OverflowError("MAX must fit a u8")
+        if int(max_value) >= NEVER_FILL or int(max_value) <= ALWAYS_FILL:
+            raise AssertionError("MAX must be in 1..=254 (lib.rs:1143-1144)")      # the reference asserts
+        a = np.moveaxis(a, axis, 0)
+        item = a.dtype.itemsize
+        if any(st < 0 or st % item for st in a.strides):
+            a = np.ascontiguousarray(a)
+        n, h, w = a.shape
+        ss, rs, cs = (st // item for st in a.strides)
+        ctx = self._ctx()
+        out = np.empty((n, h, w), dtype=np.uint8)
+        failed = ctypes.c_size_t(0)
+        rc = _ffi.lib().ws_pre_processor_batch(ctx.handle, a.ctypes.data, _ffi.WS_DTYPES[a.dtype.name], n, h, w, ss, rs, cs, int(max_value),
+                                               out.ctypes.data, None, ctypes.byref(failed))
+        if rc == _ffi.WS_ERR_UNSUPPORTED:
+            raise WatershedError(rc, f"slice {failed.value}: " + _ffi.lib().ws_last_error(ctx.handle).decode())
+        ctx.check(rc)
+        return out
+
+    def find_local_minima_cube(self, cube):
+        """find_local_minima of every slice of a (n_slices, h, w) uint8 cube as one call (ws_find_local_minima_batch).  Returns
+        (seeds, offsets): the slices' (row, col) pairs back to back as an (n, 2) uint64 array, coordinates local to the slice,
+        and n_slices + 1 offsets -- slice k's seeds are seeds[offsets[k]:offsets[k + 1]], what the *_cube methods take."""
+        a = np.asarray(cube)
+        if a.dtype != np.uint8 or a.ndim != 3:
+            raise TypeError("cube must be a 3-D uint8 array")
+        a = np.ascontiguousarray(a)
+        n, h, w = a.shape
+        ctx = self._ctx()
+        cap = ((max(h, 1) - 1) // 2 + 1) * ((max(w, 1) - 1) // 2 + 1) * n
+        out = np.empty((max(cap, 1), 2), dtype=np.uint64)
+        offsets = np.zeros(n + 1, dtype=np.uintp)
+        found = ctypes.c_size_t(0)
+        rc = _ffi.lib().ws_find_local_minima_batch(ctx.handle, a.ctypes.data, n, h, w, w, h * w, out.ctypes.data, cap,
+                                                   offsets.ctypes.data_as(_ffi.szp), ctypes.byref(found))
+        ctx.check(rc)
+        return out[: found.value].copy(), offsets.astype(np.uint64)
+
 
 class _Transform(WatershedUtils):
     _merging = False

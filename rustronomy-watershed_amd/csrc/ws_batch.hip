@@ -264,7 +264,7 @@ int lists_batch_body(ws_ctx *c, bool merging, const Batch &b, ws_lake *d_lakes, 
 // The host forms' inputs on the device, as the device forms take them: the cube as contiguous slices (c->batch_cube) and the
 // seeds as u32 pairs (c->batch_seeds) -- seeds_rc == NULL: every slice's own find_local_minima (lib.rs:1178-1197), its seeds
 // behind the previous slices'.  b (checked: its h, w and plane) becomes that batch; offs (n_slices + 1): its seed offsets;
-// n_seeds (nullable): the counts.
+// n_seeds (nullable): the counts.  The stacked minima keep the nibble plane of a whole run on the context (ws_find_local_minima_batch_device).
 int upload_batch(ws_ctx *c, const uint8_t *cube, size_t n_slices, size_t row_stride, size_t slice_stride, const uint64_t *seeds_rc,
                  const size_t *seed_offsets, Batch &b, std::vector<size_t> &offs, size_t *n_seeds, size_t *failed_slice) {
   int rc;
@@ -294,14 +294,10 @@ int upload_batch(ws_ctx *c, const uint8_t *cube, size_t n_slices, size_t row_str
   } else {
     const size_t bound = h >= 3 && w >= 3 ? ((h - 1) / 2 + 1) * ((w - 1) / 2 + 1) : 0;
     if ((rc = ensure(c, c->batch_seeds, std::max<size_t>(n_slices * bound, 1) * 2 * sizeof(uint32_t)))) return rc;
-    for (size_t k = 0; k < n_slices; ++k) {
-      size_t found = 0;
-      if (bound && (rc = ws_find_local_minima_device(c, d_cube + k * hw, h, w, w, (uint32_t *)c->batch_seeds.p + 2 * offs[k], bound, &found))) {
-        if (failed_slice) *failed_slice = k;
-        return rc;
-      }
-      offs[k + 1] = offs[k] + found;
-    }
+    // every slice's minima in one stacked call: one count, scan and write launch and one readback per run of slices
+    size_t found = 0;
+    if (bound && (rc = ws_find_local_minima_batch_device(c, d_cube, n_slices, h, w, w, hw, (uint32_t *)c->batch_seeds.p, n_slices * bound, offs.data(), &found)))
+      return rc;      // (a failure of the stacked call belongs to no one slice: *failed_slice is left as it was)
   }
   if (n_seeds)
     for (size_t k = 0; k < n_slices; ++k) n_seeds[k] = offs[k + 1] - offs[k];

@@ -185,6 +185,10 @@ hipError_t flood_step(hipStream_t s, const uint8_t *img, size_t img_stride, cons
 // local maxima: count per 1024-px row segment, scan, write
 size_t minima_segments(int h, int w);       // count words (one per row and one per strip of rows)
 size_t minima_mask_bytes(int h, int w);     // nibble plane written by minima_count, read by minima_write
+size_t minima_stack_words(size_t rows, size_t n_slices);      // count words of minima_stack
+// the same for a stack of slices, each with its own border rows (ws_find_local_minima_batch_device)
+hipError_t minima_stack(hipStream_t s, const uint8_t *cube, size_t row_stride, size_t slice_stride, size_t n_slices, int h, int w, uint32_t *words,
+                        uint8_t *nibbles, uint32_t *out_rc, size_t cap, uint32_t **d_offsets);
 hipError_t minima_count(hipStream_t s, const uint8_t *img, size_t stride, int h, int w, uint32_t *counts, uint8_t *nibbles);
 hipError_t minima_write(hipStream_t s, const uint8_t *nibbles, int h, int w, const uint32_t *counts, uint32_t *total, uint32_t *out_rc, size_t cap,      // *total: the list's length
                         uint32_t *mask = nullptr, uint32_t *word_base = nullptr,      // w % 32 == 0: the seed tables of this list (seed_tables' layout)

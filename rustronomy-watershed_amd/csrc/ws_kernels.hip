@@ -1140,4 +1140,154 @@ hipError_t minima_write(hipStream_t s, const uint8_t *nibbles, int h, int w, con
   return hipGetLastError();
 }
 
+// ---- find_local_minima of every slice of a cube (ws_find_local_minima_batch_device) -------------------------------------------------
+//
+// The same two passes over the STACK of n_slices * h rows, as new kernels: the single plane's above stay as they are.  A slice's rows
+// 0 and h - 1 are never maxima (the single plane's row clamp makes them meet their own values): here their nibbles are cleared, for the
+// row above local row 0 is another slice's.  Every other row's neighbours are rows of its own slice, so its answer is the single
+// plane's.  Strips of MIN_RS rows may straddle slices: positions are global.  The write pass takes a strip's start from the SCANNED
+// strip counts (k_minima_strip_scan) -- the single plane's sums every earlier strip in every workgroup, quadratic in the rows -- maps
+// its row to (slice, local row), writes local coordinates, and the wave that owns local row 0 of slice k stores offsets[k].
+
+template <bool ALIGNED>
+__global__ __launch_bounds__(256) void k_minima_count_stack(const uint8_t *__restrict__ img, size_t stride, size_t slice_stride, int H, int R, int W,
+                                                            uint32_t *__restrict__ counts, uint8_t *__restrict__ nibbles) {
+  __shared__ uint32_t s_wave[4 * MIN_RS];
+  const int segs = (W + SEG - 1) / SEG;
+  const int seg = blockIdx.x % segs, y0 = (blockIdx.x / segs) * MIN_RS;
+  auto row_ptr = [&](int y) {      // (workgroup uniform) stacked row y, clamped into the stack
+    y = min(max(y, 0), R - 1);
+    const int k = y / H;
+    return img + (size_t)k * slice_stride + (size_t)(y - k * H) * stride;
+  };
+  const int x0 = seg * SEG + threadIdx.x * 4;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  MinRaw raw[MIN_RS + 2];
+#pragma unroll
+  for (int r = 0; r < MIN_RS + 2; ++r) raw[r] = minima_load<ALIGNED>(row_ptr(y0 + r - 1), W, x0);
+  MinRow above = minima_row<ALIGNED>(raw[0], W, x0), mid = minima_row<ALIGNED>(raw[1], W, x0);
+  uint32_t mine = 0;      // lane r ends up with the wave's count of row y0 + r
+  uint32_t nib[MIN_RS];
+  int ly = y0 % H;        // local row of y0 + r
+#pragma unroll
+  for (int r = 0; r < MIN_RS; ++r) {
+    const MinRow below = minima_row<ALIGNED>(raw[r + 2], W, x0);
+    const uint32_t m = (ly == 0 || ly == H - 1) ? 0u : minima_nibble(above, mid, below);      // a slice's border rows: interior never
+    nib[r] = m;
+    const uint32_t c = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64((m & 1u) != 0u)) + (uint32_t)__popcll(__builtin_amdgcn_ballot_w64((m & 2u) != 0u)) +
+                       (uint32_t)__popcll(__builtin_amdgcn_ballot_w64((m & 4u) != 0u)) + (uint32_t)__popcll(__builtin_amdgcn_ballot_w64((m & 8u) != 0u));
+    if (lane == r) mine = c;
+    above = mid;
+    mid = below;
+    ly = ly + 1 == H ? 0 : ly + 1;
+  }
+#pragma unroll
+  for (int r = 0; r < MIN_RS; ++r)
+    if (y0 + r < R) nibbles[((size_t)(y0 + r) * segs + seg) * 256 + threadIdx.x] = (uint8_t)nib[r];
+  if (lane < MIN_RS) s_wave[wave * MIN_RS + lane] = mine;
+  __syncthreads();
+  if (threadIdx.x < MIN_RS) {
+    const uint32_t c = y0 + (int)threadIdx.x < R ? s_wave[threadIdx.x] + s_wave[MIN_RS + threadIdx.x] + s_wave[2 * MIN_RS + threadIdx.x] + s_wave[3 * MIN_RS + threadIdx.x] : 0u;
+    if (c) atomicAdd(&counts[y0 + threadIdx.x], c);
+    uint32_t strip = c;
+#pragma unroll
+    for (int off = MIN_RS / 2; off > 0; off >>= 1) strip += __shfl_down(strip, off, 64);
+    if (threadIdx.x == 0 && strip) atomicAdd(&counts[R + y0 / MIN_RS], strip);
+  }
+}
+
+// starts[k] = the strip counts before strip k, starts[strips] = their total: one workgroup, 16 K strips a round
+__global__ __launch_bounds__(1024) void k_minima_strip_scan(const uint32_t *__restrict__ strip_counts, int strips, uint32_t *__restrict__ starts) {
+  constexpr int PER = 16;
+  __shared__ uint32_t s_wave[16];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint32_t carry = 0;
+  for (int base = 0; base < strips; base += 1024 * PER) {
+    const int i0 = base + (int)threadIdx.x * PER;
+    uint32_t v[PER], sum = 0;
+#pragma unroll
+    for (int j = 0; j < PER; ++j) { v[j] = i0 + j < strips ? strip_counts[i0 + j] : 0u; sum += v[j]; }
+    const uint32_t incl = wave_inclusive_sum(sum);
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    uint32_t run = carry + incl - sum, all = 0;
+    for (int k = 0; k < 16; ++k) { if (k < wave) run += s_wave[k]; all += s_wave[k]; }
+#pragma unroll
+    for (int j = 0; j < PER; ++j) { if (i0 + j < strips) starts[i0 + j] = run; run += v[j]; }
+    carry += all;
+    __syncthreads();      // s_wave is the next round's
+  }
+  if (threadIdx.x == 0) starts[strips] = carry;
+}
+
+// one WAVE per stacked row, no barrier (k_minima_write's compaction, the list alone)
+__global__ __launch_bounds__(256) void k_minima_write_stack(const uint8_t *__restrict__ nibbles, int H, int R, int W, const uint32_t *__restrict__ counts,
+                                                            const uint32_t *__restrict__ starts, uint32_t *out_rc, size_t cap, uint32_t *__restrict__ offsets) {
+  __shared__ uint2 s_stage[4][1024];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, y = blockIdx.x * 4 + wave;
+  if (y >= R) return;
+  const int strip = y / MIN_RS;
+  size_t pos = starts[strip];
+  for (int r = strip * MIN_RS; r < y; ++r) pos += counts[r];
+  const int k = y / H, ly = y - k * H;
+  const uint32_t mine = counts[y];
+  if (lane == 0) {
+    if (ly == 0) offsets[k] = (uint32_t)pos;
+    if (y == R - 1) offsets[k + 1] = (uint32_t)pos + mine;      // the run's total
+  }
+  if (mine == 0) return;      // (wave uniform; every slice's border rows)
+  const int segs = (W + SEG - 1) / SEG, groups = segs * 32;
+  const uint2 *nb = reinterpret_cast<const uint2 *>(nibbles + (size_t)y * segs * 256);
+  uint2 *stage = s_stage[wave];
+  for (int g0 = 0; g0 < groups; g0 += 64) {
+    const int g = g0 + lane;
+    const uint2 eight = g < groups ? nb[g] : make_uint2(0u, 0u);
+    uint32_t lo = eight.x & 0x0F0F0F0Fu, hi = eight.y & 0x0F0F0F0Fu;
+    lo = (lo | (lo >> 4)) & 0x00FF00FFu; hi = (hi | (hi >> 4)) & 0x00FF00FFu;
+    lo = (lo | (lo >> 8)) & 0xFFFFu; hi = (hi | (hi >> 8)) & 0xFFFFu;
+    uint32_t word = lo | (hi << 16);
+    const uint32_t c = __popc(word);
+    const uint32_t incl = wave_inclusive_sum(c);
+    const uint32_t step_total = (uint32_t)__shfl((int)incl, 63, 64);
+    uint32_t at = incl - c;
+    while (word) {      // (at most one maximum per 2 x 2 block: 16 a lane, 1024 a step)
+      const int b = __builtin_ctz(word);
+      word &= word - 1u;
+      stage[at++] = make_uint2((uint32_t)ly, (uint32_t)(g * 32 + b));
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    for (uint32_t i = (uint32_t)lane; i < step_total; i += 64u)
+      if (pos + i < cap) *reinterpret_cast<uint2 *>(out_rc + 2 * (pos + i)) = stage[i];
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");      // the stage is read before the next step fills it
+    pos += step_total;
+  }
+}
+
+// words: [0, R) row counts, [R, R + strips) strip counts, then strips + 1 strip starts, then n_slices + 1 offsets
+size_t minima_stack_words(size_t rows, size_t n_slices) {
+  const size_t strips = (rows + MIN_RS - 1) / MIN_RS;
+  return rows + strips + strips + 1 + n_slices + 1;
+}
+
+// n_slices slices of h x w (h, w >= 3; n_slices * h < 2^31 - 15) at cube + k * slice_stride: their lists back to back in out_rc (cut at
+// cap; nullable with cap 0), *d_offsets (n_slices + 1 words inside `words`): where each slice's list begins, and the total
+hipError_t minima_stack(hipStream_t s, const uint8_t *cube, size_t row_stride, size_t slice_stride, size_t n_slices, int h, int w, uint32_t *words,
+                        uint8_t *nibbles, uint32_t *out_rc, size_t cap, uint32_t **d_offsets) {
+  const int R = (int)(n_slices * (size_t)h), strips = (R + MIN_RS - 1) / MIN_RS, segs = (w + SEG - 1) / SEG;
+  uint32_t *starts = words + (size_t)R + strips, *offsets = starts + strips + 1;
+  *d_offsets = offsets;
+  hipError_t e = hipMemsetAsync(words, 0, ((size_t)R + strips) * sizeof(uint32_t), s);
+  if (e != hipSuccess) return e;
+  const unsigned grid = (unsigned)((size_t)strips * segs);
+  if (((reinterpret_cast<uintptr_t>(cube) | row_stride | slice_stride) & 3u) == 0 && (w & 3) == 0 && w >= 4)
+    k_minima_count_stack<true><<<grid, 256, 0, s>>>(cube, row_stride, slice_stride, h, R, w, words, nibbles);
+  else
+    k_minima_count_stack<false><<<grid, 256, 0, s>>>(cube, row_stride, slice_stride, h, R, w, words, nibbles);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  k_minima_strip_scan<<<1, 1024, 0, s>>>(words + R, strips, starts);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  k_minima_write_stack<<<(unsigned)((R + 3) / 4), 256, 0, s>>>(nibbles, h, R, w, words, starts, out_rc, out_rc ? cap : 0, offsets);
+  return hipGetLastError();
+}
+
 }  // namespace wsk

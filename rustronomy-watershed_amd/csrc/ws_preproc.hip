@@ -22,11 +22,6 @@
 
 namespace wsk {
 
-template <typename T>
-__device__ __forceinline__ double to_f64(T v) { return (double)v; }
-
-__device__ __forceinline__ bool finite_f64(double v) { return fabs(v) <= 1.7976931348623157e308; }   // false for NaN, +-inf
-
 // a value the fold keeps: strictly below/above the running bound and finite
 template <typename T>
 __global__ __launch_bounds__(256) void k_minmax(const T *__restrict__ data, size_t n, double *partial) {
@@ -80,17 +75,7 @@ __global__ __launch_bounds__(256) void k_quantise(const T *__restrict__ data, si
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t step = (size_t)gridDim.x * blockDim.x;
   for (; i < n; i += step) {
-    const double v = to_f64(data[i]);
-    const double a = fabs(v);
-    uint8_t q;
-    if (a >= 2.2250738585072014e-308 && a <= 1.7976931348623157e308) {      // f64::is_normal
-      const double normal = (v - mn) / range;                               // lib.rs:1163
-      q = (uint8_t)(normal * maxv);                                         // lib.rs:1164: to_u8 truncates; in [0, MAX] while `range` is finite
-    } else if (v == INFINITY) {
-      q = 0;                                                                // lib.rs:1165-1167
-    } else {
-      q = 255;                                                              // lib.rs:1168-1170
-    }
+    const uint8_t q = quantise_one(to_f64(data[i]), mn, range, maxv);
     out[i] = q;
   }
 }

@@ -46,6 +46,62 @@ class DeviceEngine:
                                                               cap, ctypes.byref(n)))
         return out[: n.value]
 
+    _DTYPES = {torch.float32: 0, torch.float64: 1, torch.int32: 2, torch.int16: 4, torch.uint8: 5}
+    if hasattr(torch, "uint16"):
+        _DTYPES[torch.uint16] = 3
+
+    def _max_value(self, max_value):
+        if not 1 <= int(max_value) <= 254:
+            raise AssertionError("MAX must be in 1..=254 (lib.rs:1143-1144)")      # the reference asserts
+        return int(max_value)
+
+    def pre_processor(self, data, max_value=254):
+        """pre_processor_with_max of a device tensor of any shape (ws_pre_processor_device): one (min, max) over all of it.  Returns
+        a uint8 tensor of the same shape.  float64 data waits for the stream once (the range check); other dtypes stay asynchronous."""
+        assert data.is_cuda and data.dtype in self._DTYPES, "float32, float64, int32, int16, uint16 or uint8 on the device"
+        data = data.contiguous()
+        out = torch.empty(data.shape, dtype=torch.uint8, device=self.device)
+        self.ctx.check(_ffi.lib().ws_pre_processor_device(self.ctx.handle, data.data_ptr(), self._DTYPES[data.dtype], data.numel(),
+                                                          self._max_value(max_value), out.data_ptr()))
+        return out
+
+    def pre_processor_batch(self, data, axis=0, max_value=254, want_minmax=False):
+        """pre_processor_with_max of every slice along `axis` of a 3-D device tensor (ws_pre_processor_batch_device), each with its
+        own (min, max); the tensor's strides go to the engine as they are (a channel-last cube, axis=2, is not copied).  Returns the
+        contiguous (n_slices, h, w) uint8 cube every *_batch method takes, with want_minmax also a float64 (n_slices, 2) tensor."""
+        assert data.is_cuda and data.dim() == 3 and data.dtype in self._DTYPES
+        view = data.movedim(axis, 0)
+        if any(st < 0 for st in view.stride()):
+            view = view.contiguous()
+        n, h, w = view.shape
+        ss, rs, cs = view.stride()
+        out = torch.empty((n, h, w), dtype=torch.uint8, device=self.device)
+        minmax = torch.empty((n, 2), dtype=torch.float64, device=self.device) if want_minmax else None
+        failed = ctypes.c_size_t(0)
+        rc = _ffi.lib().ws_pre_processor_batch_device(self.ctx.handle, view.data_ptr() if view.numel() else None, self._DTYPES[data.dtype],
+                                                      n, h, w, ss, rs, cs, self._max_value(max_value), out.data_ptr() if out.numel() else None,
+                                                      minmax.data_ptr() if want_minmax and n else None, ctypes.byref(failed))
+        if rc == _ffi.WS_ERR_UNSUPPORTED:
+            from .api import WatershedError
+            raise WatershedError(rc, f"slice {failed.value}: " + _ffi.lib().ws_last_error(self.ctx.handle).decode())
+        self.ctx.check(rc)
+        return (out, minmax) if want_minmax else out
+
+    def find_local_minima_batch(self, cube):
+        """find_local_minima of every slice of a contiguous (S, H, W) uint8 device cube (ws_find_local_minima_batch_device).  Returns
+        (seeds, seed_offsets): int32 (n, 2) device tensor of slice-local (row, col) pairs, back to back, and S + 1 host integers
+        (numpy) -- the pair every *_batch method takes."""
+        import numpy as np
+        assert cube.dtype == torch.uint8 and cube.dim() == 3 and cube.is_contiguous() and cube.is_cuda
+        s, h, w = cube.shape
+        cap = ((max(h, 1) - 1) // 2 + 1) * ((max(w, 1) - 1) // 2 + 1) * s
+        out = torch.empty((max(cap, 1), 2), dtype=torch.int32, device=self.device)
+        offsets = np.zeros(s + 1, dtype=np.uintp)
+        n = ctypes.c_size_t(0)
+        self.ctx.check(_ffi.lib().ws_find_local_minima_batch_device(self.ctx.handle, cube.data_ptr() if cube.numel() else None, s, h, w, w, h * w,
+                                                                    out.data_ptr(), cap, offsets.ctypes.data_as(_ffi.szp), ctypes.byref(n)))
+        return out[: n.value], offsets
+
     def _plane(self, img, edge):
         e = 2 if edge else 0
         return img.shape[0] + e, img.shape[1] + e
