@@ -167,6 +167,13 @@ typedef struct ws_lake_stats {
   uint32_t reserved;   /* 0 */
 } ws_lake_stats;
 
+/* The second moments of one lake (ws_merge_tree_shapes): record c belongs to seed colour c, over the pixels `area` counts (M_c of
+ * ws_merge_tree_stats).  Every sum is exact in 128 bits: [0] the low, [1] the high 64 bits.  96 bytes. */
+typedef struct ws_lake_shape {
+  uint64_t sum_wrr[2], sum_wcc[2], sum_wrc[2];   /* sum of v(p) * row^2, v(p) * col^2, v(p) * row * col */
+  uint64_t sum_rr[2],  sum_cc[2],  sum_rc[2];    /* sum of row^2, col^2, row * col */
+} ws_lake_shape;
+
 /* ---- context ------------------------------------------------------------------------- */
 
 int ws_abi_version(void);
@@ -492,6 +499,40 @@ int ws_merge_tree_stats(ws_ctx *ctx, const uint8_t *img, size_t h, size_t w, siz
 int ws_merge_tree_from_arrival_device(ws_ctx *ctx, const uint32_t *d_keys, const uint32_t *d_seg_labels, size_t h, size_t w,
                                       size_t n_seeds, const ws_options *opt, const void *d_weight, int weight_dtype,
                                       size_t weight_row_stride, ws_tree_node *d_tree, ws_lake_stats *d_stats);
+/* ws_merge_tree_stats_device and the second moments of every lake from the same flood -- how big and how elongated a lake is and
+ * which way it points: d_tree and d_stats receive, byte for byte, what ws_merge_tree_stats_device writes for the same arguments,
+ * d_shapes (device, 8-byte aligned, else WS_ERR_BAD_ARG) n_seeds + 1 records, record c for colour c.  All three arrays are
+ * required; d_labels is nullable.  Record c holds the six sums over exactly the set M_c of the first-moment record (the pixels
+ * equal to c in P_(death_level - 1), in P_max if c never died, the seed pixel alone if death_level == 0), record 0 over the pixels
+ * still uncoloured after the last level; rows and columns are those of the padded plane and v(p) is ws_merge_tree_stats_device's
+ * (the u8 or u16 weight plane, NULL for the image itself, the ring weighs 0 under edge correction).  A colour that does not exist,
+ * and record 0 when nothing is uncoloured, get the identity: all twelve words 0.  n_seeds == 0 writes record 0 of all three arrays
+ * only.  Every refusal of ws_merge_tree_stats_device holds, in the same order, and leaves all three outputs untouched.  There is
+ * no further WS_ERR_TOO_LARGE: the stats call already refuses a plane unless wmax * pixels * max(ph, pw) < 2^64 with ph, pw <
+ * 2^32, and a sum of v * row^2 is at most wmax * pixels * max(ph, pw)^2 < 2^64 * 2^32 = 2^96 -- so are the other five.  Every sum
+ * is an exact integer, accumulated as two 64-bit limbs that never exchange a carry (the terms' low 32 bits: below 2^64 for fewer
+ * than 2^32 pixels; the terms >> 32: below 2^64 because the sum is below 2^96), so every record is reproducible to the bit
+ * (DESIGN.md section 4.3.2).  Stream ordered; returns with the records complete; afterwards ws_last_arrival_device behaves as
+ * after ws_merge_tree_stats_device.  Workspace kept by the context on top of ws_merge_tree_stats_device's: 96 B a colour, all of
+ * it reserved before the transform.  Cubes, tiled groups and the regions of a cut have no such call yet. */
+int ws_merge_tree_shapes_device(ws_ctx *ctx, const uint8_t *d_img, size_t h, size_t w, size_t row_stride, const uint32_t *d_seeds_rc,
+                                size_t n_seeds, const ws_options *opt, const void *d_weight, int weight_dtype,
+                                size_t weight_row_stride, ws_tree_node *d_tree, ws_lake_stats *d_stats, ws_lake_shape *d_shapes,
+                                uint32_t *d_labels);
+/* The same from and into HOST memory, as ws_merge_tree_stats: u64 seed pairs, u64 labels, the records into `tree`, `stats` and
+ * `shapes` (n_seeds + 1 each).  Keeps 96 B a colour more on the device (the records before they cross). */
+int ws_merge_tree_shapes(ws_ctx *ctx, const uint8_t *img, size_t h, size_t w, size_t row_stride, const uint64_t *seeds_rc,
+                         size_t n_seeds, const ws_options *opt, const void *weight, int weight_dtype, size_t weight_row_stride,
+                         ws_tree_node *tree, ws_lake_stats *stats, ws_lake_shape *shapes, uint64_t *labels);
+/* The same from a segmenting transform that has already run: the planes, weights and refusals of
+ * ws_merge_tree_from_arrival_device with d_stats != NULL (d_weight == NULL is WS_ERR_BAD_ARG), d_tree and d_stats byte for byte
+ * what that call writes, d_shapes as ws_merge_tree_shapes_device's for the transform that produced the planes.  All three arrays
+ * are required.  n_seeds == 0 writes record 0 only; h * w == 0 writes the identity.  ws_last_arrival_device keeps reporting what
+ * it reported before. */
+int ws_merge_tree_shapes_from_arrival_device(ws_ctx *ctx, const uint32_t *d_keys, const uint32_t *d_seg_labels, size_t h, size_t w,
+                                             size_t n_seeds, const ws_options *opt, const void *d_weight, int weight_dtype,
+                                             size_t weight_row_stride, ws_tree_node *d_tree, ws_lake_stats *d_stats,
+                                             ws_lake_shape *d_shapes);
 /* One cut of a merge tree (ws_tree_cut_device).  12 bytes. */
 typedef struct ws_tree_cut {
   uint32_t min_area;    /* a lake that was swallowed counts only if it had reached this many pixels ... */

@@ -553,6 +553,7 @@ class MergingWatershed : public Watershed<T> {        // lib.rs:1297-1562
   struct LakeCatalogue {
     MergeTree tree;
     std::vector<ws_lake_stats> stats;
+    std::vector<ws_lake_shape> shapes;      // merge_tree_shapes only: the second moments, exact 128-bit sums as (low, high)
     // the weighted centroid (row, col) of record c in the padded plane; false where the record weighs nothing
     bool centroid(std::size_t c, double *row, double *col) const {
       const ws_lake_stats &r = stats[c];
@@ -574,6 +575,21 @@ class MergingWatershed : public Watershed<T> {        // lib.rs:1297-1562
                                  bool want_labels = false) const {
     if (weights.rows != input.rows || weights.cols != input.cols) throw std::invalid_argument("weights must have the image's shape");
     return lake_catalogue(input, seeds, weights.ptr, WS_U16, weights.row_stride, want_labels);
+  }
+  // not in the reference: merge_tree_stats and the second moments of every lake from the same flood (ws_merge_tree_shapes):
+  // shapes[c] holds the exact sums of v row^2, v col^2, v row col, row^2, col^2 and row col over the pixels nodes[c].area counts.
+  LakeCatalogue merge_tree_shapes(ArrayView2<std::uint8_t> input, const std::vector<Seed> &seeds, bool want_labels = false) const {
+    return lake_catalogue(input, seeds, nullptr, 0, 0, want_labels, true);
+  }
+  LakeCatalogue merge_tree_shapes(ArrayView2<std::uint8_t> input, const std::vector<Seed> &seeds, ArrayView2<std::uint8_t> weights,
+                                  bool want_labels = false) const {
+    if (weights.rows != input.rows || weights.cols != input.cols) throw std::invalid_argument("weights must have the image's shape");
+    return lake_catalogue(input, seeds, weights.ptr, WS_U8, weights.row_stride, want_labels, true);
+  }
+  LakeCatalogue merge_tree_shapes(ArrayView2<std::uint8_t> input, const std::vector<Seed> &seeds, ArrayView2<std::uint16_t> weights,
+                                  bool want_labels = false) const {
+    if (weights.rows != input.rows || weights.cols != input.cols) throw std::invalid_argument("weights must have the image's shape");
+    return lake_catalogue(input, seeds, weights.ptr, WS_U16, weights.row_stride, want_labels, true);
   }
   // not in the reference: merge_tree of every slice of a contiguous cube (n_slices x rows x cols) as ONE call of the library
   // (ws_merge_tree_batch: slices that stack share one flood, one set of per-level unions and one fold launch per level).
@@ -830,12 +846,18 @@ class MergingWatershed : public Watershed<T> {        // lib.rs:1297-1562
     return t;
   }
   LakeCatalogue lake_catalogue(ArrayView2<std::uint8_t> input, const std::vector<Seed> &seeds, const void *weights, int dtype,
-                               std::size_t weight_stride, bool want_labels) const {
+                               std::size_t weight_stride, bool want_labels, bool want_shapes = false) const {
     const std::size_t e = this->opt_.edge_correction ? 2 : 0;
     LakeCatalogue cat{MergeTree{std::vector<ws_tree_node>(seeds.size() + 1),
                                 Array2<usize>(want_labels ? input.rows + e : 0, want_labels ? input.cols + e : 0)},
-                      std::vector<ws_lake_stats>(seeds.size() + 1)};
+                      std::vector<ws_lake_stats>(seeds.size() + 1), std::vector<ws_lake_shape>(want_shapes ? seeds.size() + 1 : 0)};
     auto packed = detail::pack(seeds);
+    if (want_shapes) {
+      this->ctx_->check(ws_merge_tree_shapes(this->ctx_->get(), input.ptr, input.rows, input.cols, input.row_stride, packed.data(), seeds.size(),
+                                             &this->opt_, weights, dtype, weight_stride, cat.tree.nodes.data(), cat.stats.data(),
+                                             cat.shapes.data(), want_labels ? cat.tree.labels.data.data() : nullptr));
+      return cat;
+    }
     this->ctx_->check(ws_merge_tree_stats(this->ctx_->get(), input.ptr, input.rows, input.cols, input.row_stride, packed.data(), seeds.size(),
                                           &this->opt_, weights, dtype, weight_stride, cat.tree.nodes.data(), cat.stats.data(),
                                           want_labels ? cat.tree.labels.data.data() : nullptr));

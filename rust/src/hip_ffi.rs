@@ -104,6 +104,19 @@ pub struct ws_lake_stats {
     pub reserved: u32,
 }
 
+/// The second moments of one lake (ws_merge_tree_shapes), 96 bytes; record c belongs to seed colour c.  Every sum is exact in
+/// 128 bits: [0] the low, [1] the high 64 bits.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct ws_lake_shape {
+    pub sum_wrr: [u64; 2],
+    pub sum_wcc: [u64; 2],
+    pub sum_wrc: [u64; 2],
+    pub sum_rr: [u64; 2],
+    pub sum_cc: [u64; 2],
+    pub sum_rc: [u64; 2],
+}
+
 pub const WS_U16: c_int = 3;
 pub const WS_U8: c_int = 5;
 
@@ -316,6 +329,15 @@ extern "C" {
     pub fn ws_merge_tree_from_arrival_device(ctx: *mut ws_ctx, d_keys: *const u32, d_seg_labels: *const u32, h: usize, w: usize, n_seeds: usize,
         opt: *const ws_options, d_weight: *const c_void, weight_dtype: c_int, weight_row_stride: usize, d_tree: *mut ws_tree_node,
         d_stats: *mut ws_lake_stats) -> c_int;
+    pub fn ws_merge_tree_shapes_device(ctx: *mut ws_ctx, d_img: *const u8, h: usize, w: usize, row_stride: usize, d_seeds_rc: *const u32,
+        n_seeds: usize, opt: *const ws_options, d_weight: *const c_void, weight_dtype: c_int, weight_row_stride: usize,
+        d_tree: *mut ws_tree_node, d_stats: *mut ws_lake_stats, d_shapes: *mut ws_lake_shape, d_labels: *mut u32) -> c_int;
+    pub fn ws_merge_tree_shapes(ctx: *mut ws_ctx, img: *const u8, h: usize, w: usize, row_stride: usize, seeds_rc: *const u64,
+        n_seeds: usize, opt: *const ws_options, weight: *const c_void, weight_dtype: c_int, weight_row_stride: usize,
+        tree: *mut ws_tree_node, stats: *mut ws_lake_stats, shapes: *mut ws_lake_shape, labels: *mut u64) -> c_int;
+    pub fn ws_merge_tree_shapes_from_arrival_device(ctx: *mut ws_ctx, d_keys: *const u32, d_seg_labels: *const u32, h: usize, w: usize,
+        n_seeds: usize, opt: *const ws_options, d_weight: *const c_void, weight_dtype: c_int, weight_row_stride: usize,
+        d_tree: *mut ws_tree_node, d_stats: *mut ws_lake_stats, d_shapes: *mut ws_lake_shape) -> c_int;
     pub fn ws_tree_cut_device(ctx: *mut ws_ctx, d_tree: *const ws_tree_node, n_seeds: usize, d_keys: *const u32, d_seg_labels: *const u32,
         h: usize, w: usize, cuts: *const ws_tree_cut, n_cuts: usize, d_out: *mut u32, plane_stride: usize, d_lakes: *mut ws_lake,
         cap: usize, n_lakes: *mut usize, offsets: *mut u64, hidden: *mut u64) -> c_int;

@@ -853,6 +853,39 @@ impl<T> MergingWatershed<T> {
         });
         (MergeTree { nodes, labels }, stats)
     }
+    /// Not in the reference: `merge_tree_stats` and the second moments of every lake from the same flood (`ws_merge_tree_shapes`):
+    /// record c of the third value holds the exact 128-bit sums of v row^2, v col^2, v row col, row^2, col^2 and row col over the
+    /// pixels `nodes[c].area` counts, each as (low, high) 64 bits, in the coordinates of the padded plane.  `weights` as
+    /// `merge_tree_stats`.
+    pub fn merge_tree_shapes(&self, input: nd::ArrayView2<u8>, seeds: &[(usize, usize)], weights: Option<nd::ArrayView2<u16>>,
+                             want_labels: bool) -> (MergeTree, Vec<hip_ffi::ws_lake_stats>, Vec<hip_ffi::ws_lake_shape>) {
+        let (h, w) = input.dim();
+        let (std_img, stride) = shim::standard(&input);
+        let packed = shim::pack_seeds(seeds);
+        let o = self.opt.ffi();
+        let plane = weights.map(|a| {
+            assert_eq!(a.dim(), (h, w), "weights must have the image's shape");
+            a.as_standard_layout().into_owned()
+        });
+        let (wt_ptr, wt_dtype) = match plane.as_ref() {
+            Some(a) => (a.as_ptr() as *const std::ffi::c_void, hip_ffi::WS_U16),
+            None => (std::ptr::null(), 0),
+        };
+        let mut nodes = vec![hip_ffi::ws_tree_node::default(); seeds.len() + 1];
+        let mut stats = vec![hip_ffi::ws_lake_stats::default(); seeds.len() + 1];
+        let mut shapes = vec![hip_ffi::ws_lake_shape::default(); seeds.len() + 1];
+        let mut labels = if want_labels { Some(nd::Array2::<usize>::zeros(self.opt.plane(h, w))) } else { None };
+        let lab_ptr = match labels.as_mut() {
+            Some(a) => a.as_slice_mut().expect("standard layout").as_mut_ptr() as *mut u64,
+            None => std::ptr::null_mut(),
+        };
+        shim::with_ctx(|ctx| unsafe {
+            let rc = hip_ffi::ws_merge_tree_shapes(ctx, std_img.as_ptr(), h, w, stride, packed.as_ptr(), seeds.len(), &o, wt_ptr, wt_dtype, w,
+                                                   nodes.as_mut_ptr(), stats.as_mut_ptr(), shapes.as_mut_ptr(), lab_ptr);
+            shim::check(ctx, rc, "ws_merge_tree_shapes");
+        });
+        (MergeTree { nodes, labels }, stats, shapes)
+    }
     /// Not in the reference: `merge_tree(cube[k], &find_local_minima(cube[k]), want_labels)` of every slice of a cube as one call
     /// (`ws_merge_tree_batch`: slices that stack share one flood, one set of per-level unions and one fold launch per level).
     /// Returns the trees, in the slices' own colours, and the number of minima of every slice.

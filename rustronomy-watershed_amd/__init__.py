@@ -4,8 +4,8 @@ through `__graft_entry__.load_package()` (registers it as `rustronomy_watershed_
 from . import _ffi
 from .api import (ALWAYS_FILL, ENGINE_AUTO, ENGINE_FUSED, ENGINE_SWEEP, NEVER_FILL, NORMAL_MAX, UNCOLOURED, BuildErr,
                   Context, Cut, HookCtx, MaxToHigh, MaxToLow, MergeTree, MergingWatershed, SeedOutOfBounds, SegmentingWatershed,
-                  TransformBuilder, WatershedError, WatershedUtils, centroids, default_context)
+                  TransformBuilder, WatershedError, WatershedUtils, centroids, default_context, ellipses)
 
 __all__ = ["ALWAYS_FILL", "ENGINE_AUTO", "ENGINE_FUSED", "ENGINE_SWEEP", "NEVER_FILL", "NORMAL_MAX", "UNCOLOURED",
            "BuildErr", "Context", "Cut", "HookCtx", "MaxToHigh", "MaxToLow", "MergeTree", "MergingWatershed", "SeedOutOfBounds",
-           "SegmentingWatershed", "TransformBuilder", "WatershedError", "WatershedUtils", "centroids", "default_context", "_ffi"]
+           "SegmentingWatershed", "TransformBuilder", "WatershedError", "WatershedUtils", "centroids", "default_context", "ellipses", "_ffi"]

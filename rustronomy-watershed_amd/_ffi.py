@@ -96,6 +96,12 @@ class LakeStats(ctypes.Structure):
                 ("reserved", ctypes.c_uint32)]
 
 
+class LakeShape(ctypes.Structure):
+    """ws_lake_shape: the second moments of one lake (ws_merge_tree_shapes), six exact 128-bit sums as (low, high) u64, 96 bytes."""
+    _fields_ = [("sum_wrr", ctypes.c_uint64 * 2), ("sum_wcc", ctypes.c_uint64 * 2), ("sum_wrc", ctypes.c_uint64 * 2),
+                ("sum_rr", ctypes.c_uint64 * 2), ("sum_cc", ctypes.c_uint64 * 2), ("sum_rc", ctypes.c_uint64 * 2)]
+
+
 class TileBlock(ctypes.Structure):
     """ws_tile_block: one rank's row block of a tiled field, device resident."""
     _fields_ = [("d_img", vp), ("d_seeds_rc", vp), ("d_colours", vp), ("n_seeds", sz),
@@ -175,6 +181,9 @@ SIGNATURES = {
     "ws_merge_tree": (ctypes.c_int, [vp, vp, sz, sz, sz, vp, sz, ctypes.POINTER(Options), vp, vp]),
     "ws_merge_tree_stats_device": (ctypes.c_int, [vp, vp, sz, sz, sz, vp, sz, ctypes.POINTER(Options), vp, ctypes.c_int, sz, vp, vp, vp]),
     "ws_merge_tree_stats": (ctypes.c_int, [vp, vp, sz, sz, sz, vp, sz, ctypes.POINTER(Options), vp, ctypes.c_int, sz, vp, vp, vp]),
+    "ws_merge_tree_shapes_device": (ctypes.c_int, [vp, vp, sz, sz, sz, vp, sz, ctypes.POINTER(Options), vp, ctypes.c_int, sz, vp, vp, vp, vp]),
+    "ws_merge_tree_shapes": (ctypes.c_int, [vp, vp, sz, sz, sz, vp, sz, ctypes.POINTER(Options), vp, ctypes.c_int, sz, vp, vp, vp, vp]),
+    "ws_merge_tree_shapes_from_arrival_device": (ctypes.c_int, [vp, vp, vp, sz, sz, sz, ctypes.POINTER(Options), vp, ctypes.c_int, sz, vp, vp, vp]),
     "ws_merge_tree_from_arrival_device": (ctypes.c_int, [vp, vp, vp, sz, sz, sz, ctypes.POINTER(Options), vp, ctypes.c_int, sz, vp, vp]),
     "ws_tree_cut_device": (ctypes.c_int, [vp, vp, sz, vp, vp, sz, sz, vp, sz, vp, sz, vp, sz, szp, vp, vp]),
     "ws_merge_tree_cut": (ctypes.c_int, [vp, vp, sz, sz, sz, vp, sz, ctypes.POINTER(Options), vp, sz, vp, vp, vp, sz, szp, vp, vp]),

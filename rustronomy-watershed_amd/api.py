@@ -184,6 +184,55 @@ def _as_weights(weights, shape):
     return a, _ffi.WS_DTYPES[a.dtype.name], (a.strides[0] // item if a.size else a.shape[1])
 
 
+LAKE_SHAPE_DTYPE = np.dtype([("sum_wrr", "<u8", (2,)), ("sum_wcc", "<u8", (2,)), ("sum_wrc", "<u8", (2,)), ("sum_rr", "<u8", (2,)),
+                             ("sum_cc", "<u8", (2,)), ("sum_rc", "<u8", (2,))])      # ws_lake_shape, 96 bytes: (low, high) of six 128-bit sums
+
+
+def _wide(words):
+    """An (n, 2) array of (low, high) u64 words as an object array of Python ints."""
+    w = np.asarray(words)
+    return np.array([int(lo) | int(hi) << 64 for lo, hi in w.reshape(-1, 2)], dtype=object)
+
+
+def ellipses(stats, shapes, weighted=True, area=None):
+    """(var_r, var_c, cov_rc, major_sigma, minor_sigma, angle) float64 arrays: the second central moments of every record of
+    merge_tree_shapes about its own centroid, the sigmas of its ellipse and the direction of its major axis, in the coordinates
+    of the padded plane.  Weighted, with S = sum_w: var_r = (S sum_wrr - sum_wr^2) / S^2, cov_rc = (S sum_wrc - sum_wr sum_wc) /
+    S^2.  weighted=False: the same of the plain sums with S = `area` (MergeTree.area, the pixels the record counts; needed then).
+    Numerator and denominator are exact Python integers divided once, so each moment is the correctly rounded value.  With a =
+    var_r, c = var_c, b = cov_rc: lambda+- = (a + c) / 2 +- sqrt(((a - c) / 2)^2 + b^2), sigma = sqrt(lambda+-), angle =
+    atan2(2 b, a - c) / 2 -- the major axis measured from the row axis towards the column axis, in (-pi/2, pi/2].  nan where
+    S == 0."""
+    n = len(shapes)
+    if weighted:
+        s0 = [int(x) for x in stats["sum_w"]]
+        s_r, s_c = [int(x) for x in stats["sum_wr"]], [int(x) for x in stats["sum_wc"]]
+        rr, cc, rc = _wide(shapes["sum_wrr"]), _wide(shapes["sum_wcc"]), _wide(shapes["sum_wrc"])
+    else:
+        if area is None:
+            raise ValueError("weighted=False needs area: the pixels every record counts (MergeTree.area)")
+        s0 = [int(x) for x in area]
+        s_r, s_c = [int(x) for x in stats["sum_r"]], [int(x) for x in stats["sum_c"]]
+        rr, cc, rc = _wide(shapes["sum_rr"]), _wide(shapes["sum_cc"]), _wide(shapes["sum_rc"])
+    if not (len(s0) == n == len(stats)):
+        raise ValueError("stats, shapes and area must have one record per colour")
+    var_r, var_c, cov = np.full(n, np.nan), np.full(n, np.nan), np.full(n, np.nan)
+    for i in range(n):
+        S = s0[i]
+        if S == 0:
+            continue
+        den = S * S
+        var_r[i] = (S * rr[i] - s_r[i] * s_r[i]) / den      # (int / int rounds once)
+        var_c[i] = (S * cc[i] - s_c[i] * s_c[i]) / den
+        cov[i] = (S * rc[i] - s_r[i] * s_c[i]) / den
+    root = np.hypot((var_r - var_c) / 2, cov)
+    mid = (var_r + var_c) / 2
+    major = np.sqrt(mid + root)
+    minor = np.sqrt(np.maximum(mid - root, 0.0))      # (rounding may leave a line's minor axis a hair below 0; nan stays nan)
+    angle = 0.5 * np.arctan2(2 * cov, var_r - var_c)
+    return var_r, var_c, cov, major, minor, angle
+
+
 def centroids(stats):
     """(row, col) float64 arrays: the weighted centroid sum_wr / sum_w, sum_wc / sum_w of every record of merge_tree_stats, in the
     coordinates of the padded plane; nan where sum_w == 0."""
@@ -1003,6 +1052,27 @@ class MergingWatershed(_Transform):
                                                  wt.ctypes.data if wt is not None else None, dtype, wstride, tree.ctypes.data,
                                                  stats.ctypes.data, labels.ctypes.data if want_labels else None))
         return MergeTree(tree[:, 0].copy(), tree[:, 1].copy(), tree[:, 2].copy(), tree[:, 3].copy(), labels), stats
+
+    def merge_tree_shapes(self, input, seeds, weights=None, want_labels=False):
+        """Not in the reference: merge_tree_stats and the second moments of every lake from the same flood (ws_merge_tree_shapes).
+        Returns (MergeTree, stats, shapes[, labels]): shapes is a numpy structured array (LAKE_SHAPE_DTYPE) of n_seeds + 1 records,
+        record c the exact 128-bit sums of v row^2, v col^2, v row col, row^2, col^2 and row col over the pixels `area[c]`
+        counts, each as (low, high) u64, record 0 those of the pixels never coloured; rows and columns are those of the padded
+        plane.  weights as merge_tree_stats.  ellipses(stats, shapes) gives sizes, elongations and position angles."""
+        a, stride = _as_image(input)
+        s, ns = _as_seeds(seeds)
+        h, w = a.shape
+        wt, dtype, wstride = _as_weights(weights, a.shape)
+        tree = np.empty((ns + 1, 4), dtype=np.uint32)
+        stats = np.empty(ns + 1, dtype=LAKE_STATS_DTYPE)
+        shapes = np.empty(ns + 1, dtype=LAKE_SHAPE_DTYPE)
+        labels = np.empty(self._shape(a), dtype=np.uint64) if want_labels else None
+        ctx = self._ctx()
+        ctx.check(_ffi.lib().ws_merge_tree_shapes(ctx.handle, a.ctypes.data, h, w, stride, s.ctypes.data, ns, ctypes.byref(self._opt),
+                                                  wt.ctypes.data if wt is not None else None, dtype, wstride, tree.ctypes.data,
+                                                  stats.ctypes.data, shapes.ctypes.data, labels.ctypes.data if want_labels else None))
+        mt = MergeTree(tree[:, 0].copy(), tree[:, 1].copy(), tree[:, 2].copy(), tree[:, 3].copy(), labels)
+        return (mt, stats, shapes, labels) if want_labels else (mt, stats, shapes)
 
     def merge_tree_cube(self, cube, seeds=None, want_labels=False):
         """merge_tree of every slice cube[k] of a 3-D u8 array with seeds[k] -- or, with seeds None, the slice's own

@@ -240,7 +240,7 @@ void ws_ctx_destroy(ws_ctx *c) {
   for (DevBuf *b : {&c->img, &c->keys, &c->labels, &c->labels2, &c->stamps, &c->flags, &c->seeds, &c->out64, &c->counts, &c->aux, &c->seed_stack, &c->min_counts, &c->min_nibbles, &c->seeds64,
                     &c->uf_parent, &c->uf_size, &c->uf_hooked, &c->uf_death, &c->uf_sd, &c->alive, &c->px_items, &c->edge_items, &c->mflags, &c->lakes, &c->refs, &c->seed_tab, &c->tile_list,
                     &c->stack_labels, &c->stack_records, &c->stack_bins, &c->batch_cube, &c->batch_seeds, &c->uf_hook, &c->history_planes,
-                    &c->tree_order, &c->tree_ws, &c->tree_out, &c->tree_forest, &c->lake_acc, &c->lake_out, &c->lake_weight, &c->tree_seed_px,
+                    &c->tree_order, &c->tree_ws, &c->tree_out, &c->tree_forest, &c->lake_acc, &c->lake_out, &c->lake_weight, &c->shape_acc, &c->shape_out, &c->tree_seed_px,
                     &c->cut_tables, &c->cut_counts, &c->cut_blocks, &c->cut_flags, &c->cut_planes, &c->cut_lakes, &c->cut_keys,
                     &c->cut_acc, &c->cut_hidden, &c->cut_region, &c->cut_forest, &c->cut_slices})
     if (b->p) (void)hipFree(b->p);

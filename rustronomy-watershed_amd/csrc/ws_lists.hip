@@ -1,6 +1,6 @@
 // ws_lists.hip -- the merging drivers (lib.rs:1328-1522) and transform_to_list (lib.rs:1551-1561, 1837-1847): per-level
 // unions over seed colours, lake areas and sparse lake records (kernels: ws_merge.hip the level loop, ws_merge_final.hip the
-// final labels alone, ws_merge_tree.hip history planes, merge tree and lake statistics; wrappers: ws_merge.hpp).  The per-level
+// final labels alone, ws_merge_tree.hip history planes, merge tree, lake statistics and lake shapes; wrappers: ws_merge.hpp).  The per-level
 // driver merge_host with the single-field entry points; the same products for cubes of slices: ws_batch.hip, which calls what
 // ws_lists.hpp declares.
 #include "ws_lists.hpp"
@@ -490,6 +490,22 @@ int wsapi::build_lake_stats(ws_ctx *c, const uint32_t *keys, const uint32_t *seg
   return WS_OK;
 }
 
+// ---- merge_tree_shapes: the lakes' second moments ---------------------------------------------------------
+
+static_assert(sizeof(ws_lake_shape) == 96 && sizeof(ws_lake_shape) == sizeof(ShapeRec) && sizeof(ws_lake_shape) == SHAPE_ACC_BYTES,
+              "ws_lake_shape is the kernels' ShapeRec");
+
+// the shapes of the tree build_tree has just finished at d_tree, after build_lake_stats, from the same transform, planes and weights
+int wsapi::build_lake_shapes(ws_ctx *c, const uint32_t *keys, const uint32_t *seg, const uint32_t *d_seeds, size_t n_seeds, const ws_options *opt, size_t ph,
+                      size_t pw, const ws_tree_node *d_tree, const LakeWeights &wt, ws_lake_shape *d_shapes) {
+  Span sp(c, KC_OTHER);
+  HIP_TRY(c, lake_shapes(c->stream, keys, seg, (const uint32_t *)c->uf_death.p,
+                         (const uint32_t *)c->uf_hook.p, reinterpret_cast<const TreeRec *>(d_tree), d_seeds, n_seeds + 1,
+                         (uint32_t)opt->max_water_level + 1, (const u64c *)c->tree_ws.p, (const uint32_t *)c->tree_order.p, wt, (int)ph, (int)pw,
+                         c->shape_acc.p, reinterpret_cast<ShapeRec *>(d_shapes)));
+  return WS_OK;
+}
+
 namespace {
 
 // what both forms check before anything runs
@@ -516,7 +532,14 @@ int ensure_lake(ws_ctx *c, size_t n_seeds, bool host_records) {
   return WS_OK;
 }
 
-// ---- the tree entry points' bodies: ws_merge_tree(_device), and with ls, ws_merge_tree_stats(_device) ---------------------------------
+int ensure_shape(ws_ctx *c, size_t n_seeds, bool host_records) {
+  int rc;
+  if ((rc = ensure(c, c->shape_acc, (n_seeds + 1) * SHAPE_ACC_BYTES))) return rc;
+  if (host_records && (rc = ensure(c, c->shape_out, (n_seeds + 1) * sizeof(ws_lake_shape)))) return rc;
+  return WS_OK;
+}
+
+// ---- the tree entry points' bodies: ws_merge_tree(_device); with ls, ws_merge_tree_stats(_device); with ls and sh, ws_merge_tree_shapes(_device)
 
 // the statistics request of ws_merge_tree_stats(_device): the weights (null: the image itself) and where the records go --
 // device pointers in the device form, host pointers in the host form
@@ -527,9 +550,16 @@ struct LakeStatsWanted {
   ws_lake_stats *stats = nullptr;
 };
 
+// the shapes request of ws_merge_tree_shapes(_device), which comes with a statistics request (its weights are the shapes'): where
+// the records go -- a device pointer in the device forms, a host pointer in the host form
+struct LakeShapesWanted {
+  ws_lake_shape *shapes = nullptr;
+};
+
 // All argument checks come before device work, and every buffer is ensured BEFORE the transform (ensure_tree).
 int merge_tree_device_body(ws_ctx *c, const uint8_t *d_img, size_t h, size_t w, size_t stride, const uint32_t *d_seeds_rc, size_t n_seeds,
-                           const ws_options *opt, ws_tree_node *d_tree, uint32_t *d_labels, const LakeStatsWanted *ls) {
+                           const ws_options *opt, ws_tree_node *d_tree, uint32_t *d_labels, const LakeStatsWanted *ls,
+                           const LakeShapesWanted *sh = nullptr) {
   size_t ph = 0, pw = 0;
   if (int rc = check_tree(c, h, w, stride, opt, n_seeds, &ph, &pw)) return rc;
   if (ls)
@@ -538,6 +568,8 @@ int merge_tree_device_body(ws_ctx *c, const uint8_t *d_img, size_t h, size_t w, 
   if (int rc = ensure_tree(c, n_seeds, false)) return rc;
   if (ls)
     if (int rc = ensure_lake(c, n_seeds, false)) return rc;
+  if (sh)
+    if (int rc = ensure_shape(c, n_seeds, false)) return rc;
   if (int rc = merge_host(c, LevelJob::from_device(true, d_img, h, w, stride, d_seeds_rc, n_seeds, opt).with_history())) return rc;
   // the seed pairs as the flood took them: the caller's, or (shifted_seeds) moved into the padded plane in the context's buffer
   const uint32_t *seeds = seed_shift_of(opt) && n_seeds ? (const uint32_t *)c->seeds.p : d_seeds_rc;
@@ -547,6 +579,8 @@ int merge_tree_device_body(ws_ctx *c, const uint8_t *d_img, size_t h, size_t w, 
     const LakeWeights wt = ls->weight ? LakeWeights{ls->weight, ls->stride, (uint32_t)h, (uint32_t)w, off, ls->dtype == WS_U16}
                                       : LakeWeights{d_img, stride, (uint32_t)h, (uint32_t)w, off, 0};
     if (int rc = build_lake_stats(c, (const uint32_t *)c->keys.p, (const uint32_t *)c->labels.p, seeds, n_seeds, opt, ph, pw, d_tree, wt, ls->stats)) return rc;
+    if (sh)
+      if (int rc = build_lake_shapes(c, (const uint32_t *)c->keys.p, (const uint32_t *)c->labels.p, seeds, n_seeds, opt, ph, pw, d_tree, wt, sh->shapes)) return rc;
   }
   if (d_labels && ph * pw) HIP_TRY(c, hipMemcpyAsync(d_labels, c->labels.p, ph * pw * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -554,7 +588,7 @@ int merge_tree_device_body(ws_ctx *c, const uint8_t *d_img, size_t h, size_t w, 
 }
 
 int merge_tree_host_body(ws_ctx *c, const uint8_t *img, size_t h, size_t w, size_t stride, const uint64_t *seeds_rc, size_t n_seeds,
-                         const ws_options *opt, ws_tree_node *tree, uint64_t *labels, const LakeStatsWanted *ls) {
+                         const ws_options *opt, ws_tree_node *tree, uint64_t *labels, const LakeStatsWanted *ls, const LakeShapesWanted *sh = nullptr) {
   size_t ph = 0, pw = 0;
   if (int rc = check_tree(c, h, w, stride, opt, n_seeds, &ph, &pw)) return rc;
   if (ls)
@@ -563,6 +597,8 @@ int merge_tree_host_body(ws_ctx *c, const uint8_t *img, size_t h, size_t w, size
   if (int rc = ensure_tree(c, n_seeds, true)) return rc;
   if (ls)
     if (int rc = ensure_lake(c, n_seeds, true)) return rc;
+  if (sh)
+    if (int rc = ensure_shape(c, n_seeds, true)) return rc;
   const size_t elem = ls && ls->weight && ls->dtype == WS_U16 ? 2 : 1;
   const bool own_plane = ls && ls->weight && h * w;
   if (own_plane) {      // contiguous on the context, before the transform: nothing moves under the level loop's graphs
@@ -578,9 +614,13 @@ int merge_tree_host_body(ws_ctx *c, const uint8_t *img, size_t h, size_t w, size
     const LakeWeights wt{own_plane ? c->lake_weight.p : c->img.p, w, (uint32_t)h, (uint32_t)w, opt->edge_correction ? 1u : 0u, elem == 2};
     if (int rc = build_lake_stats(c, (const uint32_t *)c->keys.p, (const uint32_t *)c->labels.p, seeds, n_seeds, opt, ph, pw, d_tree, wt, (ws_lake_stats *)c->lake_out.p))
       return rc;
+    if (sh)
+      if (int rc = build_lake_shapes(c, (const uint32_t *)c->keys.p, (const uint32_t *)c->labels.p, seeds, n_seeds, opt, ph, pw, d_tree, wt, (ws_lake_shape *)c->shape_out.p))
+        return rc;
   }
   HIP_TRY(c, hipMemcpyAsync(tree, d_tree, (n_seeds + 1) * sizeof(ws_tree_node), hipMemcpyDeviceToHost, c->stream));
   if (ls) HIP_TRY(c, hipMemcpyAsync(ls->stats, c->lake_out.p, (n_seeds + 1) * sizeof(ws_lake_stats), hipMemcpyDeviceToHost, c->stream));
+  if (sh) HIP_TRY(c, hipMemcpyAsync(sh->shapes, c->shape_out.p, (n_seeds + 1) * sizeof(ws_lake_shape), hipMemcpyDeviceToHost, c->stream));
   if (labels && ph * pw)
     if (int rc = labels_to_host_u64(c, (const uint32_t *)c->labels.p, labels, ph * pw)) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -589,10 +629,11 @@ int merge_tree_host_body(ws_ctx *c, const uint8_t *img, size_t h, size_t w, size
 
 // every buffer the arrival form needs that is sized by the colours alone: the tree's and the catalogue's workspace, the recovered
 // seed pairs and the union-find of the stamped level loop (the tiled forms call this on rank 0 before their gathers)
-int reserve_tree_arrival(ws_ctx *c, size_t n_seeds, bool stats) {
+int reserve_tree_arrival(ws_ctx *c, size_t n_seeds, bool stats, bool shapes = false) {
   int rc;
   if ((rc = ensure_tree(c, n_seeds, false))) return rc;
   if (stats && (rc = ensure_lake(c, n_seeds, false))) return rc;
+  if (shapes && (rc = ensure_shape(c, n_seeds, false))) return rc;
   if ((rc = ensure(c, c->tree_seed_px, std::max<size_t>(n_seeds, 1) * 2 * sizeof(uint32_t)))) return rc;
   if ((rc = ensure_uf(c, n_seeds + 1))) return rc;
   return ensure(c, c->uf_hook, (n_seeds + 1) * sizeof(uint32_t));
@@ -603,7 +644,7 @@ int reserve_tree_arrival(ws_ctx *c, size_t n_seeds, bool stats) {
 // stamp 0 marks them (seed_pixels_from_planes).  The plane is taken as it stands -- a padded plane comes in padded -- so the
 // weights have no offset.  No pixel (or no seed): the plane's record 0 alone.
 int merge_tree_arrival_body(ws_ctx *c, const uint32_t *d_keys, const uint32_t *d_seg, size_t h, size_t w, size_t n_seeds, const ws_options *opt,
-                            ws_tree_node *d_tree, const LakeStatsWanted *ls) {
+                            ws_tree_node *d_tree, const LakeStatsWanted *ls, const LakeShapesWanted *sh = nullptr) {
   ws_options plain = *opt;
   plain.edge_correction = 0;
   size_t ph = 0, pw = 0;
@@ -619,10 +660,11 @@ int merge_tree_arrival_body(ws_ctx *c, const uint32_t *d_keys, const uint32_t *d
     const ws_lake_stats nothing{0, 0, 0, 0, 0, 0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u};
     HIP_TRY(c, hipMemcpyAsync(d_tree, &none, sizeof none, hipMemcpyHostToDevice, c->stream));
     if (ls) HIP_TRY(c, hipMemcpyAsync(ls->stats, &nothing, sizeof nothing, hipMemcpyHostToDevice, c->stream));
+    if (sh) HIP_TRY(c, hipMemsetAsync(sh->shapes, 0, sizeof(ws_lake_shape), c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return WS_OK;
   }
-  if (int rc = reserve_tree_arrival(c, n_seeds, ls != nullptr)) return rc;
+  if (int rc = reserve_tree_arrival(c, n_seeds, ls != nullptr, sh != nullptr)) return rc;
   if (int rc = merge_host(c, LevelJob::from_arrival(true, d_keys, d_seg, h, w, n_seeds, &plain).with_history())) return rc;
   const uint32_t *seeds = (const uint32_t *)c->tree_seed_px.p;
   {
@@ -633,6 +675,8 @@ int merge_tree_arrival_body(ws_ctx *c, const uint32_t *d_keys, const uint32_t *d
   if (ls) {
     const LakeWeights wt{ls->weight, ls->stride, (uint32_t)h, (uint32_t)w, 0u, ls->dtype == WS_U16};
     if (int rc = build_lake_stats(c, d_keys, d_seg, seeds, n_seeds, &plain, ph, pw, d_tree, wt, ls->stats)) return rc;
+    if (sh)
+      if (int rc = build_lake_shapes(c, d_keys, d_seg, seeds, n_seeds, &plain, ph, pw, d_tree, wt, sh->shapes)) return rc;
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return WS_OK;
@@ -739,6 +783,47 @@ int ws_merge_tree_from_arrival_device(ws_ctx *c, const uint32_t *d_keys, const u
   LakeStatsWanted ls;
   ls.weight = d_weight; ls.dtype = weight_dtype; ls.stride = weight_row_stride; ls.stats = d_stats;
   return merge_tree_arrival_body(c, d_keys, d_seg_labels, h, w, n_seeds, opt, d_tree, &ls);
+}
+
+int ws_merge_tree_shapes_device(ws_ctx *c, const uint8_t *d_img, size_t h, size_t w, size_t stride, const uint32_t *d_seeds_rc, size_t n_seeds,
+                                const ws_options *opt, const void *d_weight, int weight_dtype, size_t weight_stride, ws_tree_node *d_tree,
+                                ws_lake_stats *d_stats, ws_lake_shape *d_shapes, uint32_t *d_labels) {
+  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
+  if (!c) return WS_ERR_BAD_ARG;
+  if (!opt || !d_tree || !d_stats || !d_shapes || (!d_img && h * w) || (!d_seeds_rc && n_seeds)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  if (reinterpret_cast<uintptr_t>(d_shapes) & 7u) return fail(c, WS_ERR_BAD_ARG, "d_shapes is not 8-byte aligned");
+  LakeStatsWanted ls;
+  ls.weight = d_weight; ls.dtype = weight_dtype; ls.stride = weight_stride; ls.stats = d_stats;
+  LakeShapesWanted sh;
+  sh.shapes = d_shapes;
+  return merge_tree_device_body(c, d_img, h, w, stride, d_seeds_rc, n_seeds, opt, d_tree, d_labels, &ls, &sh);
+}
+
+int ws_merge_tree_shapes(ws_ctx *c, const uint8_t *img, size_t h, size_t w, size_t stride, const uint64_t *seeds_rc, size_t n_seeds,
+                         const ws_options *opt, const void *weight, int weight_dtype, size_t weight_stride, ws_tree_node *tree,
+                         ws_lake_stats *stats, ws_lake_shape *shapes, uint64_t *labels) {
+  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
+  if (!c) return WS_ERR_BAD_ARG;
+  if (!opt || !tree || !stats || !shapes || (!img && h * w) || (!seeds_rc && n_seeds)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  LakeStatsWanted ls;
+  ls.weight = weight; ls.dtype = weight_dtype; ls.stride = weight_stride; ls.stats = stats;
+  LakeShapesWanted sh;
+  sh.shapes = shapes;
+  return merge_tree_host_body(c, img, h, w, stride, seeds_rc, n_seeds, opt, tree, labels, &ls, &sh);
+}
+
+int ws_merge_tree_shapes_from_arrival_device(ws_ctx *c, const uint32_t *d_keys, const uint32_t *d_seg_labels, size_t h, size_t w, size_t n_seeds,
+                                             const ws_options *opt, const void *d_weight, int weight_dtype, size_t weight_row_stride,
+                                             ws_tree_node *d_tree, ws_lake_stats *d_stats, ws_lake_shape *d_shapes) {
+  if (int busy_rc = refuse_if_in_flight(c)) return busy_rc;
+  if (!c) return WS_ERR_BAD_ARG;
+  if (!opt || !d_tree || !d_stats || !d_shapes || ((!d_keys || !d_seg_labels) && h * w)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  if (reinterpret_cast<uintptr_t>(d_shapes) & 7u) return fail(c, WS_ERR_BAD_ARG, "d_shapes is not 8-byte aligned");
+  LakeStatsWanted ls;
+  ls.weight = d_weight; ls.dtype = weight_dtype; ls.stride = weight_row_stride; ls.stats = d_stats;
+  LakeShapesWanted sh;
+  sh.shapes = d_shapes;
+  return merge_tree_arrival_body(c, d_keys, d_seg_labels, h, w, n_seeds, opt, d_tree, &ls, &sh);
 }
 
 // half: 0 the whole call; 1 ws_merge_device_begin (returns WS_INTERNAL_PENDING when the graph and the speculative unions

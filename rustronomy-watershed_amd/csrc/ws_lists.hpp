@@ -21,6 +21,8 @@ int build_tree(ws_ctx *c, const uint32_t *keys, const uint32_t *seg, const uint3
                ws_tree_node *d_tree);
 int build_lake_stats(ws_ctx *c, const uint32_t *keys, const uint32_t *seg, const uint32_t *d_seeds, size_t n_seeds, const ws_options *opt, size_t ph,
                      size_t pw, const ws_tree_node *d_tree, const LakeWeights &wt, ws_lake_stats *d_stats);
+int build_lake_shapes(ws_ctx *c, const uint32_t *keys, const uint32_t *seg, const uint32_t *d_seeds, size_t n_seeds, const ws_options *opt, size_t ph,
+                      size_t pw, const ws_tree_node *d_tree, const LakeWeights &wt, ws_lake_shape *d_shapes);
 
 // The cut of a cube of slices, or of one group of it (ws_tree_cut.hip): the records of n_slices trees one
 // behind the other (slice k's from seed_offsets[k] - seed_offsets[0] + k on), their stamps and labels as n_slices contiguous h x w

@@ -202,4 +202,17 @@ hipError_t lake_stats_stack(hipStream_t s, const uint32_t *keys, const uint32_t 
                             const TreeRec *forest, const uint32_t *stacked_rc, size_t n_colours, uint32_t levels, const u64c *ws,
                             const uint32_t *order, const LakeWeights &wt, const TreeStack &st, int w, void *acc, LakeRec *out);
 
+// lake shapes (ws_merge_tree_shapes_device): per colour six exact 128-bit sums -- v row^2, v col^2, v row col,
+// row^2, col^2, row col -- over the pixels `area` counts, each as (low, high) 64 bits.  Integers only.
+struct ShapeRec {      // == ws_lake_shape
+  u64c s[6][2];
+};
+constexpr size_t SHAPE_ACC_BYTES = 12 * sizeof(u64c);      // per colour: two carry-less limbs a sum (ws_shape_part.hpp)
+// After lake_stats' tree (tree: finished records; ws, order: tree_fold's buckets, left as they are; wt as lake_stats'): own sums in one
+// pass over the stamps, the segmenting labels and the weights, one fold launch per death level from 1 up, and the records into out
+// (n_colours of them, 8-byte aligned).  acc: n_colours * SHAPE_ACC_BYTES of scratch, 8-byte aligned.
+hipError_t lake_shapes(hipStream_t s, const uint32_t *keys, const uint32_t *labels, const uint32_t *death, const uint32_t *hook, const TreeRec *tree,
+                       const uint32_t *seeds_rc, size_t n_colours, uint32_t levels, const u64c *ws, const uint32_t *order, const LakeWeights &wt, int h,
+                       int w, void *acc, ShapeRec *out);
+
 }  // namespace wsk

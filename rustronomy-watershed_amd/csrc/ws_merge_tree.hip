@@ -1,8 +1,10 @@
 // ws_merge_tree.hip -- gfx950 kernels that read the stamped forest of a merging transform_history run (k_union_stamped,
 // ws_merge.hip: hook[b] = the root b was hooked under, death[b] = the level): the history planes, the merge tree and the lake
-// statistics, each for one plane and for a stack of slices.  Nothing here changes the union-find.
+// statistics, each for one plane and for a stack of slices, and the lakes' second moments for one plane.  Nothing here changes
+// the union-find.
 #include "ws_uf.hpp"
 #include "ws_lake_part.hpp"
+#include "ws_shape_part.hpp"
 
 namespace wsk {
 
@@ -653,6 +655,194 @@ hipError_t lake_stats_stack(hipStream_t s, const uint32_t *keys, const uint32_t 
   }
   if (wt.u16) k_lake_write<uint16_t, true><<<per_entry, 256, 0, s>>>(forest, stacked_rc, wt, (uint32_t)w, sum, box, n_acc, out, st);
   else k_lake_write<uint8_t, true><<<per_entry, 256, 0, s>>>(forest, stacked_rc, wt, (uint32_t)w, sum, box, n_acc, out, st);
+  return hipGetLastError();
+}
+
+// ---- lake shapes (ws_merge_tree_shapes_device) -------------------------------------------------------------
+//
+// The second moments of every lake: six exact 128-bit sums a record, carried as twelve carry-less u64 limbs (ws_shape_part.hpp), in
+// passes of their own after lake_stats over the same death[] / hook[] forest and the same order[] buckets.  Sums of integers do not
+// depend on the order the atomics arrive in: every record is reproducible to the bit.
+
+// Own shapes: k_lake_own's grid, loads, walks and three joins (the quad's pixels that share a root, the lanes that agree with the
+// wave's first lane, the workgroup's table keyed by root) with a ShapePart for a LakePart; an uncoloured pixel goes to record 0.
+// FLAT: both sides of the plane are below 65 536 (shape_wave_total).
+template <typename T, bool FLAT>
+__global__ __launch_bounds__(256) void k_shape_own(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ labels,
+                                                   const uint32_t *__restrict__ death, const uint32_t *__restrict__ hook, LakeWeights wt,
+                                                   uint32_t W, u64c *acc, size_t n_colours, size_t n, size_t steps) {
+  __shared__ u64c s_acc[SHAPE_LIMBS * SHAPE_SLOTS];
+  __shared__ uint32_t s_key[SHAPE_SLOTS], s_used;
+  for (int j = threadIdx.x; j < SHAPE_SLOTS; j += 256) {
+    s_key[j] = LAKE_EMPTY;
+    shape_store(s_acc, SHAPE_SLOTS, j, shape_none());
+  }
+  if (threadIdx.x == 0) s_used = 0;
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const bool vec = ((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(labels)) & 15u) == 0;
+  uint32_t flushed_at = 0;      // slots taken, over the run, when the table was last written out
+  for (size_t st = 0; st < steps; ++st) {      // workgroup uniform
+    const size_t i0 = (((size_t)blockIdx.x * steps + st) * 256 + threadIdx.x) * 4;
+    uint32_t arr[4], col[4];
+    if (vec && i0 + 3 < n) {
+      const u32x4_m k = *reinterpret_cast<const u32x4_m *>(keys + i0), l = *reinterpret_cast<const u32x4_m *>(labels + i0);
+      arr[0] = k.x >> 24; arr[1] = k.y >> 24; arr[2] = k.z >> 24; arr[3] = k.w >> 24;
+      col[0] = l.x; col[1] = l.y; col[2] = l.z; col[3] = l.w;
+    } else {
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        const bool in = i0 + p < n;
+        arr[p] = in ? keys[i0 + p] >> 24 : 0xFFu;
+        col[p] = in ? labels[i0 + p] : 0u;
+      }
+    }
+    uint32_t r[4], d[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const bool coloured = col[p] != 0u && arr[p] != 0xFFu;      // (as k_tree_own)
+      r[p] = coloured ? col[p] : 0u;
+      d[p] = coloured ? death[col[p]] : TREE_ALIVE;
+    }
+    for (;;) {      // the root at the pixel's arrival level, four walks side by side
+      bool go[4];
+#pragma unroll
+      for (int p = 0; p < 4; ++p) go[p] = d[p] <= arr[p];
+      if (!(go[0] || go[1] || go[2] || go[3])) break;
+#pragma unroll
+      for (int p = 0; p < 4; ++p) if (go[p]) r[p] = hook[r[p]];
+#pragma unroll
+      for (int p = 0; p < 4; ++p) if (go[p]) d[p] = death[r[p]];
+    }
+    uint32_t y = i0 < n ? (uint32_t)i0 / W : 0u, x = i0 < n ? (uint32_t)i0 % W : 0u;      // (n < 2^32)
+    ShapePart part[4];
+    bool live[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      live[p] = i0 + p < n;
+      part[p] = shape_pixel(live[p] ? lake_weight<T>(wt, y, x) : 0u, y, x);
+      if (++x == W) { x = 0; ++y; }
+    }
+#pragma unroll
+    for (int p = 1; p < 4; ++p)
+#pragma unroll
+      for (int q = 0; q < p; ++q)
+        if (live[p] && live[q] && r[p] == r[q]) { shape_join(part[q], part[p]); live[p] = false; }
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const unsigned long long todo = __builtin_amdgcn_ballot_w64(live[p]);
+      if (todo == 0) continue;      // wave uniform
+      const int leader = (int)__builtin_ctzll(todo);
+      const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)r[p], leader);
+      const bool same = live[p] && r[p] == r0;
+      if (__popcll(__builtin_amdgcn_ballot_w64(same)) > 1) {      // wave uniform
+        const ShapePart total = shape_wave_total<FLAT>(same ? part[p] : shape_none());
+        if (lane == leader) shape_add(s_key, s_acc, &s_used, acc, n_colours, r0, total);
+        else if (live[p] && !same) shape_add(s_key, s_acc, &s_used, acc, n_colours, r[p], part[p]);
+      } else if (live[p]) {
+        shape_add(s_key, s_acc, &s_used, acc, n_colours, r[p], part[p]);
+      }
+    }
+    __syncthreads();
+    const uint32_t used = s_used;      // (nobody inserts between the two barriers: workgroup uniform)
+    const bool full = used - flushed_at > SHAPE_SLOTS / 2;
+    if (full || st + 1 == steps) shape_flush(s_key, s_acc, acc, n_colours);
+    if (full) flushed_at = used;
+    __syncthreads();
+  }
+}
+
+// One death level from 1 up: every colour of the bucket joins its limbs into its parent's (children die strictly before their
+// parents: nobody reads a limb another lane is adding to).  Lanes that share a parent are joined in the wave first, as k_lake_fold.
+__global__ __launch_bounds__(256) void k_shape_fold(const TreeRec *__restrict__ tree, u64c *acc, size_t n_colours,
+                                                    const uint32_t *__restrict__ order, const u64c *__restrict__ range) {
+  const u64c first = range[0];
+  const size_t n = (size_t)(range[1] - first);
+  const int lane = threadIdx.x & 63;
+  order += first;
+  for (size_t base = (size_t)blockIdx.x * 256; base < n; base += (size_t)gridDim.x * 256) {      // uniform trip count per wave
+    const size_t i = base + threadIdx.x;
+    const bool active = i < n;
+    uint32_t p = 0xFFFFFFFFu;
+    ShapePart part = shape_none();
+    if (active) {
+      const uint32_t c = order[i];
+      p = tree[c].parent;
+      part = shape_load(acc, n_colours, c);
+    }
+    unsigned long long todo = __builtin_amdgcn_ballot_w64(active);
+    for (int round = 0; round < 2 && todo != 0; ++round) {
+      const int leader = (int)__builtin_ctzll(todo);
+      const uint32_t p0 = (uint32_t)__builtin_amdgcn_readlane((int)p, leader);
+      const bool same = active && p == p0;
+      const unsigned long long with = __builtin_amdgcn_ballot_w64(same);
+      if (__popcll(with) > 1) {      // wave uniform
+        const ShapePart total = shape_wave_total<false>(same ? part : shape_none());
+        if (lane == leader) shape_apply(acc, n_colours, p0, total);
+      } else if (lane == leader) {
+        shape_apply(acc, n_colours, p0, part);
+      }
+      todo &= ~with;
+    }
+    if ((todo >> lane) & 1ull) shape_apply(acc, n_colours, p, part);
+  }
+}
+
+// The records: every pair of limbs normalised to (low, high) once.  A colour that dies at level 0 handed on nothing and was never
+// the root of a pixel: it takes its seed pixel alone (as k_lake_write).
+template <typename T>
+__global__ __launch_bounds__(256) void k_shape_write(const TreeRec *__restrict__ tree, const uint32_t *__restrict__ seeds_rc, LakeWeights wt,
+                                                     const u64c *__restrict__ acc, size_t n_colours, ShapeRec *out) {
+  const size_t c = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (c >= n_colours) return;
+  ShapePart a = shape_load(acc, n_colours, c);
+  if (c != 0) {
+    const TreeRec t = tree[c];
+    if (t.death_level == 0u && t.n_leaves != 0u) {
+      const uint32_t y = seeds_rc[2 * (c - 1)], x = seeds_rc[2 * (c - 1) + 1];
+      a = shape_pixel(lake_weight<T>(wt, y, x), y, x);
+    }
+  }
+  ShapeRec rec;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) shape_normal(a, k, &rec.s[k][0], &rec.s[k][1]);
+  out[c] = rec;
+}
+
+hipError_t lake_shapes(hipStream_t s, const uint32_t *keys, const uint32_t *labels, const uint32_t *death, const uint32_t *hook, const TreeRec *tree,
+                       const uint32_t *seeds_rc, size_t n_colours, uint32_t levels, const u64c *ws, const uint32_t *order, const LakeWeights &wt, int h,
+                       int w, void *acc_bytes, ShapeRec *out) {
+  if (n_colours == 0) return hipSuccess;
+  const size_t n = (size_t)h * (size_t)w;
+  if (n > 0xFFFFFFFFull || ((reinterpret_cast<uintptr_t>(acc_bytes) | reinterpret_cast<uintptr_t>(out)) & 7u) != 0) return hipErrorInvalidValue;
+  u64c *acc = (u64c *)acc_bytes;
+  hipError_t e = hipMemsetAsync(acc, 0, n_colours * SHAPE_ACC_BYTES, s);      // the identity of the fold is twelve zeros
+  if (e != hipSuccess) return e;
+  if (n) {      // the grid of k_lake_own
+    const size_t quads = (n + 1023) / 1024;
+    const size_t steps = std::max<size_t>((quads + 2047) / 2048, 1);
+    const unsigned grid = (unsigned)((quads + steps - 1) / steps);
+    const bool flat = h < 65536 && w < 65536;
+    if (wt.u16) {
+      if (flat) k_shape_own<uint16_t, true><<<grid, 256, 0, s>>>(keys, labels, death, hook, wt, (uint32_t)w, acc, n_colours, n, steps);
+      else k_shape_own<uint16_t, false><<<grid, 256, 0, s>>>(keys, labels, death, hook, wt, (uint32_t)w, acc, n_colours, n, steps);
+    } else {
+      if (flat) k_shape_own<uint8_t, true><<<grid, 256, 0, s>>>(keys, labels, death, hook, wt, (uint32_t)w, acc, n_colours, n, steps);
+      else k_shape_own<uint8_t, false><<<grid, 256, 0, s>>>(keys, labels, death, hook, wt, (uint32_t)w, acc, n_colours, n, steps);
+    }
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  if (n_colours > 1) {      // (tree_fold built order[] and its bounds under the same condition)
+    const u64c *off = ws + NLEVELS + 1;
+    const unsigned grid = (unsigned)std::min<size_t>(std::max<size_t>(n_colours / (256 * 64), 1), 128);
+    for (uint32_t l = 1; l < levels; ++l) {
+      k_shape_fold<<<grid, 256, 0, s>>>(tree, acc, n_colours, order, off + l);
+      if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+  }
+  const unsigned per_colour = (unsigned)((n_colours + 255) / 256);
+  if (wt.u16) k_shape_write<uint16_t><<<per_colour, 256, 0, s>>>(tree, seeds_rc, wt, acc, n_colours, out);
+  else k_shape_write<uint8_t><<<per_colour, 256, 0, s>>>(tree, seeds_rc, wt, acc, n_colours, out);
   return hipGetLastError();
 }
 

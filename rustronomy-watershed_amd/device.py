@@ -438,6 +438,69 @@ class DeviceEngine:
                                                                     out.data_ptr(), out_stats.data_ptr() if want_stats else None))
         return (out, out_stats) if want_stats else out
 
+    @staticmethod
+    def _weight_plane(weights, h, w):
+        """(ws dtype, row stride in elements) of a 2-D device weight tensor of shape (h, w) with contiguous rows."""
+        u16 = {torch.int16, getattr(torch, "uint16", torch.int16)}
+        if weights.dtype != torch.uint8 and weights.dtype not in u16:
+            raise TypeError("weights must be a uint8, uint16 or int16 (u16 bits) tensor")
+        if not weights.is_cuda or weights.dim() != 2 or tuple(weights.shape) != (h, w) or (w > 1 and weights.stride(1) != 1):
+            raise ValueError(f"weights must be a device tensor of shape {(h, w)} with contiguous rows")
+        return _ffi.WS_DTYPES["uint8" if weights.dtype == torch.uint8 else "uint16"], (weights.stride(0) if h > 1 else w)
+
+    def _records(self, out, shape, dtype, name):
+        if out is None:
+            return torch.empty(shape, dtype=dtype, device=self.device)
+        if out.dtype != dtype or not out.is_contiguous() or tuple(out.shape) != shape:
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {shape}")
+        return out
+
+    def merge_tree_shapes(self, img, seeds, weights=None, max_level=254, edge=False, seed_shift=False, want_labels=False, out=None,
+                          out_stats=None, out_shapes=None):
+        """merge_tree_stats and the second moments of every lake from the same flood with everything in HBM
+        (ws_merge_tree_shapes_device): the tree and stats tensors of merge_tree_stats and an (n_seeds + 1, 12) int64 tensor of raw
+        ws_lake_shape words -- row c, the bits of colour c's 96 bytes: sum_wrr, sum_wcc, sum_wrc, sum_rr, sum_cc, sum_rc, each
+        exact in 128 bits as (low, high) uint64 bits.  Arguments as merge_tree_stats; `out_shapes`: a reusable contiguous tensor
+        of that shape (a view at an 8-byte offset is fine).  With want_labels returns (tree, stats, shapes, labels)."""
+        assert img.dtype == torch.uint8 and img.dim() == 2 and img.is_contiguous() and img.is_cuda
+        assert seeds.dtype == torch.int32 and seeds.is_cuda and (seeds.numel() == 0 or seeds.is_contiguous())
+        h, w = img.shape
+        ns = seeds.shape[0] if seeds.dim() == 2 else 0
+        dtype, wstride = self._weight_plane(weights, h, w) if weights is not None else (0, 0)
+        out = self._records(out, (ns + 1, 4), torch.int32, "out")
+        out_stats = self._records(out_stats, (ns + 1, 9), torch.int64, "out_stats")
+        out_shapes = self._records(out_shapes, (ns + 1, 12), torch.int64, "out_shapes")
+        labels = torch.empty(self._plane(img, edge), dtype=torch.int32, device=self.device) if want_labels else None
+        opt = self.options(max_level, edge, None, seed_shift)
+        self.ctx.check(_ffi.lib().ws_merge_tree_shapes_device(self.ctx.handle, img.data_ptr(), h, w, w, seeds.data_ptr() if ns else None, ns,
+                                                              ctypes.byref(opt), weights.data_ptr() if weights is not None else None, dtype,
+                                                              wstride, out.data_ptr(), out_stats.data_ptr(), out_shapes.data_ptr(),
+                                                              labels.data_ptr() if want_labels else None))
+        return (out, out_stats, out_shapes, labels) if want_labels else (out, out_stats, out_shapes)
+
+    def merge_tree_shapes_from_arrival(self, keys, labels, n_seeds, weights, max_level=254, out=None, out_stats=None, out_shapes=None):
+        """merge_tree_shapes of a segmenting transform that has already run, without a second flood
+        (ws_merge_tree_shapes_from_arrival_device): keys, labels, n_seeds and weights (required: this form has no image) as
+        merge_tree_from_arrival with want_stats.  Returns (tree, stats, shapes) as merge_tree_shapes."""
+        if keys.dim() != 2 or tuple(keys.shape) != tuple(labels.shape):
+            raise ValueError("keys and labels must be 2-D tensors of the same shape")
+        assert keys.dtype == torch.int32 and labels.dtype == torch.int32 and keys.is_cuda and labels.is_cuda
+        assert keys.numel() == 0 or (keys.is_contiguous() and labels.is_contiguous())
+        if weights is None:
+            raise ValueError("merge_tree_shapes_from_arrival has no image: the moments need weights")
+        h, w = keys.shape
+        ns = int(n_seeds)
+        dtype, wstride = self._weight_plane(weights, h, w)
+        out = self._records(out, (ns + 1, 4), torch.int32, "out")
+        out_stats = self._records(out_stats, (ns + 1, 9), torch.int64, "out_stats")
+        out_shapes = self._records(out_shapes, (ns + 1, 12), torch.int64, "out_shapes")
+        opt = self.options(max_level, False)
+        self.ctx.check(_ffi.lib().ws_merge_tree_shapes_from_arrival_device(self.ctx.handle, keys.data_ptr() if h * w else None,
+                                                                           labels.data_ptr() if h * w else None, h, w, ns,
+                                                                           ctypes.byref(opt), weights.data_ptr(), dtype, wstride,
+                                                                           out.data_ptr(), out_stats.data_ptr(), out_shapes.data_ptr()))
+        return out, out_stats, out_shapes
+
     def tree_cut(self, tree, keys, labels, cuts, out=None, want_lakes=False, stats=None):
         """The label planes -- with want_lakes, also the lake lists -- of a merge tree pruned by `cuts` (an api.Cut or up to 32),
         everything in HBM (ws_tree_cut_device): tree = the (n_seeds + 1, 4) int32 tensor of merge_tree, keys = the arrival stamps
