@@ -514,7 +514,8 @@ int ws_merge_tree_from_arrival_device(ws_ctx *ctx, const uint32_t *d_keys, const
  * than 2^32 pixels; the terms >> 32: below 2^64 because the sum is below 2^96), so every record is reproducible to the bit
  * (DESIGN.md section 4.3.2).  Stream ordered; returns with the records complete; afterwards ws_last_arrival_device behaves as
  * after ws_merge_tree_stats_device.  Workspace kept by the context on top of ws_merge_tree_stats_device's: 96 B a colour, all of
- * it reserved before the transform.  Cubes, tiled groups and the regions of a cut have no such call yet. */
+ * it reserved before the transform.  Cubes: ws_merge_tree_shapes_batch(_device); tiled groups and the regions of a cut have no such
+ * call yet. */
 int ws_merge_tree_shapes_device(ws_ctx *ctx, const uint8_t *d_img, size_t h, size_t w, size_t row_stride, const uint32_t *d_seeds_rc,
                                 size_t n_seeds, const ws_options *opt, const void *d_weight, int weight_dtype,
                                 size_t weight_row_stride, ws_tree_node *d_tree, ws_lake_stats *d_stats, ws_lake_shape *d_shapes,
@@ -743,6 +744,36 @@ int ws_merge_tree_stats_batch(ws_ctx *ctx, const uint8_t *cube, size_t n_slices,
                               const uint64_t *seeds_rc, const size_t *seed_offsets, const ws_options *opt, const void *weight,
                               int weight_dtype, size_t weight_row_stride, size_t weight_slice_stride, ws_tree_node *tree,
                               ws_lake_stats *stats, size_t cap, size_t *n_records, uint64_t *labels, size_t *n_seeds, size_t *failed_slice);
+/* ws_merge_tree_shapes_device of every slice of a cube in one call, everything in HBM.  Every argument
+ * but d_shapes as ws_merge_tree_stats_batch_device, and d_tree and d_stats are byte for byte what that call writes for the same
+ * arguments.  d_shapes (device, 8-byte aligned) has the same slice-major layout: slice k's n_k + 1 records start at
+ * (seed_offsets[k] - seed_offsets[0]) + k, and no other word of it is written.  Every d_shapes record is bit-identical to what
+ * ws_merge_tree_shapes_device writes for that slice alone with that slice's weight plane: rows and columns are those of the slice's
+ * own padded plane, record 0 of a slice covers the pixels of THAT slice the last level leaves uncoloured, a slice without seeds
+ * owns that one record, and the identity is twelve zero words.  Refused before anything runs, all three outputs and d_labels
+ * untouched: what ws_merge_tree_stats_batch_device refuses, in its order, then a null d_shapes and a d_shapes off 8-byte alignment
+ * (WS_ERR_BAD_ARG).  There is no further WS_ERR_TOO_LARGE: the bound of the stats call is a slice's (wmax * pixels of a slice *
+ * its longer side < 2^64), rows and columns restart in every slice, and every accumulator entry -- a colour, or a slice's
+ * uncoloured pixels -- takes pixels of ONE slice only, so the limb argument of ws_merge_tree_shapes_device (a sum below 2^96, both
+ * limbs below 2^64) holds entry by entry however many slices a group stacks.  n_slices == 0 writes nothing.  A group that stacks
+ * runs the shape kernels once over the group after the statistics kernels, one fold launch per level for all of its slices;
+ * anything else, and a stack that fails or mispredicts, runs as a loop that names the failing slice.  Scratch, kept by the context
+ * and reserved before the first transform: as ws_merge_tree_stats_batch_device and 96 B for every colour of the largest group, one
+ * more, and one per slice of a group.  Tiled groups and the regions of a cut have no such call. */
+int ws_merge_tree_shapes_batch_device(ws_ctx *ctx, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w, size_t row_stride,
+                                      size_t slice_stride, const uint32_t *d_seeds_rc, const size_t *seed_offsets, const ws_options *opt,
+                                      const void *d_weight, int weight_dtype, size_t weight_row_stride, size_t weight_slice_stride,
+                                      ws_tree_node *d_tree, ws_lake_stats *d_stats, ws_lake_shape *d_shapes, uint32_t *d_labels,
+                                      size_t *failed_slice);
+/* The same from and into HOST memory, as ws_merge_tree_stats_batch: `tree`, `stats` and `shapes` hold `cap` records each (all three
+ * required unless cap == 0).  cap too small: WS_ERR_CAPACITY once the minima are found or counted and before any flood, *n_records
+ * set, the three arrays and `labels` untouched.  The three record arrays cross the bus once each; keeps 96 B a record more on the
+ * device. */
+int ws_merge_tree_shapes_batch(ws_ctx *ctx, const uint8_t *cube, size_t n_slices, size_t h, size_t w, size_t row_stride, size_t slice_stride,
+                               const uint64_t *seeds_rc, const size_t *seed_offsets, const ws_options *opt, const void *weight,
+                               int weight_dtype, size_t weight_row_stride, size_t weight_slice_stride, ws_tree_node *tree,
+                               ws_lake_stats *stats, ws_lake_shape *shapes, size_t cap, size_t *n_records, uint64_t *labels,
+                               size_t *n_seeds, size_t *failed_slice);
 /* ws_tree_cut_catalogue_device of every slice of a cube in one call, from records and planes held in HBM.
  * d_tree and d_stats (nullable when no cut has a catalogue threshold) in the slice-major layout ws_merge_tree(_stats)_batch_device
  * writes: seed_offsets (n_slices + 1 entries, on the HOST), slice k with its n_k = seed_offsets[k + 1] - seed_offsets[k] seeds owns

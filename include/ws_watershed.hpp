@@ -660,6 +660,29 @@ class MergingWatershed : public Watershed<T> {        // lib.rs:1297-1562
                                                    bool want_labels = false, std::vector<std::size_t> *n_seeds = nullptr) const {
     return lake_catalogue_cube(cube, n_slices, rows, cols, weights, WS_U16, seeds, want_labels, n_seeds);
   }
+  // not in the reference: merge_tree_shapes of every slice of a contiguous cube as ONE call of the library
+  // (ws_merge_tree_shapes_batch: slices that stack run the shape kernels once over the stack, after the tree's and the
+  // statistics').  Every catalogue is what merge_tree_shapes returns for the slice alone, `shapes` filled: rows and columns are the
+  // slice's own.  Arguments as merge_tree_stats_cube.
+  std::vector<LakeCatalogue> merge_tree_shapes_cube(const std::uint8_t *cube, std::size_t n_slices, std::size_t rows, std::size_t cols,
+                                                    const std::vector<std::vector<Seed>> *seeds = nullptr, bool want_labels = false,
+                                                    std::vector<std::size_t> *n_seeds = nullptr) const {
+    return lake_catalogue_cube(cube, n_slices, rows, cols, nullptr, 0, seeds, want_labels, n_seeds, true);
+  }
+  std::vector<LakeCatalogue> merge_tree_shapes_cube(const std::uint8_t *cube, std::size_t n_slices, std::size_t rows, std::size_t cols,
+                                                    std::nullptr_t, bool want_labels = false, std::vector<std::size_t> *n_seeds = nullptr) const {
+    return lake_catalogue_cube(cube, n_slices, rows, cols, nullptr, 0, nullptr, want_labels, n_seeds, true);
+  }
+  std::vector<LakeCatalogue> merge_tree_shapes_cube(const std::uint8_t *cube, std::size_t n_slices, std::size_t rows, std::size_t cols,
+                                                    const std::uint8_t *weights, const std::vector<std::vector<Seed>> *seeds = nullptr,
+                                                    bool want_labels = false, std::vector<std::size_t> *n_seeds = nullptr) const {
+    return lake_catalogue_cube(cube, n_slices, rows, cols, weights, WS_U8, seeds, want_labels, n_seeds, true);
+  }
+  std::vector<LakeCatalogue> merge_tree_shapes_cube(const std::uint8_t *cube, std::size_t n_slices, std::size_t rows, std::size_t cols,
+                                                    const std::uint16_t *weights, const std::vector<std::vector<Seed>> *seeds = nullptr,
+                                                    bool want_labels = false, std::vector<std::size_t> *n_seeds = nullptr) const {
+    return lake_catalogue_cube(cube, n_slices, rows, cols, weights, WS_U16, seeds, want_labels, n_seeds, true);
+  }
 
   // not in the reference: tree_cut_catalogue of every slice of a contiguous cube as ONE call of the library
   // (ws_merge_tree_cut_catalogue_batch: slices that stack share one flood, and every stacked group is cut once, while its stamps
@@ -751,7 +774,7 @@ class MergingWatershed : public Watershed<T> {        // lib.rs:1297-1562
   }
   std::vector<LakeCatalogue> lake_catalogue_cube(const std::uint8_t *cube, std::size_t n_slices, std::size_t rows, std::size_t cols,
                                                  const void *weights, int dtype, const std::vector<std::vector<Seed>> *seeds,
-                                                 bool want_labels, std::vector<std::size_t> *n_seeds) const {
+                                                 bool want_labels, std::vector<std::size_t> *n_seeds, bool with_shapes = false) const {
     if (seeds && seeds->size() != n_slices) throw std::invalid_argument("one seed list per slice");
     const std::size_t e = this->opt_.edge_correction ? 2 : 0, prow = rows + e, pcol = cols + e, npx = prow * pcol;
     std::vector<std::uint64_t> packed;
@@ -767,15 +790,23 @@ class MergingWatershed : public Watershed<T> {        // lib.rs:1297-1562
     std::size_t cap = seeds ? offs[n_slices] + n_slices : n_slices * (rows * cols / 8 + 1), total = 0, failed = 0;
     std::vector<ws_tree_node> flat(cap);
     std::vector<ws_lake_stats> records(cap);
+    std::vector<ws_lake_shape> shapes(with_shapes ? cap : 0);
     std::vector<usize> labels(want_labels ? n_slices * npx : 0);
     for (int attempt = 0; attempt < 2; ++attempt) {
-      const int rc = ws_merge_tree_stats_batch(this->ctx_->get(), cube, n_slices, rows, cols, cols, rows * cols, seeds ? packed.data() : nullptr,
-                                               seeds ? offs.data() : nullptr, &this->opt_, weights, dtype, cols, rows * cols, flat.data(),
-                                               records.data(), cap, &total, want_labels ? labels.data() : nullptr, counts.data(), &failed);
+      const std::uint64_t *seeds_rc = seeds ? packed.data() : nullptr;
+      const std::size_t *seed_offs = seeds ? offs.data() : nullptr;
+      usize *labels_out = want_labels ? labels.data() : nullptr;
+      const int rc = with_shapes ? ws_merge_tree_shapes_batch(this->ctx_->get(), cube, n_slices, rows, cols, cols, rows * cols, seeds_rc, seed_offs,
+                                                              &this->opt_, weights, dtype, cols, rows * cols, flat.data(), records.data(),
+                                                              shapes.data(), cap, &total, labels_out, counts.data(), &failed)
+                                 : ws_merge_tree_stats_batch(this->ctx_->get(), cube, n_slices, rows, cols, cols, rows * cols, seeds_rc, seed_offs,
+                                                             &this->opt_, weights, dtype, cols, rows * cols, flat.data(), records.data(), cap,
+                                                             &total, labels_out, counts.data(), &failed);
       if (rc == WS_ERR_CAPACITY && total > cap && attempt == 0) {
         cap = total;
         flat.resize(cap);
         records.resize(cap);
+        if (with_shapes) shapes.resize(cap);
         continue;
       }
       this->ctx_->check(rc);
@@ -788,6 +819,7 @@ class MergingWatershed : public Watershed<T> {        // lib.rs:1297-1562
       LakeCatalogue cat{MergeTree{std::vector<ws_tree_node>(flat.begin() + at, flat.begin() + at + n),
                                   Array2<usize>(want_labels ? prow : 0, want_labels ? pcol : 0)},
                         std::vector<ws_lake_stats>(records.begin() + at, records.begin() + at + n)};
+      if (with_shapes) cat.shapes.assign(shapes.begin() + at, shapes.begin() + at + n);
       if (want_labels) std::copy(labels.begin() + k * npx, labels.begin() + (k + 1) * npx, cat.tree.labels.data.begin());
       out.push_back(std::move(cat));
       at += n;

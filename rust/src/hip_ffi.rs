@@ -375,6 +375,15 @@ extern "C" {
         slice_stride: usize, seeds_rc: *const u64, seed_offsets: *const usize, opt: *const ws_options, weight: *const c_void,
         weight_dtype: c_int, weight_row_stride: usize, weight_slice_stride: usize, tree: *mut ws_tree_node, stats: *mut ws_lake_stats,
         cap: usize, n_records: *mut usize, labels: *mut u64, n_seeds: *mut usize, failed_slice: *mut usize) -> c_int;
+    pub fn ws_merge_tree_shapes_batch_device(ctx: *mut ws_ctx, d_cube: *const u8, n_slices: usize, h: usize, w: usize, row_stride: usize,
+        slice_stride: usize, d_seeds_rc: *const u32, seed_offsets: *const usize, opt: *const ws_options, d_weight: *const c_void,
+        weight_dtype: c_int, weight_row_stride: usize, weight_slice_stride: usize, d_tree: *mut ws_tree_node,
+        d_stats: *mut ws_lake_stats, d_shapes: *mut ws_lake_shape, d_labels: *mut u32, failed_slice: *mut usize) -> c_int;
+    pub fn ws_merge_tree_shapes_batch(ctx: *mut ws_ctx, cube: *const u8, n_slices: usize, h: usize, w: usize, row_stride: usize,
+        slice_stride: usize, seeds_rc: *const u64, seed_offsets: *const usize, opt: *const ws_options, weight: *const c_void,
+        weight_dtype: c_int, weight_row_stride: usize, weight_slice_stride: usize, tree: *mut ws_tree_node, stats: *mut ws_lake_stats,
+        shapes: *mut ws_lake_shape, cap: usize, n_records: *mut usize, labels: *mut u64, n_seeds: *mut usize,
+        failed_slice: *mut usize) -> c_int;
     pub fn ws_tree_cut_catalogue_batch_device(ctx: *mut ws_ctx, d_tree: *const ws_tree_node, d_stats: *const ws_lake_stats, n_slices: usize,
         seed_offsets: *const usize, d_keys: *const u32, d_seg_labels: *const u32, h: usize, w: usize, d_weight: *const c_void,
         weight_dtype: c_int, weight_row_stride: usize, weight_slice_stride: usize, cuts: *const ws_lake_cut, n_cuts: usize,

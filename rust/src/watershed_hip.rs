@@ -983,6 +983,64 @@ impl<T> MergingWatershed<T> {
             .collect();
         (out, n_seeds)
     }
+    /// Not in the reference: `merge_tree_shapes(cube[k], &find_local_minima(cube[k]), weights[k], want_labels)` of every slice of a
+    /// cube as one call (`ws_merge_tree_shapes_batch`: slices that stack run the shape kernels once over the stack, after the
+    /// tree's and the statistics').  Returns per slice the tree, its first-moment records and its second moments, in the slice's
+    /// own colours, rows and columns, and the number of minima of every slice.  `weights` as `merge_tree_stats_cube`.
+    #[allow(clippy::type_complexity)]
+    pub fn merge_tree_shapes_cube(&self, cube: nd::ArrayView3<u8>, weights: Option<nd::ArrayView3<u16>>, want_labels: bool)
+                                  -> (Vec<(MergeTree, Vec<hip_ffi::ws_lake_stats>, Vec<hip_ffi::ws_lake_shape>)>, Vec<usize>) {
+        let (n, h, w) = cube.dim();
+        let std_cube = cube.as_standard_layout();
+        let o = self.opt.ffi();
+        let (ph, pw) = self.opt.plane(h, w);
+        let planes = weights.map(|a| {
+            assert_eq!(a.dim(), (n, h, w), "weights must have the cube's shape");
+            a.as_standard_layout().into_owned()
+        });
+        let (wt_ptr, wt_dtype) = match planes.as_ref() {
+            Some(a) => (a.as_ptr() as *const std::ffi::c_void, hip_ffi::WS_U16),
+            None => (std::ptr::null(), 0),
+        };
+        // (as merge_tree_cube: a too small guess is answered with the count before any flood)
+        let mut cap = n * (h * w / 8 + 1);
+        let mut flat = vec![hip_ffi::ws_tree_node::default(); cap];
+        let mut records = vec![hip_ffi::ws_lake_stats::default(); cap];
+        let mut moments = vec![hip_ffi::ws_lake_shape::default(); cap];
+        let mut labels = if want_labels { Some(nd::Array3::<usize>::zeros((n, ph, pw))) } else { None };
+        let lab_ptr = match labels.as_mut() {
+            Some(a) => a.as_slice_mut().expect("standard layout").as_mut_ptr() as *mut u64,
+            None => std::ptr::null_mut(),
+        };
+        let mut n_seeds = vec![0usize; n];
+        let (mut total, mut failed) = (0usize, 0usize);
+        shim::with_ctx(|ctx| unsafe {
+            for attempt in 0..2 {
+                let rc = hip_ffi::ws_merge_tree_shapes_batch(ctx, std_cube.as_ptr(), n, h, w, w, h * w, std::ptr::null(), std::ptr::null(), &o,
+                                                             wt_ptr, wt_dtype, w, h * w, flat.as_mut_ptr(), records.as_mut_ptr(),
+                                                             moments.as_mut_ptr(), cap, &mut total, lab_ptr, n_seeds.as_mut_ptr(), &mut failed);
+                if rc == hip_ffi::WS_ERR_CAPACITY && total > cap && attempt == 0 {
+                    cap = total;
+                    flat.resize(cap, hip_ffi::ws_tree_node::default());
+                    records.resize(cap, hip_ffi::ws_lake_stats::default());
+                    moments.resize(cap, hip_ffi::ws_lake_shape::default());
+                    continue;
+                }
+                shim::check(ctx, rc, "ws_merge_tree_shapes_batch");
+                break;
+            }
+        });
+        let mut at = 0usize;
+        let out = (0..n)
+            .map(|k| {
+                let rows = at..at + n_seeds[k] + 1;
+                at += n_seeds[k] + 1;
+                (MergeTree { nodes: flat[rows.clone()].to_vec(), labels: labels.as_ref().map(|a| a.slice(nd::s![k, .., ..]).to_owned()) },
+                 records[rows.clone()].to_vec(), moments[rows].to_vec())
+            })
+            .collect();
+        (out, n_seeds)
+    }
     /// Not in the reference: `tree_cut_catalogue(cube[k], &find_local_minima(cube[k]), weights[k], cuts)` of every slice of a cube
     /// as one call (`ws_merge_tree_cut_catalogue_batch`: slices that stack share one flood, and every stacked group is cut once,
     /// while its stamps are on the device).  Returns per slice the `CutCatalogue` of the slice alone -- its own colours, rows,

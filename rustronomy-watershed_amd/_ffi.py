@@ -199,6 +199,10 @@ SIGNATURES = {
                                                         vp, vp, vp, szp]),
     "ws_merge_tree_stats_batch": (ctypes.c_int, [vp, vp, sz, sz, sz, sz, sz, vp, szp, ctypes.POINTER(Options), vp, ctypes.c_int, sz, sz,
                                                  vp, vp, sz, szp, vp, szp, szp]),
+    "ws_merge_tree_shapes_batch_device": (ctypes.c_int, [vp, vp, sz, sz, sz, sz, sz, vp, szp, ctypes.POINTER(Options), vp, ctypes.c_int, sz, sz,
+                                                         vp, vp, vp, vp, szp]),
+    "ws_merge_tree_shapes_batch": (ctypes.c_int, [vp, vp, sz, sz, sz, sz, sz, vp, szp, ctypes.POINTER(Options), vp, ctypes.c_int, sz, sz,
+                                                  vp, vp, vp, sz, szp, vp, szp, szp]),
     "ws_tree_cut_catalogue_batch_device": (ctypes.c_int, [vp, vp, vp, sz, szp, vp, vp, sz, sz, vp, ctypes.c_int, sz, sz, vp, sz, vp, sz, vp, vp, sz, szp,
                                                           vp, vp, vp]),
     "ws_merge_tree_cut_catalogue_batch_device": (ctypes.c_int, [vp, vp, sz, sz, sz, sz, sz, vp, szp, ctypes.POINTER(Options), vp, ctypes.c_int, sz, sz,

@@ -1138,6 +1138,18 @@ class MergingWatershed(_Transform):
         per slice, as merge_tree_stats returns them for the slice alone: the slice's own colours, rows, columns and peak pixels
         (and, with seeds None, the number of minima of every slice); want_labels as merge_tree_cube.  Not a method of the
         reference."""
+        return self._tree_stats_cube(cube, seeds, weights, want_labels, False)
+
+    def merge_tree_shapes_cube(self, cube, seeds=None, weights=None, want_labels=False):
+        """merge_tree_shapes of every slice of a cube in ONE call of the library (ws_merge_tree_shapes_batch: slices that stack
+        run the shape kernels once over the stack, after the tree's and the statistics').  cube, seeds, weights and want_labels
+        as merge_tree_stats_cube.  Returns a list of (MergeTree, stats, shapes), one per slice, as merge_tree_shapes returns them
+        for the slice alone -- rows and columns are the slice's own, so ellipses(stats, shapes) works on a slice's pair unchanged
+        (and, with seeds None, the number of minima of every slice).  Not a method of the reference."""
+        return self._tree_stats_cube(cube, seeds, weights, want_labels, True)
+
+    def _tree_stats_cube(self, cube, seeds, weights, want_labels, with_shapes):
+        """merge_tree_stats_cube and, with_shapes, merge_tree_shapes_cube: the two calls differ in one record array."""
         c = np.asarray(cube)
         if c.ndim != 3:
             raise ValueError("cube must be 3-D: (slices, rows, columns)")
@@ -1173,22 +1185,25 @@ class MergingWatershed(_Transform):
         counts = np.zeros(max(n, 1), dtype=np.uintp)
         tree = np.empty((max(cap, 1), 4), dtype=np.uint32)
         stats = np.empty(max(cap, 1), dtype=LAKE_STATS_DTYPE)
+        shapes = np.empty(max(cap, 1), dtype=LAKE_SHAPE_DTYPE) if with_shapes else None
         if n:
             ctx = self._ctx()
             total = ctypes.c_size_t(0)
             failed = ctypes.c_size_t(0)
             for attempt in range(2):
-                rc = _ffi.lib().ws_merge_tree_stats_batch(ctx.handle, c.ctypes.data, n, h, w, w, h * w,
-                                                          flat.ctypes.data if flat is not None else None,
-                                                          offs.ctypes.data_as(_ffi.szp) if offs is not None else None,
-                                                          ctypes.byref(self._opt), wt.ctypes.data if wt is not None else None, dtype, w, h * w,
-                                                          tree.ctypes.data, stats.ctypes.data, cap, ctypes.byref(total),
-                                                          labels.ctypes.data if want_labels else None, counts.ctypes.data_as(_ffi.szp),
-                                                          ctypes.byref(failed))
+                inputs = (ctx.handle, c.ctypes.data, n, h, w, w, h * w, flat.ctypes.data if flat is not None else None,
+                          offs.ctypes.data_as(_ffi.szp) if offs is not None else None, ctypes.byref(self._opt),
+                          wt.ctypes.data if wt is not None else None, dtype, w, h * w, tree.ctypes.data, stats.ctypes.data)
+                rest = (cap, ctypes.byref(total), labels.ctypes.data if want_labels else None, counts.ctypes.data_as(_ffi.szp), ctypes.byref(failed))
+                if with_shapes:
+                    rc = _ffi.lib().ws_merge_tree_shapes_batch(*inputs, shapes.ctypes.data, *rest)
+                else:
+                    rc = _ffi.lib().ws_merge_tree_stats_batch(*inputs, *rest)
                 if rc == _ffi.WS_ERR_CAPACITY and total.value > cap and attempt == 0:
                     cap = total.value
                     tree = np.empty((cap, 4), dtype=np.uint32)
                     stats = np.empty(cap, dtype=LAKE_STATS_DTYPE)
+                    shapes = np.empty(cap, dtype=LAKE_SHAPE_DTYPE) if with_shapes else None
                     continue
                 ctx.check(rc)
                 break
@@ -1197,6 +1212,7 @@ class MergingWatershed(_Transform):
         out = []
         for k in range(n):
             t = tree[first[k]:first[k + 1]]
-            out.append((MergeTree(t[:, 0].copy(), t[:, 1].copy(), t[:, 2].copy(), t[:, 3].copy(), labels[k] if want_labels else None),
-                        stats[first[k]:first[k + 1]]))      # (views of one array, as the labels: 72 B a record add up)
+            mt = MergeTree(t[:, 0].copy(), t[:, 1].copy(), t[:, 2].copy(), t[:, 3].copy(), labels[k] if want_labels else None)
+            rec = (mt, stats[first[k]:first[k + 1]])      # (views of one array, as the labels: 72 B a record add up)
+            out.append(rec + (shapes[first[k]:first[k + 1]],) if with_shapes else rec)
         return out if seeds is not None else (out, counts[:n].astype(np.int64))

@@ -1,6 +1,6 @@
 // ws_batch.hip -- the cube drivers: every product of the library for a batch of equal-sized independent slices on the device
-// (final labels segmenting and merging, lake lists, history planes, merge trees, lake catalogues).  One description of a batch
-// (Batch, check_batch), one decision whether its slices run as stacks (stackable), one walk over the groups of a stack with the
+// (final labels segmenting and merging, lake lists, history planes, merge trees, lake catalogues, lake shapes).  One description of
+// a batch (Batch, check_batch), one decision whether its slices run as stacks (stackable), one walk over the groups of a stack with the
 // slice-by-slice loop behind it (run_batch); the products plug into the walk with what they do to a flooded group and to one slice.
 // The per-level driver and the single-field forms they call: ws_lists.hip (ws_lists.hpp); the flood of a stack: ws_segment.hip.
 #include "ws_lists.hpp"
@@ -363,12 +363,15 @@ int build_tree_stack(ws_ctx *c, const BatchGroup &grp, const Batch &b, ws_tree_n
 // ---- merge_tree_stats of a cube of slices (ws_merge_tree_stats_batch(_device)) ------------------------------
 
 // the statistics request of a batch: the weight cube (null: the image cube itself, u8) with its strides in elements, and where the
-// records go (the layout of the tree's) -- device pointers in the device form, host pointers in the host form
+// records go (the layout of the tree's) -- device pointers in the device form, host pointers in the host form.  with_shapes
+// (ws_merge_tree_shapes_batch(_device)): the second moments too, from the same weights, into `shapes` in the same layout
 struct LakeBatchWanted {
   const void *weight = nullptr;
   int dtype = 0;
   size_t stride = 0, slice_stride = 0;
   ws_lake_stats *stats = nullptr;
+  bool with_shapes = false;
+  ws_lake_shape *shapes = nullptr;
 };
 
 // what both forms check after check_batch, before anything runs: the weights as check_lake_weights for one slice's plane (the
@@ -399,10 +402,24 @@ int build_lake_stats_stack(ws_ctx *c, const BatchGroup &grp, const Batch &b, con
   return WS_OK;
 }
 
+// the shapes of the same forest, after build_lake_stats_stack (the buckets are still where tree_fold left them), into the caller's
+// layout at d_shapes
+int build_lake_shapes_stack(ws_ctx *c, const BatchGroup &grp, const Batch &b, const LakeWeights &wt, ws_lake_shape *d_shapes) {
+  const TreeStack st{grp.base, (uint32_t)grp.g, (uint32_t)b.plane()};
+  Span sp(c, KC_OTHER);
+  HIP_TRY(c, lake_shapes_stack(c->stream, grp.keys, grp.labels, (const uint32_t *)c->uf_death.p, (const uint32_t *)c->uf_hook.p,
+                               (const TreeRec *)c->tree_forest.p, (const uint32_t *)c->seed_stack.p, grp.ns + 1, (uint32_t)b.opt->max_water_level + 1,
+                               (const u64c *)c->tree_ws.p, (const uint32_t *)c->tree_order.p, wt, st, (int)b.pw, c->shape_acc.p,
+                               reinterpret_cast<ShapeRec *>(d_shapes)));
+  return WS_OK;
+}
+
 // The trees of a batch into d_tree (device; slice k's n_k + 1 records from (seed_offsets[k] - seed_offsets[0]) + k on), every group's
 // segmenting labels handed to labels(BatchGroup) while they are on the context; with ls, every group's statistics into
 // ls->stats (device) in the same layout -- a stacked group's from the forest (lake_stats_stack: one fold launch per level for the group),
-// a looped slice's as ws_merge_tree_stats_device's with that slice's weight plane.  Every buffer the tree and statistics kernels
+// a looped slice's as ws_merge_tree_stats_device's with that slice's weight plane; with ls->with_shapes, the shapes after them into
+// ls->shapes, a stacked group's from the same forest and buckets (lake_shapes_stack), a looped slice's as
+// ws_merge_tree_shapes_device's.  Every buffer the tree and statistics kernels
 // need is sized for the largest group BEFORE the first transform (nothing moves under the level loop's captured graphs).
 template <class F>
 int tree_batch_run(ws_ctx *c, const Batch &b, ws_tree_node *d_tree, size_t *failed_slice, F labels, const LakeBatchWanted *ls) {
@@ -420,26 +437,33 @@ int tree_batch_run(ws_ctx *c, const Batch &b, ws_tree_node *d_tree, size_t *fail
   }
   // (the accumulator planes: a group's colours, the forest's entry 0 and one record 0 per slice of the group)
   if (ls && (rc = ensure(c, c->lake_acc, (std::max(most, most_group) + 1 + per_group) * LAKE_ACC_BYTES))) return rc;
+  const bool shapes = ls && ls->with_shapes;
+  if (shapes && (rc = ensure(c, c->shape_acc, (std::max(most, most_group) + 1 + per_group) * SHAPE_ACC_BYTES))) return rc;
   return history_batch_run(c, true, b, per_group, failed_slice, [&](const BatchGroup &grp) -> int {
     const size_t k = grp.k_first, at = b.seeds_in(0, k) + k;
     ws_tree_node *out = d_tree + at;
     ws_lake_stats *out_stats = ls ? ls->stats + at : nullptr;
+    ws_lake_shape *out_shapes = shapes ? ls->shapes + at : nullptr;
     if (grp.base) {
       if (int rc_t = build_tree_stack(c, grp, b, out)) return rc_t;
       if (ls)
         if (int rc_t = build_lake_stats_stack(c, grp, b, lake_weights_from(*ls, b, k), out_stats)) return rc_t;
+      if (shapes)
+        if (int rc_t = build_lake_shapes_stack(c, grp, b, lake_weights_from(*ls, b, k), out_shapes)) return rc_t;
     } else {
       // the seed pairs as the flood took them: the caller's, or (shifted_seeds) moved into the padded plane
       const uint32_t *seeds = seed_shift_of(b.opt) && grp.ns ? (const uint32_t *)c->seeds.p : b.d_seeds_rc + 2 * b.seed_offsets[k];
       if (int rc_t = build_tree(c, grp.keys, grp.labels, seeds, grp.ns, b.opt, b.ph, b.pw, out)) return rc_t;
       if (ls)
         if (int rc_t = build_lake_stats(c, grp.keys, grp.labels, seeds, grp.ns, b.opt, b.ph, b.pw, out, lake_weights_from(*ls, b, k), out_stats)) return rc_t;
+      if (shapes)
+        if (int rc_t = build_lake_shapes(c, grp.keys, grp.labels, seeds, grp.ns, b.opt, b.ph, b.pw, out, lake_weights_from(*ls, b, k), out_shapes)) return rc_t;
     }
     return labels(grp);
   });
 }
 
-// ws_merge_tree_batch_device and, with ls, ws_merge_tree_stats_batch_device
+// ws_merge_tree_batch_device, with ls ws_merge_tree_stats_batch_device and, with ls->with_shapes, ws_merge_tree_shapes_batch_device
 int tree_batch_device_body(ws_ctx *c, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w, size_t row_stride, size_t slice_stride,
                            const uint32_t *d_seeds_rc, const size_t *seed_offsets, const ws_options *opt, ws_tree_node *d_tree, uint32_t *d_labels,
                            size_t *failed_slice, LakeBatchWanted *ls) {
@@ -450,7 +474,8 @@ int tree_batch_device_body(ws_ctx *c, const uint8_t *d_cube, size_t n_slices, si
     if (int rc = check_lake_batch(c, n_slices, b, *ls)) return rc;
   if (n_slices == 0) return WS_OK;
   if (b.seeds_in(0, n_slices) >= 0xFFFFFFFFull) return fail(c, WS_ERR_TOO_LARGE, "too many seeds");
-  if (!d_tree || (ls && !ls->stats) || b.missing_input()) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  if (!d_tree || (ls && !ls->stats) || (ls && ls->with_shapes && !ls->shapes) || b.missing_input()) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  if (ls && ls->with_shapes && (reinterpret_cast<uintptr_t>(ls->shapes) & 7u)) return fail(c, WS_ERR_BAD_ARG, "d_shapes is not 8-byte aligned");
   if (ls && h * w == 0) ls->weight = nullptr;
   const size_t plane = b.plane();
   const auto labels_to_caller = [&](const BatchGroup &grp) -> int {
@@ -476,8 +501,8 @@ int upload_weights(ws_ctx *c, const LakeBatchWanted &want, size_t n_slices, size
   return WS_OK;
 }
 
-// ws_merge_tree_batch and, with want (host pointers), ws_merge_tree_stats_batch: the inputs to the device, the device form's run
-// into the context's record buffers, the records back.  A cap below the need is counted, nothing flooded: the caller learns how
+// ws_merge_tree_batch, with want (host pointers) ws_merge_tree_stats_batch and, with want->with_shapes, ws_merge_tree_shapes_batch:
+// the inputs to the device, the device form's run into the context's record buffers, the records back, one copy an array.  A cap below the need is counted, nothing flooded: the caller learns how
 // many records to make room for.
 int tree_batch_host_body(ws_ctx *c, const uint8_t *cube, size_t n_slices, size_t h, size_t w, size_t row_stride, size_t slice_stride,
                          const uint64_t *seeds_rc, const size_t *seed_offsets, const ws_options *opt, ws_tree_node *tree, size_t cap, size_t *n_records,
@@ -491,7 +516,8 @@ int tree_batch_host_body(ws_ctx *c, const uint8_t *cube, size_t n_slices, size_t
     if (n_records) *n_records = 0;
     return WS_OK;
   }
-  if ((!cube && h * w) || ((!tree || (want && !want->stats)) && cap)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
+  const bool shapes = want && want->with_shapes;
+  if ((!cube && h * w) || ((!tree || (want && !want->stats) || (shapes && !want->shapes)) && cap)) return fail(c, WS_ERR_BAD_ARG, "null pointer");
   if (seeds_rc && seed_offsets[n_slices] - seed_offsets[0] >= 0xFFFFFFFFull) return fail(c, WS_ERR_TOO_LARGE, "too many seeds");
   std::vector<size_t> offs;
   if ((rc = upload_batch(c, cube, n_slices, row_stride, slice_stride, seeds_rc, seed_offsets, b, offs, n_seeds, failed_slice))) return rc;
@@ -501,9 +527,11 @@ int tree_batch_host_body(ws_ctx *c, const uint8_t *cube, size_t n_slices, size_t
   if (cap < total) return fail(c, WS_ERR_CAPACITY, want ? "record buffers too small" : "tree buffer too small");
   if ((rc = ensure(c, c->tree_out, total * sizeof(ws_tree_node)))) return rc;
   if (want && (rc = ensure(c, c->lake_out, total * sizeof(ws_lake_stats)))) return rc;
+  if (shapes && (rc = ensure(c, c->shape_out, total * sizeof(ws_lake_shape)))) return rc;
   if (labels && (rc = ensure(c, c->out64, std::max<size_t>(plane, 1) * sizeof(uint64_t)))) return rc;      // (the plane-by-plane copy widens there)
   LakeBatchWanted ls;
   ls.stats = (ws_lake_stats *)c->lake_out.p;
+  ls.with_shapes = shapes; ls.shapes = (ws_lake_shape *)c->shape_out.p;
   if (want && (rc = upload_weights(c, *want, n_slices, h, w, ls))) return rc;
   const auto labels_to_caller = [&](const BatchGroup &grp) -> int {
     if (!labels || !plane) return WS_OK;
@@ -512,6 +540,7 @@ int tree_batch_host_body(ws_ctx *c, const uint8_t *cube, size_t n_slices, size_t
   if ((rc = tree_batch_run(c, b, (ws_tree_node *)c->tree_out.p, failed_slice, labels_to_caller, want ? &ls : nullptr))) return rc;
   HIP_TRY(c, hipMemcpyAsync(tree, c->tree_out.p, total * sizeof(ws_tree_node), hipMemcpyDeviceToHost, c->stream));
   if (want) HIP_TRY(c, hipMemcpyAsync(want->stats, c->lake_out.p, total * sizeof(ws_lake_stats), hipMemcpyDeviceToHost, c->stream));
+  if (shapes) HIP_TRY(c, hipMemcpyAsync(want->shapes, c->shape_out.p, total * sizeof(ws_lake_shape), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return WS_OK;
 }
@@ -856,6 +885,24 @@ int ws_merge_tree_stats_batch(ws_ctx *c, const uint8_t *cube, size_t n_slices, s
                               size_t weight_row_stride, size_t weight_slice_stride, ws_tree_node *tree, ws_lake_stats *stats, size_t cap,
                               size_t *n_records, uint64_t *labels, size_t *n_seeds, size_t *failed_slice) {
   const LakeBatchWanted want{weight, weight_dtype, weight_row_stride, weight_slice_stride, stats};
+  return tree_batch_host_body(c, cube, n_slices, h, w, row_stride, slice_stride, seeds_rc, seed_offsets, opt, tree, cap, n_records, labels, n_seeds,
+                              failed_slice, &want);
+}
+
+int ws_merge_tree_shapes_batch_device(ws_ctx *c, const uint8_t *d_cube, size_t n_slices, size_t h, size_t w, size_t row_stride,
+                                      size_t slice_stride, const uint32_t *d_seeds_rc, const size_t *seed_offsets, const ws_options *opt,
+                                      const void *d_weight, int weight_dtype, size_t weight_row_stride, size_t weight_slice_stride,
+                                      ws_tree_node *d_tree, ws_lake_stats *d_stats, ws_lake_shape *d_shapes, uint32_t *d_labels,
+                                      size_t *failed_slice) {
+  LakeBatchWanted ls{d_weight, weight_dtype, weight_row_stride, weight_slice_stride, d_stats, true, d_shapes};
+  return tree_batch_device_body(c, d_cube, n_slices, h, w, row_stride, slice_stride, d_seeds_rc, seed_offsets, opt, d_tree, d_labels, failed_slice, &ls);
+}
+
+int ws_merge_tree_shapes_batch(ws_ctx *c, const uint8_t *cube, size_t n_slices, size_t h, size_t w, size_t row_stride, size_t slice_stride,
+                               const uint64_t *seeds_rc, const size_t *seed_offsets, const ws_options *opt, const void *weight, int weight_dtype,
+                               size_t weight_row_stride, size_t weight_slice_stride, ws_tree_node *tree, ws_lake_stats *stats,
+                               ws_lake_shape *shapes, size_t cap, size_t *n_records, uint64_t *labels, size_t *n_seeds, size_t *failed_slice) {
+  const LakeBatchWanted want{weight, weight_dtype, weight_row_stride, weight_slice_stride, stats, true, shapes};
   return tree_batch_host_body(c, cube, n_slices, h, w, row_stride, slice_stride, seeds_rc, seed_offsets, opt, tree, cap, n_records, labels, n_seeds,
                               failed_slice, &want);
 }

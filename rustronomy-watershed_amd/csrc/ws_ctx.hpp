@@ -63,7 +63,9 @@ struct ws_ctx {
   // ws_merge_tree_stats_batch(_device): the planes of the largest group (its colours, one entry more and one per slice of a group),
   // the host form's records of the whole cube and its weight cube, contiguous
   wsapi::DevBuf lake_acc, lake_out, lake_weight;
-  // ws_merge_tree_shapes(_device): the twelve limb planes (96 B a colour); the host form's records before they cross (96 B a colour)
+  // ws_merge_tree_shapes(_device): the twelve limb planes (96 B a colour); the host form's records before they cross (96 B a colour).
+  // ws_merge_tree_shapes_batch(_device): the planes of the largest group (its colours, one entry more and one per slice of a group),
+  // the host form's records of the whole cube
   wsapi::DevBuf shape_acc, shape_out;
   // ws_merge_tree_from_arrival_device: the seed pairs recovered from the planes (8 B a colour: seed_pixels_from_planes)
   wsapi::DevBuf tree_seed_px;

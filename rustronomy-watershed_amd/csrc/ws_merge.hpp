@@ -214,5 +214,13 @@ constexpr size_t SHAPE_ACC_BYTES = 12 * sizeof(u64c);      // per colour: two ca
 hipError_t lake_shapes(hipStream_t s, const uint32_t *keys, const uint32_t *labels, const uint32_t *death, const uint32_t *hook, const TreeRec *tree,
                        const uint32_t *seeds_rc, size_t n_colours, uint32_t levels, const u64c *ws, const uint32_t *order, const LakeWeights &wt, int h,
                        int w, void *acc, ShapeRec *out);
+// The same over the forest of a stack (ws_merge_tree_shapes_batch_device), after lake_stats_stack and with its arguments: rows and
+// columns are those of a pixel within its own slice, its weight comes from its slice's plane, an uncoloured pixel of slice k goes to
+// accumulator entry n_colours + k: acc holds (n_colours + st.g) * SHAPE_ACC_BYTES, cleared here.  The 96-bit bound of a sum is a
+// slice's (every entry belongs to one slice), and so is the choice of the wave join: the sides of ONE slice, st.plane / w and w.
+// Writes the caller's slice-major layout as lake_stats_stack does -- n_colours - 1 + st.g records, out 8-byte aligned.
+hipError_t lake_shapes_stack(hipStream_t s, const uint32_t *keys, const uint32_t *labels, const uint32_t *death, const uint32_t *hook,
+                             const TreeRec *forest, const uint32_t *stacked_rc, size_t n_colours, uint32_t levels, const u64c *ws,
+                             const uint32_t *order, const LakeWeights &wt, const TreeStack &st, int w, void *acc, ShapeRec *out);
 
 }  // namespace wsk

@@ -1,7 +1,6 @@
 // ws_merge_tree.hip -- gfx950 kernels that read the stamped forest of a merging transform_history run (k_union_stamped,
 // ws_merge.hip: hook[b] = the root b was hooked under, death[b] = the level): the history planes, the merge tree and the lake
-// statistics, each for one plane and for a stack of slices, and the lakes' second moments for one plane.  Nothing here changes
-// the union-find.
+// statistics and the lakes' second moments, each for one plane and for a stack of slices.  Nothing here changes the union-find.
 #include "ws_uf.hpp"
 #include "ws_lake_part.hpp"
 #include "ws_shape_part.hpp"
@@ -667,10 +666,16 @@ hipError_t lake_stats_stack(hipStream_t s, const uint32_t *keys, const uint32_t 
 // Own shapes: k_lake_own's grid, loads, walks and three joins (the quad's pixels that share a root, the lanes that agree with the
 // wave's first lane, the workgroup's table keyed by root) with a ShapePart for a LakePart; an uncoloured pixel goes to record 0.
 // FLAT: both sides of the plane are below 65 536 (shape_wave_total).
-template <typename T, bool FLAT>
+// STACKED (lake_shapes_stack), as k_lake_own's: labels hold every slice's own colours and the accumulator planes have n_colours = the
+// forest's colours + stack.g entries.  A quad's slice is k = i0 / stack.plane (stack.plane % 4 == 0: a quad never straddles two
+// slices, a workgroup's step may); its colours move to the forest's numbering before the walk, its uncoloured pixels go to entry
+// n_colours - stack.g + k -- the slice's own record 0, which stands in for the root in the lane's join, the wave's and the table --
+// and rows, columns and the weight plane are those of the slice.  FLAT is then about the sides of ONE slice.
+template <typename T, bool FLAT, bool STACKED>
 __global__ __launch_bounds__(256) void k_shape_own(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ labels,
                                                    const uint32_t *__restrict__ death, const uint32_t *__restrict__ hook, LakeWeights wt,
-                                                   uint32_t W, u64c *acc, size_t n_colours, size_t n, size_t steps) {
+                                                   uint32_t W, u64c *acc, size_t n_colours, size_t n, size_t steps,
+                                                   TreeStack stack) {
   __shared__ u64c s_acc[SHAPE_LIMBS * SHAPE_SLOTS];
   __shared__ uint32_t s_key[SHAPE_SLOTS], s_used;
   for (int j = threadIdx.x; j < SHAPE_SLOTS; j += 256) {
@@ -697,11 +702,19 @@ __global__ __launch_bounds__(256) void k_shape_own(const uint32_t *__restrict__ 
         col[p] = in ? labels[i0 + p] : 0u;
       }
     }
+    uint32_t slice = 0, none = 0;      // the quad's slice and where its uncoloured pixels go
+    if constexpr (STACKED) {
+      slice = i0 < n ? (uint32_t)i0 / stack.plane : 0u;      // (n < 2^32: lake_shapes_stack)
+      none = (uint32_t)n_colours - stack.g + slice;
+      const uint32_t b = stack.base[slice];
+#pragma unroll
+      for (int p = 0; p < 4; ++p) col[p] += col[p] != 0u ? b : 0u;
+    }
     uint32_t r[4], d[4];
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       const bool coloured = col[p] != 0u && arr[p] != 0xFFu;      // (as k_tree_own)
-      r[p] = coloured ? col[p] : 0u;
+      r[p] = coloured ? col[p] : none;
       d[p] = coloured ? death[col[p]] : TREE_ALIVE;
     }
     for (;;) {      // the root at the pixel's arrival level, four walks side by side
@@ -714,13 +727,17 @@ __global__ __launch_bounds__(256) void k_shape_own(const uint32_t *__restrict__ 
 #pragma unroll
       for (int p = 0; p < 4; ++p) if (go[p]) d[p] = death[r[p]];
     }
-    uint32_t y = i0 < n ? (uint32_t)i0 / W : 0u, x = i0 < n ? (uint32_t)i0 % W : 0u;      // (n < 2^32)
+    const uint32_t in0 = STACKED ? (uint32_t)i0 - slice * stack.plane : (uint32_t)i0;      // the quad's first pixel within its plane
+    uint32_t y = i0 < n ? in0 / W : 0u, x = i0 < n ? in0 % W : 0u;      // (n < 2^32)
     ShapePart part[4];
     bool live[4];
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       live[p] = i0 + p < n;
-      part[p] = shape_pixel(live[p] ? lake_weight<T>(wt, y, x) : 0u, y, x);
+      uint32_t v = 0u;
+      if constexpr (STACKED) v = live[p] ? lake_weight_of_slice<T>(wt, slice, y, x) : 0u;
+      else v = live[p] ? lake_weight<T>(wt, y, x) : 0u;
+      part[p] = shape_pixel(v, y, x);
       if (++x == W) { x = 0; ++y; }
     }
 #pragma unroll
@@ -790,13 +807,33 @@ __global__ __launch_bounds__(256) void k_shape_fold(const TreeRec *__restrict__ 
 
 // The records: every pair of limbs normalised to (low, high) once.  A colour that dies at level 0 handed on nothing and was never
 // the root of a pixel: it takes its seed pixel alone (as k_lake_write).
-template <typename T>
+// STACKED, as k_lake_write's: entry c of the n_colours accumulator entries is forest colour c (1 .. n_colours - stack.g - 1: the
+// record at out[c + its slice], its seed pair in stacked rows of W columns) or slice k's uncoloured pixels (n_colours - stack.g + k:
+// the record at out[base[k] + k]); entry 0 of the forest is nobody's.
+template <typename T, bool STACKED>
 __global__ __launch_bounds__(256) void k_shape_write(const TreeRec *__restrict__ tree, const uint32_t *__restrict__ seeds_rc, LakeWeights wt,
-                                                     const u64c *__restrict__ acc, size_t n_colours, ShapeRec *out) {
+                                                     const u64c *__restrict__ acc, size_t n_colours, ShapeRec *out, uint32_t W,
+                                                     TreeStack stack) {
   const size_t c = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (c >= n_colours) return;
   ShapePart a = shape_load(acc, n_colours, c);
-  if (c != 0) {
+  size_t at = c;
+  if constexpr (STACKED) {
+    const size_t forest = n_colours - stack.g;
+    if (c == 0) return;
+    if (c >= forest) {
+      const uint32_t k = (uint32_t)(c - forest);
+      at = (size_t)stack.base[k] + k;
+    } else {
+      const uint32_t k = slice_of_colour(stack.base, stack.g, (uint32_t)c);
+      at = c + k;
+      const TreeRec t = tree[c];
+      if (t.death_level == 0u && t.n_leaves != 0u) {
+        const uint32_t y = seeds_rc[2 * (c - 1)] - k * (stack.plane / W), x = seeds_rc[2 * (c - 1) + 1];
+        a = shape_pixel(lake_weight_of_slice<T>(wt, k, y, x), y, x);
+      }
+    }
+  } else if (c != 0) {
     const TreeRec t = tree[c];
     if (t.death_level == 0u && t.n_leaves != 0u) {
       const uint32_t y = seeds_rc[2 * (c - 1)], x = seeds_rc[2 * (c - 1) + 1];
@@ -806,7 +843,24 @@ __global__ __launch_bounds__(256) void k_shape_write(const TreeRec *__restrict__
   ShapeRec rec;
 #pragma unroll
   for (int k = 0; k < 6; ++k) shape_normal(a, k, &rec.s[k][0], &rec.s[k][1]);
-  out[c] = rec;
+  out[at] = rec;
+}
+
+// the grid of k_lake_own over n pixels and the launch of the instantiation the weights, the sides of ONE plane and the form ask for
+template <bool STACKED>
+hipError_t shape_own_launch(hipStream_t s, const uint32_t *keys, const uint32_t *labels, const uint32_t *death, const uint32_t *hook,
+                            const LakeWeights &wt, bool flat, uint32_t w, u64c *acc, size_t n_entries, size_t n, const TreeStack &st) {
+  const size_t quads = (n + 1023) / 1024;
+  const size_t steps = std::max<size_t>((quads + 2047) / 2048, 1);
+  const unsigned grid = (unsigned)((quads + steps - 1) / steps);
+  if (wt.u16) {
+    if (flat) k_shape_own<uint16_t, true, STACKED><<<grid, 256, 0, s>>>(keys, labels, death, hook, wt, w, acc, n_entries, n, steps, st);
+    else k_shape_own<uint16_t, false, STACKED><<<grid, 256, 0, s>>>(keys, labels, death, hook, wt, w, acc, n_entries, n, steps, st);
+  } else {
+    if (flat) k_shape_own<uint8_t, true, STACKED><<<grid, 256, 0, s>>>(keys, labels, death, hook, wt, w, acc, n_entries, n, steps, st);
+    else k_shape_own<uint8_t, false, STACKED><<<grid, 256, 0, s>>>(keys, labels, death, hook, wt, w, acc, n_entries, n, steps, st);
+  }
+  return hipGetLastError();
 }
 
 hipError_t lake_shapes(hipStream_t s, const uint32_t *keys, const uint32_t *labels, const uint32_t *death, const uint32_t *hook, const TreeRec *tree,
@@ -818,20 +872,8 @@ hipError_t lake_shapes(hipStream_t s, const uint32_t *keys, const uint32_t *labe
   u64c *acc = (u64c *)acc_bytes;
   hipError_t e = hipMemsetAsync(acc, 0, n_colours * SHAPE_ACC_BYTES, s);      // the identity of the fold is twelve zeros
   if (e != hipSuccess) return e;
-  if (n) {      // the grid of k_lake_own
-    const size_t quads = (n + 1023) / 1024;
-    const size_t steps = std::max<size_t>((quads + 2047) / 2048, 1);
-    const unsigned grid = (unsigned)((quads + steps - 1) / steps);
-    const bool flat = h < 65536 && w < 65536;
-    if (wt.u16) {
-      if (flat) k_shape_own<uint16_t, true><<<grid, 256, 0, s>>>(keys, labels, death, hook, wt, (uint32_t)w, acc, n_colours, n, steps);
-      else k_shape_own<uint16_t, false><<<grid, 256, 0, s>>>(keys, labels, death, hook, wt, (uint32_t)w, acc, n_colours, n, steps);
-    } else {
-      if (flat) k_shape_own<uint8_t, true><<<grid, 256, 0, s>>>(keys, labels, death, hook, wt, (uint32_t)w, acc, n_colours, n, steps);
-      else k_shape_own<uint8_t, false><<<grid, 256, 0, s>>>(keys, labels, death, hook, wt, (uint32_t)w, acc, n_colours, n, steps);
-    }
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
+  if (n && (e = shape_own_launch<false>(s, keys, labels, death, hook, wt, h < 65536 && w < 65536, (uint32_t)w, acc, n_colours, n, TreeStack{})) != hipSuccess)
+    return e;
   if (n_colours > 1) {      // (tree_fold built order[] and its bounds under the same condition)
     const u64c *off = ws + NLEVELS + 1;
     const unsigned grid = (unsigned)std::min<size_t>(std::max<size_t>(n_colours / (256 * 64), 1), 128);
@@ -841,8 +883,37 @@ hipError_t lake_shapes(hipStream_t s, const uint32_t *keys, const uint32_t *labe
     }
   }
   const unsigned per_colour = (unsigned)((n_colours + 255) / 256);
-  if (wt.u16) k_shape_write<uint16_t><<<per_colour, 256, 0, s>>>(tree, seeds_rc, wt, acc, n_colours, out);
-  else k_shape_write<uint8_t><<<per_colour, 256, 0, s>>>(tree, seeds_rc, wt, acc, n_colours, out);
+  if (wt.u16) k_shape_write<uint16_t, false><<<per_colour, 256, 0, s>>>(tree, seeds_rc, wt, acc, n_colours, out, (uint32_t)w, TreeStack{});
+  else k_shape_write<uint8_t, false><<<per_colour, 256, 0, s>>>(tree, seeds_rc, wt, acc, n_colours, out, (uint32_t)w, TreeStack{});
+  return hipGetLastError();
+}
+
+hipError_t lake_shapes_stack(hipStream_t s, const uint32_t *keys, const uint32_t *labels, const uint32_t *death, const uint32_t *hook,
+                             const TreeRec *forest, const uint32_t *stacked_rc, size_t n_colours, uint32_t levels, const u64c *ws,
+                             const uint32_t *order, const LakeWeights &wt, const TreeStack &st, int w, void *acc_bytes, ShapeRec *out) {
+  if (n_colours == 0 || st.g == 0) return hipSuccess;
+  const size_t n = (size_t)st.g * st.plane, n_acc = n_colours + st.g;      // every slice's record 0 behind the forest's colours
+  // (slices, rows and columns are u32 divisions; a quad must not straddle two slices, a row must not either)
+  if (n > 0xFFFFFFFFull || n_acc > 0xFFFFFFFFull || st.plane == 0 || (st.plane & 3u) != 0 || w <= 0 || st.plane % (uint32_t)w != 0 ||
+      ((reinterpret_cast<uintptr_t>(acc_bytes) | reinterpret_cast<uintptr_t>(out)) & 7u) != 0)
+    return hipErrorInvalidValue;
+  u64c *acc = (u64c *)acc_bytes;
+  hipError_t e = hipMemsetAsync(acc, 0, n_acc * SHAPE_ACC_BYTES, s);      // the identity of the fold is twelve zeros
+  if (e != hipSuccess) return e;
+  // FLAT from the sides of a slice: rows restart in every slice, the stacked height g * ph never enters a term
+  const bool flat = st.plane / (uint32_t)w < 65536u && w < 65536;
+  if ((e = shape_own_launch<true>(s, keys, labels, death, hook, wt, flat, (uint32_t)w, acc, n_acc, n, st)) != hipSuccess) return e;
+  if (n_colours > 1) {      // ONE launch per level for the whole stack: parents are the forest's, the planes are n_acc long
+    const u64c *off = ws + NLEVELS + 1;
+    const unsigned grid = (unsigned)std::min<size_t>(std::max<size_t>(n_colours / (256 * 64), 1), 128);
+    for (uint32_t l = 1; l < levels; ++l) {
+      k_shape_fold<<<grid, 256, 0, s>>>(forest, acc, n_acc, order, off + l);
+      if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+  }
+  const unsigned per_entry = (unsigned)((n_acc + 255) / 256);
+  if (wt.u16) k_shape_write<uint16_t, true><<<per_entry, 256, 0, s>>>(forest, stacked_rc, wt, acc, n_acc, out, (uint32_t)w, st);
+  else k_shape_write<uint8_t, true><<<per_entry, 256, 0, s>>>(forest, stacked_rc, wt, acc, n_acc, out, (uint32_t)w, st);
   return hipGetLastError();
 }
 

@@ -681,6 +681,32 @@ class DeviceEngine:
                                                                        labels.data_ptr() if want_labels else None, ctypes.byref(failed)))
         return (out, out_stats, labels) if want_labels else (out, out_stats)
 
+    def merge_tree_shapes_batch(self, cube, seeds, seed_offsets, weights=None, max_level=254, edge=False, seed_shift=False,
+                                want_labels=False, out=None, out_stats=None, out_shapes=None):
+        """merge_tree_shapes of every slice of a cube with everything in HBM (ws_merge_tree_shapes_batch_device); every argument
+        as merge_tree_stats_batch.  Returns (tree, stats, shapes): the two tensors of merge_tree_stats_batch and an
+        (n_seeds_total + S, 12) int64 tensor of raw ws_lake_shape words as merge_tree_shapes's, in the same slice-major layout --
+        every slice's records are those of merge_tree_shapes on the slice alone.  With want_labels returns (tree, stats, shapes,
+        labels).  `out`, `out_stats`, `out_shapes`: reusable contiguous tensors of those shapes."""
+        offs = self._batch_args(cube, seeds, seed_offsets)
+        s, h, w = cube.shape
+        e = 2 if edge else 0
+        wptr, dtype, wrow, wslice = self._cube_weights(weights, (s, h, w)) if weights is not None else (None, 0, 0, 0)
+        total = int(seed_offsets[-1]) - int(seed_offsets[0]) + s
+        out = self._records(out, (total, 4), torch.int32, "out")
+        out_stats = self._records(out_stats, (total, 9), torch.int64, "out_stats")
+        out_shapes = self._records(out_shapes, (total, 12), torch.int64, "out_shapes")
+        labels = torch.empty((s, h + e, w + e), dtype=torch.int32, device=self.device) if want_labels else None
+        if s:
+            opt = self.options(max_level, edge, None, seed_shift)
+            failed = ctypes.c_size_t(0)
+            self.ctx.check(_ffi.lib().ws_merge_tree_shapes_batch_device(self.ctx.handle, cube.data_ptr(), s, h, w, w, h * w,
+                                                                        seeds.data_ptr() if seeds.numel() else None, offs, ctypes.byref(opt),
+                                                                        wptr, dtype, wrow, wslice, out.data_ptr(), out_stats.data_ptr(),
+                                                                        out_shapes.data_ptr(), labels.data_ptr() if want_labels else None,
+                                                                        ctypes.byref(failed)))
+        return (out, out_stats, out_shapes, labels) if want_labels else (out, out_stats, out_shapes)
+
     @staticmethod
     def _cube_weights(weights, shape):
         """(pointer, dtype, row stride, slice stride) of a 3-D weight tensor of `shape` with contiguous rows."""
