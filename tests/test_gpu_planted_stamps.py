@@ -22,7 +22,8 @@ carry itself is KEY_INF and shows nowhere.  A stamp that comes out too LOW is pe
 compared bit for bit.
 
 Out of reach of planted stamps: k_relax0_tall, k_relax_strips_tall and the queue kernels need a seed plane or persist_mode,
-which the block calls do not set.
+which the block calls do not set.  The queue kernels (k_relax, PERSIST 1 and 2: 128 x 128 tiles, 32 bands) have corridors of
+their own, flooded from seeds, in tests/test_gpu_queue_corridors.py (tests/queue_cases.py).
 
 Relaxation passes observed (ws_ctx_get_stats; pass_loop launches passes in groups of 2, 1, 2, 4, 8, 16 and counts what it
 launched, so the values are 3, 5, 9, 17, 33: 33 = the first pass that changed nothing was one of 9 .. 16, past pass 7, the
